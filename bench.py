@@ -18,6 +18,8 @@ N > 1 is ONE coupled simulation cut into N z-slabs (SURVEY.md 8e, config C4 weak
 coarse multigrid level travel over RCCL/xGMI (csrc/comm.cpp).  Weak scaling: per-GPU work is fixed as N grows.
 `value` counts C3-sized slab-steps per second over the whole job (= N x coupled steps/s of the N-slab box; identical to coupled
 steps/s at N = 1).  Rank 0 prints ONE JSON line.
+`--dump-outputs DIR` writes what the last timed step computed (forces, found flags, U, p; a fixed, seeded sample of the larger ones) as
+DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -659,6 +661,30 @@ def aggregate_value(world, steps, elapsed):
     return world * steps / elapsed
 
 
+DUMP_ROWS = 1 << 19             # --dump-outputs: rows kept per array (forces 6 + U 3 + p 1 doubles + found 1 float per row: 44 MB in all)
+DUMP_SEED = 2024
+
+
+def dump_rows(n, cap):
+    """the rows --dump-outputs keeps of an n-row output: all of them up to `cap`, else a fixed, seeded sample in ascending order"""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_ROWS, prefix=""):
+    """--dump-outputs: every array (one row per particle or per cell) as out_dir/<prefix><name>.npy -- float64 as it is, anything else as
+    float32; an array of more than `cap` rows keeps the dump_rows sample.  Returns {name: [rows kept, rows computed]}"""
+    os.makedirs(out_dir, exist_ok=True)
+    kept = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        rows = dump_rows(a.shape[0], cap)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float64 if a.dtype == np.float64 else np.float32))
+        kept[name] = [int(rows.size), int(a.shape[0])]
+    return kept
+
+
 def rccl_selftest_child(args):
     """child of rccl_preflight: join the throw-away communicator, run the library's known-answer pattern, exit 0 / 3"""
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
@@ -740,8 +766,13 @@ def main():
     ap.add_argument("--no-moving", action="store_true", help="skip the moving-bed sub-record that follows the timed region (N = 1, C3 only)")
     ap.add_argument("--pmc", type=int, default=-1, help="1: measure roofline.traffic live (two rocprofv3 --pmc child passes of this command, FETCH_SIZE and "
                     "WRITE_SIZE, after everything else); 0: print null + the committed profile's path; -1 (default): live when rocprofv3 is there, N = 1, default C3")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed region write what its last step computed -- the particles' forces "
+                    "(Np x 6) and found flags, the fluid's U (cells x 3) and p -- as DIR/<name>.npy (rank<r>_<name>.npy for N > 1); arrays of more than "
+                    f"{DUMP_ROWS:,} rows (divided by N) keep a fixed, seeded sample of them (44 MB in all at most)")
     handed = os.environ.pop("FOAMYADE_BENCH_ARGV", None)           # (self_launch's ranks: the command line of the process that launched them)
     args = ap.parse_args(json.loads(handed) if (handed and len(sys.argv) == 1) else None)
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
     if args.rccl_selftest:
         rccl_selftest_child(args)
     if args.laplacian_probe:
@@ -949,6 +980,11 @@ def main():
         return acc, max_over_ranks(time.perf_counter() - t0, dist, ddev, ctl_group)
 
     acc, elapsed = timed_region(args.steps, args.moving)
+    dumped = None
+    if args.dump_outputs:
+        # what the caller of the timed path receives from its last step (the step's closing setSourceZero has cleared the coupling fields)
+        dumped = dump_outputs(args.dump_outputs, {"forces": solver.forces(), "found": solver.found(), "U": solver.get("U").reshape(-1, 3), "p": solver.get("p")},
+                              cap=DUMP_ROWS // world, prefix=f"rank{rank}_" if world > 1 else "")
 
     K = args.steps
     steps_per_s = K / elapsed if strong else aggregate_value(world, K, elapsed)      # strong: steps of the one box; weak: slab-steps
@@ -1049,6 +1085,9 @@ def main():
         "kernels": {k: {"avg_ms": round(v["avg_ms"], 4), "launches": v["launches"], "GBps": round(v["compulsory"] / (v["avg_ms"] * 1e-3) / 1e9, 1),
                         "design_GBps": round(v["achieved_GBps"], 1)} for k, v in kern.items()},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "rows": dumped, "seed": DUMP_SEED,
+                                 "what": "the last timed step's forces, found flags, U and p; [rows kept, rows computed] per array"}
     if world > 1 and slabs_ok >= 1.0:
         # how long each rank's stream sat waiting for slab exchanges, by phase -- sampled in a few EXTRA steps after the timed region (the clock costs an
         # event pair per exchange, which would slow the steps it measures).  FOAMYADE_HALO_OVERLAP=0 runs the exchange-then-consume schedule: the A/B
