@@ -54,3 +54,62 @@ def test_product_never_touches_the_oracle():
             if re.search(r"oracle", s) and not (s.startswith("//") or s.startswith("#") or s.startswith("*") or s.startswith('"""') or "never" in s):
                 bad.append((h, s))
     assert not bad, bad
+
+
+CSRC = os.path.join(ROOT, "yade-openfoam-coupling_amd", "csrc")
+
+
+def csrc_sources():
+    """{file name: text with comments blanked out} of every source under csrc/"""
+    out = {}
+    for nm in sorted(os.listdir(CSRC)):
+        if nm.endswith((".cpp", ".hpp", ".hip", ".inc")):
+            text = open(os.path.join(CSRC, nm)).read()
+            text = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), text, flags=re.S)
+            out[nm] = re.sub(r"//[^\n]*", "", text)
+    return out
+
+
+def test_environment_is_read_in_one_place():
+    """the library reads the environment in fy::options() only (and libfoamyade_mpi, which does not link it, once for
+    FOAMYADE_WIRE_CUT_AXIS), and the variables it reads are exactly the ones the section's tables list."""
+    src = csrc_sources()
+    outside = []
+    for nm, text in src.items():
+        spans = []
+        if nm == "transport_mpi.cpp":
+            spans = [m.span() for m in re.finditer(r'getenv\("FOAMYADE_WIRE_CUT_AXIS"\)', text)][:1]
+        m = re.search(r"\nOptions options\(\) \{\n.*?\n\}\n", text, flags=re.S)
+        if m:
+            spans.append(m.span())
+        for g in re.finditer(r"\bgetenv\b", text):
+            if not any(a <= g.start() < b for a, b in spans):
+                outside.append(f"{nm}:{text.count(chr(10), 0, g.start()) + 1}")
+    assert not outside, f"getenv outside fy::options(): {outside}"
+    read = {v for text in src.values() for v in re.findall(r'"(FOAMYADE_[A-Z0-9_]+)"', text)}
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = re.search(r"\n## 7\..*?(?=\n## |\Z)", doc, flags=re.S).group(0)
+    listed = set(re.findall(r"^\| `(FOAMYADE_[A-Z0-9_]+)", sec, flags=re.M))
+    assert read == listed, f"read but not in section 7: {sorted(read - listed)}; in section 7 but not read: {sorted(listed - read)}"
+
+
+def test_no_build_variant_chooses_code():
+    """timing experiments are build variants of a copy of a kernel file (tools/build_variant.sh): the shipped sources may let a macro set a number
+    (#ifndef FY_X / #define FY_X <default> / #endif), but no FY_* macro other than FY_FVK_GRADED and FY_WITH_MPI chooses between two code paths."""
+    allowed = {"FY_FVK_GRADED", "FY_WITH_MPI"}
+    bad = []
+    for nm, text in csrc_sources().items():
+        lines = text.split("\n")
+        for i, line in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            used = set(re.findall(r"\bFY_[A-Z0-9_]+\b", m.group(2))) - allowed
+            if not used:
+                continue
+            if m.group(1) == "ifndef" and i + 2 < len(lines):      # the default-value pattern
+                x = m.group(2).strip()
+                if re.match(rf"\s*#\s*define\s+{x}\b", lines[i + 1]) and re.match(r"\s*#\s*endif\b", lines[i + 2]):
+                    continue
+            bad.append(f"{nm}:{i + 1}: {line.strip()}")
+    assert not bad, bad

@@ -5,7 +5,6 @@
 
 #include <dlfcn.h>
 
-#include <chrono>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -92,20 +91,11 @@ struct LocalShared {
     std::vector<int> device;
     double* red_all = nullptr;                 // [n x 32] device slots of the all-reduce, folded in rank order by every rank
     bool ordered_decided = false;              // stream_ordered's final value is set (LocalComm::init_rank, once, under init_m)
-    bool stream_ordered = false;               // FOAMYADE_LOCALCOMM_STREAM=1 (measured: no faster at 2 slabs, slower at 8 -- DESIGN.md 8)
-    // FOAMYADE_LOCALCOMM_TURNS=1 (profiling aid): between two collectives only ONE rank at a time enqueues and runs its work -- a rank takes the turn when it leaves
-    // a collective and gives it up, its device work drained, when it enters the next.  The slabs then do not share the GPU kernel by kernel, so a kernel trace shows
-    // every kernel of a slab at the duration it has with the GPU to itself (tools/r05/slab_kernels.sh); the wall time means nothing in this mode.
-    bool turns = false;
-    std::timed_mutex turn_m;
+    bool stream_ordered = options().localcomm_stream;      // FOAMYADE_LOCALCOMM_STREAM=1 (measured: no faster at 2 slabs, slower at 8 -- DESIGN.md 8)
     std::mutex init_m;
     explicit LocalShared(int n_) : n(n_), bar(n_), lists(n_), gather_src(n_), red(n_), ready(n_), done(n_), device(n_, -1) {
         for (auto& r : ready) r.fill(nullptr);
         for (auto& d : done) d.fill(nullptr);
-        const char* e = std::getenv("FOAMYADE_LOCALCOMM_STREAM");
-        if (e && e[0] == '1') stream_ordered = true;
-        const char* t = std::getenv("FOAMYADE_LOCALCOMM_TURNS");
-        if (t && t[0] == '1') { turns = true; stream_ordered = false; }
     }
     ~LocalShared() {
         for (auto& r : ready) for (hipEvent_t e : r) if (e) (void)hipEventDestroy(e);
@@ -117,22 +107,7 @@ struct LocalShared {
 struct LocalComm : Comm {
     std::shared_ptr<LocalShared> sh;
     uint64_t seq = 0;                                          // collectives issued by this rank so far
-    bool inited = false, my_turn = false;
-    struct Turn {                                              // scoped: give the turn up on entry (device drained), take it again on exit
-        LocalComm* c;
-        explicit Turn(LocalComm* c_) : c(c_) {
-            if (!c->sh->turns) return;
-            (void)hipDeviceSynchronize();
-            if (c->my_turn) { c->my_turn = false; c->sh->turn_m.unlock(); }
-        }
-        ~Turn() {
-            if (!c->sh->turns) return;
-            (void)hipDeviceSynchronize();                      // (the collective's own copies)
-            // (bounded wait: the rank that holds the turn when its step ends only gives it up in the next step's first collective)
-            c->my_turn = c->sh->turn_m.try_lock_for(std::chrono::milliseconds(100));
-        }
-    };
-    ~LocalComm() override { if (my_turn) { my_turn = false; sh->turn_m.unlock(); } }
+    bool inited = false;
     int init_rank() {
         if (inited) return FY_OK;
         // (a rank whose HIP call fails still takes part in both barriers -- the others must not hang on it -- and reports afterwards)
@@ -214,7 +189,6 @@ struct LocalComm : Comm {
         return rc2;
     }
     int exchange_many_sync(hipStream_t s, const Xchg* x, size_t n) {
-        Turn turn(this);
         FY_HIP(hipStreamSynchronize(s));                       // my planes are final
         sh->lists[rank] = x;
         sh->bar.wait();
@@ -249,7 +223,6 @@ struct LocalComm : Comm {
             FY_TRY(close(s, slot, 0, size - 1));
             return bad ? fail(FY_ERR_HIP, "all-reduce: fold launch failed") : FY_OK;
         }
-        Turn turn(this);
         std::vector<double>& mine = sh->red[rank];
         mine.resize((size_t)n);
         FY_HIP(hipMemcpyAsync(mine.data(), dev, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -280,7 +253,6 @@ struct LocalComm : Comm {
             FY_TRY(close(s, slot, 0, size - 1));
             return bad ? fail(FY_ERR_HIP, "all-gather: device copy failed") : FY_OK;
         }
-        Turn turn(this);
         FY_HIP(hipStreamSynchronize(s));
         sh->gather_src[rank] = send;
         sh->bar.wait();
@@ -291,7 +263,6 @@ struct LocalComm : Comm {
         return FY_OK;
     }
     int barrier(hipStream_t s) override {
-        Turn turn(this);
         FY_HIP(hipStreamSynchronize(s));
         sh->bar.wait();
         return FY_OK;
@@ -716,14 +687,12 @@ int ipc_comm_create(int rank, int size, const fy_comm_callbacks* cb, int device,
     FY_HIP(hipSetDevice(device));
     std::unique_ptr<IpcComm> c(new IpcComm());
     c->rank = rank; c->size = size; c->cb = *cb; c->device = device;
-    const char* e = std::getenv("FOAMYADE_IPC_SLOT_MB");
-    const size_t mb = e && std::atoi(e) > 0 ? (size_t)std::atoi(e) : 8;
+    const Options opt = options();
+    const size_t mb = opt.ipc_slot_mb > 0 ? (size_t)opt.ipc_slot_mb : 8;
     c->slot_nb = mb * (1u << 20) / sizeof(double);
-    const char* ek = std::getenv("FOAMYADE_IPC_SLOT_KB");      // (tests: slots small enough that the test meshes' groups travel in chunks)
-    if (ek && std::atoi(ek) > 0) c->slot_nb = (size_t)std::atoi(ek) * 1024 / sizeof(double);
+    if (opt.ipc_slot_kb > 0) c->slot_nb = (size_t)opt.ipc_slot_kb * 1024 / sizeof(double);      // (tests: slots small enough that the test meshes' groups travel in chunks)
     c->slot_coll = std::min<size_t>((256u << 10) / sizeof(double), c->slot_nb);
-    const char* t = std::getenv("FOAMYADE_IPC_TIMEOUT_MS");
-    const long long ms = t && std::atoll(t) > 0 ? std::atoll(t) : 20000;
+    const long long ms = opt.ipc_timeout_ms > 0 ? opt.ipc_timeout_ms : 20000;
     c->timeout_ticks = ms * 100000;                               // wall_clock64: 100 MHz
     c->win_bytes = c->header_bytes() + c->data_doubles() * sizeof(double);
     // uncached device memory where the runtime offers it (a peer GPU's stores must not meet stale lines of this GPU's L2), plain device memory otherwise
@@ -898,7 +867,7 @@ int rccl_comm_create(int rank, int size, const void* id128, int device, Comm** o
     if (r != 0) { delete c; return fail(FY_ERR_TRANSPORT, "ncclCommInitRank failed: %s", A->GetErrorString ? A->GetErrorString(r) : "?"); }
     // the second communicator (collective over the same ranks); without ncclCommSplit, or if it fails, the overlapped exchanges share
     // the first one as in round 1
-    if (A->CommSplit && !options().no_aux_comm) {
+    if (A->CommSplit) {
         if (A->CommSplit(c->comm, 0, rank, &c->comm_aux, nullptr) != 0) c->comm_aux = nullptr;
     }
     *out = c;

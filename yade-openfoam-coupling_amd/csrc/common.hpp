@@ -13,29 +13,39 @@
 
 namespace fy {
 
-// Run-time switches: environment variables, read here and nowhere else, when an object is created.  Deployment and
-// diagnosis knobs only -- timing experiments are build variants (tools/build_variant.sh), not switches in the shipped library.
+// Run-time switches: environment variables, read here and nowhere else, when an object is created.  None changes a
+// result.  Deployment options and test aids only -- an A/B timing experiment is a build variant (tools/build_variant.sh), never a shipped switch.
 struct Options {
-    bool explicit_tree;          // FOAMYADE_EXPLICIT_TREE=1     32-byte explicit tree nodes even on a lattice block (what a general mesh gets)
-    bool no_locate_lists;        // FOAMYADE_NO_LOCATE_LISTS=1   the plain tree walk places every particle (what a general mesh gets); tests/test_locate_paths.py
+    // deployment
     std::string tree_cache_dir;  // FOAMYADE_TREE_CACHE_DIR      ranks of one node share the k-d build through this directory ("" = off)
     int rebin_interval;          // FOAMYADE_REBIN_INTERVAL      counting sort of the particles every this many steps (default 32; locality only)
-    bool no_halo_overlap;        // FOAMYADE_NO_HALO_OVERLAP=1   slab smoother: exchange, then sweep (serial schedule; identical results)
+    int strip_blocks;            // FOAMYADE_STRIP_BLOCKS=n       blocks per strip of the FV cell sweeps (0: off; unset, -1: ~8 rows of cells)
     bool halo_overlap;           // FOAMYADE_HALO_OVERLAP=0       every slab exchange is followed by its consumer (serial schedule; identical results); default 1
-    bool no_aux_comm;            // FOAMYADE_NO_AUX_COMM=1       slab mode: no second RCCL communicator for the overlapped halo
-    bool no_deep_vcycle;         // FOAMYADE_NO_DEEP_VCYCLE=1    slab multigrid: one exchange per sweep (round 3's schedule) instead of one per level and cycle
-    bool no_fused_corrector;     // FOAMYADE_NO_FUSED_CORRECTOR=1  the corrector as five sweeps (rounds 1 - 4) instead of the two fused ones (A/B switch, identical results)
-    int strip_blocks;            // FOAMYADE_STRIP_BLOCKS=n       blocks per strip of the FV cell sweeps (0: off; unset: ~8 rows of cells)
-    bool faces_from_arrays;      // FOAMYADE_FACES_FROM_ARRAYS=1   the fused sweeps stream rAUf / alphacf from their face arrays instead of re-forming them from rAU / alpha
-    bool no_pairs;               // FOAMYADE_NO_PAIRS=1          pressure solver: one cell per thread in every sweep (fv_kernels.hip "two cells per thread"; identical results)
+    int ipc_slot_mb;             // FOAMYADE_IPC_SLOT_MB         peer-store communicator: MiB per neighbour slot (0: unset)
+    long long ipc_timeout_ms;    // FOAMYADE_IPC_TIMEOUT_MS      peer-store communicator: bound of a device-side wait for a peer (0: unset)
+    bool wire_trace;             // FOAMYADE_WIRE_TRACE          drop-in leg: per-step trace of the wire's copies on the device clock (stderr)
+    bool explicit_tree;          // FOAMYADE_EXPLICIT_TREE=1     32-byte explicit tree nodes even on a lattice block (what a general mesh gets)
+    // test aids: the path that a test holds the default against
+    bool no_locate_lists;        // FOAMYADE_NO_LOCATE_LISTS=1   the plain tree walk places every particle (what a general mesh gets)
+    int locate_stack;            // FOAMYADE_LOCATE_STACK=n      explicit tree: the walk's LDS stack depth (0: the full depth; unset, -1: measured per step)
+    bool locate_wide;            // FOAMYADE_LOCATE_WIDE=1       explicit tree: the 16-byte stack entries of 2^25 cells and more on any tree
+    bool no_deep_vcycle;         // FOAMYADE_NO_DEEP_VCYCLE=1    slab multigrid: one exchange per sweep instead of one per level and cycle
+    bool localcomm_stream;       // FOAMYADE_LOCALCOMM_STREAM=1  in-process slab groups: collectives as event waits on the ranks' streams
+    bool no_fused_corrector;     // FOAMYADE_NO_FUSED_CORRECTOR=1  the corrector as five sweeps instead of the two fused ones
+    bool faces_from_arrays;      // FOAMYADE_FACES_FROM_ARRAYS=1   the fused sweeps stream rAUf / alphacf from their face arrays instead of re-forming them
+    bool no_pairs;               // FOAMYADE_NO_PAIRS=1          pressure solver: one cell per thread in every sweep instead of two
+    bool no_tail_cache;          // FOAMYADE_NO_TAIL_CACHE=1     multigrid tail: the first level from global memory instead of LDS
+    int ipc_slot_kb;             // FOAMYADE_IPC_SLOT_KB         peer-store communicator: KiB per neighbour slot, overrides ipc_slot_mb (0: unset)
 };
 Options options();
 
 // thread-local last-error text behind fy_last_error()
 std::string& last_error();
 int fail(int code, const char* fmt, ...);
-// FOAMYADE_NO_PAIRS=1: the pressure solver's one-cell-per-thread kernels everywhere (A/B switch of the two-cell kernels, same bits); read when options() is
-bool pairs_disabled();
+// The kernel layer's switches, as the latest options() call read them (a process-wide snapshot: the launchers are not handed an object)
+bool pairs_disabled();           // no_pairs
+bool tail_cache_disabled();      // no_tail_cache
+bool locate_wide_forced();       // locate_wide
 
 #define FY_HIP(expr)                                                                                      \
     do {                                                                                                  \

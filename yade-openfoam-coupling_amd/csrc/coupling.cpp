@@ -18,32 +18,40 @@
 
 namespace fy {
 
-static std::atomic<int> g_no_pairs{-1};
-bool pairs_disabled() {
-    int v = g_no_pairs.load(std::memory_order_relaxed);
-    if (v < 0) { const char* e = getenv("FOAMYADE_NO_PAIRS"); v = (e != nullptr && *e != 0 && strcmp(e, "0") != 0) ? 1 : 0; g_no_pairs.store(v, std::memory_order_relaxed); }
-    return v != 0;
+// bit 0 no_pairs, bit 1 no_tail_cache, bit 2 locate_wide; -1: options() has not run yet
+static std::atomic<int> g_kernel_flags{-1};
+static bool kernel_flag(int bit) {
+    if (g_kernel_flags.load(std::memory_order_relaxed) < 0) (void)options();
+    return (g_kernel_flags.load(std::memory_order_relaxed) >> bit) & 1;
 }
+bool pairs_disabled() { return kernel_flag(0); }
+bool tail_cache_disabled() { return kernel_flag(1); }
+bool locate_wide_forced() { return kernel_flag(2); }
 
 Options options() {
     auto on = [](const char* nm) { const char* e = getenv(nm); return e != nullptr && *e != 0 && strcmp(e, "0") != 0; };
+    auto num = [](const char* nm, long long unset) { const char* e = getenv(nm); return e ? atoll(e) : unset; };
     Options q{};
+    if (const char* d = getenv("FOAMYADE_TREE_CACHE_DIR")) q.tree_cache_dir = d;
+    q.rebin_interval = std::max(1, (int)num("FOAMYADE_REBIN_INTERVAL", 32));
+    q.strip_blocks = (int)num("FOAMYADE_STRIP_BLOCKS", -1);
+    q.halo_overlap = getenv("FOAMYADE_HALO_OVERLAP") == nullptr || on("FOAMYADE_HALO_OVERLAP");
+    q.ipc_slot_mb = (int)num("FOAMYADE_IPC_SLOT_MB", 0);
+    q.ipc_timeout_ms = num("FOAMYADE_IPC_TIMEOUT_MS", 0);
+    q.wire_trace = getenv("FOAMYADE_WIRE_TRACE") != nullptr;
     q.explicit_tree = on("FOAMYADE_EXPLICIT_TREE");
     q.no_locate_lists = on("FOAMYADE_NO_LOCATE_LISTS");
-    if (const char* d = getenv("FOAMYADE_TREE_CACHE_DIR")) q.tree_cache_dir = d;
-    q.rebin_interval = 32;
-    if (const char* e = getenv("FOAMYADE_REBIN_INTERVAL")) q.rebin_interval = std::max(1, atoi(e));
-    q.no_halo_overlap = on("FOAMYADE_NO_HALO_OVERLAP");
-    q.no_aux_comm = on("FOAMYADE_NO_AUX_COMM");
-    q.halo_overlap = true;
-    if (const char* e = getenv("FOAMYADE_HALO_OVERLAP")) q.halo_overlap = !(*e == 0 || strcmp(e, "0") == 0);
+    q.locate_stack = (int)num("FOAMYADE_LOCATE_STACK", -1);
+    q.locate_wide = num("FOAMYADE_LOCATE_WIDE", 0) != 0;
     q.no_deep_vcycle = on("FOAMYADE_NO_DEEP_VCYCLE");
+    const char* ls = getenv("FOAMYADE_LOCALCOMM_STREAM");
+    q.localcomm_stream = ls != nullptr && ls[0] == '1';
     q.no_fused_corrector = on("FOAMYADE_NO_FUSED_CORRECTOR");
     q.faces_from_arrays = on("FOAMYADE_FACES_FROM_ARRAYS");
     q.no_pairs = on("FOAMYADE_NO_PAIRS");
-    g_no_pairs.store(q.no_pairs ? 1 : 0, std::memory_order_relaxed);
-    q.strip_blocks = -1;
-    if (const char* e = getenv("FOAMYADE_STRIP_BLOCKS")) q.strip_blocks = atoi(e);
+    q.no_tail_cache = on("FOAMYADE_NO_TAIL_CACHE");
+    q.ipc_slot_kb = (int)num("FOAMYADE_IPC_SLOT_KB", 0);
+    g_kernel_flags.store((q.no_pairs ? 1 : 0) | (q.no_tail_cache ? 2 : 0) | (q.locate_wide ? 4 : 0), std::memory_order_relaxed);
     return q;
 }
 
@@ -78,6 +86,7 @@ int Coupling::create(const fy_mesh_desc* m, const fy_field_ptrs* f, int gaussian
         return fail(FY_ERR_NO_DEVICE, "no HIP device visible: libfoamyade_hip has no CPU path");
     if (device_ordinal < 0 || device_ordinal >= ndev) return fail(FY_ERR_INVALID, "device ordinal %d out of range (%d devices)", device_ordinal, ndev);
     device = device_ordinal;
+    opt = options();
     FY_HIP(hipSetDevice(device));
     if (ext_stream) { stream = ext_stream; owns_stream = false; }
     else { FY_HIP(hipStreamCreate(&stream)); owns_stream = true; }
@@ -108,7 +117,7 @@ int Coupling::create(const fy_mesh_desc* m, const fy_field_ptrs* f, int gaussian
     {
         // implicit-coordinate nodes: legal only if EVERY centre equals origin + (i + 0.5) * dx bit for bit (checked here, so a
         // real OpenFOAM mesh whose centres come from pyramid decomposition simply keeps the explicit path)
-        bool exact = structured && !rectilinear && !options().explicit_tree && m->nx <= 1024 && m->ny <= 1024 && m->nz <= 4096 &&
+        bool exact = structured && !rectilinear && !opt.explicit_tree && m->nx <= 1024 && m->ny <= 1024 && m->nz <= 4096 &&
                      n_cells < (1 << 25);
         if (exact)
             for (int k = 0; k < m->nz && exact; ++k) for (int j = 0; j < m->ny && exact; ++j) for (int i = 0; i < m->nx; ++i) {
@@ -121,7 +130,7 @@ int Coupling::create(const fy_mesh_desc* m, const fy_field_ptrs* f, int gaussian
         // FOAMYADE_TREE_CACHE_DIR=/dev/shm ; the first rank to create the lock file builds and publishes, the others wait.
         std::vector<int32_t> pre;      // preorder cell ids
         std::string cache;
-        const std::string cache_dir = options().tree_cache_dir;
+        const std::string& cache_dir = opt.tree_cache_dir;
         if (exact && !cache_dir.empty()) {
             char nm[512];
             snprintf(nm, sizeof(nm), "%s/fy_tree_%dx%dx%d_%016llx.bin", cache_dir.c_str(), m->nx, m->ny, m->nz,
@@ -288,7 +297,7 @@ int Coupling::create(const fy_mesh_desc* m, const fy_field_ptrs* f, int gaussian
     }
     for (auto& t : timers) FY_TRY(t.init());
     FY_TRY(marks.init());
-    rebin_interval = options().rebin_interval;
+    rebin_interval = opt.rebin_interval;
     if (has_transport || fields_on_host) {
         // The two copy streams get priorities of their own: the runtime multiplexes a process's streams onto a handful of hardware queues (4 by default),
         // and two streams that land on one queue wait for each other's packets -- round 5's trace of the drop-in leg: the last records' H2D copies sat behind
@@ -335,7 +344,7 @@ int Coupling::ensure_locate_tables(double maxdist) {
         FY_TRY(launch_build_locate_start(stream, d_tree_packed.p, implicit, n_cells, maxdist, d_loc_start.p));
     }
     // candidate lists: 384 B per cell; valid while the rounding of a coordinate stays far below the builder's margins
-    if (!options().no_locate_lists && !loc_lists_tried) {
+    if (!opt.no_locate_lists && !loc_lists_tried) {
         loc_lists_tried = true;
         const double ext = std::max({std::fabs(implicit.ox), std::fabs(implicit.oy), std::fabs(implicit.oz), std::fabs(implicit.ox + implicit.nx * implicit.dx),
                                      std::fabs(implicit.oy + implicit.ny * implicit.dx), std::fabs(implicit.oz + implicit.nz * implicit.dx)});
@@ -659,7 +668,6 @@ int Coupling::run_batch(Batch& b) {
             // the stack of this step: the depth that served 99.8 % of the walks sampled in the current window of steps, as last copied back (the first step runs the full
             // depth and measures); the others overflow into the second launch.  The histogram starts anew every 32 steps, so a cloud that moves on is followed; while a
             // window is still short the last window's depth stands; and if more than 1 % of the walks overflowed last step the stack grows by two entries at once
-            static const int forced = [] { const char* e = getenv("FOAMYADE_LOCATE_STACK"); return e ? atoi(e) : -1; }();      // (experiments: 0 = always the full depth)
             unsigned long long total = 0, run = 0;
             unsigned int hist[kLocDepthBins];
             for (int q = 0; q < kLocDepthBins; ++q) { hist[q] = ((volatile unsigned int*)h_loc_hwm.p)[q]; total += hist[q]; }
@@ -673,7 +681,7 @@ int Coupling::run_batch(Batch& b) {
             loc_last_n = b.n;
             const int seen = loc_stack_cap > 0 ? std::max(loc_stack_cap, loc_stack_floor) : 0;
             loc_stack_used = seen;
-            ll = LocateLists{nullptr, d_loc_fb.p, d_loc_fb_n.p, 0, 0, forced >= 0 ? forced : seen, d_loc_hwm.p};
+            ll = LocateLists{nullptr, d_loc_fb.p, d_loc_fb_n.p, 0, 0, opt.locate_stack >= 0 ? opt.locate_stack : seen, d_loc_hwm.p};      // (FOAMYADE_LOCATE_STACK: a forced depth, tests)
         }
         const CellWindow cw{slab.active ? slab.base : 0, n_field};
         // the scatters' tables are flushed into per-tile buckets sized from the demand they counted in this batch's last step
@@ -711,25 +719,17 @@ int Coupling::run_batch(Batch& b) {
         // schedule, in the same order per cell: the same bits.
         const bool ovl = slab_overlap() && slab.nz > 2 * slab.gz;
         auto pack_records = [&]() -> int {
-            if (cellrec_fresh && !cellrec_ghosts_stale) return FY_OK;
+            if (cellrec_fresh) return FY_OK;
             if (slab.fields_event) { FY_HIP(hipStreamWaitEvent(stream, slab.fields_event, 0)); slab.fields_event = nullptr; }      // gradP / divT ghost planes have landed
-            if (cellrec_fresh) {
-                // a slab whose solver's pre-coupling sweep wrote the records of the OWNED cells (fy_solver, as on a single domain): what is left are the
-                // ghost planes either side, whose gradP / divT came from the neighbours -- 2 gz planes instead of nz + 2 gz
-                const size_t gc = (size_t)slab.gz * slab.plane, hi = (size_t)(slab.gz + slab.nz) * slab.plane;
-                FY_TRY(launch_pack_cells(stream, (int64_t)gc, dU, dAlpha, dGradP, dDivT, d_vol.p, nu, rhoF, d_cellrec.p));
-                FY_TRY(launch_pack_cells(stream, (int64_t)gc, dU + 3 * hi, dAlpha + hi, dGradP + 3 * hi, dDivT + 3 * hi, d_vol.p + hi, nu, rhoF, d_cellrec.p + 8 * hi));
-            } else {
-                FY_TRY(launch_pack_cells(stream, n_field, dU, dAlpha, dGradP, dDivT, d_vol.p, nu, rhoF, d_cellrec.p));
-            }
-            cellrec_fresh = true; cellrec_ghosts_stale = false;
+            FY_TRY(launch_pack_cells(stream, n_field, dU, dAlpha, dGradP, dDivT, d_vol.p, nu, rhoF, d_cellrec.p));
+            cellrec_fresh = true;
             return FY_OK;
         };
         // z-slabs: the 8-plane tile layers that lie wholly inside the planes no reverse halo reaches ([2 gz, nz) in storage planes) are finished by the
         // reduction itself (k_tile_reduce<3> / <4>); k_finalize_cells / k_fold_sources keep the planes outside [z0, z1)
         int tk_lo = 0, tk_hi = 0;
         if (slab.active && tbD.cell) { tk_lo = (2 * slab.gz + 7) / 8; tk_hi = slab.nz / 8; if (tk_hi <= tk_lo) tk_lo = tk_hi = 0; }
-        const bool layers = tk_hi > tk_lo && getenv("FOAMYADE_NO_TILE_LAYERS") == nullptr;
+        const bool layers = tk_hi > tk_lo;
         const int64_t z0 = 8 * (int64_t)tk_lo * (int64_t)slab.plane, z1 = 8 * (int64_t)tk_hi * (int64_t)slab.plane;
         if (!ovl) FY_TRY(pack_records());
         if (side.stream && ll.lists) FY_HIP(hipStreamWaitEvent(stream, side.join, 0));
@@ -834,8 +834,7 @@ int Coupling::run_batch(Batch& b) {
         if (timing) marks.mark(5, stream);
         // the NEXT call's bucket capacities (one workgroup's scan of the demand this call counted: 20 us that used to open the next particle phase) on the side
         // stream now, beside whatever the caller does next; a batch whose arrays are renewed in between forms them again (caps_key)
-        static const bool early_caps = getenv("FOAMYADE_NO_EARLY_CAPS") == nullptr;      // (A/B switch)
-        if (early_caps && side.stream && tbD.cell) {
+        if (side.stream && tbD.cell) {
             if (!b.ev_caps) FY_HIP(hipEventCreateWithFlags(&b.ev_caps, hipEventDisableTiming));
             FY_HIP(hipEventRecord(side.fork, stream));
             FY_HIP(hipStreamWaitEvent(side.stream, side.fork, 0));
@@ -882,7 +881,6 @@ int Coupling::set_particle_action(double dt) {
     mid_hook_done = false;
     if (!gaussian || n_batches == 0 || fields_on_host) FY_TRY(run_mid_hook());      // (nobody further down would, or the sweep's output is needed at once)
     cellrec_fresh = cellrec_external;       // (fy_solver's pre-coupling sweep may have written the records already)
-    cellrec_ghosts_stale = cellrec_external && slab.active;      // (... of the owned cells: a slab's ghost planes are packed here, when the neighbours' fields have landed)
     cellrec_external = false;
 
     // ---- receive particles, and per Yade proc: locate + deposit + finalize + force (FoamYade.C:609, 612-628).  With a transport every
@@ -949,7 +947,7 @@ int Coupling::collect_timings() {
     if (copy_stream) {
         FY_HIP(hipStreamSynchronize(copy_stream));
         FY_HIP(hipStreamSynchronize(copy_out_stream));
-        if (getenv("FOAMYADE_WIRE_TRACE") && !piece_clocks.empty() && piece_clocks[0].armed) {
+        if (opt.wire_trace && !piece_clocks.empty() && piece_clocks[0].armed) {
             // development trace: where the pieces' H2D copies and the batches' D2H copies sat on the device's clock, relative to the first piece's copy
             hipEvent_t z = piece_clocks[0].a;
             std::string line = "[wire] H2D pieces (start+dur ms):";
@@ -1083,7 +1081,7 @@ int Coupling::recv_yade_pieces(const std::vector<std::pair<int, int> >& in_comm)
     };
     size_t outstanding = 0;
     for (size_t q = 0; q < nb; ++q) outstanding += (size_t)left[q];
-    static const bool trace = getenv("FOAMYADE_WIRE_TRACE") != nullptr;
+    const bool trace = opt.wire_trace;
     const WallClock wall;
     double t_wait = 0, t_copy = 0, t_run = 0, first_piece = -1, last_piece = 0;
     while (outstanding > 0) {
@@ -1201,20 +1199,10 @@ int Coupling::start_results_copy(Batch& b) {
     }
     b.t_out.start(copy_out_stream);
     if (b.n) {
-        // FOAMYADE_D2H_STORES=1: into the transport's page-locked arena the answers go by kernel stores (launch_copy_out) instead of DMA copies, so that
-        // the copy engine carries the incoming records only.  Measured (round 5, drop-in leg): no gain -- 47 GB/s by stores against 55 GB/s by DMA, and what
-        // had delayed the copies was two streams sharing a hardware queue (see the copy streams' priorities), not the engine.  Kept as a switch.
-        static const bool dma = getenv("FOAMYADE_D2H_STORES") == nullptr;
-        void *df = nullptr, *dF = nullptr;
-        const bool by_stores = !dma && wire_views && view_locked && hipHostGetDevicePointer(&df, hf, 0) == hipSuccess && hipHostGetDevicePointer(&dF, hF, 0) == hipSuccess;
-        if (by_stores) {
-            FY_TRY(launch_copy_out(copy_out_stream, df, b.found.p, (size_t)b.n * sizeof(int32_t)));
-            FY_TRY(launch_copy_out(copy_out_stream, dF, b.force.p, 6 * (size_t)b.n * sizeof(double)));
-        } else {
-            (void)hipGetLastError();
-            FY_HIP(hipMemcpyAsync(hf, b.found.p, (size_t)b.n * sizeof(int32_t), hipMemcpyDeviceToHost, copy_out_stream));
-            FY_HIP(hipMemcpyAsync(hF, b.force.p, 6 * (size_t)b.n * sizeof(double), hipMemcpyDeviceToHost, copy_out_stream));
-        }
+        // (kernel stores into the page-locked arena instead of these DMA copies were measured in round 5, drop-in leg: no gain -- 47 GB/s against 55 GB/s;
+        // what had delayed the copies was two streams sharing a hardware queue, see the copy streams' priorities)
+        FY_HIP(hipMemcpyAsync(hf, b.found.p, (size_t)b.n * sizeof(int32_t), hipMemcpyDeviceToHost, copy_out_stream));
+        FY_HIP(hipMemcpyAsync(hF, b.force.p, 6 * (size_t)b.n * sizeof(double), hipMemcpyDeviceToHost, copy_out_stream));
         tm.bytes_out += b.n * (int64_t)(sizeof(int32_t) + 6 * sizeof(double));
     }
     b.t_out.stop(copy_out_stream);

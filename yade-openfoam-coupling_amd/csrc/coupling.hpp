@@ -76,6 +76,7 @@ struct Coupling {
     int64_t n_field = 0;                 // length of the cell arrays (n_cells, or slab.n_store)
     DevBuf<double> halo_tmp;             // 2 x gz x plane x 3 staging for reverse-halo sums
     // ---- configuration
+    Options opt{};                       // the run-time switches, read by create()
     int device = -1;
     hipStream_t stream = nullptr;
     hipStream_t ext_stream = nullptr;    // set before create() to run on a caller-owned stream (fy_solver does)
@@ -141,13 +142,12 @@ struct Coupling {
     DevBuf<double> d_pvol_acc, d_up_acc;           // per-batch deposit accumulators (pVolContrib / uParticleContrib)
     bool cellrec_fresh = false;                    // d_cellrec was packed in this setParticleAction call
     hipEvent_t ev_last_caps = nullptr;            // the latest end-of-batch capacities kernel on the side stream (it also clears d_loc_fb_n); not owned
-    bool cellrec_ghosts_stale = false;             // slab: the caller's sweep wrote the OWNED cells' records only
-    bool cellrec_external = false;                 // ... by the caller (fy_solver's pre-coupling sweep), for the NEXT setParticleAction only
+    bool cellrec_external = false;                 // d_cellrec was written by the caller (fy_solver's pre-coupling sweep), for the NEXT setParticleAction only
     DevBuf<double> d_cellrec;                      // 8 doubles per cell: what the force pass gathers (k_pack_cells), rebuilt every setParticleAction
     DevBuf<double> d_drag_acc;                     // per-batch sum of -coeff w / rho_f per cell, folded into uSourceDrag / uSource by k_fold_sources
     DevBuf<unsigned char> d_touched;
     BinGrid bins{};
-    int rebin_interval = 32;             // full counting sort every this many steps (options().rebin_interval; 1 = every step)
+    int rebin_interval = 32;             // full counting sort every this many steps (opt.rebin_interval; 1 = every step)
     DevBuf<uint32_t> d_hist, d_tile_sums;
     std::vector<Batch*> batches;
     int n_batches = 0;

@@ -14,30 +14,6 @@
 #define FY_FVK_GRADED 0
 #endif
 
-// register caps of the gather-first sweeps (waves per SIMD the compiler must leave room for; 0 = its own choice): build-time constants, measured per kernel
-#ifndef FY_WPE_FRONT
-#define FY_WPE_FRONT 4
-#endif
-#ifndef FY_WPE_BACK
-#define FY_WPE_BACK 0
-#endif
-#ifndef FY_WPE_PRE
-#define FY_WPE_PRE 0
-#endif
-#ifndef FY_WPE_BMOM
-#define FY_WPE_BMOM 0
-#endif
-#define FY_WPE_ATTR_(n) __attribute__((amdgpu_waves_per_eu(n)))
-#define FY_WPE_ATTR(n) FY_WPE_ATTR_IF(n)
-#define FY_WPE_ATTR_IF(n) FY_WPE_PICK_##n
-#define FY_WPE_PICK_0
-#define FY_WPE_PICK_2 FY_WPE_ATTR_(2)
-#define FY_WPE_PICK_3 FY_WPE_ATTR_(3)
-#define FY_WPE_PICK_4 FY_WPE_ATTR_(4)
-#define FY_WPE_PICK_5 FY_WPE_ATTR_(5)
-#define FY_WPE_PICK_6 FY_WPE_ATTR_(6)
-#define FY_WPE_PICK_7 FY_WPE_ATTR_(7)
-#define FY_WPE_PICK_8 FY_WPE_ATTR_(8)
 namespace fy {
 #if FY_FVK_GRADED
 namespace gr {
@@ -592,7 +568,7 @@ __global__ __launch_bounds__(256) void k_courant(FvGeo g, CFace3 phi, double* __
 // In pimple mode the only consumer of grad(U) is the explicit stress term of divDevRhoReff (the Gaussian torque that would read vGrad
 // is disabled in the reference, FoamYade.C:618), so the kernel can emit G = alpha nu dev2(T(grad U)) directly (Gout != nullptr) and
 // skip the 72 B/cell vGrad store (write_vgrad = 0): one stencil pass instead of two plus a tensor round trip through HBM.
-__global__ __launch_bounds__(256) FY_WPE_ATTR(FY_WPE_PRE) void k_pre_coupling(FvGeo g, const double* __restrict__ U, const double* __restrict__ p,
+__global__ __launch_bounds__(256) void k_pre_coupling(FvGeo g, const double* __restrict__ U, const double* __restrict__ p,
                                                       const double* __restrict__ alpha, CFace3 psn, double* __restrict__ vGrad,
                                                       double* __restrict__ gradP, double* __restrict__ divT, double* __restrict__ Gout,
                                                       int write_vgrad, int write_pfields, CFace3 phi, double* __restrict__ ddtU, double* __restrict__ Uold_out,
@@ -1204,7 +1180,7 @@ __global__ __launch_bounds__(256) void k_bmom(FvGeo g, const double* __restrict_
 // pimple: rAUcf / phicForces (UcEqn.H:15-20) and the momentum predictor's right-hand side (UcEqn.H:22-33) in one gather-first sweep:
 // k_rAUf_phi_forces_cells + k_bmom without the two face fields being read back; a cell forms its six faces' rAUcf and phicForces itself (same
 // expressions as rAUf_phi_forces_face), the face's owner stores phicForces (and rAUcf where somebody still streams it: rf_out.a[0] != nullptr)
-__global__ __launch_bounds__(256) FY_WPE_ATTR(FY_WPE_BMOM) void k_bmom_faces(FvGeo g, const double* __restrict__ rAU, const double* __restrict__ uSource, const double* __restrict__ src,
+__global__ __launch_bounds__(256) void k_bmom_faces(FvGeo g, const double* __restrict__ rAU, const double* __restrict__ uSource, const double* __restrict__ src,
                                                     const double* __restrict__ p, CFace3 psn, Face3 rf_out, Face3 pf_out, double* __restrict__ bmom) {
     const int t = fv_block(g, blockIdx.x, gridDim.x) * 256 + (int)threadIdx.x;
     if (t >= g.Nc) return;
@@ -1522,7 +1498,7 @@ __device__ __forceinline__ double ub_normal(const FvGeo& g, int patch, int d, do
 // flux correction + velocity correction [+ continuity errors + the next pass's Courant sums] in one sweep (icoFoamYade.C:127-137, pEqn.H:39-45,
 // continuityErrs.H, CourantNo.H): k_flux_correct_cells and k_U_correct<DIAG> without the face field between them
 template <bool DIAG, bool FFC>
-__global__ __launch_bounds__(256) FY_WPE_ATTR(FY_WPE_BACK) void k_corr_back(FvGeo g, const double* __restrict__ p, CFace3 phiHbyA, FaceSrc rAUf, FaceSrc alphaf, CFace3 psn,
+__global__ __launch_bounds__(256) void k_corr_back(FvGeo g, const double* __restrict__ p, CFace3 phiHbyA, FaceSrc rAUf, FaceSrc alphaf, CFace3 psn,
                                                    CFace3 phiForces, Face3 phi, const double* __restrict__ HbyA, const double* __restrict__ rAU,
                                                    double* __restrict__ U, const double* __restrict__ alpha, const double* __restrict__ alphaOld,
                                                    double* __restrict__ partials) {
@@ -1631,9 +1607,10 @@ __global__ __launch_bounds__(256) FY_WPE_ATTR(FY_WPE_BACK) void k_corr_back(FvGe
 // coefficient is 0 there, skipped here) and the block partition of k_p_init, so r0 and the two sums are k_p_init's bits.
 // dcorr: the old-time part of the ddtCorr term per face, left by k_pre_coupling at the start of the step (coef / deltaT (phi.old - flux(U.old)));
 // the term itself is rAUf dcorr [alphacf], the same product in every corrector.  STORE_A = false: a later corrector of the same momentum
-// assembly -- the matrix in A stands (same rAU, same alphacf)
+// assembly -- the matrix in A stands (same rAU, same alphacf).  Register cap: room for 4 waves per SIMD (measured per kernel; the other gather-first
+// sweeps keep the compiler's own choice)
 template <bool STORE_A, bool FFC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FY_WPE_FRONT))) void k_corr_front(FvGeo g, const double* __restrict__ HbyA, const double* __restrict__ U, CFace3 dcorr,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_corr_front(FvGeo g, const double* __restrict__ HbyA, const double* __restrict__ U, CFace3 dcorr,
                                                     FaceSrc rAUf, FaceSrc alphaf, CFace3 phiForces, Face3 phiHbyA, Face3 psn,
                                                     const double* __restrict__ rAU, const double* __restrict__ alpha, const double* __restrict__ alphaOld, PMat A,
                                                     double* __restrict__ rhs, const double* __restrict__ x, const double* __restrict__ xbar_dev, double xsum_val,
@@ -2976,8 +2953,7 @@ int launch_mg_coarse_factor(hipStream_t s, PMat A, double* fac) {
     // positions per thread shorten the round trip, fewer waves the barrier (measured at the 5^3 level, band 25, 325 positions: 1024 threads x 4 positions of the
     // full window 72 us, 256 x 4 of the full window 51; of the triangle: 64 x 6 81, 128 x 3 54, 192 x 2 44, 384 x 1 39 us)
     const int tri = bw * (bw + 1) / 2;
-    static const int force_q = [] { const char* e = getenv("FOAMYADE_FACTOR_Q"); return e ? atoi(e) : 0; }();      // (experiments)
-    const int q = force_q > 0 ? force_q : (tri <= 1024 ? 1 : (tri <= 2048 ? 2 : 3));
+    const int q = tri <= 1024 ? 1 : (tri <= 2048 ? 2 : 3);
     const int nt = std::min(1024, ((tri + q - 1) / q + 63) / 64 * 64);
     if (q == 1) hipLaunchKernelGGL(k_mg_coarse_factor<1>, dim3(1), dim3(nt), fac_lds_bytes(A.N, bw), s, A, bw, fac);
     else if (q == 2) hipLaunchKernelGGL(k_mg_coarse_factor<2>, dim3(1), dim3(nt), fac_lds_bytes(A.N, bw), s, A, bw, fac);
@@ -3005,9 +2981,7 @@ int launch_mg_tail(hipStream_t s, const PMat* A, double* const* x0, double* cons
         lds = fac_lds_bytes(A[n - 1].N, band_width(A[n - 1]));
     }
     T.cache_n = 0; T.cache_off = (int)(lds / sizeof(double));
-    const char* tc = getenv("FOAMYADE_NO_TAIL_CACHE");                                 // (A/B switch, read per launch: tests flip it inside one process)
-    const bool tail_cache = !(tc && *tc && strcmp(tc, "0") != 0);
-    if (tail_cache && n >= 2 && A[0].N <= kMgTailCells) { T.cache_n = A[0].N; lds += 7 * (size_t)A[0].N * sizeof(double); }
+    if (!tail_cache_disabled() && n >= 2 && A[0].N <= kMgTailCells) { T.cache_n = A[0].N; lds += 7 * (size_t)A[0].N * sizeof(double); }
     for (int l = 0; l < n; ++l) {
         if (A[l].c0 != 0) return fail(FY_ERR_INVALID, "multigrid tail levels must not carry ghost planes");
         T.A[l] = A[l]; T.x0[l] = x0[l]; T.x1[l] = x1[l]; T.b[l] = b[l];

@@ -40,10 +40,10 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     FY_HIP(hipEventCreateWithFlags(&ev_usum1, hipEventDisableTiming));
     FY_HIP(hipEventCreateWithFlags(&ev_coarse, hipEventDisableTiming));
     FY_HIP(hipEventCreateWithFlags(&ev_factor, hipEventDisableTiming));
-    overlap_halos = !options().no_halo_overlap && options().halo_overlap;
-    overlap_sweeps = options().halo_overlap;
-    fused_corrector = !options().no_fused_corrector;
-    faces_from_cells = !options().faces_from_arrays;
+    const Options opt = options();
+    overlap_halos = opt.halo_overlap;
+    fused_corrector = !opt.no_fused_corrector;
+    faces_from_cells = !opt.faces_from_arrays;
     comm->set_aux_stream(comm_stream);
     // ---- slab extents: the case describes the GLOBAL block; rank r owns planes [r*nz, (r+1)*nz)
     const int S = comm->size;
@@ -81,7 +81,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     // strip order of the cell sweeps (fv_kernels.hip, fv_block): only where a plane is a whole number of 256-cell blocks and every XCD gets whole planes
     g.strip_B = g.strip_bp = g.strip_nzx = 0;
     {
-        const int want = options().strip_blocks;
+        const int want = opt.strip_blocks;
         if (want != 0 && plane % 256 == 0 && nzl % 8 == 0) {
             const int bp = (int)(plane / 256);
             const int target = want > 0 ? want : std::max(1, (int)std::lround(8.0 * c->nx / 256.0));      // ~8 rows of cells
@@ -265,7 +265,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
         if (S > 1 && cs.p_solver == FY_PSOLVER_PCG_MG && mg_rep >= mg.size()) return fail(FY_ERR_UNSUPPORTED, "multigrid hierarchy never became replicable");
         if (mg.back()->A.N > 1024 && cs.p_solver == FY_PSOLVER_PCG_MG) return fail(FY_ERR_UNSUPPORTED, "coarsest multigrid level too large");
         if (mg_rep < mg.size()) FY_TRY(rep_stage.alloc_exact(4 * ((size_t)mg[mg_rep]->A.N / S + 8)));
-        mg_deep = S > 1 && cs.p_solver == FY_PSOLVER_PCG_MG && mgw.n == 2 && !options().no_deep_vcycle && mg_rep < mg.size();
+        mg_deep = S > 1 && cs.p_solver == FY_PSOLVER_PCG_MG && mgw.n == 2 && !opt.no_deep_vcycle && mg_rep < mg.size();
         for (auto& L : mg) if (L->distributed && (L->gz < kMgDeepGhost || L->A.nz < kMgDeepGhost)) mg_deep = false;
     }
     for (auto& t : tim) FY_TRY(t.init());
@@ -317,7 +317,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
             cpl->c.slab.active = true; cpl->c.slab.comm = comm; cpl->c.slab.gz = gz; cpl->c.slab.nz = nzl; cpl->c.slab.plane = plane;
             cpl->c.slab.n_store = nstore; cpl->c.slab.base = ((int64_t)g.kglob0 - gz) * (int64_t)plane;
             cpl->c.slab.kglob0 = g.kglob0; cpl->c.slab.nzglob = g.nzglob;
-            if (overlap_halos && overlap_sweeps) cpl->c.slab.aux = comm_stream;       // the particle phase's exchanges beside independent work (coupling.cpp)
+            if (overlap_halos) cpl->c.slab.aux = comm_stream;       // the particle phase's exchanges beside independent work (coupling.cpp)
         }
         FY_TRY(cpl->c.create(&md, &fp, pimple ? 1 : 0, tr, device));      // gaussianInterp: false for ico, true for pimple (icoFoamYade.C:53, pimpleFoamYade.C:53)
         cpl->c.rhoP = c->rho_particle; cpl->c.rhoF = c->rho_fluid; cpl->c.nu = c->nu;   // setScalarProperties (icoFoamYade.C:55)
@@ -641,17 +641,16 @@ int Solver::step() {
     const bool want_vgrad = !pimple || (fm & FY_FORCE_GAUSSIAN_TORQUE), want_ddtU = pimple && (fm & FY_FORCE_ADDED_MASS);
     // single domain, Gaussian mode: the sweep also leaves the force pass's packed cell records (the coupling then skips its own pack pass)
     // (a slab keeps the coupling's own pack pass: measured in round 6, the records written from this sweep cost a slab 0.17 ms per step -- the sweep is not hidden
-    //  beside the walk there -- against 0.12 for the pass; the coupling can take owned-cell records from here all the same: Coupling::cellrec_ghosts_stale)
+    //  beside the walk there -- against 0.12 for the pass)
     double* rec_out = (pimple && comm->size == 1) ? cpl->c.d_cellrec.p : nullptr;
     // On a single domain in Gaussian mode the sweep is handed to the coupling as a hook and launched right after the locate + deposit (which
     // read no fluid field): it then runs beside the side stream's tree walk of the few particles the candidate lists hand over -- ~90 us of
     // memory latency that would otherwise sit alone between the locate and the cells' finalisation (Coupling::mid_hook)
     const bool defer_sweep = comm->size == 1 && cpl->c.gaussian;
-    // U.oldTime() of the owned cells is written by the pre-coupling sweep that reads U anyway
-    const bool fuse_uold = true;
+    // (U.oldTime() of the owned cells is written by the pre-coupling sweep that reads U anyway)
     auto sweep_on = [&](const FvGeo& gw) -> int {
         return FVK(launch_pre_coupling, stream, gw, U.p, p.p, alpha.p, C3(psn), vGrad.p, gradP.p, divT.p, nullptr, want_vgrad ? 1 : 0, 1, phi_now(),
-                   want_ddtU ? ddtU.p : nullptr, fuse_uold ? Uold.p : nullptr, rec_out, cpl->c.nu, cpl->c.rhoF,
+                   want_ddtU ? ddtU.p : nullptr, Uold.p, rec_out, cpl->c.nu, cpl->c.rhoF,
                    (fused_corrector && !adjust_phi) ? F3(dcorr) : Face3{});
     };
     std::function<int()> pre_sweep = [&]() -> int { return sweep_on(g); };

@@ -99,7 +99,7 @@ struct Solver {
     DevBuf<int> adj_err;
     DevBuf<double> partials, red_out, sc, xbar3;
     bool hold_sources = false, sources_pending = false;
-    bool overlap_halos = true;            // FOAMYADE_NO_HALO_OVERLAP=1: serial schedule (A/B switch, same results)
+    bool overlap_halos = true;            // FOAMYADE_HALO_OVERLAP=0: every exchange, then its consumer (serial schedule, same results); see can_window
     double* red_host = nullptr;           // mapped pinned host memory (+ its device alias): reduce_read's landing zone (8 doubles) + deferred slots
     double* red_host_dev = nullptr;
     unsigned long long* red_flag = nullptr;      // 8 arrival flags (mapped pinned) the host spins on, and their device alias
@@ -161,8 +161,7 @@ struct Solver {
     // communicator's second channel), the two end planes follow when it has landed.  A plane window is a window of 256-cell BLOCKS (FvGeo::win_*): the
     // cells, their order inside a block and the slot a reducing kernel's partial sum goes to are those of the one-launch sweep, so fields and folds are
     // the serial schedule's bit for bit.  Needs planes that are whole numbers of blocks; otherwise (and with FOAMYADE_HALO_OVERLAP=0) exchange, then sweep.
-    bool overlap_sweeps = true;
-    bool can_window() const { return comm->size > 1 && overlap_halos && overlap_sweeps && plane % 256 == 0 && g.nz >= 3; }
+    bool can_window() const { return comm->size > 1 && overlap_halos && plane % 256 == 0 && g.nz >= 3; }
     FvGeo window(int ka, int kb) const {
         FvGeo w = g;
         const int bp = (int)(plane / 256);

@@ -382,8 +382,7 @@ struct LduSolver {
     int step_pimple() {
         // The pre-coupling sweeps (1.3 ms at 4.1 M cells, bandwidth bound) on a side stream, beside the coupling's tree walk and deposit (4.3 + 1.2 ms, latency bound,
         // no fluid field read): the coupling waits for them where it first gathers a fluid field (Coupling::run_batch, pack_records: fields_event), as on z-slabs
-        static const bool pre_beside = getenv("FOAMYADE_LDU_PRE_SERIAL") == nullptr;      // (A/B switch)
-        const bool beside = pre_beside && cpl->c.gaussian;
+        const bool beside = cpl->c.gaussian;
         if (beside && !side) {
             FY_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
             FY_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); FY_HIP(hipEventCreateWithFlags(&ev_fields, hipEventDisableTiming));

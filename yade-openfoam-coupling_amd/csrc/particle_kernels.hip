@@ -205,9 +205,6 @@ __device__ __forceinline__ bool own_planes(const SlabOwn& own, int wire_index, i
     return ka >= a0 && ka < a1;
 }
 
-#ifndef FY_NODE_LOAD2
-#define FY_NODE_LOAD2 1
-#endif
 template <bool IMPLICIT>
 __device__ __forceinline__ NodeVal fetch_node(const KdNode* __restrict__ tree, const uint32_t* __restrict__ packed, const ImplicitGeom& ig, uint32_t o) {
     NodeVal v;
@@ -219,17 +216,12 @@ __device__ __forceinline__ NodeVal fetch_node(const KdNode* __restrict__ tree, c
         v.z = ig.oz + ((double)k + 0.5) * ig.dx;
         v.id = i + ig.nx * (j + ig.ny * k);
     } else {
-#if FY_NODE_LOAD2
         // the 32-byte node as two 16-byte loads: the compiler's own split of the struct copy is 16 + 8 + 4, three passes of the address unit over one line -- the explicit walk of
         // 10 M particles through 4.1 M nodes 4.45 -> 3.80 ms.  (One line access per visit -- neighbouring lanes fetching both their nodes together, a half each, and swapping
         // halves by DPP -- was built too: same chains, 7 % SLOWER.  Past two accesses the walk is bound by the latency of its slowest lane's fetch, not by the address unit.)
         const uint4* q = reinterpret_cast<const uint4*>(tree + o);
         const uint4 lo = q[0], hi = q[1];
         v.x = __hiloint2double((int)lo.y, (int)lo.x); v.y = __hiloint2double((int)lo.w, (int)lo.z); v.z = __hiloint2double((int)hi.y, (int)hi.x); v.id = (int32_t)hi.z;
-#else
-        const KdNode nd = tree[o];
-        v.x = nd.x; v.y = nd.y; v.z = nd.z; v.id = nd.id;
-#endif
     }
     return v;
 }
@@ -688,11 +680,6 @@ __device__ __forceinline__ void lds_add_f64(double* p, double v) { unsafeAtomicA
 // 16 random slots of a lane group on 16 bank pairs (~3 deep), same-cell adds (an atomic cannot broadcast) and the 4-byte CAS probes.
 template <int NSLOTS> __device__ __forceinline__ int agg_at(int h, int j) { return j * NSLOTS + h; }
 
-// ---- quad-lane exchange without the LDS: v_mov_b32 under a DPP quad_perm control -- every lane reads lane J of its own quad.  All four lanes of the
-// quad must be active at the call (a disabled source lane reads as zero).
-#ifndef FY_FORCE_QUAD
-#define FY_FORCE_QUAD 0
-#endif
 // register budgets of the two hot kernels (build-time constants; tools/build_variant.sh overrides them for A/B runs)
 //   k_force_gaussian: room for 6 waves per SIMD = 80 VGPRs (the compiler's own choice is 82: five waves, i.e. TWO 512-thread workgroups per CU; with 80 a third one
 //   fits: 1.05 -> 0.93 ms at C3, no spills; 8 waves = 64 VGPRs spills 68 bytes per lane and is slower again)
@@ -704,17 +691,9 @@ template <int NSLOTS> __device__ __forceinline__ int agg_at(int h, int j) { retu
 #ifndef FY_LD_ATTR
 #define FY_LD_ATTR __attribute__((amdgpu_waves_per_eu(8)))
 #endif
-#ifndef FY_LD_QUAD
-#define FY_LD_QUAD 1
-#endif
-#ifndef FY_LD_QUADROW
-#define FY_LD_QUADROW 1
-#endif
+// ---- quad-lane exchange without the LDS: v_mov_b32 under a DPP quad_perm control -- every lane reads lane J of its own quad.  All four lanes of the
+// quad must be active at the call (a disabled source lane reads as zero).
 template <int J> __device__ __forceinline__ int quad_bcast(int v) { return __builtin_amdgcn_mov_dpp(v, J * 0x55, 0xf, 0xf, true); }
-template <int J> __device__ __forceinline__ double quad_bcast(double v) {
-    return __hiloint2double(quad_bcast<J>(__double2hiint(v)), quad_bcast<J>(__double2loint(v)));
-}
-template <int J> __device__ __forceinline__ double2 quad_bcast2(double2 v) { return make_double2(quad_bcast<J>(v.x), quad_bcast<J>(v.y)); }
 // 4 x 4 transpose inside every quad, one dword per (lane, register): on entry register r of lane q holds M[q][r], on return register w of lane j
 // holds M[w][j].  Two butterfly stages (lane ^ 1 on the register pairs (0,1), (2,3); lane ^ 2 on (0,2), (1,3)), each a select of what to send, one DPP
 // move and two selects of what to keep: 16 VALU operations per dword against 28 for "broadcast each source lane, pick mine".
@@ -731,12 +710,6 @@ __device__ __forceinline__ void quad_transpose(uint4& m0, uint4& m1, uint4& m2, 
     quad_transpose(m0.x, m1.x, m2.x, m3.x, b0, b1); quad_transpose(m0.y, m1.y, m2.y, m3.y, b0, b1);
     quad_transpose(m0.z, m1.z, m2.z, m3.z, b0, b1); quad_transpose(m0.w, m1.w, m2.w, m3.w, b0, b1);
 }
-#if FY_FORCE_QUAD
-__device__ __forceinline__ double2 quad_pick(double2 v0, double2 v1, double2 v2, double2 v3, int lq) {
-    const double2 lo = lq & 1 ? v1 : v0, hi = lq & 1 ? v3 : v2;
-    return lq & 2 ? hi : lo;
-}
-#endif
 __device__ __forceinline__ double2 as_double2(uint4 v) {
     return make_double2(__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z));
 }
@@ -987,9 +960,6 @@ __device__ __forceinline__ void deposit_pair(uint32_t* keys, double* vals, int32
 #ifndef FY_DEP_ATTR
 #define FY_DEP_ATTR
 #endif
-#ifndef FY_DEP_REEXP
-#define FY_DEP_REEXP 1      // the deposit loop forms exp(-d2 ...) a second time instead of reading back a stored unnormalised weight: one store per pair less (1.12 -> 1.06 ms)
-#endif
 __global__ __launch_bounds__(kDepThreads) FY_DEP_ATTR void k_deposit(ParticleSoA p, int64_t n, GaussParams gp, CellWindow cw, double* __restrict__ pvol_acc,
                                                           double* __restrict__ up_acc, unsigned char* __restrict__ touched,
                                                           const int32_t* __restrict__ work, const unsigned int* __restrict__ work_n, TileBuckets tb) {
@@ -1019,10 +989,7 @@ __global__ __launch_bounds__(kDepThreads) FY_DEP_ATTR void k_deposit(ParticleSoA
             for (int t = 0; t < kMaxK; ++t) {
                 if (t < k) {
                     const size_t slot = (size_t)((chain - 1 - t) & (kMaxK - 1)) * p.cap + (size_t)i;
-                    const double wt = exp(-p.w[slot] * (1.0 / gp.two_sigma2)) * gp.range_cu * gp.sigma_pi;      // (the expressions of k_locate_deposit's list path, so that
-#if !FY_DEP_REEXP
-                    p.w[slot] = wt;                                                                             //  a particle's weights do not depend on which path placed it)
-#endif
+                    const double wt = exp(-p.w[slot] * (1.0 / gp.two_sigma2)) * gp.range_cu * gp.sigma_pi;      // (k_locate_deposit's list path's expressions: a particle's weights do not depend on which path placed it)
                     allwt += wt;
                 }
             }
@@ -1032,11 +999,7 @@ __global__ __launch_bounds__(kDepThreads) FY_DEP_ATTR void k_deposit(ParticleSoA
             int32_t id_next = p.ids[slot];
 #pragma unroll 1
             for (int t = 0; t < k; ++t) {
-#if FY_DEP_REEXP
                 const double weight = (exp(-w_next * (1.0 / gp.two_sigma2)) * gp.range_cu * gp.sigma_pi) * rallwt_;
-#else
-                const double weight = w_next * rallwt_;                       // FoamYade.C:312-314
-#endif
                 const int64_t cl = (int64_t)id_next - cw.base;                // storage index (slab window)
                 p.w[slot] = weight;
                 if (t + 1 < k) {
@@ -1079,7 +1042,6 @@ __global__ __launch_bounds__(kDepThreads) FY_LD_ATTR void k_locate_deposit(Locat
     const int64_t i = (int64_t)blockIdx.x * kDepThreads + threadIdx.x;
     // an 80-byte record of a 16-byte aligned array is five aligned 16-byte words, of which this kernel wants words 0, 1, 2 and 4
     const bool rec16 = rec && (reinterpret_cast<uintptr_t>(rec) & 15) == 0;      // (uniform)
-#if FY_LD_QUAD
     // the four lanes of a quad fetch one record per instruction (lane q: word q, lane 3: word 4) -- a wave instruction looks up 16 record
     // starts instead of 64 -- and the words go home to the record's lane by DPP quad_perm moves (same values, no arithmetic involved)
     double2 qa = make_double2(0, 0), qb = qa, qc = qa, qe = qa;
@@ -1092,7 +1054,6 @@ __global__ __launch_bounds__(kDepThreads) FY_LD_ATTR void k_locate_deposit(Locat
         quad_transpose(g0, g1, g2, g3, lq);              // -> register w: word w (lane 3's: word 4) of MY record
         qa = as_double2(g0); qb = as_double2(g1); qc = as_double2(g2); qe = as_double2(g3);
     }
-#endif
     // Straight-line (predicated) down to the list row, so that the four lanes of a quad are still together when the rows are fetched
     const bool live = i < n;
     double qx = 0, qy = 0, qz = 0, pvx = 0, pvy = 0, pvz = 0, prad = 0;
@@ -1100,12 +1061,7 @@ __global__ __launch_bounds__(kDepThreads) FY_LD_ATTR void k_locate_deposit(Locat
         if (rec) {
             const double* r = rec + 10 * (size_t)p.orig[i];
             if (rec16) {
-#if FY_LD_QUAD
                 const double2 a = qa, b = qb, cc = qc, e = qe;
-#else
-                const double2* r2 = reinterpret_cast<const double2*>(r);
-                const double2 a = r2[0], b = r2[1], cc = r2[2], e = r2[4];
-#endif
                 qx = a.x; qy = a.y; qz = b.x; pvx = b.y; pvy = cc.x; pvz = cc.y; prad = e.y;
             } else {
                 qx = r[0]; qy = r[1]; qz = r[2]; pvx = r[3]; pvy = r[4]; pvz = r[5]; prad = r[9];
@@ -1151,7 +1107,6 @@ __global__ __launch_bounds__(kDepThreads) FY_LD_ATTR void k_locate_deposit(Locat
         // the wave a dependent memory round trip (round 5); what lies behind a list's end mark is never looked at
         const uint4* __restrict__ L4 = reinterpret_cast<const uint4*>(lists);
         static_assert(kListLen * sizeof(unsigned short) == 3 * sizeof(uint4), "a list row is three 16-byte words");
-#if FY_LD_QUADROW
         // quad-cooperative as the record fetch above: round j, lanes 0..2 fetch their word of quad lane j's row (48 contiguous bytes per quad and
         // instruction instead of 16 bytes from each of four rows), lane 3 fetches nothing; then the 4 x 4 transpose
         const int lq = (int)(threadIdx.x & 3u);
@@ -1159,10 +1114,6 @@ __global__ __launch_bounds__(kDepThreads) FY_LD_ATTR void k_locate_deposit(Locat
         const int32_t w0 = quad_bcast<0>(rowi), w1 = quad_bcast<1>(rowi), w2 = quad_bcast<2>(rowi), w3 = quad_bcast<3>(rowi);
         if (lq < 3) { c0 = L4[3 * (size_t)w0 + lq]; c1 = L4[3 * (size_t)w1 + lq]; c2 = L4[3 * (size_t)w2 + lq]; c3 = L4[3 * (size_t)w3 + lq]; }
         quad_transpose(c0, c1, c2, c3, lq);              // -> c0, c1, c2: the three words of MY row (c3: lane 3's, nothing)
-#else
-        uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0, c2 = c0;
-        if (ok) { c0 = L4[3 * (size_t)rowi]; c1 = L4[3 * (size_t)rowi + 1]; c2 = L4[3 * (size_t)rowi + 2]; }
-#endif
         if (ok) {
             v[0] = c0;
             ok = (c0.x & 0xffffu) != kListOverflow;
@@ -1369,18 +1320,6 @@ __device__ __forceinline__ ParticleForce force_law(const ForceParams& fp, const 
     return r;
 }
 
-#if FY_FORCE_QUAD
-// round J of a quad's cooperative gather, in two halves so that the four rounds' loads are all in flight before the first is consumed:
-// the load of chunk lq of the 64-byte record of cell cj (quad lane J's; < 0: none -- record 0 is fetched and dropped) ...
-__device__ __forceinline__ double2 quad_fetch(const double2* __restrict__ R2, int32_t cj, int lq) {
-    return R2[(size_t)(cj > 0 ? cj : 0) * (kRecDoubles / 2) + (size_t)lq];
-}
-// ... and, times lane J's weight, onto the running pair of sums this lane keeps for lane J's particle (FoamYade.C:361-365, 421-424: product
-// first, then the addition, as interp_add)
-__device__ __forceinline__ void quad_accumulate(double2& acc, double2 r, int32_t cj, double wj) {
-    if (cj >= 0) { acc.x += (r.x * wj); acc.y += (r.y * wj); }
-}
-#else
 __device__ __forceinline__ void interp_add(Interp& s, const double* __restrict__ R, int64_t cl, double w, double volp) {
     const double2* r = reinterpret_cast<const double2*>(R + kRecDoubles * (size_t)cl);
     const double2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
@@ -1389,8 +1328,6 @@ __device__ __forceinline__ void interp_add(Interp& s, const double* __restrict__
     s.pv += (volp * w);
     s.sax += (r2.x * w); s.say += (r2.y * w); s.saz += (r3.x * w);                    // FoamYade.C:421-424 (per-cell combination, k_pack_cells)
 }
-
-#endif
 
 __device__ __forceinline__ void model_add(ModelSums& ms, const ForceParams& fp, const double* __restrict__ vGrad, const double* __restrict__ ddtU, int64_t cl,
                                           double w, double volp) {
@@ -1428,105 +1365,6 @@ __global__ __launch_bounds__(kForceThreads) FY_FORCE_ATTR void k_force_gaussian(
         vals[q] = 0.0; vals[q + kSlots] = 0.0; vals[q + 2 * kSlots] = 0.0; vals[q + 3 * kSlots] = 0.0;
     }
     __syncthreads();
-#if FY_FORCE_QUAD
-    // Quad-cooperative record gathers.  A lane that pulls its own 64-byte cell record issues four 16-byte loads whose 64 lanes touch 64 different
-    // lines each: 256 line look-ups per wave and stencil entry, and the line look-up, not the bytes, is what the L1 charges for (round 5's counters:
-    // 4.6 L1 accesses per pair, texture-data unit 94 % busy at 0.34 lines per clock).  Here the four lanes of a quad fetch ONE record per instruction:
-    // in round j lane q loads 16-byte chunk q of the record quad lane j asks for (id and weight come over by DPP quad_perm moves, no LDS), so a wave
-    // instruction touches 16 lines, contiguous 64 bytes each.  No transpose per pair: lane q keeps, for each of the quad's four particles, the running
-    // sums of ITS chunk (two doubles) -- the same products added in the same order as the owner lane would add them -- and the four particles' sums
-    // go home to their owners once, after the loop.  Identical bits.
-    const int64_t i = (int64_t)blockIdx.x * kForceThreads + threadIdx.x;
-    const bool live = i < n;
-    const size_t ii = live ? (size_t)i : 0;
-    const int chain = live ? p.chain_len[ii] : 0;
-    const int k = chain < kMaxK ? chain : kMaxK;
-    const int first = chain - k;                        // oldest first: see the note on the row order below
-    const int lq = (int)(threadIdx.x & 3u);
-    const int kq = max(max(quad_bcast<0>(k), quad_bcast<1>(k)), max(quad_bcast<2>(k), quad_bcast<3>(k)));
-    const double dia = 2 * p.rad[ii];
-    const double volp = M_PI * cube3(dia) / 6.0;
-    Interp s{0, 0, 0, 0, 0, 0, 0, 0};
-    {
-        const double2* __restrict__ R2 = reinterpret_cast<const double2*>(R);
-        double2 a0 = make_double2(0, 0), a1 = a0, a2 = a0, a3 = a0;
-        size_t slot = (size_t)(first & (kMaxK - 1)) * p.cap + ii;
-        int32_t id_n = 0;
-        double w_n = 0.0;
-        if (k > 0) { id_n = p.ids[slot]; w_n = p.w[slot]; }
-        for (int t = 0; t < kq; ++t) {                   // (quad-uniform trip count: the four lanes stay together for the DPP moves)
-            const int64_t cl = (int64_t)id_n - cw.base;
-            const int32_t c32 = (t < k && cl >= 0 && cl < cw.n_field) ? (int32_t)cl : -1;
-            const double w = w_n;
-            if (t + 1 < k) {                             // the next entry's id and weight travel while this entry's records do
-                slot = (size_t)((first + t + 1) & (kMaxK - 1)) * p.cap + ii;
-                id_n = p.ids[slot]; w_n = p.w[slot];
-            }
-            if (c32 >= 0) s.pv += (volp * w);
-            const int32_t c0 = quad_bcast<0>(c32), c1 = quad_bcast<1>(c32), c2 = quad_bcast<2>(c32), c3 = quad_bcast<3>(c32);
-            const double w0 = quad_bcast<0>(w), w1 = quad_bcast<1>(w), w2 = quad_bcast<2>(w), w3 = quad_bcast<3>(w);
-            const double2 r0 = quad_fetch(R2, c0, lq), r1 = quad_fetch(R2, c1, lq), r2 = quad_fetch(R2, c2, lq), r3 = quad_fetch(R2, c3, lq);
-            quad_accumulate(a0, r0, c0, w0);
-            quad_accumulate(a1, r1, c1, w1);
-            quad_accumulate(a2, r2, c2, w2);
-            quad_accumulate(a3, r3, c3, w3);
-        }
-        // home: owner lane j takes chunk c of its sums from quad lane c (which holds it as its a_j)
-        const double2 o0 = quad_pick(quad_bcast2<0>(a0), quad_bcast2<0>(a1), quad_bcast2<0>(a2), quad_bcast2<0>(a3), lq);
-        const double2 o1 = quad_pick(quad_bcast2<1>(a0), quad_bcast2<1>(a1), quad_bcast2<1>(a2), quad_bcast2<1>(a3), lq);
-        const double2 o2 = quad_pick(quad_bcast2<2>(a0), quad_bcast2<2>(a1), quad_bcast2<2>(a2), quad_bcast2<2>(a3), lq);
-        const double2 o3 = quad_pick(quad_bcast2<3>(a0), quad_bcast2<3>(a1), quad_bcast2<3>(a2), quad_bcast2<3>(a3), lq);
-        s.ufx = o0.x; s.ufy = o0.y; s.ufz = o1.x; s.alpha_f = o1.y; s.sax = o2.x; s.say = o2.y; s.saz = o3.x;
-    }
-    if (live) {
-        ParticleForce pf{0.0, 0.0, 0.0, 0.0};
-        const int32_t orig = p.orig[i];
-        double* F = force_out + 6 * (size_t)orig;
-        if (k == 0) {                                   // zeros for particles nobody located (FoamYade.C:142)
-            F[0] = F[1] = F[2] = 0.0;
-            if (!fp.torque_prezeroed) { F[3] = F[4] = F[5] = 0.0; }
-        } else {
-            ModelSums ms{0, 0, 0, 0, 0, 0, 0};
-            if (fp.models)                              // uniform: off in the shipped reference
-                for (int t = 0; t < k; ++t) {
-                    const size_t slot = (size_t)((first + t) & (kMaxK - 1)) * p.cap + (size_t)i;
-                    const int64_t cl = (int64_t)p.ids[slot] - cw.base;
-                    if (cl < 0 || cl >= cw.n_field) continue;
-                    model_add(ms, fp, vGrad, ddtU, cl, p.w[slot], volp);
-                }
-            pf = force_law(fp, s, ms, k, dia, p.vx[i], p.vy[i], p.vz[i], rec + 10 * (size_t)orig, F);
-            const double irho = 1 / fp.rhoF;
-            // a uniform block's cell volume is a constant, not a gather
-            const double ooUniform = fp.uniform_vol > 0 ? 1. / (fp.uniform_vol * fp.rhoF) : 0.0;
-            size_t slot_b = (size_t)(first & (kMaxK - 1)) * p.cap + (size_t)i;
-            int32_t idb_n = p.ids[slot_b];
-            double wb_n = p.w[slot_b];
-            for (int t = 0; t < k; ++t) {
-                const int64_t cl = (int64_t)idb_n - cw.base;
-                const double w = wb_n;
-                if (t + 1 < k) {                         // (prefetched as in the gather loop)
-                    slot_b = (size_t)((first + t + 1) & (kMaxK - 1)) * p.cap + (size_t)i;
-                    idb_n = p.ids[slot_b]; wb_n = p.w[slot_b];
-                }
-                if (cl < 0 || cl >= cw.n_field) continue;
-                const int32_t c = (int32_t)cl;
-                const double ooCellVol = fp.uniform_vol > 0 ? ooUniform : 1. / (vol[c] * fp.rhoF);  // FoamYade.C:432
-                const double c0 = (-pf.coeff * w) * irho;                                      // FoamYade.C:385 (and, times uParticle[c], :386)
-                const double c1 = (-pf.bx * w) * ooCellVol, c2 = (-pf.by * w) * ooCellVol, c3 = (-pf.bz * w) * ooCellVol;   // FoamYade.C:433, 406-411
-                const int h = agg_slot<kForceLog2>(keys, (uint32_t)c);
-                if (h >= 0) {
-                    lds_add_f64(&vals[agg_at<kSlots>(h, 0)], c0); lds_add_f64(&vals[agg_at<kSlots>(h, 1)], c1);
-                    lds_add_f64(&vals[agg_at<kSlots>(h, 2)], c2); lds_add_f64(&vals[agg_at<kSlots>(h, 3)], c3);
-                } else {
-                    atomic_add_f64(&drag_acc[c], c0);
-                    atomic_add_f64(&uSource[3 * (size_t)c + 0], c1);
-                    atomic_add_f64(&uSource[3 * (size_t)c + 1], c2);
-                    atomic_add_f64(&uSource[3 * (size_t)c + 2], c3);
-                }
-            }
-        }
-    }
-#else
     const int64_t i = (int64_t)blockIdx.x * kForceThreads + threadIdx.x;
     if (i < n) {
         const int chain = p.chain_len[i];
@@ -1607,7 +1445,6 @@ __global__ __launch_bounds__(kForceThreads) FY_FORCE_ATTR void k_force_gaussian(
             }
         }
     }
-#endif
     __syncthreads();
     flush_table<kSlots, kForceThreads>(keys, vals, tmap, tb, drag_acc, uSource, nullptr);
 }
@@ -1845,8 +1682,7 @@ int launch_build_locate_start(hipStream_t s, const uint32_t* packed, ImplicitGeo
 // 300 000 particles on 293 waves took 0.74 ms, 2.5 us per particle against 0.41 at 10 M; particle phase on the explicit tree, same box, 1024 per wave / at most 2048 / 4096 /
 // 8192 / 16384 waves: 300 k 0.92 / 0.42 / 0.43 / 0.41 / 0.41 ms, 1 M 1.69 / 1.25 / 1.24 / 1.17 / 1.26, 2.5 M 2.42 / 2.42 / 2.56 / 2.37 / 2.39
 static unsigned locate_grid(int64_t n) {
-    static const int64_t cap = [] { const char* e = getenv("FOAMYADE_LOCATE_WAVES"); return (int64_t)(e ? atoi(e) : 8192); }();      // (experiments)
-    const int64_t big = div_up(n, kLocPPB), spread = std::min<int64_t>(div_up(n, 64), cap);
+    const int64_t big = div_up(n, kLocPPB), spread = std::min<int64_t>(div_up(n, 64), 8192);
     return (unsigned)std::max<int64_t>(std::max(big, spread), 1);
 }
 int launch_locate(hipStream_t s, const KdNode* tree, const uint32_t* packed, ImplicitGeom ig, int32_t n_cells, int levels,
@@ -1854,8 +1690,7 @@ int launch_locate(hipStream_t s, const KdNode* tree, const uint32_t* packed, Imp
     if (n <= 0) return FY_OK;
     // 8-byte entries need offsets and sizes < 2^25; an explicit tree past that takes the instance with 16-byte entries (an implicit one has no other)
     if (packed && n_cells >= (1 << 25)) return fail(FY_ERR_UNSUPPORTED, "implicit-coordinate tree limited to 2^25 cells");
-    static const bool force_wide = [] { const char* e = getenv("FOAMYADE_LOCATE_WIDE"); return e && atoi(e) != 0; }();      // (tests: the 16-byte entries on a small tree)
-    const bool wide = !packed && (n_cells >= (1 << 25) || force_wide);
+    const bool wide = !packed && (n_cells >= (1 << 25) || locate_wide_forced());      // (FOAMYADE_LOCATE_WIDE: the 16-byte entries on a small tree, tests)
     const size_t esz = wide ? sizeof(uint4) : sizeof(unsigned long long);
     const size_t lds = (size_t)(levels + 1) * kWave * esz;
     const dim3 grid(locate_grid(n));
@@ -2075,34 +1910,6 @@ int launch_point_force(hipStream_t s, const double* rec, int64_t n, BlockGeom g,
     hipLaunchKernelGGL(k_point_force, dim3(div_up(n, 256)), dim3(256), 0, s, rec, n, g, fp, cw, vol, U, vGrad, uSource, force_out, found_out, incell_out, own);
     FY_LAUNCH_CHECK();
     return FY_OK;
-}
-
-// D2H by STORES: the answers (found flags, forces) written into mapped host memory by a kernel instead of a DMA copy.  The copy engine then carries one
-// direction only -- the records still coming in -- and PCIe runs both ways at once (round 5: the H2D and D2H DMA copies of the drop-in leg executed one
-// after the other, 16 + 9.5 ms per step).  16-byte words; a modest grid: the link, not the shader, bounds it
-template <class W>
-__global__ __launch_bounds__(256) void k_copy_out(W* __restrict__ dst, const W* __restrict__ src, size_t nw, unsigned char* __restrict__ dtail,
-                                                  const unsigned char* __restrict__ stail, int ntail) {
-    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < nw; q += (size_t)gridDim.x * 256) dst[q] = src[q];
-    if (blockIdx.x == 0 && (int)threadIdx.x < ntail) dtail[threadIdx.x] = stail[threadIdx.x];
-}
-template <class W>
-static int copy_out_words(hipStream_t s, void* dst, const void* src, size_t bytes) {
-    const size_t nw = bytes / sizeof(W);
-    const int ntail = (int)(bytes - sizeof(W) * nw);
-    const unsigned blocks = (unsigned)std::min<size_t>(256, std::max<size_t>(1, (nw + 255) / 256));
-    hipLaunchKernelGGL(k_copy_out<W>, dim3(blocks), dim3(256), 0, s, static_cast<W*>(dst), static_cast<const W*>(src), nw,
-                       static_cast<unsigned char*>(dst) + sizeof(W) * nw, static_cast<const unsigned char*>(src) + sizeof(W) * nw, ntail);
-    FY_LAUNCH_CHECK();
-    return FY_OK;
-}
-int launch_copy_out(hipStream_t s, void* dst_mapped, const void* src, size_t bytes) {
-    if (!bytes) return FY_OK;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(dst_mapped) | reinterpret_cast<uintptr_t>(src);
-    if (!(al & 15)) return copy_out_words<uint4>(s, dst_mapped, src, bytes);
-    if (!(al & 7)) return copy_out_words<uint2>(s, dst_mapped, src, bytes);
-    if (!(al & 3)) return copy_out_words<uint32_t>(s, dst_mapped, src, bytes);
-    return fail(FY_ERR_INVALID, "launch_copy_out: buffers must be 4-byte aligned");
 }
 
 int launch_add_mark(hipStream_t s, double* y, const double* x, size_t n, unsigned char* mark) {
