@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 13
+#define FY_ABI_VERSION 14
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -242,7 +242,7 @@ enum { FY_PSOLVER_PCG_JACOBI = 0, FY_PSOLVER_PCG_MG = 1 };
 #define FY_TURBULENCE_LAMINAR 0        /* simulationType laminar / laminarModel Stokes (DPMTurbulenceModels.C:67-68) */
 #define FY_TURBULENCE_SMAGORINSKY 1    /* simulationType LES, LESModel Smagorinsky (DPMTurbulenceModels.C:73-74), delta cubeRootVol */
 #define FY_TURBULENCE_KEQN 2           /* simulationType LES, LESModel kEqn (DPMTurbulenceModels.C:76-77), delta cubeRootVol */
-#define FY_TURBULENCE_KEPSILON 3       /* simulationType RAS, RASModel kEpsilon (DPMTurbulenceModels.C:70-71); no wall functions */
+#define FY_TURBULENCE_KEPSILON 3       /* simulationType RAS, RASModel kEpsilon (DPMTurbulenceModels.C:70-71) */
 #define FY_BC_NUT_ZERO_GRADIENT 0
 #define FY_BC_NUT_FIXED_VALUE 1
 #define FY_BC_NUT_CALCULATED 3          /* nut_bc: `calculated` patch = the model's expression on the boundary values of k (and epsilon); kEqn / kEpsilon */
@@ -474,7 +474,7 @@ int fy_solver_get_exchange_wait(fy_solver*, double ms[4], int64_t waits[4]);
  * correctNonOrthogonal loop iterates on), PCG in its single-reduction form with the diagonal or an agglomeration-multigrid preconditioner (p_solver),
  * Jacobi sweeps for U.  Patches: fixedValue / zeroGradient / symmetry (slip) for U (noSlip = fixedValue 0), translational cyclic pairs; zeroGradient / fixedValue for p, fixedFluxPressure with
  * pimpleFoamYade.  pimpleFoamYade (fy_ldu_case.solver): Gaussian 4-way coupling, the void-fraction-weighted UcEqn / pEqn, gravity, PIMPLE outer correctors,
- * relaxation, adjustable time step, laminar Stokes stress, LES Smagorinsky / kEqn or RAS kEpsilon (no wall functions).  The coupling object (fy_ldu_solver_coupling) works on the mesh's own
+ * relaxation, adjustable time step, laminar Stokes stress, LES Smagorinsky / kEqn or RAS kEpsilon, with nutkWallFunction / epsilonWallFunction patches (nearWallDist on any face).  The coupling object (fy_ldu_solver_coupling) works on the mesh's own
  * cell centres and volumes: explicit k-d tree, and for the point-force locate (mesh.findCell, FoamYade.C:251) the nearest centre followed by a walk
  * across the faces the point lies outside of. */
 typedef struct fy_poly_mesh {
@@ -517,7 +517,9 @@ typedef struct fy_ldu_case {
     /* continuousPhaseTurbulence (pimpleFoamYade only): FY_TURBULENCE_LAMINAR | FY_TURBULENCE_SMAGORINSKY | FY_TURBULENCE_KEQN (LES, delta cubeRootVol) | FY_TURBULENCE_KEPSILON as in fy_case_desc */
     int32_t turbulence_model;
     double les_ck, les_ce, les_delta_coeff, nut_initial;
-    const int32_t* nut_bc;           /* per patch: FY_BC_NUT_ZERO_GRADIENT | FY_BC_NUT_FIXED_VALUE (NULL: zeroGradient everywhere) */
+    const int32_t* nut_bc;           /* per patch: FY_BC_NUT_ZERO_GRADIENT | FY_BC_NUT_FIXED_VALUE (NULL: zeroGradient everywhere); FY_BC_WALL_FUNCTION (nutkWallFunction)
+                                        with kEqn / kEpsilon: the file's value until the first correctNut(), nu (y+ kappa / ln(E y+) - 1) above yPlusLam afterwards,
+                                        y+ = Cmu^1/4 y sqrt(k_P) / nu with y the face's nearWallDist (wf_kappa, wf_E below) */
     const double* nut_value;         /* [n_patches] */
     int32_t convection_scheme;       /* FY_CONVECTION_LINEAR (default) .. FY_CONVECTION_QUICK for div(phi,U) / div(alphaPhic,Uc), as fy_case_desc.convection_scheme */
     double convection_limiter_k;     /* limitedLinear's coefficient in [0, 1] */
@@ -530,9 +532,10 @@ typedef struct fy_ldu_case {
     int32_t k_convection_scheme;
     double k_tol, k_rel_tol; int32_t k_max_iter;
     double k_relax;
-    /* turbulence_model FY_TURBULENCE_KEPSILON (RAS kEpsilon, DPMTurbulenceModels.C:70-71), WITHOUT wall functions on a general mesh (nutkWallFunction /
-     * epsilonWallFunction need nearWallDist: the block solver carries them): the coefficients, the 0/epsilon file and its controls as in fy_case_desc; k as above;
-     * a FY_BC_NUT_CALCULATED nut patch then carries Cmu k_b^2 / epsilon_b */
+    /* turbulence_model FY_TURBULENCE_KEPSILON (RAS kEpsilon, DPMTurbulenceModels.C:70-71): the coefficients, the 0/epsilon file and its controls as in fy_case_desc;
+     * k as above (kqRWallFunction = FY_BC_NUT_ZERO_GRADIENT); a FY_BC_NUT_CALCULATED nut patch then carries Cmu k_b^2 / epsilon_b.  eps_bc FY_BC_WALL_FUNCTION
+     * (epsilonWallFunction, the patch's nut a nutkWallFunction): each cell with such faces has its epsilon imposed, (1/W) sum Cmu^3/4 k^3/2 / (kappa y), and its
+     * production replaced by (1/W) sum (nut_w + nu) |snGrad U| Cmu^1/4 sqrt(k) / (kappa y) over its W faces on those patches, y the faces' nearWallDist */
     double ras_cmu, ras_c1, ras_c2, ras_c3, ras_sigmak, ras_sigmaeps;      /* fy_ldu_case_defaults: 0.09, 1.44, 1.92, 0, 1, 1.3 */
     double eps_initial;
     const int32_t* eps_bc;           /* NULL: zeroGradient everywhere */
@@ -540,6 +543,7 @@ typedef struct fy_ldu_case {
     int32_t eps_convection_scheme;
     double eps_tol, eps_rel_tol; int32_t eps_max_iter;
     double eps_relax;
+    double wf_kappa, wf_E;           /* the wall functions' constants [OF-6 nutkWallFunction]; fy_ldu_case_defaults: 0.41, 9.8 */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */
@@ -549,7 +553,9 @@ int fy_ldu_solver_get_stats(fy_ldu_solver*, fy_step_stats* out);
 int fy_ldu_solver_hold_sources(fy_ldu_solver*, int on);                    /* as fy_solver_hold_sources: setSourceZero deferred to the next step's start (runTime.write() sees alpha / uSource) */
 fy_ctx* fy_ldu_solver_coupling(fy_ldu_solver*);                              /* FoamYade on this mesh (point force); fy_set_particles_* as usual */
 /* fields by name, host copies: "U" [nc][3], "p", "phi" [n_faces], "uSource" [nc][3] (added to what the coupling leaves: an external momentum source),
- * "rAU", "HbyA", "phiHbyA", "p_diag", "p_coef" [n_faces], "p_rhs", "vGrad" [nc][9]; geometry: "C" "V" "Cf" "Sf" "magSf" "w" "dcNO" "kvec" */
+ * "rAU", "HbyA", "phiHbyA", "p_diag", "p_coef" [n_faces], "p_rhs", "vGrad" [nc][9]; geometry: "C" "V" "Cf" "Sf" "magSf" "w" "dcNO" "kvec";
+ * "nearWallDist" [n_faces - n_internal_faces]: y of each boundary face on a patch with a wall-function nut or epsilon (0 elsewhere) [OF-6 nearWallDist::correct];
+ * "nut_boundary" [n_faces - n_internal_faces]: nut on each boundary face as the equations see it now (what the last correctNut() left; the file's value before) */
 int fy_ldu_solver_field_count(fy_ldu_solver*, const char* name, int64_t* count);
 int fy_ldu_solver_read_field_host(fy_ldu_solver*, const char* name, double* out);
 int fy_ldu_solver_write_field_host(fy_ldu_solver*, const char* name, const double* in);

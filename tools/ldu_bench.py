@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """fy_ldu_solver (icoFoamYade on a general polyhedral mesh, LDU addressing) at scale: a lid-driven cavity on n^3 hexahedra written as a polyhedral mesh,
 plain and wavy (non-orthogonal + skewed, one non-orthogonal corrector), against the structured fy_solver on the same lattice.
-usage: ldu_bench.py [n=128] [steps=10] [kind=wavy|lattice|prisms] [particles=0] [p_solver=mg|diag] [nu=1e-4] [solver=ico|pimple]     -> one JSON line
-pimple: a closed box under gravity (fixedFluxPressure walls), the cloud at rest in its lower 60 %, Gaussian 4-way coupling"""
+usage: ldu_bench.py [n=128] [steps=10] [kind=wavy|lattice|prisms] [particles=0] [p_solver=mg|diag] [nu=1e-4] [solver=ico|pimple] [turb=laminar|kEpsilon|kEpsilonWF]
+                                                                                                                                     -> one JSON line
+pimple: a closed box under gravity (fixedFluxPressure walls), the cloud at rest in its lower 60 %, Gaussian 4-way coupling; turb (pimple only): RAS kEpsilon with
+zero-gradient k / epsilon / nut patches, or kEpsilonWF: with nutkWallFunction / epsilonWallFunction on every side of the box"""
 import json
 import os
 import sys
@@ -22,7 +24,10 @@ npart = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 psolver = sys.argv[5] if len(sys.argv) > 5 else "mg"
 nu = float(sys.argv[6]) if len(sys.argv) > 6 else 1e-4
 solver = sys.argv[7] if len(sys.argv) > 7 else "ico"
+turb = sys.argv[8] if len(sys.argv) > 8 else "laminar"
 pimple = solver == "pimple"
+if turb not in ("laminar", "kEpsilon", "kEpsilonWF") or (turb != "laminar" and not pimple):
+    sys.exit("turb: laminar | kEpsilon | kEpsilonWF (the last two with solver=pimple)")
 prod = ge.load_product()
 L = 0.1
 t0 = time.time()
@@ -38,6 +43,10 @@ t0 = time.time()
 if pimple:
     dt = 1e-4
     kw.update(solver=1, g=(0.0, 0.0, -9.81), n_outer_correctors=1, u_relax=1.0)
+    if turb != "laminar":
+        kw.update(turbulence_model=prod.TURBULENCE_KEPSILON, nut_initial=9e-6, k_initial=1e-4, eps_initial=1e-4, k_tol=1e-8, eps_tol=1e-8)
+        if turb == "kEpsilonWF":
+            kw.update(nut_bc=[prod.BC_WALL_FUNCTION] * 6, eps_bc=[prod.BC_WALL_FUNCTION] * 6)
     s = prod.LduSolver(mesh, dt, 1e-6, [0] * 6, [(0, 0, 0)] * 6, [2] * 6, **kw)
 else:
     s = prod.LduSolver(mesh, dt, nu, [0] * 6, lid, [0] * 6, **kw)
@@ -59,7 +68,7 @@ for _ in range(steps):
     st = s.stats()
     its += st["p_iters_total"]; uits += st["u_iters_total"]; ms += st["ms_total"]; mp += st["ms_particle"]
 wall = time.time() - t0
-out = dict(tool="ldu_bench", kind=kind, cells=int(mesh["n_cells"]), faces=int(len(mesh["owner"])), steps=steps, steps_per_s=steps / wall, ms_per_step_wall=1e3 * wall / steps,
+out = dict(tool="ldu_bench", kind=kind, turb=turb, cells=int(mesh["n_cells"]), faces=int(len(mesh["owner"])), steps=steps, steps_per_s=steps / wall, ms_per_step_wall=1e3 * wall / steps,
            ms_per_step_stream=ms / steps, ms_particle=mp / steps, solver=solver, pcg_iters_per_step=its / steps, p_solver=psolver, nu=nu, u_sweeps_per_step=uits / steps, us_per_pcg_iter=1e3 * ms / max(its, 1), courant_max=st["courant_max"],
            cont_err=st["cont_err_sum_local"], particles=npart, mesh_build_s=t_mesh, create_s=t_create, non_orth=kw["n_non_orth"])
 s.close()

@@ -94,7 +94,7 @@ class LduCase(C.Structure):
                 ("k_convection_scheme", C.c_int32), ("k_tol", C.c_double), ("k_rel_tol", C.c_double), ("k_max_iter", C.c_int32), ("k_relax", C.c_double),
                 ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double), ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double),
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
-                ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double)]
+                ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double)]
 
 
 class ParticleTimings(C.Structure):

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -211,5 +213,12 @@ struct KernelClock {
 };
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// nutWallFunction::yPlusLam [OF-6 nutWallFunctionFvPatchScalarField.C]: ten fixed-point sweeps of y+ = ln(E y+) / kappa from 11 (both solvers' wall functions)
+inline double wall_yplus_lam(double kappa, double E) {
+    double ypl = 11.0;
+    for (int it = 0; it < 10; ++it) ypl = std::log(std::max(E * ypl, 1.0)) / kappa;
+    return ypl;
+}
 
 }  // namespace fy

@@ -801,7 +801,8 @@ int read_general_fields(fy_foam_case* c) {
         }
     }
     if (c->desc.turbulence_model != FY_TURBULENCE_LAMINAR) {
-        // nut.<phase> [OF-6 eddyViscosity: MUST_READ]: patches zeroGradient | fixedValue (uniform) | calculated with a uniform value (= keeps its value: fixedValue here)
+        // nut.<phase> [OF-6 eddyViscosity: MUST_READ]: patches zeroGradient | fixedValue (uniform) | calculated with a uniform value (= keeps its value: fixedValue here) |
+        // nutkWallFunction on a wall patch with kEqn / kEpsilon
         const std::string path = join(c->fdir, c->start_name + "/nut." + c->phase);
         FoamDict f;
         FY_TRY(need_file(path, &f));
@@ -810,6 +811,7 @@ int read_general_fields(fy_foam_case* c) {
         const FoamDict* bf = f.subdict("boundaryField");
         if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
         c->g_nut_bc.assign(np, FY_BC_NUT_ZERO_GRADIENT); c->g_nut_val.assign(np, 0.0); c->g_nut_text.assign(np, std::string());
+        int wf_patch = -1;                 // the first nutkWallFunction patch
         for (size_t pa = 0; pa < np; ++pa) {
             const char* pn = c->g_patch_name[pa].c_str();
             const FoamDict* pd = bf->subdict(c->g_patch_name[pa]);
@@ -817,17 +819,33 @@ int read_general_fields(fy_foam_case* c) {
             if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), pn);
             c->g_nut_text[pa] = entry_text(*pd);
             const auto* vt = pd->tokens("value");
-            if (ty == "calculated" && (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON)) {      // the file's value until the first correctNut(), the model's expression afterwards
+            // [OF-6 nutWallFunctionFvPatchScalarField::checkType]: a wall function sits on a wall patch
+            if (ty.find("WallFunction") != std::string::npos && c->g_patch_class[pa] != "wall")
+                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s is a wall function, but the patch is of type '%s' (constant/polyMesh/boundary), not wall", path.c_str(), pn, ty.c_str(), c->g_patch_class[pa].c_str());
+            if (ty == "nutkWallFunction") {
+                if (c->desc.turbulence_model != FY_TURBULENCE_KEQN && c->desc.turbulence_model != FY_TURBULENCE_KEPSILON)
+                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': nutkWallFunction needs a model with a k equation (kEqn, kEpsilon)", path.c_str(), pn);
+                // [OF-6 nutkWallFunctionFvPatchScalarField]: Cmu / kappa / E per patch (defaults 0.09, 0.41, 9.8); one set serves the case here
+                c->g_nut_bc[pa] = FY_BC_WALL_FUNCTION;
+                if (vt && vt->size() >= 2 && (*vt)[0] == "uniform") fy::foam_tok_is_number((*vt)[1], &c->g_nut_val[pa]);
+                double cmu = c->desc.ras_cmu, kap = 0.41, E = 9.8;
+                pd->scalar("kappa", &kap); pd->scalar("E", &E);
+                if (pd->scalar("Cmu", &cmu) && cmu != c->desc.ras_cmu) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': a wall-function Cmu other than the model's is not supported", path.c_str(), pn);
+                if (wf_patch >= 0 && (kap != c->desc.wf_kappa || E != c->desc.wf_E))
+                    return fail(FY_ERR_UNSUPPORTED, "%s: patches '%s' and '%s' give nutkWallFunction different kappa / E: one set serves the case", path.c_str(), c->g_patch_name[(size_t)wf_patch].c_str(), pn);
+                c->desc.wf_kappa = kap; c->desc.wf_E = E;
+                wf_patch = (int)pa;
+            } else if (ty == "calculated" && (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON)) {      // the file's value until the first correctNut(), the model's expression afterwards
                 c->g_nut_bc[pa] = FY_BC_NUT_CALCULATED;
                 if (vt && vt->size() >= 2 && (*vt)[0] == "uniform") fy::foam_tok_is_number((*vt)[1], &c->g_nut_val[pa]);
             } else if (ty == "fixedValue" || ty == "calculated") {
                 c->g_nut_bc[pa] = FY_BC_NUT_FIXED_VALUE;
                 if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->g_nut_val[pa]))
                     return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s needs 'value uniform <nut>'", path.c_str(), pn, ty.c_str());
-            } else if (ty != "zeroGradient" && ty != "symmetryPlane" && ty != "symmetry" && ty != "cyclic") return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': nut boundary type '%s' is not supported on a general mesh (zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue, calculated)", path.c_str(), pn, ty.c_str());
+            } else if (ty != "zeroGradient" && ty != "symmetryPlane" && ty != "symmetry" && ty != "cyclic") return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': nut boundary type '%s' is not supported on a general mesh (zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue, calculated; nutkWallFunction with kEqn / kEpsilon)", path.c_str(), pn, ty.c_str());
         }
     }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) {     // epsilon.<phase> [OF-6 kEpsilon: epsilon_ is MUST_READ]; zeroGradient | fixedValue (uniform); no epsilonWallFunction on a general mesh
+    if (c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) {     // epsilon.<phase> [OF-6 kEpsilon: epsilon_ is MUST_READ]; zeroGradient | fixedValue (uniform) | epsilonWallFunction on a wall patch
         const std::string path = join(c->fdir, c->start_name + "/epsilon." + c->phase);
         FoamDict f;
         FY_TRY(need_file(path, &f));
@@ -843,12 +861,19 @@ int read_general_fields(fy_foam_case* c) {
             if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), pn);
             c->g_eps_text[pa] = entry_text(*pd);
             const auto* vt = pd->tokens("value");
+            if (ty.find("WallFunction") != std::string::npos && c->g_patch_class[pa] != "wall")
+                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s is a wall function, but the patch is of type '%s' (constant/polyMesh/boundary), not wall", path.c_str(), pn, ty.c_str(), c->g_patch_class[pa].c_str());
             if (ty == "fixedValue") {
                 c->g_eps_bc[pa] = FY_BC_NUT_FIXED_VALUE;
                 if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->g_eps_val[pa]))
                     return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <epsilon>'", path.c_str(), pn);
+            } else if (ty == "epsilonWallFunction") {
+                // [OF-6 epsilonWallFunctionFvPatchScalarField::calculate: nutWallFunctionFvPatchScalarField::nutw(turbModel, patchi)]: kappa and E are the patch's nut wall function's
+                if (c->g_nut_bc[pa] != FY_BC_WALL_FUNCTION)
+                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': epsilonWallFunction takes its constants from the patch's nut wall function, and nut.%s is not nutkWallFunction there", path.c_str(), pn, c->phase.c_str());
+                c->g_eps_bc[pa] = FY_BC_WALL_FUNCTION;
             } else if (ty != "zeroGradient" && ty != "symmetryPlane" && ty != "symmetry" && ty != "cyclic")
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': epsilon boundary type '%s' is not supported on a general mesh (zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue; the wall functions need the block solver)", path.c_str(), pn, ty.c_str());
+                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': epsilon boundary type '%s' is not supported on a general mesh (zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue, epsilonWallFunction)", path.c_str(), pn, ty.c_str());
         }
     }
     if (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) {         // k.<phase> [OF-6: k_ is MUST_READ]; patches zeroGradient | fixedValue (uniform); kqRWallFunction is a zeroGradient condition
@@ -1444,6 +1469,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->ras_cmu = d.ras_cmu; out->ras_c1 = d.ras_c1; out->ras_c2 = d.ras_c2; out->ras_c3 = d.ras_c3; out->ras_sigmak = d.ras_sigmak; out->ras_sigmaeps = d.ras_sigmaeps;
     out->eps_initial = d.eps_initial; out->eps_bc = c->g_eps_bc.empty() ? nullptr : c->g_eps_bc.data(); out->eps_value = c->g_eps_val.empty() ? nullptr : c->g_eps_val.data();
     out->eps_convection_scheme = d.eps_convection_scheme; out->eps_tol = d.eps_tol; out->eps_rel_tol = d.eps_rel_tol; out->eps_max_iter = d.eps_max_iter; out->eps_relax = d.eps_relax;
+    out->wf_kappa = d.wf_kappa; out->wf_E = d.wf_E;
     out->u_bc = c->g_u_bc.data(); out->u_value = c->g_u_val.data(); out->p_bc = c->g_p_bc.data(); out->p_value = c->g_p_val.data();
     return FY_OK;
 }

@@ -118,9 +118,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
         les_delta = c->les_delta_coeff * std::pow(g.V, 1.0 / 3.0);
         {   // nutWallFunction::yPlusLam [OF-6 nutWallFunctionFvPatchScalarField.C]
             if (!(c->wf_kappa > 0 && c->wf_E > 0)) return fail(FY_ERR_INVALID, "fy_solver_create: wall-function constants kappa, E must be positive");
-            double ypl = 11.0;
-            for (int it = 0; it < 10; ++it) ypl = std::log(std::max(c->wf_E * ypl, 1.0)) / c->wf_kappa;
-            g.wf_yPlusLam = ypl; g.wf_kappa = c->wf_kappa; g.wf_E = c->wf_E; g.wf_cmu25 = std::pow(c->ras_cmu, 0.25);
+            g.wf_yPlusLam = wall_yplus_lam(c->wf_kappa, c->wf_E); g.wf_kappa = c->wf_kappa; g.wf_E = c->wf_E; g.wf_cmu25 = std::pow(c->ras_cmu, 0.25);
             g.nut_wall_live = 0;
             g.turb_model = c->turbulence_model; g.turb_ck = c->les_ck; g.turb_cmu = c->ras_cmu; g.turb_delta = les_delta; g.turb_dcoeff = c->les_delta_coeff;
             for (int q = 0; q < 6; ++q) {

@@ -31,6 +31,12 @@ struct LduHostMesh {
     std::vector<int32_t> orig_face, f_off, f_pts, f_own, f_nei, f_pstart, f_psize;
     int fold_cyclics(fy_poly_mesh* m);
     int build(const fy_poly_mesh* m);                   // FY_OK or an error (malformed addressing)
+    // the points and, per patch, its first face in the solver's numbering; per boundary face (f - nInt) its points: what nearWallDist measures to
+    std::vector<double> pts;
+    std::vector<int32_t> pstart, psize, bf_off, bf_pts;
+    // nearWallDist [OF-6 nearWallDist::correct, cellDistFuncs]: per boundary face of a patch with on[patch] set, the distance from its owner's centre to the nearest of
+    // the faces of the same patch that share a point with it (itself included); 0 on the other patches
+    void near_wall_dist(const std::vector<char>& on, std::vector<double>* y) const;
 };
 
 // what the kernels see (device pointers), passed by value
@@ -84,6 +90,15 @@ struct LduPim {
     const int32_t* eps_bc;
     const double* eps_val;
     double cmu;
+    // nutkWallFunction patches (FY_BC_WALL_FUNCTION in nut_bc): y per boundary face (nearWallDist; null without such a patch), Cmu^1/4, kappa, E, yPlusLam
+    const double* ywall;
+    double wf_cmu25, wf_kappa, wf_E, wf_yplam;
+};
+// the cells with epsilonWallFunction faces: per wall cell its faces (on such patches) [off[w], off[w + 1]) of face[]
+struct LduWallCells {
+    int n;
+    const int32_t *cell, *off, *face;
+    double cmu75;
 };
 // one transport equation of a closure (fv_kernels.hip's modes): 0 kEqn's k, 1 kEpsilon's epsilon, 2 kEpsilon's k; X the transported field with its patches
 struct LduKEqn {
@@ -94,6 +109,9 @@ struct LduKEqn {
     const double* X;
     const int32_t* x_bc;
     const double* x_val;
+    // epsilonWallFunction (kEpsilon's two equations; null without it): per cell its wall-cell index or -1, per wall cell the imposed epsilon and the production G
+    const int32_t* wall_of;
+    const double *wall_eps, *wall_G;
 };
 
 int ldu_red_blocks(int n);      // partials per slot of the reducing kernels (= red_blocks(n) of fv_kernels.hpp: the folds are shared)
@@ -131,6 +149,11 @@ int launch_ldu_smagorinsky_nut(hipStream_t s, LduGeo g, const double* vGrad, dou
 int launch_ldu_grad_k(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, double* gk);
 int launch_ldu_k_assemble(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, const double* phi, const double* vGrad, const double* gk, LduMom M, double* face_corr, double* x3);
 int launch_ldu_k_bound_nut(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, const double* x3, double* X, double* nut);
+// epsilonWallFunction::calculate before the epsilon equation: per wall cell the imposed epsilon and G (k of this correct()'s start, U of the last corrector)
+int launch_ldu_wall_functions(hipStream_t s, LduGeo g, LduPim P, LduWallCells W, const double* U, double* wall_eps, double* wall_G);
+// fvMatrix::setValues' last part on the epsilon matrix: the wall cells' faces lose their coefficients (the rows were imposed by k_ldu_k_cells)
+int launch_ldu_wall_set_values(hipStream_t s, LduGeo g, LduWallCells W, LduMom M);
+int launch_ldu_nut_boundary(hipStream_t s, LduGeo g, LduPim P, double* out);      // out[f - nInt] = nut on boundary face f as the equations see it
 int launch_ldu_forces(hipStream_t s, LduGeo g, LduPim P, const double* rAU, double* rAUf, double* phiForces);
 int launch_ldu_ssf_predictor(hipStream_t s, LduGeo g, const double* phiForces, const double* rAUf, const double* p, const double* gradp, double* ssf);
 int launch_ldu_reconstruct(hipStream_t s, LduGeo g, const double* ssf, const double* base, const double* scale, double* out);

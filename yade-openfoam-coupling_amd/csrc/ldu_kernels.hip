@@ -576,7 +576,12 @@ __device__ __forceinline__ double ldu_nut_b(const LduGeo& g, const LduPim& P, in
     if (!P.nut) return 0.0;
     const int pa = g.patch_of[f - g.nInt], c = g.own[f];
     const int t = P.nut_bc[pa];
-    if (t == FY_BC_NUT_FIXED_VALUE || (t == FY_BC_NUT_CALCULATED && !(P.k && P.nut_live))) return P.nut_val[pa];
+    if (t == FY_BC_NUT_FIXED_VALUE || (t == FY_BC_NUT_CALCULATED && !(P.k && P.nut_live)) || (t == FY_BC_WALL_FUNCTION && !P.nut_live)) return P.nut_val[pa];
+    // nutkWallFunction [OF-6 nutkWallFunctionFvPatchScalarField::nut]: y+ = Cmu^1/4 y sqrt(k_P) / nu, nu (y+ kappa / ln(E y+) - 1) above yPlusLam, else 0 (fv_kernels.hip: nut_boundary)
+    if (t == FY_BC_WALL_FUNCTION) {
+        const double yPlus = P.wf_cmu25 * P.ywall[f - g.nInt] * sqrt(P.k[c]) / g.nu;
+        return yPlus > P.wf_yplam ? g.nu * (yPlus * P.wf_kappa / log(P.wf_E * yPlus) - 1.0) : 0.0;
+    }
     // calculated [OF-6 GeometricField::operator=: nut_ = Ck sqrt(k_) delta | Cmu sqr(k_) / epsilon_ assigns the patches too]
     if (t == FY_BC_NUT_CALCULATED && P.eps) {
         const double kb = ldu_k_b(g, P, P.k, f), eb = P.eps_bc[pa] == FY_BC_NUT_FIXED_VALUE ? P.eps_val[pa] : P.eps[c];
@@ -740,11 +745,13 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= g.nCells) return;
     const double Vc = g.V[c], ac = P.alpha[c], xc = K.X[c];
-    double dg = ac * Vc / g.dt, b = ac * Vc / g.dt * xc, sumPhi = 0.0, offsum = 0.0;
+    double dg = ac * Vc / g.dt, b = ac * Vc / g.dt * xc, sumPhi = 0.0, offsum = 0.0, moved = 0.0;
+    const bool setv = K.wall_of && K.mode == 1;                // epsilonWallFunction: the epsilon equation's setValues
     FY_CELL_FACES(g, c, f, nb) {
         if (f < g.nInt) {
             if (nb > c) { dg -= M.lower[f]; offsum += fabs(M.upper[f]); sumPhi += phi[f]; b += corr[f]; }
             else { dg -= M.upper[f]; offsum += fabs(M.lower[f]); sumPhi -= phi[f]; b -= corr[f]; }
+            if (setv) { const int wn = K.wall_of[nb]; if (wn >= 0) moved += (nb > c ? M.upper[f] : M.lower[f]) * K.wall_eps[wn]; }
         } else {
             const int pa = g.patch_of[f - g.nInt];
             const double fl = P.alphaf[f] * phi[f];
@@ -762,7 +769,8 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int q = 0; q < 3; ++q) GG += T[3 * a + q] * ((T[3 * a + q] + T[3 * q + a]) - (a == q ? (1.0 / 3.0) * tr2 : 0.0));
-    const double G = P.nut[c] * GG, divU = sumPhi / Vc;
+    const int wc = K.wall_of ? K.wall_of[c] : -1;
+    const double G = wc >= 0 ? K.wall_G[wc] : P.nut[c] * GG, divU = sumPhi / Vc;      // (a wall cell's production: the wall function's, k_ldu_wall_functions)
     // mode 0 (kEqn's k): Su = alpha G, c1 = 2/3 alpha divU, c2 = Ce alpha sqrt(k) / delta; mode 1 (epsilon): Su = C1 alpha G eps / k, c1 = (2/3 C1 - C3) alpha divU, c2 = C2 alpha eps / k;
     // mode 2 (kEpsilon's k): Su = alpha G, c1 = 2/3 alpha divU, c2 = alpha eps / k
     double Su, c1, c2;
@@ -776,9 +784,49 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
         b += (dn - dg) * xc;
         dg = dn;
     }
+    // epsEqn.boundaryManipulate -> fvMatrix::setValues [OF-6 fvMatrix.C setValuesFromList], after relax() as on the block: a wall cell's row becomes dg x = dg eps_w
+    // and it starts from eps_w; a row next to wall cells moves those coefficients times their eps_w to its source (the faces' coefficients are zeroed after this
+    // kernel, k_ldu_wall_set_values: every row here still reads the assembled ones)
+    double x0 = xc;
+    if (setv && wc >= 0) { x0 = K.wall_eps[wc]; b = dg * x0; }
+    else if (setv) b -= moved;
     M.diag[c] = dg;
     st3(M.b, c, D3{b, 0.0, 0.0});
-    st3(x3, c, D3{xc, 0.0, 0.0});
+    st3(x3, c, D3{x0, 0.0, 0.0});
+}
+
+// epsilonWallFunction::calculate [OF-6 epsilonWallFunctionFvPatchScalarField.C], one lane per wall cell over its W faces on epsilonWallFunction patches (fv_kernels.hip:
+// k_assemble_turb, wall_epsilon): eps_w = (1/W) sum Cmu^3/4 k^3/2 / (kappa y), G_w = (1/W) sum (nut_w + nu) |snGrad U| Cmu^1/4 sqrt(k) / (kappa y), snGrad U =
+// (U_b - U_P) deltaCoeffs with the boundary face's 1 / (n . (Cf - C_P)); k of the cell as this correct() found it
+__global__ __launch_bounds__(256) void k_ldu_wall_functions(LduGeo g, LduPim P, LduWallCells W, const double* __restrict__ U, double* __restrict__ wall_eps, double* __restrict__ wall_G) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= W.n) return;
+    const int c = W.cell[w], q0 = W.off[w], q1 = W.off[w + 1];
+    const double kc = P.k[c], uk = pow(kc, 1.5), sk = sqrt(kc);
+    const D3 uc = ld3(U, c);
+    double se = 0.0, sg = 0.0;
+    for (int q = q0; q < q1; ++q) {
+        const int f = W.face[q];
+        const double y = P.ywall[f - g.nInt], dc = g.dcNO[f];
+        const D3 ub = Ub(g, U, f);
+        const double d0 = (ub.x - uc.x) * dc, d1 = (ub.y - uc.y) * dc, d2 = (ub.z - uc.z) * dc;
+        se += W.cmu75 * uk / (P.wf_kappa * y);
+        sg += (ldu_nut_b(g, P, f) + g.nu) * sqrt(d0 * d0 + d1 * d1 + d2 * d2) * P.wf_cmu25 * sk / (P.wf_kappa * y);
+    }
+    wall_eps[w] = se / (double)(q1 - q0);
+    wall_G[w] = sg / (double)(q1 - q0);
+}
+// ... and the coefficients of the wall cells' internal faces become 0 (fvMatrix::setValues: upper = lower = 0); two wall cells across a face store the same 0
+__global__ __launch_bounds__(256) void k_ldu_wall_set_values(LduGeo g, LduWallCells W, LduMom M) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= W.n) return;
+    const int c = W.cell[w];
+    FY_CELL_FACES(g, c, f, nb) if (nb >= 0) { M.lower[f] = 0.0; M.upper[f] = 0.0; }
+}
+__global__ __launch_bounds__(256) void k_ldu_nut_boundary(LduGeo g, LduPim P, double* __restrict__ out) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= g.nFaces - g.nInt) return;
+    out[b] = ldu_nut_b(g, P, g.nInt + b);
 }
 // bound(k, kMin) [OF-6 bound.C: k = max(max(k, fvc::average(max(k, kMin)) pos0(-k)), kMin), fvc::average = sum |Sf| k_f / sum |Sf|], then correctNut(): nut = Ck sqrt(k) delta
 __global__ __launch_bounds__(256) void k_ldu_k_bound_nut(LduGeo g, LduPim P, LduKEqn K, const double* __restrict__ x3, double* __restrict__ X, double* __restrict__ nut) {
@@ -1101,6 +1149,24 @@ int launch_ldu_k_assemble(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, const do
 }
 int launch_ldu_k_bound_nut(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, const double* x3, double* X, double* nut) {
     hipLaunchKernelGGL(k_ldu_k_bound_nut, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, P, K, x3, X, nut);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_wall_functions(hipStream_t s, LduGeo g, LduPim P, LduWallCells W, const double* U, double* wall_eps, double* wall_G) {
+    if (W.n == 0) return FY_OK;
+    hipLaunchKernelGGL(k_ldu_wall_functions, dim3(div_up(W.n, 256)), dim3(256), 0, s, g, P, W, U, wall_eps, wall_G);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_wall_set_values(hipStream_t s, LduGeo g, LduWallCells W, LduMom M) {
+    if (W.n == 0) return FY_OK;
+    hipLaunchKernelGGL(k_ldu_wall_set_values, dim3(div_up(W.n, 256)), dim3(256), 0, s, g, W, M);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_nut_boundary(hipStream_t s, LduGeo g, LduPim P, double* out) {
+    if (g.nFaces == g.nInt) return FY_OK;
+    hipLaunchKernelGGL(k_ldu_nut_boundary, dim3(div_up(g.nFaces - g.nInt, 256)), dim3(256), 0, s, g, P, out);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

@@ -144,6 +144,13 @@ int LduHostMesh::build(const fy_poly_mesh* m_in) {
             patch_of[(size_t)(f - nInt)] = pa;
         }
     for (int32_t v : patch_of) if (v < 0) return fail(FY_ERR_INVALID, "fy_poly_mesh: a boundary face belongs to no patch");
+    pts.assign(m->points, m->points + 3 * (size_t)nPoints);
+    pstart.assign(m->patch_start, m->patch_start + nPatches); psize.assign(m->patch_size, m->patch_size + nPatches);
+    bf_off.assign(1, 0); bf_pts.clear();
+    for (int f = nInt; f < nFaces; ++f) {
+        bf_pts.insert(bf_pts.end(), m->face_points + m->face_offsets[f], m->face_points + m->face_offsets[f + 1]);
+        bf_off.push_back((int32_t)bf_pts.size());
+    }
     // ---- faces
     Cf.assign(3 * (size_t)nFaces, 0.0); Sf = Cf; magSf.assign((size_t)nFaces, 0.0);
     for (int f = 0; f < nFaces; ++f) {
@@ -243,6 +250,61 @@ int LduHostMesh::build(const fy_poly_mesh* m_in) {
         dcNO[(size_t)f] = 1.0 / nd;
     }
     return FY_OK;
+}
+
+namespace {
+// the point of triangle (a, b, c) nearest to p (the Voronoi regions of its vertices, edges and interior)
+V3 nearest_on_triangle(V3 p, V3 a, V3 b, V3 c) {
+    const V3 ab = b - a, ac = c - a, ap = p - a;
+    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
+    if (d1 <= 0 && d2 <= 0) return a;
+    const V3 bp = p - b;
+    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
+    if (d3 >= 0 && d4 <= d3) return b;
+    const double vc = d1 * d4 - d3 * d2;
+    if (vc <= 0 && d1 >= 0 && d3 <= 0) return a + (d1 / (d1 - d3)) * ab;
+    const V3 cp = p - c;
+    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
+    if (d6 >= 0 && d5 <= d6) return c;
+    const double vb = d5 * d2 - d1 * d6;
+    if (vb <= 0 && d2 >= 0 && d6 <= 0) return a + (d2 / (d2 - d6)) * ac;
+    const double va = d3 * d6 - d5 * d4;
+    if (va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0) return b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) * (c - b);
+    const double r = 1.0 / (va + vb + vc);
+    return a + (vb * r) * ab + (vc * r) * ac;
+}
+}  // namespace
+
+// [OF-6 nearWallDist::correct -> cellDistFuncs::getPointNeighbours, smallestDist; face::nearestPointClassify]: y_f = min over the faces g of f's patch that share a point
+// with f (f included) of |C_own(f) - nearest point of g|; a triangle is measured as itself, any other face as the fan of triangles (face centre, p_i, p_i+1)
+void LduHostMesh::near_wall_dist(const std::vector<char>& on, std::vector<double>* y) const {
+    y->assign((size_t)(nFaces - nInt), 0.0);
+    std::vector<std::pair<int32_t, int32_t> > pf;      // (point, boundary face) of one patch, sorted by point
+    std::vector<int32_t> cand;
+    for (int pa = 0; pa < nPatches; ++pa) {
+        if (!on[(size_t)pa] || psize[(size_t)pa] == 0) continue;
+        const int b0 = pstart[(size_t)pa] - nInt, b1 = b0 + psize[(size_t)pa];
+        pf.clear();
+        for (int b = b0; b < b1; ++b) for (int32_t q = bf_off[(size_t)b]; q < bf_off[(size_t)b + 1]; ++q) pf.push_back({bf_pts[(size_t)q], b});
+        std::sort(pf.begin(), pf.end());
+        for (int b = b0; b < b1; ++b) {
+            cand.clear();
+            for (int32_t q = bf_off[(size_t)b]; q < bf_off[(size_t)b + 1]; ++q)
+                for (auto it = std::lower_bound(pf.begin(), pf.end(), std::make_pair(bf_pts[(size_t)q], (int32_t)-1)); it != pf.end() && it->first == bf_pts[(size_t)q]; ++it) cand.push_back(it->second);
+            std::sort(cand.begin(), cand.end());
+            cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+            const V3 P = at(C.data(), own[(size_t)(nInt + b)]);
+            double best = 1e300;
+            for (int32_t g : cand) {
+                const int32_t* q = bf_pts.data() + bf_off[(size_t)g];
+                const int n = bf_off[(size_t)g + 1] - bf_off[(size_t)g];
+                if (n == 3) { best = std::min(best, mag(P - nearest_on_triangle(P, at(pts.data(), q[0]), at(pts.data(), q[1]), at(pts.data(), q[2])))); continue; }
+                const V3 ctr = at(Cf.data(), nInt + g);
+                for (int a = 0; a < n; ++a) best = std::min(best, mag(P - nearest_on_triangle(P, at(pts.data(), q[a]), at(pts.data(), q[(a + 1) % n]), ctr)));
+            }
+            (*y)[(size_t)b] = best;
+        }
+    }
 }
 
 }  // namespace fy

@@ -43,10 +43,19 @@ struct LduSolver {
     bool keps = false;
     DevBuf<double> kturb, d_kval, gradk, epsturb, d_epsval;
     DevBuf<int32_t> d_kbc, d_epsbc;
+    // wall functions: nearWallDist per boundary face (host: ywall, zeros without a wall-function patch), the epsilonWallFunction cells (LduWallCells) and what
+    // k_ldu_wall_functions forms for them once per correct(); nutBnd: the "nut_boundary" read-out
+    std::vector<double> ywall;
+    DevBuf<double> d_ywall, wall_eps, wall_G, nutBnd;
+    DevBuf<int32_t> d_wc_cell, d_wc_off, d_wc_face, d_wall_of;
+    int n_wall_cells = 0;
+    double wf_yplam = 0.0;
+    LduWallCells WC() const { return LduWallCells{n_wall_cells, d_wc_cell.p, d_wc_off.p, d_wc_face.p, std::pow(cs.ras_cmu, 0.75)}; }
     LduPim P() const {
         return LduPim{alpha.p, alpha.p, alphaf.p, uSourceDrag.p, uSource.p, {cs.g[0], cs.g[1], cs.g[2]}, les ? nut.p : nullptr, d_nutbc.p, d_nutval.p,
                       (keqn || keps) ? kturb.p : nullptr, d_kbc.p, d_kval.p, nut_live ? 1 : 0, cs.les_ck, cs.les_delta_coeff,
-                      keps ? epsturb.p : nullptr, d_epsbc.p, d_epsval.p, cs.ras_cmu};
+                      keps ? epsturb.p : nullptr, d_epsbc.p, d_epsval.p, cs.ras_cmu,
+                      d_ywall.p, std::pow(cs.ras_cmu, 0.25), cs.wf_kappa, cs.wf_E, wf_yplam};
     }      // alphac.oldTime() == alphac
     DevBuf<int> adj_err;
     bool need_ref = true, ext_source = false, has_slip = false;
@@ -106,6 +115,7 @@ struct LduSolver {
         if (c->convection_scheme == FY_CONVECTION_LIMITED_LINEAR && !(c->convection_limiter_k >= 0 && c->convection_limiter_k <= 1)) return fail(FY_ERR_INVALID, "fy_ldu_solver: limitedLinear takes a coefficient in [0, 1]");
         if (les && !(c->les_ck > 0 && c->les_ce > 0 && c->les_delta_coeff > 0)) return fail(FY_ERR_INVALID, "fy_ldu_solver: Smagorinsky needs Ck, Ce and the delta coefficient positive");
         nc = hm.nCells; nf = hm.nFaces; ni = hm.nInt;
+        ywall.assign((size_t)(nf - ni), 0.0);
         std::vector<int32_t> ubc(c->u_bc, c->u_bc + hm.nPatches), pbc(c->p_bc, c->p_bc + hm.nPatches);
         std::vector<double> uval(c->u_value, c->u_value + 3 * (size_t)hm.nPatches), pval(c->p_value, c->p_value + hm.nPatches);
         need_ref = true;
@@ -177,21 +187,23 @@ struct LduSolver {
                 for (int pa = 0; pa < hm.nPatches; ++pa) {
                     if (c->nut_bc) nb[(size_t)pa] = c->nut_bc[pa];
                     if (c->nut_value) nv[(size_t)pa] = c->nut_value[pa];
-                    if (nb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && nb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE && !((keqn || keps) && nb[(size_t)pa] == FY_BC_NUT_CALCULATED))
-                        return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: nut patch type %d (zeroGradient, fixedValue; calculated with kEqn / kEpsilon; the wall functions need the block solver)", nb[(size_t)pa]);
+                    if (nb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && nb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE && !((keqn || keps) && (nb[(size_t)pa] == FY_BC_NUT_CALCULATED || nb[(size_t)pa] == FY_BC_WALL_FUNCTION)))
+                        return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: nut patch type %d (zeroGradient, fixedValue; calculated or nutkWallFunction with kEqn / kEpsilon)", nb[(size_t)pa]);
                 }
                 FY_TRY(up(d_nutbc, nb)); FY_TRY(up(d_nutval, nv));
                 FY_TRY(nut.alloc_exact(n));
                 FY_TRY(launch_fill_f64(stream, nut.p, n, c->nut_initial));
             }
-            if (keps) {                                                       // epsilon of the start time, its patches (no epsilonWallFunction on a general mesh)
+            std::vector<char> wf_eps((size_t)hm.nPatches, 0);
+            if (keps) {                                                       // epsilon of the start time, its patches (an epsilonWallFunction patch is a zero-gradient one wherever its face value is asked for)
                 std::vector<int32_t> eb((size_t)hm.nPatches, FY_BC_NUT_ZERO_GRADIENT);
                 std::vector<double> ev((size_t)hm.nPatches, 0.0);
                 for (int pa = 0; pa < hm.nPatches; ++pa) {
                     if (c->eps_bc) eb[(size_t)pa] = c->eps_bc[pa];
                     if (c->eps_value) ev[(size_t)pa] = c->eps_value[pa];
-                    if (eb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && eb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE)
-                        return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: epsilon patch type %d (zeroGradient, fixedValue; epsilonWallFunction needs the block solver)", eb[(size_t)pa]);
+                    if (eb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && eb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE && eb[(size_t)pa] != FY_BC_WALL_FUNCTION)
+                        return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: epsilon patch type %d (zeroGradient, fixedValue, epsilonWallFunction)", eb[(size_t)pa]);
+                    wf_eps[(size_t)pa] = eb[(size_t)pa] == FY_BC_WALL_FUNCTION;
                 }
                 FY_TRY(up(d_epsbc, eb)); FY_TRY(up(d_epsval, ev));
                 FY_TRY(epsturb.alloc_exact(n));
@@ -211,6 +223,7 @@ struct LduSolver {
                 FY_TRY(launch_fill_f64(stream, kturb.p, n, c->k_initial));
                 cs.k_bc = nullptr; cs.k_value = nullptr;
             }
+            FY_TRY(setup_wall_functions(c, wf_eps));
         }
         for (auto& t : tim) FY_TRY(t.init());
         if (cs.convection_scheme >= FY_CONVECTION_LIMITED_LINEAR) { FY_TRY(gradL.alloc_exact(3 * n)); FY_TRY(zero(gradL)); g.gradL = gradL.p; }
@@ -234,6 +247,33 @@ struct LduSolver {
         }
         FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                    // createPhi
         FY_HIP(hipStreamSynchronize(stream));
+        return FY_OK;
+    }
+
+    // nearWallDist on the patches with a wall-function nut or epsilon, and the list of the cells with epsilonWallFunction faces (what k_ldu_wall_functions runs over)
+    int setup_wall_functions(const fy_ldu_case* c, const std::vector<char>& wf_eps) {
+        const int nb = nf - ni;
+        std::vector<char> on((size_t)hm.nPatches, 0);
+        bool any = false;
+        for (int pa = 0; pa < hm.nPatches; ++pa) {
+            on[(size_t)pa] = wf_eps[(size_t)pa] || (les && c->nut_bc && c->nut_bc[pa] == FY_BC_WALL_FUNCTION);
+            any = any || on[(size_t)pa];
+        }
+        if (!any) return FY_OK;
+        if (!(c->wf_kappa > 0 && c->wf_E > 0)) return fail(FY_ERR_INVALID, "fy_ldu_solver: wall-function constants kappa, E must be positive");
+        wf_yplam = wall_yplus_lam(c->wf_kappa, c->wf_E);
+        hm.near_wall_dist(on, &ywall);
+        FY_TRY(up(d_ywall, ywall));
+        std::vector<int32_t> cnt((size_t)nc, 0), wall_of((size_t)nc, -1), cell, off(1, 0), face;
+        for (int b = 0; b < nb; ++b) if (wf_eps[(size_t)hm.patch_of[(size_t)b]]) ++cnt[(size_t)hm.own[(size_t)(ni + b)]];
+        for (int q = 0; q < nc; ++q) if (cnt[(size_t)q]) { wall_of[(size_t)q] = (int32_t)cell.size(); cell.push_back(q); off.push_back(off.back() + cnt[(size_t)q]); }
+        n_wall_cells = (int)cell.size();
+        if (n_wall_cells == 0) return FY_OK;
+        face.assign((size_t)off.back(), 0);
+        std::vector<int32_t> fill(off.begin(), off.end() - 1);
+        for (int b = 0; b < nb; ++b) if (wf_eps[(size_t)hm.patch_of[(size_t)b]]) { const int w = wall_of[(size_t)hm.own[(size_t)(ni + b)]]; face[(size_t)fill[(size_t)w]++] = ni + b; }
+        FY_TRY(up(d_wc_cell, cell)); FY_TRY(up(d_wc_off, off)); FY_TRY(up(d_wc_face, face)); FY_TRY(up(d_wall_of, wall_of));
+        FY_TRY(wall_eps.alloc_exact((size_t)n_wall_cells)); FY_TRY(wall_G.alloc_exact((size_t)n_wall_cells));
         return FY_OK;
     }
 
@@ -424,6 +464,7 @@ struct LduSolver {
                 if (keqn || keps) {                                                                               // kEqn::correct() / kEpsilon::correct(): epsilon first, then k with the new epsilon
                     LduMom Mk = M();
                     Mk.bdiag = nullptr;
+                    if (n_wall_cells) FY_TRY(launch_ldu_wall_functions(stream, g, P(), WC(), U.p, wall_eps.p, wall_G.p));       // epsilon_.boundaryFieldRef().updateCoeffs(): G and eps_w, once
                     const int modes[2] = {keps ? 1 : 0, 2};                                                       // (LduKEqn::mode) kEqn: k; kEpsilon: epsilon, then k
                     for (int mi = 0; mi < (keps ? 2 : 1); ++mi) {
                         const int mode = modes[mi];
@@ -432,8 +473,10 @@ struct LduSolver {
                         double tol, rel; int maxit;
                         if (mode == 1) { K.relax = cs.eps_relax; K.upwind = cs.eps_convection_scheme == FY_CONVECTION_UPWIND; K.sigma = cs.ras_sigmaeps; K.X = epsturb.p; K.x_bc = d_epsbc.p; K.x_val = d_epsval.p; tol = cs.eps_tol; rel = cs.eps_rel_tol; maxit = cs.eps_max_iter; }
                         else { K.relax = cs.k_relax; K.upwind = cs.k_convection_scheme == FY_CONVECTION_UPWIND; K.sigma = mode == 0 ? 1.0 : cs.ras_sigmak; K.X = kturb.p; K.x_bc = d_kbc.p; K.x_val = d_kval.p; tol = cs.k_tol; rel = cs.k_rel_tol; maxit = cs.k_max_iter; }
+                        if (n_wall_cells) { K.wall_of = d_wall_of.p; K.wall_eps = wall_eps.p; K.wall_G = wall_G.p; }
                         FY_TRY(launch_ldu_grad_k(stream, g, P(), K, gradk.p));
                         FY_TRY(launch_ldu_k_assemble(stream, g, P(), K, phi.p, vGrad.p, gradk.p, Mk, fcorr.p, HbyA.p));
+                        if (n_wall_cells && mode == 1) FY_TRY(launch_ldu_wall_set_values(stream, g, WC(), Mk));
                         int it = 0;
                         FY_TRY(solve_vec3(&it, Mk, mb.p, nullptr, &HbyA.p, &xscr.p, tol, rel, maxit));
                         k_iters_total += it;
@@ -510,8 +553,19 @@ struct LduSolver {
                          {"divT", divT.p, pimple ? 3 * n : 0}, {"ddtU", ddtU.p, pimple ? 3 * n : 0}, {"phiForces", phiForces.p, pimple ? (size_t)nf : 0}, {"alphaf", alphaf.p, pimple ? (size_t)nf : 0},
                          {"rAUf", rAUf.p, (size_t)nf}, {"uSourceCoupling", uSource.p, 3 * n}, {"nut", nut.p, les ? n : 0}, {"k", kturb.p, (keqn || keps) ? n : 0}, {"epsilon", epsturb.p, keps ? n : 0}};
         for (const E& e : tab) if (s == e.nm) { *ptr = e.p; *count = e.c; return FY_OK; }
+        if (s == "nut_boundary") {                                                 // formed on request: nut_b as ldu_nut_b gives it now
+            *count = les ? (size_t)(nf - ni) : 0;
+            if (*count) {
+                FY_HIP(hipSetDevice(device));
+                if (!nutBnd.p) FY_TRY(nutBnd.alloc_exact(*count));
+                FY_TRY(launch_ldu_nut_boundary(stream, g, P(), nutBnd.p));
+            }
+            *ptr = nutBnd.p;
+            return FY_OK;
+        }
         const struct { const char* nm; const std::vector<double>* v; } geo[] = {{"C", &hm.C}, {"V", &hm.V}, {"Cf", &hm.Cf}, {"Sf", &hm.Sf}, {"magSf", &hm.magSf}, {"w", &hm.w},
-                                                                                  {"dcNO", &hm.dcNO}, {"kvec", &hm.kvec}, {"sep", &hm.sep}, {"orig_face", &orig_face_d}};
+                                                                                  {"dcNO", &hm.dcNO}, {"kvec", &hm.kvec}, {"sep", &hm.sep}, {"orig_face", &orig_face_d},
+                                                                                  {"nearWallDist", &ywall}};
         for (const auto& e : geo) if (s == e.nm) { *host = e.v; *count = e.v->size(); *ptr = nullptr; return FY_OK; }
         return fail(FY_ERR_INVALID, "unknown fy_ldu_solver field '%s'", s.c_str());
     }
@@ -538,6 +592,7 @@ void fy_ldu_case_defaults(fy_ldu_case* c) {
     c->ras_cmu = 0.09; c->ras_c1 = 1.44; c->ras_c2 = 1.92; c->ras_c3 = 0.0; c->ras_sigmak = 1.0; c->ras_sigmaeps = 1.3;
     c->eps_initial = 0.0; c->eps_bc = nullptr; c->eps_value = nullptr; c->eps_convection_scheme = FY_CONVECTION_LINEAR; c->eps_tol = 1e-6; c->eps_rel_tol = 0.0; c->eps_max_iter = 1000; c->eps_relax = 0.0;
     c->k_initial = 0.0; c->k_bc = nullptr; c->k_value = nullptr; c->k_convection_scheme = FY_CONVECTION_LINEAR; c->k_tol = 1e-6; c->k_rel_tol = 0.0; c->k_max_iter = 1000; c->k_relax = 0.0;
+    c->wf_kappa = 0.41; c->wf_E = 9.8;
 }
 
 int fy_ldu_solver_create(const fy_poly_mesh* m, const fy_ldu_case* c, const fy_transport* tr, int device_ordinal, fy_ldu_solver** out) {
