@@ -888,13 +888,18 @@ class FoamCase:
         self._h = h
         self.case = CaseDesc()
         _check(lib().fy_foam_case_desc(self._h, C.byref(self.case)))
+        info = self._read_info()
+        self.patch_of_side = [bytes(info.patch_of_side[s]).split(b"\0", 1)[0].decode() for s in range(6)]
+
+    def _read_info(self):
+        """fy_foam_case_info_get -> the times, cell counts and names as attributes; returns the struct"""
         info = FoamCaseInfo()
         _check(lib().fy_foam_case_info_get(self._h, C.byref(info)))
         self.start_time, self.end_time, self.delta_t = info.start_time, info.end_time, info.delta_t
         self.write_interval_steps, self.n_cells = info.write_interval_steps, info.n_cells
         self.field_cells, self.field_offset = info.field_cells, info.field_offset
         self.u_name, self.phase, self.start_name = info.u_name.decode(), info.phase.decode(), info.start_name.decode()
-        self.patch_of_side = [bytes(info.patch_of_side[s]).split(b"\0", 1)[0].decode() for s in range(6)]
+        return info
 
     def initial_fields(self):
         U = np.zeros((self.field_cells, 3)); p = np.zeros(self.field_cells)
@@ -950,12 +955,7 @@ class GeneralFoamCase(FoamCase):
         self.pm, self.ldu_case = PolyMesh(), LduCase()
         _check(L.fy_foam_case_poly_mesh(self._h, C.byref(self.pm)))
         _check(L.fy_foam_case_ldu_desc(self._h, C.byref(self.ldu_case)))
-        info = FoamCaseInfo()
-        _check(L.fy_foam_case_info_get(self._h, C.byref(info)))
-        self.start_time, self.end_time, self.delta_t = info.start_time, info.end_time, info.delta_t
-        self.write_interval_steps, self.n_cells = info.write_interval_steps, info.n_cells
-        self.field_cells, self.field_offset = info.field_cells, info.field_offset
-        self.u_name, self.phase, self.start_name = info.u_name.decode(), info.phase.decode(), info.start_name.decode()
+        self._read_info()
         m = self.pm
         arr = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt) if n else np.zeros(0, dt)
         nfp = int(m.face_offsets[m.n_faces])

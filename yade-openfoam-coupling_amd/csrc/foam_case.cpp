@@ -19,11 +19,24 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
 #include "foam_dict.hpp"
+
+// a case's fields (the order of fy_case_desc's and fy_ldu_case's condition arrays); alpha is written only, it has no start-time file
+enum { F_U, F_P, F_NUT, F_K, F_EPS, F_ALPHA };
+
+// one field's boundary conditions, indexed by the case's patch list (field_patches): per patch the FY_BC_* code, the value (U: three), and the
+// boundaryField entry as read, re-emitted on write; extra: a block case's entries of other names (a decomposed case's processor patches), as read
+struct PatchField {
+    std::vector<int32_t> bc;
+    std::vector<double> val;
+    std::vector<std::string> text;
+    std::vector<std::pair<std::string, std::string> > extra;
+};
 
 struct fy_foam_case {
     std::string dir;
@@ -35,9 +48,8 @@ struct fy_foam_case {
     std::string patch_of_side[6];               // blockMesh patch name covering XMIN, XMAX, YMIN, YMAX, ZMIN, ZMAX
     std::vector<double> grading[3];             // graded block: cell sizes per axis (fy_case_desc.hx / hy / hz point here)
     std::vector<std::string> patch_order;       // patch names in blockMeshDict order (one side each here)
-    std::string u_bc_text[6], p_bc_text[6];     // the boundaryField entries as read, re-emitted on write
     std::vector<double> U0, p0, nut0, k0, eps0; // internalField of the start time (nut0, k0, eps0: turbulence cases only)
-    std::string nut_bc_text[6], k_bc_text[6], eps_bc_text[6];
+    PatchField bcs[5];                          // per field (U, p, nut, k, epsilon): the start time's boundary conditions
     // controlDict's output settings [OF-6 Time::readDict]: writeFormat ascii | binary, writePrecision (ASCII digits; absent: 17, lossless --
     // OpenFOAM's own default of 6 would not restart a run where it stopped), purgeWrite N (keep the N newest time directories this run wrote)
     bool write_binary = false;
@@ -49,7 +61,6 @@ struct fy_foam_case {
     std::string fdir;                           // where the time directories are: dir, or dir/processorR
     size_t fcells = 0, foffset = 0;             // cells per field file, global number of the first one
     int proc_rank = -1, proc_count = 0;
-    std::vector<std::pair<std::string, std::string> > extra_patches[5];   // per field (U, p, nut, k, epsilon): boundaryField entries of other patches, as read
     // constant/polyMesh read instead of blockMeshDict: the mesh's cell numbers may differ from the lattice's (several blocks): file_cell[L] = the mesh's
     // cell at lattice index L = i + nx (j + ny k); empty = the same numbering (one block)
     std::vector<int32_t> file_cell;
@@ -58,14 +69,10 @@ struct fy_foam_case {
     bool general = false;
     int g_cells = 0, g_internal = 0;
     std::vector<double> g_points;
-    std::vector<int32_t> g_face_off, g_face_pts, g_own, g_nei, g_patch_start, g_patch_size, g_u_bc, g_p_bc;
-    std::vector<std::string> g_patch_name, g_u_text, g_p_text, g_nut_text, g_k_text;
-    std::vector<int32_t> g_k_bc; std::vector<double> g_k_val;
-    std::vector<std::string> g_eps_text; std::vector<int32_t> g_eps_bc; std::vector<double> g_eps_val;
+    std::vector<int32_t> g_face_off, g_face_pts, g_own, g_nei, g_patch_start, g_patch_size;
+    std::vector<std::string> g_patch_name;
     std::vector<int32_t> g_patch_neighbour;      // per patch: its cyclic partner, or -1
-    std::vector<std::string> g_patch_class;      // the boundary file's `type` per patch (wall | patch | symmetryPlane | symmetry)
-    std::vector<double> g_u_val, g_p_val, g_nut_val;
-    std::vector<int32_t> g_nut_bc;
+    std::vector<std::string> g_patch_class;      // the boundary file's `type` per patch (wall | patch | symmetryPlane | symmetry | cyclic)
 };
 
 namespace {
@@ -514,167 +521,188 @@ bool empty_patch_value(const std::vector<std::string>* vt, int ncomp) {
     return fy::foam_read_list(*vt, 2, ncomp, &v) && v.empty();
 }
 
-int read_fields(fy_foam_case* c) {
-    const size_t ncell = c->fcells;
-    {
-        const std::string path = join(c->fdir, c->start_name + "/" + c->u_name);
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 3, ncell, &c->U0, &c->file_cell));
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        keep_extra_patches(c, *bf, 3, &c->extra_patches[0]);
-        for (int s = 0; s < 6; ++s) {
-            const FoamDict* pd = bf->subdict(c->patch_of_side[s]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), c->patch_of_side[s].c_str());
-            c->u_bc_text[s] = entry_text(*pd);
-            for (int q = 0; q < 3; ++q) c->desc.u_value[s][q] = 0.0;
+// `value uniform <x>` / `value uniform (x y z)` -> v
+bool uniform_scalar(const FoamDict& pd, double* v) {
+    const auto* vt = pd.tokens("value");
+    return vt && vt->size() >= 2 && (*vt)[0] == "uniform" && fy::foam_tok_is_number((*vt)[1], v);
+}
+bool uniform_vector(const FoamDict& pd, double* v) {
+    const auto* vt = pd.tokens("value");
+    return vt && !vt->empty() && (*vt)[0] == "uniform" && pd.vector3("value", v);
+}
+
+// whether the case has field F: U and p always, nut with a turbulence model, k with kEqn / kEpsilon, epsilon with kEpsilon, alpha with pimpleFoamYade
+bool has_field(const fy_foam_case* c, int F) {
+    const int tm = c->desc.turbulence_model;
+    switch (F) {
+        case F_NUT: return tm != FY_TURBULENCE_LAMINAR;
+        case F_K: return tm == FY_TURBULENCE_KEQN || tm == FY_TURBULENCE_KEPSILON;
+        case F_EPS: return tm == FY_TURBULENCE_KEPSILON;
+        case F_ALPHA: return c->solver == FY_SOLVER_PIMPLE;
+        default: return true;
+    }
+}
+
+std::string field_name(const fy_foam_case* c, int F) {
+    static const char* const group[] = {"", "", "nut.", "k.", "epsilon.", "alpha."};
+    return F == F_U ? c->u_name : F == F_P ? std::string("p") : group[F] + c->phase;
+}
+
+// the patch list a field's conditions are indexed by: the six sides of a block (XMIN .. ZMAX; one patch may cover several), every patch of a general mesh
+std::vector<std::string> field_patches(const fy_foam_case* c) {
+    return c->general ? c->g_patch_name : std::vector<std::string>(c->patch_of_side, c->patch_of_side + 6);
+}
+
+// one patch's entry of field F (type ty): its FY_BC_* code and value, or the refusal.  The two kinds of case take different sets of types:
+//   both      U: fixedValue (uniform), noSlip, zeroGradient, symmetryPlane / symmetry / slip.  p: zeroGradient, symmetryPlane / symmetry, fixedValue (uniform).
+//             nut: zeroGradient, symmetryPlane / symmetry, fixedValue (uniform), calculated and nutkWallFunction with kEqn / kEpsilon.
+//             k: zeroGradient, symmetryPlane / symmetry, kqRWallFunction, fixedValue (uniform).  epsilon: those of k but kqRWallFunction, epsilonWallFunction
+//   a block   also takes `value nonuniform List<...> 0()` for a fixedValue U or p (decomposePar's value of a patch without a face on the processor), and
+//             fixedFluxPressure with either solver; a wall function's kappa / E are taken as read, the last side's winning
+//   a general mesh  also takes cyclic entries (folded into internal faces: their code is not used), fixedFluxPressure with pimpleFoamYade only, and nut
+//             calculated without a k equation as a fixed value; it checks an entry's type against a constraint patch's (U, p) and a wall function's patch
+//             class (nut, epsilon), defaults kappa / E per patch and refuses patches that differ, and needs nutkWallFunction under an epsilonWallFunction
+int patch_condition(fy_foam_case* c, int F, const std::string& path, size_t pa, const std::string& name, const FoamDict& pd, const std::string& ty, int32_t* bc, double* val) {
+    const bool g = c->general;
+    const char* pn = name.c_str();
+    const std::string cls = g ? c->g_patch_class[pa] : std::string();
+    const bool k_model = has_field(c, F_K);
+    const bool zero_grad = ty == "zeroGradient" || ty == "symmetryPlane" || ty == "symmetry" || (g && ty == "cyclic");      // (a scalar on a symmetry plane: the cell value)
+    // [OF-6 fvPatchField::New]: a field's entry on a constraint patch must carry the patch's own type
+    if (g && (F == F_U || F == F_P) && (cls == "symmetryPlane" || cls == "symmetry" || cls == "cyclic") && c->g_patch_size[pa] > 0 && ty != cls)
+        return fail(FY_ERR_INVALID, "%s: patch '%s' is a %s patch (constant/polyMesh/boundary): its entry must be of that type, not '%s'", path.c_str(), pn, cls.c_str(), ty.c_str());
+    // [OF-6 nutWallFunctionFvPatchScalarField::checkType]: a wall function sits on a wall patch
+    if (g && (F == F_NUT || F == F_EPS) && ty.find("WallFunction") != std::string::npos && cls != "wall")
+        return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s is a wall function, but the patch is of type '%s' (constant/polyMesh/boundary), not wall", path.c_str(), pn, ty.c_str(), cls.c_str());
+    switch (F) {
+        case F_U:
             if (ty == "fixedValue") {
-                c->desc.u_bc[s] = FY_BC_U_FIXED_VALUE;
-                const auto* vt = pd->tokens("value");
-                if (empty_patch_value(vt, 3)) { /* no face of this patch on this processor */ }
-                else if (!vt || vt->empty() || (*vt)[0] != "uniform" || !pd->vector3("value", c->desc.u_value[s]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform (x y z)'", path.c_str(), c->patch_of_side[s].c_str());
-            } else if (ty == "noSlip") {
-                c->desc.u_bc[s] = FY_BC_U_FIXED_VALUE;
-            } else if (ty == "zeroGradient") {
-                c->desc.u_bc[s] = FY_BC_U_ZERO_GRADIENT;
-            } else if (ty == "symmetryPlane" || ty == "symmetry" || ty == "slip") {       // (one and the same on a planar patch)
-                c->desc.u_bc[s] = FY_BC_U_SLIP;
-            } else {
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': velocity boundary type '%s' is not supported (fixedValue, noSlip, zeroGradient, symmetryPlane, symmetry, slip)", path.c_str(),
-                            c->patch_of_side[s].c_str(), ty.c_str());
+                *bc = FY_BC_U_FIXED_VALUE;
+                if ((g || !empty_patch_value(pd.tokens("value"), 3)) && !uniform_vector(pd, val))
+                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform (x y z)'", path.c_str(), pn);
+                return FY_OK;
             }
-        }
-    }
-    {
-        const std::string path = join(c->fdir, c->start_name + "/p");
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 1, ncell, &c->p0, &c->file_cell));
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        keep_extra_patches(c, *bf, 1, &c->extra_patches[1]);
-        for (int s = 0; s < 6; ++s) {
-            const FoamDict* pd = bf->subdict(c->patch_of_side[s]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), c->patch_of_side[s].c_str());
-            c->p_bc_text[s] = entry_text(*pd);
-            c->desc.p_value[s] = 0.0;
-            if (ty == "zeroGradient" || ty == "symmetryPlane" || ty == "symmetry") c->desc.p_bc[s] = FY_BC_P_ZERO_GRADIENT;       // (a scalar on a symmetry plane: the cell value)
-            else if (ty == "fixedFluxPressure") c->desc.p_bc[s] = FY_BC_P_FIXED_FLUX;
-            else if (ty == "fixedValue") {
-                c->desc.p_bc[s] = FY_BC_P_FIXED_VALUE;
-                const auto* vt = pd->tokens("value");
-                if (empty_patch_value(vt, 1)) { /* no face of this patch on this processor */ }
-                else if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->desc.p_value[s]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <p>'", path.c_str(), c->patch_of_side[s].c_str());
-            } else {
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': pressure boundary type '%s' is not supported (zeroGradient, fixedValue, fixedFluxPressure)", path.c_str(),
-                            c->patch_of_side[s].c_str(), ty.c_str());
+            if (ty == "noSlip") { *bc = FY_BC_U_FIXED_VALUE; return FY_OK; }
+            if (ty == "zeroGradient" || (g && ty == "cyclic")) { *bc = FY_BC_U_ZERO_GRADIENT; return FY_OK; }
+            if (ty == "symmetryPlane" || ty == "symmetry" || ty == "slip") { *bc = FY_BC_U_SLIP; return FY_OK; }      // (one and the same on a planar patch or face)
+            break;
+        case F_P:
+            if (ty == "fixedValue") {
+                *bc = FY_BC_P_FIXED_VALUE;
+                if ((g || !empty_patch_value(pd.tokens("value"), 1)) && !uniform_scalar(pd, val))
+                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <p>'", path.c_str(), pn);
+                return FY_OK;
             }
-        }
-    }
-    if (c->desc.turbulence_model != FY_TURBULENCE_LAMINAR) {
-        // nut.<phase> [OF-6 eddyViscosity: nut_ is MUST_READ, named with the velocity's group]; uniform or nonuniform, patches zeroGradient |
-        // fixedValue (uniform) | calculated with a uniform value -- the latter only keeps its value, which is what fixedValue does here
-        const std::string path = join(c->fdir, c->start_name + "/nut." + c->phase);
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 1, ncell, &c->nut0, &c->file_cell));
-        c->desc.nut_initial = c->nut0.empty() ? 0.0 : c->nut0[0];
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        keep_extra_patches(c, *bf, 1, &c->extra_patches[2]);
-        for (int s = 0; s < 6; ++s) {
-            const FoamDict* pd = bf->subdict(c->patch_of_side[s]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), c->patch_of_side[s].c_str());
-            c->nut_bc_text[s] = entry_text(*pd);
-            c->desc.nut_value[s] = 0.0;
-            if (ty == "zeroGradient" || ty == "symmetryPlane" || ty == "symmetry") c->desc.nut_bc[s] = FY_BC_NUT_ZERO_GRADIENT;
-            else if (ty == "fixedValue") {
-                c->desc.nut_bc[s] = FY_BC_NUT_FIXED_VALUE;
-                const auto* vt = pd->tokens("value");
-                if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->desc.nut_value[s]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <nut>'", path.c_str(), c->patch_of_side[s].c_str());
-            } else if (ty == "calculated" && (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON)) {
-                c->desc.nut_bc[s] = FY_BC_NUT_CALCULATED;              // file value until the first correct(), the model's expression afterwards
-                const auto* vt = pd->tokens("value");
-                if (vt && vt->size() >= 2 && (*vt)[0] == "uniform") fy::foam_tok_is_number((*vt)[1], &c->desc.nut_value[s]);
-            } else if (ty == "nutkWallFunction" && (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON)) {
-                // [OF-6 nutkWallFunctionFvPatchScalarField]: Cmu / kappa / E may be given per patch; one set serves the case here
-                c->desc.nut_bc[s] = FY_BC_WALL_FUNCTION;
-                const auto* vt = pd->tokens("value");
-                if (vt && vt->size() >= 2 && (*vt)[0] == "uniform") fy::foam_tok_is_number((*vt)[1], &c->desc.nut_value[s]);
-                double cmu = c->desc.ras_cmu;
-                pd->scalar("kappa", &c->desc.wf_kappa); pd->scalar("E", &c->desc.wf_E);
-                if (pd->scalar("Cmu", &cmu) && cmu != c->desc.ras_cmu) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': a wall-function Cmu other than the model's is not supported", path.c_str(), c->patch_of_side[s].c_str());
-            } else {
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': nut boundary type '%s' is not supported (zeroGradient, fixedValue; calculated / nutkWallFunction with kEqn / kEpsilon)", path.c_str(),
-                            c->patch_of_side[s].c_str(), ty.c_str());
+            if (ty == "fixedFluxPressure" && (!g || c->solver == FY_SOLVER_PIMPLE)) { *bc = FY_BC_P_FIXED_FLUX; return FY_OK; }
+            if (zero_grad) { *bc = FY_BC_P_ZERO_GRADIENT; return FY_OK; }
+            break;
+        case F_NUT:
+            if (ty == "nutkWallFunction" && (k_model || g)) {
+                if (!k_model) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': nutkWallFunction needs a model with a k equation (kEqn, kEpsilon)", path.c_str(), pn);
+                // [OF-6 nutkWallFunctionFvPatchScalarField]: Cmu / kappa / E per patch (defaults 0.09, 0.41, 9.8); one set serves the case here
+                *bc = FY_BC_WALL_FUNCTION;
+                uniform_scalar(pd, val);
+                double cmu = c->desc.ras_cmu, kap = g ? 0.41 : c->desc.wf_kappa, E = g ? 9.8 : c->desc.wf_E;
+                pd.scalar("kappa", &kap); pd.scalar("E", &E);
+                if (pd.scalar("Cmu", &cmu) && cmu != c->desc.ras_cmu) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': a wall-function Cmu other than the model's is not supported", path.c_str(), pn);
+                for (size_t q = pa; g && q-- > 0;)                  // the last wall-function patch before this one
+                    if (c->bcs[F_NUT].bc[q] == FY_BC_WALL_FUNCTION) {
+                        if (kap != c->desc.wf_kappa || E != c->desc.wf_E)
+                            return fail(FY_ERR_UNSUPPORTED, "%s: patches '%s' and '%s' give nutkWallFunction different kappa / E: one set serves the case", path.c_str(), c->g_patch_name[q].c_str(), pn);
+                        break;
+                    }
+                c->desc.wf_kappa = kap; c->desc.wf_E = E;
+                return FY_OK;
             }
-        }
-    }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) {
-        // k.<phase> [OF-6 kEqn / kEpsilon: k_ is MUST_READ]; patches zeroGradient | fixedValue (uniform); kqRWallFunction is a zeroGradient condition
-        const std::string path = join(c->fdir, c->start_name + "/k." + c->phase);
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 1, ncell, &c->k0, &c->file_cell));
-        c->desc.k_initial = c->k0.empty() ? 0.0 : c->k0[0];
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        keep_extra_patches(c, *bf, 1, &c->extra_patches[3]);
-        for (int s = 0; s < 6; ++s) {
-            const FoamDict* pd = bf->subdict(c->patch_of_side[s]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), c->patch_of_side[s].c_str());
-            c->k_bc_text[s] = entry_text(*pd);
-            c->desc.k_value[s] = 0.0;
-            if ((ty == "zeroGradient" || ty == "symmetryPlane" || ty == "symmetry") || ty == "kqRWallFunction") c->desc.k_bc[s] = FY_BC_NUT_ZERO_GRADIENT;
-            else if (ty == "fixedValue") {
-                c->desc.k_bc[s] = FY_BC_NUT_FIXED_VALUE;
-                const auto* vt = pd->tokens("value");
-                if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->desc.k_value[s]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <k>'", path.c_str(), c->patch_of_side[s].c_str());
-            } else {
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': k boundary type '%s' is not supported (zeroGradient, kqRWallFunction, fixedValue)", path.c_str(),
-                            c->patch_of_side[s].c_str(), ty.c_str());
+            if (ty == "calculated" && k_model) { *bc = FY_BC_NUT_CALCULATED; uniform_scalar(pd, val); return FY_OK; }      // the file's value until the first correctNut(), the model's expression afterwards
+            if (ty == "fixedValue" || (g && ty == "calculated")) {           // (calculated keeps its value: what fixedValue does here)
+                *bc = FY_BC_NUT_FIXED_VALUE;
+                if (!uniform_scalar(pd, val)) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s needs 'value uniform <nut>'", path.c_str(), pn, ty.c_str());
+                return FY_OK;
             }
-        }
-    }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) {
-        // epsilon.<phase> [OF-6 kEpsilon: epsilon_ is MUST_READ]; zeroGradient | fixedValue (uniform) | epsilonWallFunction
-        const std::string path = join(c->fdir, c->start_name + "/epsilon." + c->phase);
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 1, ncell, &c->eps0, &c->file_cell));
-        c->desc.eps_initial = c->eps0.empty() ? 0.0 : c->eps0[0];
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        keep_extra_patches(c, *bf, 1, &c->extra_patches[4]);
-        for (int s = 0; s < 6; ++s) {
-            const FoamDict* pd = bf->subdict(c->patch_of_side[s]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), c->patch_of_side[s].c_str());
-            c->eps_bc_text[s] = entry_text(*pd);
-            c->desc.eps_value[s] = 0.0;
-            if (ty == "zeroGradient" || ty == "symmetryPlane" || ty == "symmetry") c->desc.eps_bc[s] = FY_BC_NUT_ZERO_GRADIENT;
-            else if (ty == "fixedValue") {
-                c->desc.eps_bc[s] = FY_BC_NUT_FIXED_VALUE;
-                const auto* vt = pd->tokens("value");
-                if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->desc.eps_value[s]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <epsilon>'", path.c_str(), c->patch_of_side[s].c_str());
-            } else if (ty == "epsilonWallFunction") {
-                c->desc.eps_bc[s] = FY_BC_WALL_FUNCTION;
-            } else {
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': epsilon boundary type '%s' is not supported (zeroGradient, fixedValue, epsilonWallFunction)", path.c_str(),
-                            c->patch_of_side[s].c_str(), ty.c_str());
+            if (zero_grad) { *bc = FY_BC_NUT_ZERO_GRADIENT; return FY_OK; }
+            break;
+        case F_K:
+        case F_EPS:
+            if (ty == "fixedValue") {
+                *bc = FY_BC_NUT_FIXED_VALUE;
+                if (!uniform_scalar(pd, val)) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <%s>'", path.c_str(), pn, F == F_K ? "k" : "epsilon");
+                return FY_OK;
             }
-        }
+            if (zero_grad || (F == F_K && ty == "kqRWallFunction")) { *bc = FY_BC_NUT_ZERO_GRADIENT; return FY_OK; }
+            if (F == F_EPS && ty == "epsilonWallFunction") {
+                // [OF-6 epsilonWallFunctionFvPatchScalarField::calculate: nutWallFunctionFvPatchScalarField::nutw(turbModel, patchi)]: kappa and E are the patch's nut wall function's
+                if (g && c->bcs[F_NUT].bc[pa] != FY_BC_WALL_FUNCTION)
+                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': epsilonWallFunction takes its constants from the patch's nut wall function, and nut.%s is not nutkWallFunction there", path.c_str(), pn, c->phase.c_str());
+                *bc = FY_BC_WALL_FUNCTION;
+                return FY_OK;
+            }
+            break;
     }
+    static const char* const what[] = {"velocity", "pressure", "nut", "k", "epsilon"};
+    static const char* const block_types[] = {"fixedValue, noSlip, zeroGradient, symmetryPlane, symmetry, slip", "zeroGradient, fixedValue, fixedFluxPressure",
+                                              "zeroGradient, fixedValue; calculated / nutkWallFunction with kEqn / kEpsilon", "zeroGradient, kqRWallFunction, fixedValue",
+                                              "zeroGradient, fixedValue, epsilonWallFunction"};
+    static const char* const general_types[] = {"fixedValue, noSlip, zeroGradient, symmetryPlane, symmetry, slip",
+                                                "zeroGradient, symmetryPlane, symmetry, fixedValue; fixedFluxPressure with pimpleFoamYade",
+                                                "zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue, calculated; nutkWallFunction with kEqn / kEpsilon",
+                                                "zeroGradient, kqRWallFunction, symmetryPlane, symmetry, cyclic, fixedValue",
+                                                "zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue, epsilonWallFunction"};
+    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s boundary type '%s' is not supported%s (%s)", path.c_str(), pn, what[F], ty.c_str(), g ? " on a general mesh" : "",
+                (g ? general_types : block_types)[F]);
+}
+
+// <startTime>/<field F> of either kind of case [OF-6: U, p MUST_READ; nut_ of eddyViscosity, k_ of kEqn / kEpsilon, epsilon_ of kEpsilon MUST_READ, named
+// with the velocity's group]: internalField uniform or nonuniform (-> *internal, a block's in lattice order; its first value -> *initial), and a typed
+// boundaryField entry for every patch of the case's list -> c->bcs[F]
+int read_field(fy_foam_case* c, int F, std::vector<double>* internal, double* initial = nullptr) {
+    const int ncomp = F == F_U ? 3 : 1;
+    const std::string path = join(c->fdir, c->start_name + "/" + field_name(c, F));
+    FoamDict f;
+    FY_TRY(need_file(path, &f));
+    FY_TRY(read_internal(f, path, ncomp, c->fcells, internal, c->general ? nullptr : &c->file_cell));
+    if (initial) *initial = internal->empty() ? 0.0 : (*internal)[0];
+    const FoamDict* bf = f.subdict("boundaryField");
+    if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
+    PatchField& r = c->bcs[F];
+    if (!c->general) keep_extra_patches(c, *bf, ncomp, &r.extra);
+    const std::vector<std::string> names = field_patches(c);
+    r.bc.assign(names.size(), 0); r.val.assign(names.size() * ncomp, 0.0); r.text.assign(names.size(), std::string());
+    for (size_t pa = 0; pa < names.size(); ++pa) {
+        const FoamDict* pd = bf->subdict(names[pa]);
+        std::string ty;
+        if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), names[pa].c_str());
+        r.text[pa] = entry_text(*pd);
+        FY_TRY(patch_condition(c, F, path, pa, names[pa], *pd, ty, &r.bc[pa], &r.val[(size_t)ncomp * pa]));
+    }
+    return FY_OK;
+}
+
+// a block's field files, the six sides' conditions then copied into fy_case_desc
+int read_fields(fy_foam_case* c) {
+    FY_TRY(read_field(c, F_U, &c->U0));
+    FY_TRY(read_field(c, F_P, &c->p0));
+    if (has_field(c, F_NUT)) FY_TRY(read_field(c, F_NUT, &c->nut0, &c->desc.nut_initial));
+    if (has_field(c, F_K)) FY_TRY(read_field(c, F_K, &c->k0, &c->desc.k_initial));
+    if (has_field(c, F_EPS)) FY_TRY(read_field(c, F_EPS, &c->eps0, &c->desc.eps_initial));
+    fy_case_desc& d = c->desc;
+    const struct { int F; int32_t* bc; double* val; } to[] = {{F_U, d.u_bc, &d.u_value[0][0]}, {F_P, d.p_bc, d.p_value}, {F_NUT, d.nut_bc, d.nut_value},
+                                                             {F_K, d.k_bc, d.k_value}, {F_EPS, d.eps_bc, d.eps_value}};
+    for (const auto& t : to) {
+        if (!has_field(c, t.F)) continue;
+        std::copy(c->bcs[t.F].bc.begin(), c->bcs[t.F].bc.end(), t.bc);
+        std::copy(c->bcs[t.F].val.begin(), c->bcs[t.F].val.end(), t.val);
+    }
+    return FY_OK;
+}
+
+// a general mesh's field files: fy_foam_case_ldu_desc hands out the records (epsilon before k: an epsilonWallFunction looks at nut's patch)
+int read_general_fields(fy_foam_case* c) {
+    FY_TRY(read_field(c, F_U, &c->U0));
+    FY_TRY(read_field(c, F_P, &c->p0));
+    if (has_field(c, F_NUT)) FY_TRY(read_field(c, F_NUT, &c->nut0, &c->desc.nut_initial));
+    if (has_field(c, F_EPS)) FY_TRY(read_field(c, F_EPS, &c->eps0, &c->desc.eps_initial));
+    if (has_field(c, F_K)) FY_TRY(read_field(c, F_K, &c->k0, &c->desc.k_initial));
     return FY_OK;
 }
 
@@ -755,151 +783,6 @@ int read_general_mesh(fy_foam_case* c) {
         if (c->g_patch_neighbour[a] < 0) return fail(FY_ERR_INVALID, "%s/boundary: cyclic patch '%s': neighbourPatch '%s' is not another cyclic patch", base.c_str(), c->g_patch_name[a].c_str(), cyc_nbr[a].c_str());
     }
     c->patch_order = c->g_patch_name;
-    return FY_OK;
-}
-
-// <startTime>/U and p of a general mesh: one entry per patch, the types fy_ldu_solver takes (fixedValue / noSlip / zeroGradient; zeroGradient / fixedValue)
-int read_general_fields(fy_foam_case* c) {
-    const size_t ncell = (size_t)c->g_cells, np = c->g_patch_name.size();
-    c->g_u_bc.assign(np, FY_BC_U_FIXED_VALUE); c->g_p_bc.assign(np, FY_BC_P_ZERO_GRADIENT);
-    c->g_u_val.assign(3 * np, 0.0); c->g_p_val.assign(np, 0.0);
-    c->g_u_text.assign(np, std::string()); c->g_p_text.assign(np, std::string());
-    for (int which = 0; which < 2; ++which) {
-        const std::string path = join(c->fdir, c->start_name + "/" + (which ? std::string("p") : c->u_name));
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, which ? 1 : 3, ncell, which ? &c->p0 : &c->U0));
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        for (size_t pa = 0; pa < np; ++pa) {
-            const char* pn = c->g_patch_name[pa].c_str();
-            const FoamDict* pd = bf->subdict(c->g_patch_name[pa]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), pn);
-            (which ? c->g_p_text : c->g_u_text)[pa] = entry_text(*pd);
-            // [OF-6 fvPatchField::New]: a field's entry on a constraint patch must carry the patch's own type
-            if ((c->g_patch_class[pa] == "symmetryPlane" || c->g_patch_class[pa] == "symmetry" || c->g_patch_class[pa] == "cyclic") && c->g_patch_size[pa] > 0 && ty != c->g_patch_class[pa])
-                return fail(FY_ERR_INVALID, "%s: patch '%s' is a %s patch (constant/polyMesh/boundary): its entry must be of that type, not '%s'", path.c_str(), pn, c->g_patch_class[pa].c_str(), ty.c_str());
-            if (ty == "cyclic") { (which ? c->g_p_bc[pa] : c->g_u_bc[pa]) = which ? FY_BC_P_ZERO_GRADIENT : FY_BC_U_ZERO_GRADIENT; continue; }      // (folded into internal faces: the codes are not used)
-            const auto* vt = pd->tokens("value");
-            if (!which) {
-                if (ty == "fixedValue") {
-                    if (!vt || vt->empty() || (*vt)[0] != "uniform" || !pd->vector3("value", &c->g_u_val[3 * pa]))
-                        return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform (x y z)'", path.c_str(), pn);
-                } else if (ty == "zeroGradient") c->g_u_bc[pa] = FY_BC_U_ZERO_GRADIENT;
-                else if (ty == "symmetryPlane" || ty == "symmetry" || ty == "slip") c->g_u_bc[pa] = FY_BC_U_SLIP;      // (each face with its own normal: one and the same on a planar patch)
-                else if (ty != "noSlip") return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': velocity boundary type '%s' is not supported on a general mesh (fixedValue, noSlip, zeroGradient, symmetryPlane, symmetry, slip)", path.c_str(), pn, ty.c_str());
-            } else {
-                if (ty == "fixedValue") {
-                    c->g_p_bc[pa] = FY_BC_P_FIXED_VALUE;
-                    if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->g_p_val[pa]))
-                        return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <p>'", path.c_str(), pn);
-                } else if (ty == "fixedFluxPressure" && c->solver == FY_SOLVER_PIMPLE) c->g_p_bc[pa] = FY_BC_P_FIXED_FLUX;
-                else if (ty != "zeroGradient" && ty != "symmetryPlane" && ty != "symmetry")      // (a scalar on a symmetry patch: the cell value)
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': pressure boundary type '%s' is not supported on a general mesh (zeroGradient, symmetryPlane, symmetry, fixedValue; fixedFluxPressure with pimpleFoamYade)", path.c_str(), pn, ty.c_str());
-            }
-        }
-    }
-    if (c->desc.turbulence_model != FY_TURBULENCE_LAMINAR) {
-        // nut.<phase> [OF-6 eddyViscosity: MUST_READ]: patches zeroGradient | fixedValue (uniform) | calculated with a uniform value (= keeps its value: fixedValue here) |
-        // nutkWallFunction on a wall patch with kEqn / kEpsilon
-        const std::string path = join(c->fdir, c->start_name + "/nut." + c->phase);
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 1, ncell, &c->nut0));
-        c->desc.nut_initial = c->nut0.empty() ? 0.0 : c->nut0[0];
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        c->g_nut_bc.assign(np, FY_BC_NUT_ZERO_GRADIENT); c->g_nut_val.assign(np, 0.0); c->g_nut_text.assign(np, std::string());
-        int wf_patch = -1;                 // the first nutkWallFunction patch
-        for (size_t pa = 0; pa < np; ++pa) {
-            const char* pn = c->g_patch_name[pa].c_str();
-            const FoamDict* pd = bf->subdict(c->g_patch_name[pa]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), pn);
-            c->g_nut_text[pa] = entry_text(*pd);
-            const auto* vt = pd->tokens("value");
-            // [OF-6 nutWallFunctionFvPatchScalarField::checkType]: a wall function sits on a wall patch
-            if (ty.find("WallFunction") != std::string::npos && c->g_patch_class[pa] != "wall")
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s is a wall function, but the patch is of type '%s' (constant/polyMesh/boundary), not wall", path.c_str(), pn, ty.c_str(), c->g_patch_class[pa].c_str());
-            if (ty == "nutkWallFunction") {
-                if (c->desc.turbulence_model != FY_TURBULENCE_KEQN && c->desc.turbulence_model != FY_TURBULENCE_KEPSILON)
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': nutkWallFunction needs a model with a k equation (kEqn, kEpsilon)", path.c_str(), pn);
-                // [OF-6 nutkWallFunctionFvPatchScalarField]: Cmu / kappa / E per patch (defaults 0.09, 0.41, 9.8); one set serves the case here
-                c->g_nut_bc[pa] = FY_BC_WALL_FUNCTION;
-                if (vt && vt->size() >= 2 && (*vt)[0] == "uniform") fy::foam_tok_is_number((*vt)[1], &c->g_nut_val[pa]);
-                double cmu = c->desc.ras_cmu, kap = 0.41, E = 9.8;
-                pd->scalar("kappa", &kap); pd->scalar("E", &E);
-                if (pd->scalar("Cmu", &cmu) && cmu != c->desc.ras_cmu) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': a wall-function Cmu other than the model's is not supported", path.c_str(), pn);
-                if (wf_patch >= 0 && (kap != c->desc.wf_kappa || E != c->desc.wf_E))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patches '%s' and '%s' give nutkWallFunction different kappa / E: one set serves the case", path.c_str(), c->g_patch_name[(size_t)wf_patch].c_str(), pn);
-                c->desc.wf_kappa = kap; c->desc.wf_E = E;
-                wf_patch = (int)pa;
-            } else if (ty == "calculated" && (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON)) {      // the file's value until the first correctNut(), the model's expression afterwards
-                c->g_nut_bc[pa] = FY_BC_NUT_CALCULATED;
-                if (vt && vt->size() >= 2 && (*vt)[0] == "uniform") fy::foam_tok_is_number((*vt)[1], &c->g_nut_val[pa]);
-            } else if (ty == "fixedValue" || ty == "calculated") {
-                c->g_nut_bc[pa] = FY_BC_NUT_FIXED_VALUE;
-                if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->g_nut_val[pa]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s needs 'value uniform <nut>'", path.c_str(), pn, ty.c_str());
-            } else if (ty != "zeroGradient" && ty != "symmetryPlane" && ty != "symmetry" && ty != "cyclic") return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': nut boundary type '%s' is not supported on a general mesh (zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue, calculated; nutkWallFunction with kEqn / kEpsilon)", path.c_str(), pn, ty.c_str());
-        }
-    }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) {     // epsilon.<phase> [OF-6 kEpsilon: epsilon_ is MUST_READ]; zeroGradient | fixedValue (uniform) | epsilonWallFunction on a wall patch
-        const std::string path = join(c->fdir, c->start_name + "/epsilon." + c->phase);
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 1, ncell, &c->eps0));
-        c->desc.eps_initial = c->eps0.empty() ? 0.0 : c->eps0[0];
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        c->g_eps_bc.assign(np, FY_BC_NUT_ZERO_GRADIENT); c->g_eps_val.assign(np, 0.0); c->g_eps_text.assign(np, std::string());
-        for (size_t pa = 0; pa < np; ++pa) {
-            const char* pn = c->g_patch_name[pa].c_str();
-            const FoamDict* pd = bf->subdict(c->g_patch_name[pa]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), pn);
-            c->g_eps_text[pa] = entry_text(*pd);
-            const auto* vt = pd->tokens("value");
-            if (ty.find("WallFunction") != std::string::npos && c->g_patch_class[pa] != "wall")
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s is a wall function, but the patch is of type '%s' (constant/polyMesh/boundary), not wall", path.c_str(), pn, ty.c_str(), c->g_patch_class[pa].c_str());
-            if (ty == "fixedValue") {
-                c->g_eps_bc[pa] = FY_BC_NUT_FIXED_VALUE;
-                if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->g_eps_val[pa]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <epsilon>'", path.c_str(), pn);
-            } else if (ty == "epsilonWallFunction") {
-                // [OF-6 epsilonWallFunctionFvPatchScalarField::calculate: nutWallFunctionFvPatchScalarField::nutw(turbModel, patchi)]: kappa and E are the patch's nut wall function's
-                if (c->g_nut_bc[pa] != FY_BC_WALL_FUNCTION)
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': epsilonWallFunction takes its constants from the patch's nut wall function, and nut.%s is not nutkWallFunction there", path.c_str(), pn, c->phase.c_str());
-                c->g_eps_bc[pa] = FY_BC_WALL_FUNCTION;
-            } else if (ty != "zeroGradient" && ty != "symmetryPlane" && ty != "symmetry" && ty != "cyclic")
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': epsilon boundary type '%s' is not supported on a general mesh (zeroGradient, symmetryPlane, symmetry, cyclic, fixedValue, epsilonWallFunction)", path.c_str(), pn, ty.c_str());
-        }
-    }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) {         // k.<phase> [OF-6: k_ is MUST_READ]; patches zeroGradient | fixedValue (uniform); kqRWallFunction is a zeroGradient condition
-        const std::string path = join(c->fdir, c->start_name + "/k." + c->phase);
-        FoamDict f;
-        FY_TRY(need_file(path, &f));
-        FY_TRY(read_internal(f, path, 1, ncell, &c->k0));
-        c->desc.k_initial = c->k0.empty() ? 0.0 : c->k0[0];
-        const FoamDict* bf = f.subdict("boundaryField");
-        if (!bf) return fail(FY_ERR_INVALID, "%s: no boundaryField", path.c_str());
-        c->g_k_bc.assign(np, FY_BC_NUT_ZERO_GRADIENT); c->g_k_val.assign(np, 0.0); c->g_k_text.assign(np, std::string());
-        for (size_t pa = 0; pa < np; ++pa) {
-            const char* pn = c->g_patch_name[pa].c_str();
-            const FoamDict* pd = bf->subdict(c->g_patch_name[pa]);
-            std::string ty;
-            if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), pn);
-            c->g_k_text[pa] = entry_text(*pd);
-            const auto* vt = pd->tokens("value");
-            if (ty == "fixedValue") {
-                c->g_k_bc[pa] = FY_BC_NUT_FIXED_VALUE;
-                if (!vt || vt->size() < 2 || (*vt)[0] != "uniform" || !fy::foam_tok_is_number((*vt)[1], &c->g_k_val[pa]))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <k>'", path.c_str(), pn);
-            } else if (ty != "zeroGradient" && ty != "kqRWallFunction" && ty != "symmetryPlane" && ty != "symmetry" && ty != "cyclic")
-                return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': k boundary type '%s' is not supported on a general mesh (zeroGradient, kqRWallFunction, symmetryPlane, symmetry, cyclic, fixedValue)", path.c_str(), pn, ty.c_str());
-        }
-    }
     return FY_OK;
 }
 
@@ -1200,8 +1083,7 @@ int read_controls(fy_foam_case* c) {
 }
 
 int write_field(const fy_foam_case* c, const std::string& tdir, const std::string& tname, const std::string& name, const char* cls, const char* dims, int ncomp,
-                const std::vector<double>& v, const std::string bc_text[6], const char* default_bc,
-                const std::vector<std::pair<std::string, std::string> >* extras = nullptr) {
+                const std::vector<double>& v, const PatchField* bcs, const char* default_bc, const std::vector<std::pair<std::string, std::string> >& extras) {
     const std::string path = tdir + "/" + name;
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f) return fail(FY_ERR_INVALID, "cannot write %s", path.c_str());
@@ -1228,20 +1110,30 @@ int write_field(const fy_foam_case* c, const std::string& tdir, const std::strin
         }
     }
     std::fprintf(f, ")\n;\n\nboundaryField\n{\n");
-    if (c->general) {
-        const std::vector<std::string>& tx = bc_text == c->u_bc_text ? c->g_u_text : (bc_text == c->nut_bc_text ? c->g_nut_text : (bc_text == c->k_bc_text ? c->g_k_text : (bc_text == c->eps_bc_text ? c->g_eps_text : c->g_p_text)));
-        for (size_t pa = 0; pa < c->g_patch_name.size(); ++pa) std::fprintf(f, "    %s\n    {\n%s    }\n", c->g_patch_name[pa].c_str(), (!bc_text || tx[pa].empty()) ? default_bc : tx[pa].c_str());
-    }
-    for (const std::string& pn : c->general ? std::vector<std::string>() : c->patch_order) {
-        int side = -1;
-        for (int s = 0; s < 6; ++s) if (c->patch_of_side[s] == pn) side = s;
-        std::fprintf(f, "    %s\n    {\n%s    }\n", pn.c_str(), (bc_text && side >= 0 && !bc_text[side].empty()) ? bc_text[side].c_str() : default_bc);
+    // every patch in the mesh's order with its entry as read (a field without a start-time file -- alpha -- or without an entry: default_bc)
+    const std::vector<std::string> names = field_patches(c);
+    for (const std::string& pn : c->patch_order) {
+        size_t pa = names.size();
+        for (size_t q = 0; q < names.size(); ++q) if (names[q] == pn) pa = q;
+        const bool known = bcs && pa < bcs->text.size() && !bcs->text[pa].empty();
+        std::fprintf(f, "    %s\n    {\n%s    }\n", pn.c_str(), known ? bcs->text[pa].c_str() : default_bc);
     }
     // a decomposed case's processor patches, as the start time's file had them (fields without a start-time file: those of U, type only)
-    if (extras) for (const auto& e : *extras) std::fprintf(f, "    %s\n    {\n%s    }\n", e.first.c_str(), e.second.c_str());
+    for (const auto& e : extras) std::fprintf(f, "    %s\n    {\n%s    }\n", e.first.c_str(), e.second.c_str());
     std::fprintf(f, "}\n");
     std::fclose(f);
     return FY_OK;
+}
+
+// the fields the case has, read from a solver (read(name, host) in the given order: it decides which field a solver of another model is first missing) and written
+template <class Read>
+int write_solver_fields(const fy_foam_case* c, const char* time_name, std::initializer_list<int> order, Read read) {
+    static const char* const solver_name[] = {"U", "p", "nut", "k", "epsilon", "alpha"};
+    std::vector<double> v[6];
+    for (int F : order)
+        if (has_field(c, F)) { v[F].resize((F == F_U ? 3 : 1) * c->fcells); FY_TRY(read(solver_name[F], v[F].data())); }
+    auto ptr = [&](int F) { return v[F].empty() ? nullptr : v[F].data(); };
+    return fy_foam_case_write_fields(c, time_name, ptr(F_U), ptr(F_P), ptr(F_ALPHA), ptr(F_NUT), ptr(F_K), ptr(F_EPS));
 }
 
 }  // namespace
@@ -1359,24 +1251,23 @@ int fy_foam_case_write_fields(const fy_foam_case* c, const char* time_name, cons
     const size_t n = c->fcells;
     // (a field the start time had no file for -- alpha -- takes the processor patches of U with their type alone)
     std::vector<std::pair<std::string, std::string> > bare;
-    for (const auto& e : c->extra_patches[0]) {
+    for (const auto& e : c->bcs[F_U].extra) {
         const size_t a = e.second.find("type");
         const size_t b = a == std::string::npos ? a : e.second.find('\n', a);
         bare.emplace_back(e.first, (a == std::string::npos ? e.second : e.second.substr(0, b + 1)) + "        value uniform 1;\n");      // (alphac = 1 where nothing was deposited)
     }
     const char* zg = "        type            zeroGradient;\n";
     auto vec = [&](const double* src, int nc) { return std::vector<double>(src, src + n * (size_t)nc); };
-    FY_TRY(write_field(c, tdir, time_name, c->u_name, "volVectorField", "[0 1 -1 0 0 0 0]", 3, vec(U, 3), c->u_bc_text, zg, &c->extra_patches[0]));
-    FY_TRY(write_field(c, tdir, time_name, "p", "volScalarField", "[0 2 -2 0 0 0 0]", 1, vec(p, 1), c->p_bc_text, zg, &c->extra_patches[1]));
     // alphac is AUTO_WRITE (pimpleFoamYade/createFields.H:139-150) and is written BEFORE setSourceZero resets it (pimpleFoamYade.C:106-108):
-    // run the solver with fy_solver_hold_sources(s, 1) to get that
-    if (c->solver == FY_SOLVER_PIMPLE && alpha) FY_TRY(write_field(c, tdir, time_name, "alpha." + c->phase, "volScalarField", "[0 0 0 0 0 0 0]", 1, vec(alpha, 1), nullptr, zg, &bare));
-    if (c->desc.turbulence_model != FY_TURBULENCE_LAMINAR && nut)          // eddyViscosity::nut_ is AUTO_WRITE
-        FY_TRY(write_field(c, tdir, time_name, "nut." + c->phase, "volScalarField", "[0 2 -1 0 0 0 0]", 1, vec(nut, 1), c->nut_bc_text, zg, &c->extra_patches[2]));
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEPSILON && epsilon)
-        FY_TRY(write_field(c, tdir, time_name, "epsilon." + c->phase, "volScalarField", "[0 2 -3 0 0 0 0]", 1, vec(epsilon, 1), c->eps_bc_text, zg, &c->extra_patches[4]));
-    if ((c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) && k)
-        FY_TRY(write_field(c, tdir, time_name, "k." + c->phase, "volScalarField", "[0 2 -2 0 0 0 0]", 1, vec(k, 1), c->k_bc_text, zg, &c->extra_patches[3]));
+    // run the solver with fy_solver_hold_sources(s, 1) to get that.  eddyViscosity::nut_ is AUTO_WRITE, and so are k_ and epsilon_
+    const struct { int F; const double* v; const char* dims; } out[] = {{F_U, U, "[0 1 -1 0 0 0 0]"}, {F_P, p, "[0 2 -2 0 0 0 0]"}, {F_ALPHA, alpha, "[0 0 0 0 0 0 0]"},
+                                                                     {F_NUT, nut, "[0 2 -1 0 0 0 0]"}, {F_EPS, epsilon, "[0 2 -3 0 0 0 0]"}, {F_K, k, "[0 2 -2 0 0 0 0]"}};
+    for (const auto& o : out) {
+        if (!o.v || !has_field(c, o.F)) continue;
+        const int nc = o.F == F_U ? 3 : 1;
+        const PatchField* r = o.F == F_ALPHA ? nullptr : &c->bcs[o.F];
+        FY_TRY(write_field(c, tdir, time_name, field_name(c, o.F), nc == 3 ? "volVectorField" : "volScalarField", o.dims, nc, vec(o.v, nc), r, zg, r ? r->extra : bare));
+    }
     if (c->purge_write > 0) {
         // purgeWrite [OF-6 Time::writeObject]: once more than N time directories have been written, the oldest of them goes
         bool known = false;
@@ -1400,19 +1291,10 @@ int fy_foam_case_write_fields(const fy_foam_case* c, const char* time_name, cons
 
 int fy_foam_case_write_time(const fy_foam_case* c, fy_solver* s, const char* time_name) {
     if (!c || !s || !time_name || !*time_name) return fail(FY_ERR_INVALID, "fy_foam_case_write_time: null argument");
-    const size_t n = c->fcells;
     int64_t cnt = 0;
     FY_TRY(fy_solver_field_count(s, "p", &cnt));
-    if ((size_t)cnt != n) return fail(FY_ERR_UNSUPPORTED, "fy_foam_case_write_time: the solver holds %lld cells, the case's field files %zu (a slab of an undecomposed case: gather the slabs and use fy_foam_case_write_fields)", (long long)cnt, n);
-    std::vector<double> U(3 * n), p(n), a, nt, kk, ee;
-    FY_TRY(fy_solver_read_field_host(s, "U", U.data()));
-    FY_TRY(fy_solver_read_field_host(s, "p", p.data()));
-    if (c->solver == FY_SOLVER_PIMPLE) { a.resize(n); FY_TRY(fy_solver_read_field_host(s, "alpha", a.data())); }
-    if (c->desc.turbulence_model != FY_TURBULENCE_LAMINAR) { nt.resize(n); FY_TRY(fy_solver_read_field_host(s, "nut", nt.data())); }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) { ee.resize(n); FY_TRY(fy_solver_read_field_host(s, "epsilon", ee.data())); }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) { kk.resize(n); FY_TRY(fy_solver_read_field_host(s, "k", kk.data())); }
-    return fy_foam_case_write_fields(c, time_name, U.data(), p.data(), a.empty() ? nullptr : a.data(), nt.empty() ? nullptr : nt.data(), kk.empty() ? nullptr : kk.data(),
-                                     ee.empty() ? nullptr : ee.data());
+    if ((size_t)cnt != c->fcells) return fail(FY_ERR_UNSUPPORTED, "fy_foam_case_write_time: the solver holds %lld cells, the case's field files %zu (a slab of an undecomposed case: gather the slabs and use fy_foam_case_write_fields)", (long long)cnt, c->fcells);
+    return write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_EPS, F_K}, [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); });
 }
 
 int fy_foam_case_open_general(const char* case_dir, int solver, fy_foam_case** out) {
@@ -1462,15 +1344,16 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->u_relax = d.u_relax; out->u_relax_final = d.u_relax_final; out->p_relax = d.p_relax; out->p_relax_final = d.p_relax_final;
     out->adjust_time_step = d.adjust_time_step; out->max_co = d.max_co; out->max_delta_t = d.max_delta_t;
     out->turbulence_model = d.turbulence_model; out->les_ck = d.les_ck; out->les_ce = d.les_ce; out->les_delta_coeff = d.les_delta_coeff; out->nut_initial = d.nut_initial;
-    out->nut_bc = c->g_nut_bc.empty() ? nullptr : c->g_nut_bc.data(); out->nut_value = c->g_nut_val.empty() ? nullptr : c->g_nut_val.data();
+    const PatchField &U = c->bcs[F_U], &p = c->bcs[F_P], &nut = c->bcs[F_NUT], &k = c->bcs[F_K], &eps = c->bcs[F_EPS];      // (nut, k, epsilon: NULL where the case has no such field)
+    out->nut_bc = nut.bc.empty() ? nullptr : nut.bc.data(); out->nut_value = nut.val.empty() ? nullptr : nut.val.data();
     out->convection_scheme = d.convection_scheme; out->convection_limiter_k = d.convection_limiter_k;
-    out->k_initial = d.k_initial; out->k_bc = c->g_k_bc.empty() ? nullptr : c->g_k_bc.data(); out->k_value = c->g_k_val.empty() ? nullptr : c->g_k_val.data();
+    out->k_initial = d.k_initial; out->k_bc = k.bc.empty() ? nullptr : k.bc.data(); out->k_value = k.val.empty() ? nullptr : k.val.data();
     out->k_convection_scheme = d.k_convection_scheme; out->k_tol = d.k_tol; out->k_rel_tol = d.k_rel_tol; out->k_max_iter = d.k_max_iter; out->k_relax = d.k_relax;
     out->ras_cmu = d.ras_cmu; out->ras_c1 = d.ras_c1; out->ras_c2 = d.ras_c2; out->ras_c3 = d.ras_c3; out->ras_sigmak = d.ras_sigmak; out->ras_sigmaeps = d.ras_sigmaeps;
-    out->eps_initial = d.eps_initial; out->eps_bc = c->g_eps_bc.empty() ? nullptr : c->g_eps_bc.data(); out->eps_value = c->g_eps_val.empty() ? nullptr : c->g_eps_val.data();
+    out->eps_initial = d.eps_initial; out->eps_bc = eps.bc.empty() ? nullptr : eps.bc.data(); out->eps_value = eps.val.empty() ? nullptr : eps.val.data();
     out->eps_convection_scheme = d.eps_convection_scheme; out->eps_tol = d.eps_tol; out->eps_rel_tol = d.eps_rel_tol; out->eps_max_iter = d.eps_max_iter; out->eps_relax = d.eps_relax;
     out->wf_kappa = d.wf_kappa; out->wf_E = d.wf_E;
-    out->u_bc = c->g_u_bc.data(); out->u_value = c->g_u_val.data(); out->p_bc = c->g_p_bc.data(); out->p_value = c->g_p_val.data();
+    out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
     return FY_OK;
 }
 
@@ -1488,17 +1371,8 @@ int fy_foam_case_write_time_ldu(const fy_foam_case* c, fy_ldu_solver* s, const c
     int64_t cnt = 0;
     FY_TRY(fy_ldu_solver_field_count(s, "p", &cnt));
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_INVALID, "fy_foam_case_write_time_ldu: the solver holds %lld cells, the case %zu", (long long)cnt, c->fcells);
-    std::vector<double> U(3 * c->fcells), p(c->fcells), a;
-    FY_TRY(fy_ldu_solver_read_field_host(s, "U", U.data()));
-    FY_TRY(fy_ldu_solver_read_field_host(s, "p", p.data()));
-    std::vector<double> nt;
-    if (c->solver == FY_SOLVER_PIMPLE) { a.resize(c->fcells); FY_TRY(fy_ldu_solver_read_field_host(s, "alpha", a.data())); }       // (with fy_ldu_solver_hold_sources: before setSourceZero)
-    if (c->desc.turbulence_model != FY_TURBULENCE_LAMINAR) { nt.resize(c->fcells); FY_TRY(fy_ldu_solver_read_field_host(s, "nut", nt.data())); }
-    std::vector<double> kt;
-    std::vector<double> et;
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEQN || c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) { kt.resize(c->fcells); FY_TRY(fy_ldu_solver_read_field_host(s, "k", kt.data())); }
-    if (c->desc.turbulence_model == FY_TURBULENCE_KEPSILON) { et.resize(c->fcells); FY_TRY(fy_ldu_solver_read_field_host(s, "epsilon", et.data())); }
-    return fy_foam_case_write_fields(c, time_name, U.data(), p.data(), a.empty() ? nullptr : a.data(), nt.empty() ? nullptr : nt.data(), kt.empty() ? nullptr : kt.data(), et.empty() ? nullptr : et.data());
+    // (alpha: with fy_ldu_solver_hold_sources, before setSourceZero)
+    return write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_K, F_EPS}, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); });
 }
 
 int fy_foam_case_close(fy_foam_case* c) {
