@@ -2,9 +2,11 @@
 """Headline benchmark: coupled CFD-DEM steps/s at BASELINE.json configs[2] ("C3"):
 pimpleFoamYade 4-way coupling, 10 M particles, 160^3 = 4 096 000 cells, one MI355X.
 `--config c2` is BASELINE configs[1] at full size instead (icoFoamYade point force, 200 x 100 x 50 = 1 M-cell channel, 1 M particles).
-After the timed, HBM-resident region the same workload runs a few steps through the DROP-IN path (`--wire`, rank 0 of a single-GPU run):
-an in-process fake Yade (parallel-Yade protocol, 4 workers) hands the records over as host buffers through the fy_transport callbacks
-and takes the forces back, so that the PCIe copies and the wire-side host time are measured beside the headline number (never in it).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.  `--full` adds everything else the
+benchmark measures beside the headline (never in it), after the timed region: the moving bed, C2 at full size, the general-mesh solver, the
+DROP-IN path (`--wire`, rank 0 of a single-GPU run: a fake Yade hands the records over as host buffers through the fy_transport callbacks
+and takes the forces back, so that the PCIe copies and the wire-side host time are measured), the CPU baseline with the parity of the
+headline configuration, live PMC traffic, the pEqn Laplacian past the Infinity Cache and, for N > 1, the slab exchanges' waits.
 
 A "step" is one pass of pimpleFoamYade's time-loop body (pimpleFoamYade.C:60-114): Courant number, pre-coupling fields,
 FoamYade::setParticleAction (k-d locate, Gaussian weights, void-fraction deposit, drag + Archimedes, momentum-source
@@ -616,7 +618,7 @@ def live_pmc_traffic(extra_args, nc, steps=5, warmup=2, timeout=420):
         for tag in ("FETCH_SIZE", "WRITE_SIZE"):
             od = os.path.join(d, tag)
             cmd = [rp, "--pmc", tag, "--kernel-trace", "--output-format", "csv", "-d", od, "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--wire", "0", "--no-moving", "--no-extras", "--pmc", "0"] + extra_args
+                   "--steps", str(steps), "--warmup", str(warmup)] + extra_args          # a plain run: the timed loop alone
             env = dict(os.environ, TMPDIR="/tmp")
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout)
             files = glob.glob(os.path.join(od, "**", "*counter_collection.csv"), recursive=True)
@@ -745,27 +747,29 @@ def main():
     ap.add_argument("--particles", type=int, default=10_000_000)
     ap.add_argument("--dt", type=float, default=1e-4)
     ap.add_argument("--p-solver", type=int, default=1, help="0 PCG+Jacobi, 1 PCG+multigrid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample-n", type=int, default=0, help="CPU baseline on an n^3 sample of the workload instead of the full size (0 = full size)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, measure and check everything else beside the headline (see the module "
+                    "docstring); the options below that shape those records take effect with --full only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-sample-n", type=int, default=0, help="--full: CPU baseline on an n^3 sample of the workload instead of the full size (0 = full size)")
     ap.add_argument("--config", default="c3", choices=["c3", "c2", "c5"], help="c3: BASELINE configs[2] (the metric's configuration); c2: configs[1] at full size; "
                     "c5: configs[4] at full size (320^3 cells, 100 M particles, fluidized bed: bottom inlet, top outlet) -- on one GPU, or with --gpus N cut into N z-slabs")
-    ap.add_argument("--wire", type=int, default=2, help="steps of the drop-in (host-buffer / fake-Yade) leg after the timed region, 0 = skip")
-    ap.add_argument("--wire-workers", type=int, default=-1, help="Yade worker processes of the drop-in leg (-1: as many as the host's usable cores carry beside the solver side, at most 6)")
+    ap.add_argument("--wire", type=int, default=2, help="--full: steps of the drop-in (host-buffer / fake-Yade) leg after the timed region, 0 = skip")
+    ap.add_argument("--wire-workers", type=int, default=-1, help="--full: Yade worker processes of the drop-in leg (-1: as many as the host's usable cores carry beside the solver side, at most 6)")
     ap.add_argument("--laplacian-probe", type=int, default=0, help=argparse.SUPPRESS)       # child mode of laplacian_past_cache
     ap.add_argument("--laplacian-reps", type=int, default=40, help=argparse.SUPPRESS)
-    ap.add_argument("--no-extras", action="store_true", help="skip the C2 and general-mesh sub-records and the past-the-Infinity-Cache Laplacian probe of the default run")
-    ap.add_argument("--wire-helpers", type=int, default=-1, help="(-1: as many as --wire-workers) " "wire-helper ranks beside the computing rank in the drop-in leg over MPI (0: one solver rank receives everything)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the C2 and general-mesh sub-records and the past-the-Infinity-Cache Laplacian probe")
+    ap.add_argument("--wire-helpers", type=int, default=-1, help="--full: (-1: as many as --wire-workers) " "wire-helper ranks beside the computing rank in the drop-in leg over MPI (0: one solver rank receives everything)")
     ap.add_argument("--moving", action="store_true", help="not the BASELINE configuration: particles carry random velocities (+-0.05 m/s) and are displaced by "
                     "~0.1 dx per step (alternating random offsets, applied between the steps inside the timed region), so that the momentum deposit, "
                     "the re-bin amortisation and the pressure solver see a cloud that changes from step to step")
     ap.add_argument("--strong", action="store_true", help="N > 1: cut the ONE C3 box into N slabs (BASELINE configs[3]) instead of growing it (weak, the default)")
     ap.add_argument("--force-rccl", action="store_true", help="use the RCCL communicator even with one rank (smoke test of the RCCL path)")
     ap.add_argument("--rccl-selftest", default="", help=argparse.SUPPRESS)     # child mode: hex of the 128-byte RCCL id (see rccl_preflight)
-    ap.add_argument("--ref-as-written", action="store_true", help="also time oracle/_ref/ref_driver (FoamYade.C + meshTree.C as written, built in the development "
+    ap.add_argument("--ref-as-written", action="store_true", help="--full: also time oracle/_ref/ref_driver (FoamYade.C + meshTree.C as written, built in the development "
                     "container against a stand-in OpenFOAM header) on a small sample; off by default")
-    ap.add_argument("--no-moving", action="store_true", help="skip the moving-bed sub-record that follows the timed region (N = 1, C3 only)")
-    ap.add_argument("--pmc", type=int, default=-1, help="1: measure roofline.traffic live (two rocprofv3 --pmc child passes of this command, FETCH_SIZE and "
-                    "WRITE_SIZE, after everything else); 0: print null + the committed profile's path; -1 (default): live when rocprofv3 is there, N = 1, default C3")
+    ap.add_argument("--no-moving", action="store_true", help="--full: skip the moving-bed sub-record that follows the timed region (N = 1, C3 only)")
+    ap.add_argument("--pmc", type=int, default=-1, help="--full: 1: measure roofline.traffic live (two rocprofv3 --pmc child passes of this command's plain run, "
+                    "FETCH_SIZE and WRITE_SIZE, after everything else); 0: print null + the committed profile's path; -1 (default): live when rocprofv3 is there, N = 1, default C3")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed region write what its last step computed -- the particles' forces "
                     "(Np x 6) and found flags, the fluid's U (cells x 3) and p -- as DIR/<name>.npy (rank<r>_<name>.npy for N > 1); arrays of more than "
                     f"{DUMP_ROWS:,} rows (divided by N) keep a fixed, seeded sample of them (44 MB in all at most)")
@@ -773,6 +777,8 @@ def main():
     args = ap.parse_args(json.loads(handed) if (handed and len(sys.argv) == 1) else None)
     if args.steps < 1:
         ap.error("--steps: at least one timed step")
+    if not args.full and (args.pmc == 1 or args.ref_as_written):
+        ap.error("--pmc 1 and --ref-as-written measure beside the headline: add --full")
     if args.rccl_selftest:
         rccl_selftest_child(args)
     if args.laplacian_probe:
@@ -1088,7 +1094,8 @@ def main():
     if dumped is not None:
         out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "rows": dumped, "seed": DUMP_SEED,
                                  "what": "the last timed step's forces, found flags, U and p; [rows kept, rows computed] per array"}
-    if world > 1 and slabs_ok >= 1.0:
+    # ---- the records beside the headline, each measured after the timed region, run with --full only: a plain run adds traffic_note and prints the line
+    if args.full and world > 1 and slabs_ok >= 1.0:
         # how long each rank's stream sat waiting for slab exchanges, by phase -- sampled in a few EXTRA steps after the timed region (the clock costs an
         # event pair per exchange, which would slow the steps it measures).  FOAMYADE_HALO_OVERLAP=0 runs the exchange-then-consume schedule: the A/B
         try:
@@ -1113,7 +1120,7 @@ def main():
                              for r, t in enumerate(allw)]}
         except Exception as e:                                        # noqa: BLE001  (reported in the line)
             out["exchange_wait"] = {"error": f"{type(e).__name__}: {e}"}
-    if default_c3 and world == 1 and not args.moving and not args.no_moving:
+    if args.full and default_c3 and world == 1 and not args.moving and not args.no_moving:
         # the BASELINE cloud is at rest and identical every step -- the workload's best case (1 PCG iteration per solve, zero momentum deposits
         # skipped, re-bin amortised).  The same run with a cloud that MOVES, for the same number of steps, so that the spread is in this record
         rec0 = rec.clone()
@@ -1124,7 +1131,7 @@ def main():
                          "per_step_ms": per_step(macc, K)}
         rec.copy_(rec0)
         del rec0
-    if rank == 0 and world == 1 and default_c3 and not args.moving and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and default_c3 and not args.moving and not args.no_extras:
         # driver-observed since round 4: BASELINE configs[1] at full size, and the pEqn Laplacian where no cache holds it
         try:
             out["c2"] = c2_subrecord(prod, torch, dev, local_rank)
@@ -1138,7 +1145,7 @@ def main():
         args.wire_workers = max(2, min(6, (cpu_info()[1] - 2) // 2))
     if args.wire_helpers < 0:
         args.wire_helpers = args.wire_workers
-    if rank == 0 and world == 1 and args.wire > 0:
+    if args.full and rank == 0 and world == 1 and args.wire > 0:
         # the drop-in leg needs the device memory: the HBM-resident solver is done
         rec_host = rec.cpu().numpy()
         solver.close(); solver = None
@@ -1163,7 +1170,7 @@ def main():
             out["per_step_ms"].update({"h2d": dp["per_step_ms"]["h2d"], "d2h": dp["per_step_ms"]["d2h"],
                                        "wire": round(dp["per_step_ms"]["wire_recv"] + dp["per_step_ms"]["wire_send"], 3)})
             out["per_step_ms_note"] = "h2d / d2h / wire are the drop-in leg's (host buffers through the transport), measured after the timed region; every other entry and `value` are the HBM-resident run"
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         model, ncores = cpu_info()
         full = args.cpu_sample_n == 0 and not c5                  # C5 at full size would be minutes per CPU step: a 96^3 sample of it by default
         n_s = (100 if c2 else args.n) if full else (args.cpu_sample_n or 96)
@@ -1199,7 +1206,7 @@ def main():
         # roofline.traffic: measured live or null (never a committed figure passed off as this run's)
         committed = sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
         note = "not measured in this run" + (f"; the builder's committed passes of the same command: {os.path.relpath(committed[-1], ROOT)}" if committed else "")
-        want = args.pmc == 1 or (args.pmc < 0 and default_c3 and not args.moving)
+        want = args.full and (args.pmc == 1 or (args.pmc < 0 and default_c3 and not args.moving))
         if want:
             solver_closed = solver is None
             if not solver_closed:
@@ -1218,7 +1225,7 @@ def main():
             else:
                 note = f"live PMC pass failed ({why}); " + note
         out["traffic_note"] = note
-        if default_c3 and not args.moving and not args.no_extras and args.pmc != 0:
+        if args.full and default_c3 and not args.moving and not args.no_extras and args.pmc != 0:
             if solver is not None:
                 solver.close(); solver = None
             torch.cuda.empty_cache()

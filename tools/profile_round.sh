@@ -6,10 +6,10 @@ R=$GRAFT_REPO_ROOT
 RND=${RND:-r03}
 O=$R/gpurun_out/$RND
 rm -rf $O; mkdir -p $O
-python $R/bench.py > $O/bench_line.json 2> $O/bench.err
+python $R/bench.py --full > $O/bench_line.json 2> $O/bench.err
 tail -c 300 $O/bench_line.json
-python $R/bench.py --config c2 --wire 0 > $O/bench_line_c2.json 2> $O/bench_c2.err
-python $R/bench.py --config c5 --steps 5 --warmup 2 --pmc 1 --wire 0 > $O/bench_line_c5.json 2> $O/bench_c5.err
+python $R/bench.py --full --config c2 --wire 0 > $O/bench_line_c2.json 2> $O/bench_c2.err
+python $R/bench.py --full --config c5 --steps 5 --warmup 2 --pmc 1 --wire 0 > $O/bench_line_c5.json 2> $O/bench_c5.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -- python $R/bench.py --no-cpu-baseline --wire 0 --pmc 0 --no-moving > $O/ks.log 2>&1
 cd $R
 # bench.py runs its sub-records (C2, general mesh, Laplacian probe) in child processes, each with its own csv: the timed loop's is the one that holds k_locate_deposit most often
