@@ -49,6 +49,7 @@ public:
     void setSourceZero() { check(fy_set_source_zero(ctx_)); }                                                                    // FoamYade.C:556-566
     // opt-in: the two force models the reference carries without a call site (FoamYade.C:392-413, 465-479); default off = shipped behaviour
     void setForceModels(unsigned flags) { check(fy_set_force_models(ctx_, flags)); }
+    void setDragLaw(int law) { check(fy_set_drag_law(ctx_, law)); }            // FY_DRAG_*
     // FoamYade.H:102: a PUBLIC flag the reference's callers set by assignment (`yadeCoupling.fibreCpl = true;`); it is read at the top of
     // setParticleAction here, so that an unchanged caller gets the 15-double records it asked for (setFibreCoupling does the same at once)
     bool fibreCpl = false;

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 14
+#define FY_ABI_VERSION 15
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -140,10 +140,28 @@ int fy_set_scalar_properties(fy_ctx*, double rhoP, double rhoF, double nu);
  *                             reads fields.vGrad and the angular velocity of the records; fills force[3..5]
  *   FY_FORCE_ADDED_MASS       addedMassForce, FoamYade.C:392-413 (never called): reads fields.ddtU and the dt passed to
  *                             fy_set_particle_action; adds to force[0..2] and back-scatters into uSource
+ * A third flag is a model the reference does not have at all:
+ *   FY_FORCE_SAFFMAN_MEI_LIFT Saffman's shear lift with Mei's finite-Reynolds-number factor on the interpolated vorticity w = curl U (reads fields.vGrad):
+ *                             Re_p = |u_r| d / nu, Re_w = |w| d^2 / nu, b = Re_w / (2 (Re_p + small)), a = 0.3314 sqrt(b),
+ *                             f = Re_p < 40 ? (1 - a) exp(-Re_p / 10) + a : 0.0524 sqrt(b Re_p), Cl = 3 / (2 pi sqrt(Re_w + small)) 6.46 f,
+ *                             F = rho_f pv Cl (u_r x w); adds to force[0..2] and back-scatters into uSource like Archimedes' force
  * Returns FY_ERR_INVALID in point-force mode or when the field a model needs was not supplied to fy_create. */
 #define FY_FORCE_ADDED_MASS 1u
 #define FY_FORCE_GAUSSIAN_TORQUE 2u
+#define FY_FORCE_SAFFMAN_MEI_LIFT 4u
 int fy_set_force_models(fy_ctx*, unsigned flags);
+/* The drag closure.  FY_DRAG_REFERENCE (the default) is what FoamYade computes: Wen-Yu / Ergun switched at alpha_f = 0.8 in Gaussian mode
+ * (FoamYade.C:366-382), Stokes drag in point-force mode (FoamYade.C:437-444).  The others replace it; with eps = alpha_f, phi = max(1 - eps, 0),
+ * m = |u_r| and Re = small + m d / nu they give K = beta / phi, the force pv K u_r and the scattered coefficient K phi (formulas: DESIGN.md section 3):
+ *   Gaussian mode    FY_DRAG_DI_FELICE, FY_DRAG_KOCH_HILL, FY_DRAG_BEETSTRA
+ *   point-force mode FY_DRAG_SCHILLER_NAUMANN: Stokes drag times f = Re < 1000 ? 1 + 0.15 Re^0.687 : 0.44 Re / 24
+ * One law for all particles.  Returns FY_ERR_INVALID (the message lists the names the mode accepts) for a law of the other mode or an unknown value. */
+#define FY_DRAG_REFERENCE 0
+#define FY_DRAG_DI_FELICE 1
+#define FY_DRAG_KOCH_HILL 2
+#define FY_DRAG_BEETSTRA 3
+#define FY_DRAG_SCHILLER_NAUMANN 4
+int fy_set_drag_law(fy_ctx*, int law);
 /* FoamYade::fibreCpl (public flag, FoamYade.H:102; off by default and never set by the two solvers).  When on, Yade sends 15 doubles per
  * particle instead of 10 (FoamYade.C:131-136 parallel, :161-165 serial) and the position is read with that stride (:194-198) while
  * velocity, spin and radius are still read from buf[np*10+3..9] of the same buffer (:211-221) -- mirrored literally.  After this call
@@ -314,6 +332,10 @@ typedef struct fy_case_desc {
        block runs on one domain) */
     const double *hx, *hy, *hz;
     double convection_limiter_k;            /* FY_CONVECTION_LIMITED_LINEAR: the k of `Gauss limitedLinear k` (fy_case_defaults: 1) */
+    /* constant/couplingProperties (optional; zero = the reference's behaviour): applied to the solver's coupling object at fy_solver_create with
+       fy_set_drag_law / fy_set_force_models, whose refusals (a law of the other mode, models in point-force mode) then fail the create */
+    int32_t drag_law;                       /* FY_DRAG_* */
+    uint32_t force_models;                  /* FY_FORCE_* flags */
 } fy_case_desc;
 
 typedef struct fy_solver fy_solver;
@@ -544,6 +566,8 @@ typedef struct fy_ldu_case {
     double eps_tol, eps_rel_tol; int32_t eps_max_iter;
     double eps_relax;
     double wf_kappa, wf_E;           /* the wall functions' constants [OF-6 nutkWallFunction]; fy_ldu_case_defaults: 0.41, 9.8 */
+    int32_t drag_law;                /* constant/couplingProperties as in fy_case_desc: FY_DRAG_* and FY_FORCE_* flags, zero = the reference's behaviour */
+    uint32_t force_models;
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */

@@ -22,6 +22,9 @@ def main():
     ap.add_argument("--vel", type=float, default=0.0, help="particle velocity scale (0: at rest, the C3 cloud)")
     ap.add_argument("--mesh", default="block", help="block | wavy: the block's centres displaced by 0.6 dx sin sin sin, handed over as a general mesh (explicit k-d tree: "
                     "k_locate<false>, k_deposit)")
+    ap.add_argument("--drag", default="reference", help="drag closure (fy_set_drag_law): reference | DiFelice | KochHill | Beetstra in Gaussian mode, reference | SchillerNaumann "
+                    "in point mode; several names separated by commas are timed one after the other on the same inputs")
+    ap.add_argument("--lift", action="store_true", help="with the Saffman-Mei lift (Gaussian mode)")
     a = ap.parse_args()
     import torch
     prod = ge.load_product()
@@ -62,16 +65,23 @@ def main():
     fy.setScalarProperties(2650.0, 1000.0, 1e-6)
     fy.enable_timing(True)
     fy.setParticlesDevice([rec])
-    for s in range(a.steps):
-        torch.cuda.synchronize()
-        t0 = time.time()
-        fy.setParticleAction(1e-4)
-        torch.cuda.synchronize()
-        wall = (time.time() - t0) * 1e3
-        t = fy.timings()
-        print(f"step {s}: wall {wall:.2f} ms | bin {t['bin']:.2f} locate+deposit {t['locate_deposit']:.2f} finalize {t['finalize']:.2f} "
-              f"force {t['force']:.2f} total {t['total']:.2f}", flush=True)
-        fy.setSourceZero()
+    if a.lift:
+        fy.setForceModels(prod.FORCE_SAFFMAN_MEI_LIFT)
+    for drag in a.drag.split(","):
+        fy.setDragLaw(prod.DRAG_LAWS[drag])
+        force = []
+        for s in range(a.steps):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            fy.setParticleAction(1e-4)
+            torch.cuda.synchronize()
+            wall = (time.time() - t0) * 1e3
+            t = fy.timings()
+            force.append(t["force"])
+            print(f"{drag} step {s}: wall {wall:.2f} ms | bin {t['bin']:.2f} locate+deposit {t['locate_deposit']:.2f} finalize {t['finalize']:.2f} "
+                  f"force {t['force']:.2f} total {t['total']:.2f}", flush=True)
+            fy.setSourceZero()
+        print(f"{drag}{' + lift' if a.lift else ''}: force pass median {np.median(force[1:] or force):.3f} ms over {len(force[1:] or force)} steps (first step left out)", flush=True)
     k = fy.stencils(0)[0] if a.np <= 2_000_000 else None
     if k is not None:
         print("mean k", k[k > 0].mean(), "found", (k > 0).mean())

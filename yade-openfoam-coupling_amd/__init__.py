@@ -25,7 +25,10 @@ MAXK = 16
 
 FY_OK = 0
 FY_ERR_NO_DEVICE = 2
-FORCE_ADDED_MASS, FORCE_GAUSSIAN_TORQUE = 1, 2        # fy_set_force_models flags
+FORCE_ADDED_MASS, FORCE_GAUSSIAN_TORQUE, FORCE_SAFFMAN_MEI_LIFT = 1, 2, 4        # fy_set_force_models flags
+DRAG_REFERENCE, DRAG_DI_FELICE, DRAG_KOCH_HILL, DRAG_BEETSTRA, DRAG_SCHILLER_NAUMANN = 0, 1, 2, 3, 4      # fy_set_drag_law
+DRAG_LAWS = {"reference": DRAG_REFERENCE, "DiFelice": DRAG_DI_FELICE, "KochHill": DRAG_KOCH_HILL, "Beetstra": DRAG_BEETSTRA,
+             "SchillerNaumann": DRAG_SCHILLER_NAUMANN}       # constant/couplingProperties dragModel words
 FY_MEM_HOST, FY_MEM_DEVICE = 0, 1
 FY_T_INT, FY_T_DOUBLE = 0, 1
 FY_OP_MAX, FY_OP_SUM = 0, 1
@@ -94,7 +97,8 @@ class LduCase(C.Structure):
                 ("k_convection_scheme", C.c_int32), ("k_tol", C.c_double), ("k_rel_tol", C.c_double), ("k_max_iter", C.c_int32), ("k_relax", C.c_double),
                 ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double), ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double),
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
-                ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double)]
+                ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32)]
 
 
 class ParticleTimings(C.Structure):
@@ -125,7 +129,8 @@ class CaseDesc(C.Structure):
                 ("ras_sigmaeps", C.c_double), ("eps_bc", C.c_int32 * 6), ("eps_value", C.c_double * 6), ("eps_initial", C.c_double),
                 ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double), ("eps_max_iter", C.c_int32),
                 ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
-                ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double)]
+                ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double),
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32)]
 
 
 BC_WALL_FUNCTION, BC_NUT_CALCULATED = 2, 3
@@ -189,6 +194,7 @@ def lib():
     L.fy_set_scalar_properties.argtypes = [vp, C.c_double, C.c_double, C.c_double]
     L.fy_set_particle_action.argtypes = [vp, C.c_double]
     L.fy_set_force_models.argtypes = [vp, C.c_uint]
+    L.fy_set_drag_law.argtypes = [vp, C.c_int]
     L.fy_set_fibre_coupling.argtypes = [vp, C.c_int]
     L.fy_set_source_zero.argtypes = [vp]
     L.fy_finalize_run.argtypes = [vp, C.POINTER(C.c_int)]
@@ -420,6 +426,10 @@ class FoamYade:
         """opt-in models the reference has no call site for: FORCE_ADDED_MASS (FoamYade.C:392-413) | FORCE_GAUSSIAN_TORQUE
         (FoamYade.C:465-479, commented out at :618)"""
         _check(lib().fy_set_force_models(self._h, int(flags)))
+
+    def setDragLaw(self, law):
+        """fy_set_drag_law: DRAG_REFERENCE (the default), DRAG_DI_FELICE | DRAG_KOCH_HILL | DRAG_BEETSTRA in Gaussian mode, DRAG_SCHILLER_NAUMANN in point mode"""
+        _check(lib().fy_set_drag_law(self._h, int(law)))
 
     def setFibreCoupling(self, on):
         """FoamYade::fibreCpl (FoamYade.H:102): records become 15 doubles per particle (FoamYade.C:131-136,161-165,189-198)"""
@@ -655,6 +665,10 @@ class Solver:
     def set_force_models(self, flags):
         """fy_set_force_models on the embedded coupling object (Gaussian torque / added mass, off by default)"""
         _check(lib().fy_set_force_models(self._cpl, int(flags)))
+
+    def set_drag_law(self, law):
+        """fy_set_drag_law on the embedded coupling object (DRAG_*)"""
+        _check(lib().fy_set_drag_law(self._cpl, int(law)))
 
     def set_particles(self, records):
         """direct mode: the particle records the next step() will couple with ((n,10) host array, or None for none)"""
@@ -1211,6 +1225,14 @@ class LduSolver:
         out = np.zeros(self.n_cells)
         _check(L.fy_ldu_solver_apply(self._h, op.encode(), _d(x), _d(out)))
         return out
+
+    def set_drag_law(self, law):
+        """fy_set_drag_law on the embedded coupling object (DRAG_*)"""
+        _check(lib().fy_set_drag_law(self._cpl, int(law)))
+
+    def set_force_models(self, flags):
+        """fy_set_force_models on the embedded coupling object (pimpleFoamYade: Gaussian mode)"""
+        _check(lib().fy_set_force_models(self._cpl, int(flags)))
 
     def set_particles(self, records):
         L = lib()

@@ -401,7 +401,7 @@ int Coupling::stage_readonly_in() {
     if (gaussian) {
         FY_HIP(hipMemcpyAsync(own_gradP.p, fields.gradP, 3 * n, hipMemcpyHostToDevice, stream));
         FY_HIP(hipMemcpyAsync(own_divT.p, fields.divT, 3 * n, hipMemcpyHostToDevice, stream));
-        if (force_models & FY_FORCE_GAUSSIAN_TORQUE) FY_HIP(hipMemcpyAsync(own_vGrad.p, fields.vGrad, 9 * n, hipMemcpyHostToDevice, stream));
+        if (force_models & (FY_FORCE_GAUSSIAN_TORQUE | FY_FORCE_SAFFMAN_MEI_LIFT)) FY_HIP(hipMemcpyAsync(own_vGrad.p, fields.vGrad, 9 * n, hipMemcpyHostToDevice, stream));
         if (force_models & FY_FORCE_ADDED_MASS) FY_HIP(hipMemcpyAsync(own_ddtU.p, fields.ddtU, 3 * n, hipMemcpyHostToDevice, stream));
     } else {
         FY_HIP(hipMemcpyAsync(own_vGrad.p, fields.vGrad, 9 * n, hipMemcpyHostToDevice, stream));
@@ -412,15 +412,29 @@ int Coupling::stage_readonly_in() {
 // Opt-in force models without a call site in the reference (see foamyade_hip.h)
 int Coupling::set_force_models(unsigned flags) {
     if (!created) return fail(FY_ERR_INVALID, "fy_set_force_models before fy_create");
-    if (flags & ~(FY_FORCE_ADDED_MASS | FY_FORCE_GAUSSIAN_TORQUE)) return fail(FY_ERR_INVALID, "fy_set_force_models: unknown flag");
+    if (flags & ~(FY_FORCE_ADDED_MASS | FY_FORCE_GAUSSIAN_TORQUE | FY_FORCE_SAFFMAN_MEI_LIFT)) return fail(FY_ERR_INVALID, "fy_set_force_models: unknown flag");
     if (flags && !gaussian) return fail(FY_ERR_INVALID, "fy_set_force_models: Gaussian mode only (point mode always runs stokesDragTorque)");
-    if ((flags & FY_FORCE_GAUSSIAN_TORQUE) && !(fields_on_host ? fields.vGrad : dVGrad)) return fail(FY_ERR_INVALID, "Gaussian torque needs vGrad");
+    if ((flags & (FY_FORCE_GAUSSIAN_TORQUE | FY_FORCE_SAFFMAN_MEI_LIFT)) && !(fields_on_host ? fields.vGrad : dVGrad))
+        return fail(FY_ERR_INVALID, "Gaussian torque and Saffman-Mei lift need vGrad");
     if ((flags & FY_FORCE_ADDED_MASS) && !(fields_on_host ? fields.ddtU : dDdtU)) return fail(FY_ERR_INVALID, "added mass needs ddtU");
     if (fields_on_host && (flags & FY_FORCE_ADDED_MASS) && !own_ddtU.p) {
         FY_TRY(own_ddtU.alloc_exact(3 * (size_t)n_cells));
         dDdtU = own_ddtU.p;
     }
     force_models = flags;
+    return FY_OK;
+}
+
+// The drag closure (see foamyade_hip.h): which instantiation of the force kernel the launchers pick
+int Coupling::set_drag_law(int law) {
+    if (!created) return fail(FY_ERR_INVALID, "fy_set_drag_law before fy_create");
+    const bool known = law >= FY_DRAG_REFERENCE && law <= FY_DRAG_SCHILLER_NAUMANN;
+    const bool fits = law == FY_DRAG_REFERENCE || (gaussian ? law != FY_DRAG_SCHILLER_NAUMANN : law == FY_DRAG_SCHILLER_NAUMANN);
+    if (!known || !fits)
+        return fail(FY_ERR_INVALID, "fy_set_drag_law: %s %d; %s mode accepts %s", known ? "no kernel in this mode for law" : "unknown law", law,
+                    gaussian ? "Gaussian" : "point-force",
+                    gaussian ? "FY_DRAG_REFERENCE, FY_DRAG_DI_FELICE, FY_DRAG_KOCH_HILL, FY_DRAG_BEETSTRA" : "FY_DRAG_REFERENCE, FY_DRAG_SCHILLER_NAUMANN");
+    drag_law = law;
     return FY_OK;
 }
 
@@ -620,7 +634,7 @@ int Coupling::ensure_found(Batch& b) {
 // the device part of setParticleAction for one Yade proc (FoamYade.C:612-628 loop body)
 int Coupling::run_batch(Batch& b) {
     if (b.n == 0 && !slab.active) return FY_OK;      // (in slab mode the halo exchanges are collective: every rank walks the same path)
-    ForceParams fp{rhoF, nu, 1e-09, rhoP, delta_t, force_models, 0, vol_uniform ? v0 : 0.0};
+    ForceParams fp{rhoF, nu, 1e-09, rhoP, delta_t, force_models, 0, vol_uniform ? v0 : 0.0, drag_law};
     if (gaussian) {
         ParticleSoA p = soa_of(b);
         if (timing) marks.mark(0, stream);
@@ -1471,6 +1485,7 @@ int fy_create(const fy_mesh_desc* mesh, const fy_field_ptrs* fields, int gaussia
 
 int fy_set_scalar_properties(fy_ctx* c, double rhoP, double rhoF, double nu) { FY_CTX(c); c->c.rhoP = rhoP; c->c.rhoF = rhoF; c->c.nu = nu; return FY_OK; }
 int fy_set_force_models(fy_ctx* c, unsigned flags) { FY_CTX(c); return c->c.set_force_models(flags); }
+int fy_set_drag_law(fy_ctx* c, int law) { FY_CTX(c); return c->c.set_drag_law(law); }
 int fy_set_fibre_coupling(fy_ctx* c, int on) { FY_CTX(c); return c->c.set_fibre_coupling(on); }
 int fy_set_particle_action(fy_ctx* c, double dt) { FY_CTX(c); return c->c.set_particle_action(dt); }
 int fy_set_source_zero(fy_ctx* c) { FY_CTX(c); return c->c.set_source_zero(); }

@@ -138,6 +138,7 @@ struct Coupling {
     const double *dU = nullptr, *dGradP = nullptr, *dVGrad = nullptr, *dDivT = nullptr, *dDdtU = nullptr;
     bool fibre = false;                  // fibreCpl (FoamYade.H:102)
     unsigned force_models = 0;           // FY_FORCE_*: the reference's call-site-less models (off = shipped behaviour)
+    int drag_law = FY_DRAG_REFERENCE;    // FY_DRAG_*: fy_set_drag_law
     double *dUSourceDrag = nullptr, *dAlpha = nullptr, *dUSource = nullptr, *dUParticle = nullptr;
     DevBuf<double> d_pvol_acc, d_up_acc;           // per-batch deposit accumulators (pVolContrib / uParticleContrib)
     bool cellrec_fresh = false;                    // d_cellrec was packed in this setParticleAction call
@@ -202,6 +203,7 @@ struct Coupling {
     int ensure_found(Batch& b);
     int run_batch(Batch& b);
     int set_force_models(unsigned flags);
+    int set_drag_law(int law);
     int set_fibre_coupling(int on);
     int rec_len() const { return fibre ? 15 : 10; }   // doubles per particle on the wire (FoamYade.C:131-136)
     int set_particle_action(double dt);

@@ -805,6 +805,44 @@ int check_general_schemes(const fy_foam_case* c) {
     return FY_OK;
 }
 
+
+// constant/couplingProperties (optional; not a file of the reference, whose closures are fixed in FoamYade.C): the drag closure and the opt-in force
+// models of the case's coupling object -- fy_set_drag_law / fy_set_force_models, applied when a solver is made from the case.  One reader for block and
+// general cases; a missing file or entry leaves the reference's behaviour, a word the case's solver cannot take is refused here
+int read_coupling_properties(fy_foam_case* c) {
+    c->desc.drag_law = FY_DRAG_REFERENCE; c->desc.force_models = 0;
+    const std::string path = join(c->dir, "constant/couplingProperties");
+    if (!file_exists(path)) return FY_OK;
+    FoamDict d;
+    FY_TRY(need_file(path, &d));
+    const bool gaussian = c->solver == FY_SOLVER_PIMPLE;          // pimpleFoamYade.C:52; icoFoamYade couples point forces (icoFoamYade.C:53)
+    const char* solver = gaussian ? "pimpleFoamYade" : "icoFoamYade";
+    std::string w;
+    if (d.word("dragModel", &w)) {
+        static const struct { const char* word; int law; bool gaussian, point; } laws[] = {
+            {"reference", FY_DRAG_REFERENCE, true, true}, {"DiFelice", FY_DRAG_DI_FELICE, true, false}, {"KochHill", FY_DRAG_KOCH_HILL, true, false},
+            {"Beetstra", FY_DRAG_BEETSTRA, true, false}, {"SchillerNaumann", FY_DRAG_SCHILLER_NAUMANN, false, true}};
+        bool ok = false;
+        for (const auto& l : laws) if (w == l.word && (gaussian ? l.gaussian : l.point)) { c->desc.drag_law = l.law; ok = true; }
+        if (!ok) return fail(FY_ERR_UNSUPPORTED, "%s: dragModel %s; %s accepts %s", path.c_str(), w.c_str(), solver,
+                             gaussian ? "reference | DiFelice | KochHill | Beetstra" : "reference | SchillerNaumann");
+    }
+    if (d.word("liftModel", &w)) {
+        if (w == "SaffmanMei" && gaussian) c->desc.force_models |= FY_FORCE_SAFFMAN_MEI_LIFT;
+        else if (w != "none") return fail(FY_ERR_UNSUPPORTED, "%s: liftModel %s; %s accepts %s", path.c_str(), w.c_str(), solver, gaussian ? "none | SaffmanMei" : "none");
+    }
+    const struct { const char* key; unsigned flag; } switches[] = {{"addedMass", FY_FORCE_ADDED_MASS}, {"gaussianTorque", FY_FORCE_GAUSSIAN_TORQUE}};
+    for (const auto& sw : switches) {
+        if (!d.has(sw.key)) continue;
+        bool on = false;
+        d.word(sw.key, &w);
+        if (!d.boolean(sw.key, &on) || (on && !gaussian))
+            return fail(FY_ERR_UNSUPPORTED, "%s: %s %s; %s accepts %s", path.c_str(), sw.key, w.c_str(), solver, gaussian ? "on | off" : "off");
+        if (on) c->desc.force_models |= sw.flag;
+    }
+    return FY_OK;
+}
+
 int read_controls(fy_foam_case* c) {
     {
         const std::string path = join(c->dir, "system/controlDict");
@@ -882,6 +920,7 @@ int read_controls(fy_foam_case* c) {
         FY_TRY(need_file(path, &d));          // readGravitationalAcceleration.H (createFields.H:1 of both solvers)
         if (!d.vector3("value", c->desc.g)) return fail(FY_ERR_INVALID, "%s: 'value (gx gy gz)' missing", path.c_str());
     }
+    FY_TRY(read_coupling_properties(c));
     if (c->solver == FY_SOLVER_PIMPLE) {
         // continuousPhaseTurbulence (pimpleFoamYade/createFields.H): PhaseIncompressibleTurbulenceModel::New reads
         // constant/turbulenceProperties.<phase> [OF-6: IOobject::groupName(turbulenceModel::propertiesName, U.group())]; the plain name is
@@ -1353,6 +1392,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->eps_initial = d.eps_initial; out->eps_bc = eps.bc.empty() ? nullptr : eps.bc.data(); out->eps_value = eps.val.empty() ? nullptr : eps.val.data();
     out->eps_convection_scheme = d.eps_convection_scheme; out->eps_tol = d.eps_tol; out->eps_rel_tol = d.eps_rel_tol; out->eps_max_iter = d.eps_max_iter; out->eps_relax = d.eps_relax;
     out->wf_kappa = d.wf_kappa; out->wf_E = d.wf_E;
+    out->drag_law = d.drag_law; out->force_models = d.force_models;
     out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
     return FY_OK;
 }

@@ -319,6 +319,8 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
         }
         FY_TRY(cpl->c.create(&md, &fp, pimple ? 1 : 0, tr, device));      // gaussianInterp: false for ico, true for pimple (icoFoamYade.C:53, pimpleFoamYade.C:53)
         cpl->c.rhoP = c->rho_particle; cpl->c.rhoF = c->rho_fluid; cpl->c.nu = c->nu;   // setScalarProperties (icoFoamYade.C:55)
+        if (c->drag_law != FY_DRAG_REFERENCE) FY_TRY(cpl->c.set_drag_law(c->drag_law));                 // constant/couplingProperties
+        if (c->force_models) FY_TRY(cpl->c.set_force_models(c->force_models));
     }
     FY_TRY(halo_U());
     FY_TRY(FVK(launch_flux_of, stream, g, U.p, F3(phi)));                     // createPhi
@@ -636,7 +638,8 @@ int Solver::step() {
     // coupling call with this step's alpha; only gradP / divT are needed now.
     // the opt-in force models (fy_set_force_models on fy_solver_coupling()) read vGrad / ddtU_f, which the shipped path never does
     const unsigned fm = cpl->c.force_models;
-    const bool want_vgrad = !pimple || (fm & FY_FORCE_GAUSSIAN_TORQUE), want_ddtU = pimple && (fm & FY_FORCE_ADDED_MASS);
+    const bool curl_models = (fm & (FY_FORCE_GAUSSIAN_TORQUE | FY_FORCE_SAFFMAN_MEI_LIFT)) != 0;      // both gather the vorticity
+    const bool want_vgrad = !pimple || curl_models, want_ddtU = pimple && (fm & FY_FORCE_ADDED_MASS);
     // single domain, Gaussian mode: the sweep also leaves the force pass's packed cell records (the coupling then skips its own pack pass)
     // (a slab keeps the coupling's own pack pass: measured in round 6, the records written from this sweep cost a slab 0.17 ms per step -- the sweep is not hidden
     //  beside the walk there -- against 0.12 for the pass)
@@ -693,7 +696,7 @@ int Solver::step() {
         }
         comm->group_begin();
         FY_TRY(halo_cells(gradP, 3, g.gz, on)); FY_TRY(halo_cells(divT, 3, g.gz, on));
-        if (fm & FY_FORCE_GAUSSIAN_TORQUE) FY_TRY(halo_cells(vGrad, 9, g.gz, on));
+        if (curl_models) FY_TRY(halo_cells(vGrad, 9, g.gz, on));
         if (want_ddtU) FY_TRY(halo_cells(ddtU, 3, g.gz, on));
         FY_TRY(comm->group_end(on));
         if (side_ch) { FY_HIP(hipEventRecord(ev_fields, comm_stream)); cpl->c.slab.fields_event = ev_fields; }

@@ -244,6 +244,8 @@ struct LduSolver {
             cpl->c.ldu_geo = &g;
             FY_TRY(cpl->c.create(&md, &fp, pimple ? 1 : 0, tr, device));        // gaussianInterp: false in icoFoamYade (icoFoamYade.C:53), true in pimpleFoamYade (pimpleFoamYade.C:52)
             cpl->c.rhoP = c->rho_particle; cpl->c.rhoF = c->rho_fluid; cpl->c.nu = c->nu;      // setScalarProperties (icoFoamYade.C:55)
+            if (c->drag_law != FY_DRAG_REFERENCE) FY_TRY(cpl->c.set_drag_law(c->drag_law));                  // constant/couplingProperties
+            if (c->force_models) FY_TRY(cpl->c.set_force_models(c->force_models));
         }
         FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                    // createPhi
         FY_HIP(hipStreamSynchronize(stream));

@@ -1279,6 +1279,36 @@ struct Interp { double ufx, ufy, ufz, alpha_f, pv, sax, say, saz; };
 struct ModelSums { double t1, t2, t3, dux, duy, duz, pva; };
 struct ParticleForce { double coeff, bx, by, bz; };
 
+// The selectable closures (fy_set_drag_law; DESIGN.md section 3 "force laws"): K = beta / phi, the drag coefficient per unit SOLID volume, with
+// eps = alpha_f, phi = max(1 - eps, 0), m = |u_r| and Re = small + m d / nu as in the reference law.  Every beta carries a factor phi, so K is formed
+// without a division by phi: the force is pv K u_r and the scattered coefficient K phi.
+template <int LAW> __device__ __forceinline__ double drag_K(double eps, double phi, double Re, double m, double dia, double rhoF, double nu) {
+    if constexpr (LAW == FY_DRAG_DI_FELICE) {
+        const double Re_e = eps * Re, q = 0.63 + 4.8 / sqrt(Re_e), l = 1.5 - log10(Re_e);
+        const double chi = 3.7 - 0.65 * exp(-0.5 * (l * l));
+        return 0.75 * (q * q) * rhoF * m * pow(eps, 2 - chi) / dia;
+    } else if constexpr (LAW == FY_DRAG_KOCH_HILL) {
+        const double Re_h = 0.5 * eps * Re;
+        double F0;
+        if (phi < 0.4) {
+            const double plnp = phi > 0 ? phi * log(phi) : 0.0;
+            F0 = (1 + 3 * sqrt(phi / 2) + (135.0 / 64.0) * plnp + 16.14 * phi) / (1 + 0.681 * phi - 8.48 * (phi * phi) + 8.16 * ((phi * phi) * phi));
+        } else {
+            F0 = 10 * phi / ((eps * eps) * eps);
+        }
+        const double e2 = eps * eps;
+        const double F3 = 0.0673 + 0.212 * phi + 0.0232 / ((e2 * e2) * eps);
+        return 18 * nu * rhoF * e2 / (dia * dia) * (F0 + 0.5 * F3 * Re_h);
+    } else {                                                                          // FY_DRAG_BEETSTRA
+        const double Re_e = eps * Re, e2 = eps * eps;
+        const double num = 1 / eps + 3 * eps * phi + 8.4 * pow(Re_e, -0.343);
+        const double den = 1 + pow(10.0, 3 * phi) * pow(Re_e, -0.5 * (1 + 4 * phi));
+        const double Fb = 10 * phi / e2 + e2 * (1 + 1.5 * sqrt(phi)) + (0.413 * Re_e / (24 * e2)) * (num / den);
+        return 18 * nu * rhoF * eps / (dia * dia) * Fb;
+    }
+}
+
+template <int LAW, bool MODELS>
 __device__ __forceinline__ ParticleForce force_law(const ForceParams& fp, const Interp& s, const ModelSums& ms, int k, double dia, double lvx, double lvy,
                                                    double lvz, const double* __restrict__ rec_orig, double* __restrict__ F) {
     const double rhoF = fp.rhoF, nu = fp.nu;
@@ -1286,21 +1316,30 @@ __device__ __forceinline__ ParticleForce force_law(const ForceParams& fp, const 
     const double urx = s.ufx - lvx, ury = s.ufy - lvy, urz = s.ufz - lvz;
     const double magUR = sqrt(urx * urx + ury * ury + urz * urz);
     const double Re = fp.small + ((magUR * dia) / nu);                                // FoamYade.C:370
-    const double cd = Re < 1000 ? (24 / (Re)) * (1 + (0.15 * pow(Re, 0.687))) : 0.44;
-    double coeff;
-    if (s.alpha_f > 0.8) {                                                            // FoamYade.C:373-374
-        coeff = 0.75 * cd * s.alpha_f * alpha_p * rhoF * magUR * pow(s.alpha_f, -2.65);
-    } else {                                                                          // FoamYade.C:376-378
-        const double cf1 = 150 * ((alpha_p * alpha_p) / s.alpha_f) * ((nu * rhoF) / (dia * dia));
-        const double cf2 = 1.75 * alpha_p * rhoF * (1 / dia) * magUR;
-        coeff = cf1 + cf2;
+    double coeff, hfx, hfy, hfz;
+    if constexpr (LAW == FY_DRAG_REFERENCE) {
+        const double cd = Re < 1000 ? (24 / (Re)) * (1 + (0.15 * pow(Re, 0.687))) : 0.44;
+        if (s.alpha_f > 0.8) {                                                        // FoamYade.C:373-374
+            coeff = 0.75 * cd * s.alpha_f * alpha_p * rhoF * magUR * pow(s.alpha_f, -2.65);
+        } else {                                                                      // FoamYade.C:376-378
+            const double cf1 = 150 * ((alpha_p * alpha_p) / s.alpha_f) * ((nu * rhoF) / (dia * dia));
+            const double cf2 = 1.75 * alpha_p * rhoF * (1 / dia) * magUR;
+            coeff = cf1 + cf2;
+        }
+        const double s1 = s.pv * coeff, ia = 1 / (alpha_p);                           // FoamYade.C:381
+        hfx = (s1 * urx) * ia; hfy = (s1 * ury) * ia; hfz = (s1 * urz) * ia;
+    } else {
+        const double phi = alpha_p > 0 ? alpha_p : 0.0;
+        const double K = drag_K<LAW>(s.alpha_f, phi, Re, magUR, dia, rhoF, nu);
+        const double s1 = s.pv * K;
+        coeff = K * phi;                                                              // what FoamYade.C:385-386 scatter
+        hfx = s1 * urx; hfy = s1 * ury; hfz = s1 * urz;
     }
-    const double s1 = s.pv * coeff, ia = 1 / (alpha_p);                               // FoamYade.C:381
-    const double hfx = (s1 * urx) * ia, hfy = (s1 * ury) * ia, hfz = (s1 * urz) * ia;
     const double afx = s.pv * s.sax, afy = s.pv * s.say, afz = s.pv * s.saz;          // FoamYade.C:426
     double fx = (0.0 + hfx) + afx, fy_ = (0.0 + hfy) + afy, fz = (0.0 + hfz) + afz;   // FoamYade.C:382,427
     double tqx = 0.0, tqy = 0.0, tqz = 0.0;                                           // Gaussian torque disabled, FoamYade.C:618
     ParticleForce r{coeff, afx, afy, afz};
+    if constexpr (MODELS) {
     if (fp.models & FY_FORCE_GAUSSIAN_TORQUE) {                                       // FoamYade.C:477-478
         const double c3 = M_PI * (pow(dia, 3.0));
         tqx = 0.0 + (((c3 * (ms.t1 - rec_orig[6])) * nu) * rhoF);
@@ -1314,6 +1353,20 @@ __device__ __forceinline__ ParticleForce force_law(const ForceParams& fp, const 
         const double amz = (pva * (ms.duz - (lvz / fp.delta_t))) * fp.rhoP;
         fx = fx + amx; fy_ = fy_ + amy; fz = fz + amz;
         r.bx = r.bx + amx; r.by = r.by + amy; r.bz = r.bz + amz;                      // FoamYade.C:406-411: same -f w / (V rho_f) reaction
+    }
+    if (fp.models & FY_FORCE_SAFFMAN_MEI_LIFT) {
+        // Saffman's shear lift with Mei's finite-Reynolds-number factor on the interpolated vorticity (ms.t = curl U, the torque's gather):
+        // Cl = 3 / (2 pi sqrt(Re_w)) 6.46 f(Re_p, Re_w), F = rho_f pv Cl (u_r x omega); `small` keeps both quotients finite at rest and without shear
+        const double magW = sqrt(ms.t1 * ms.t1 + ms.t2 * ms.t2 + ms.t3 * ms.t3);
+        const double Re_p = (magUR * dia) / nu, Re_w = (magW * (dia * dia)) / nu;
+        const double b = 0.5 * Re_w / (Re_p + fp.small), a = 0.3314 * sqrt(b);
+        const double f = Re_p < 40 ? (1 - a) * exp(-0.1 * Re_p) + a : 0.0524 * sqrt(b * Re_p);
+        const double cl = 3 / (2 * M_PI * sqrt(Re_w + fp.small)) * 6.46 * f;
+        const double sl = rhoF * s.pv * cl;
+        const double lx = sl * (ury * ms.t3 - urz * ms.t2), ly = sl * (urz * ms.t1 - urx * ms.t3), lz = sl * (urx * ms.t2 - ury * ms.t1);
+        fx = fx + lx; fy_ = fy_ + ly; fz = fz + lz;
+        r.bx = r.bx + lx; r.by = r.by + ly; r.bz = r.bz + lz;                         // the reaction reaches uSource like Archimedes' and the added mass's
+    }
     }
     F[0] = fx; F[1] = fy_; F[2] = fz;
     if (!fp.torque_prezeroed) { F[3] = tqx; F[4] = tqy; F[5] = tqz; }    // permuted 48-byte records: half the store traffic when the torque is identically zero
@@ -1331,7 +1384,7 @@ __device__ __forceinline__ void interp_add(Interp& s, const double* __restrict__
 
 __device__ __forceinline__ void model_add(ModelSums& ms, const ForceParams& fp, const double* __restrict__ vGrad, const double* __restrict__ ddtU, int64_t cl,
                                           double w, double volp) {
-    if (fp.models & FY_FORCE_GAUSSIAN_TORQUE) {                                       // calcHydroTorque FoamYade.C:468-476
+    if (fp.models & (FY_FORCE_GAUSSIAN_TORQUE | FY_FORCE_SAFFMAN_MEI_LIFT)) {         // calcHydroTorque FoamYade.C:468-476; the lift reads the same curl
         const double* G = vGrad + 9 * (size_t)cl;                                     // xx xy xz yx yy yz zx zy zz
         ms.t1 += ((G[5] - G[7]) * w); ms.t2 += ((G[6] - G[2]) * w); ms.t3 += ((G[3] - G[1]) * w);
     }
@@ -1352,10 +1405,14 @@ __device__ __forceinline__ void model_add(ModelSums& ms, const ForceParams& fp, 
 #define FY_FORCE_LOG2 10
 #endif
 constexpr int kForceThreads = FY_FORCE_THREADS, kForceLog2 = FY_FORCE_LOG2;
-__global__ __launch_bounds__(kForceThreads) FY_FORCE_ATTR void k_force_gaussian(
-        ParticleSoA p, int64_t n, ForceParams fp, CellWindow cw, const double* __restrict__ vol, const double* __restrict__ R,
+// One instantiation per (drag law, "any opt-in model on"): the launcher picks, the lane's loops carry no branch on either.  k_force_gaussian<FY_DRAG_REFERENCE>
+// is the shipped kernel less the models' cold branch (62 registers where that kernel needed the budget's 80); the opt-in models' gathers and the lift do not fit its 80 registers with every law, so their kernels (k_force_gaussian_models) leave the
+// budget to the compiler instead of spilling.
+template <int LAW, bool MODELS>
+__device__ __forceinline__ void force_gaussian_body(
+        ParticleSoA p, int64_t n, const ForceParams& fp, CellWindow cw, const double* __restrict__ vol, const double* __restrict__ R,
         const double* __restrict__ vGrad, const double* __restrict__ ddtU, const double* __restrict__ rec,
-        double* __restrict__ drag_acc, double* __restrict__ uSource, double* __restrict__ force_out, TileBuckets tb) {
+        double* __restrict__ drag_acc, double* __restrict__ uSource, double* __restrict__ force_out, const TileBuckets& tb) {
     constexpr int kSlots = 1 << kForceLog2;
     __shared__ uint32_t keys[kSlots];
     __shared__ double vals[kSlots * 4];
@@ -1406,14 +1463,14 @@ __global__ __launch_bounds__(kForceThreads) FY_FORCE_ATTR void k_force_gaussian(
                     interp_add(s, R, cl, w, volp);
                 }
             }
-            if (fp.models)                              // uniform: off in the shipped reference
+            if constexpr (MODELS)                       // off in the shipped reference
                 for (int t = 0; t < k; ++t) {
                     const size_t slot = (size_t)((first + t) & (kMaxK - 1)) * p.cap + (size_t)i;
                     const int64_t cl = (int64_t)p.ids[slot] - cw.base;
                     if (cl < 0 || cl >= cw.n_field) continue;
                     model_add(ms, fp, vGrad, ddtU, cl, p.w[slot], volp);
                 }
-            pf = force_law(fp, s, ms, k, dia, p.vx[i], p.vy[i], p.vz[i], rec + 10 * (size_t)orig, F);
+            pf = force_law<LAW, MODELS>(fp, s, ms, k, dia, p.vx[i], p.vy[i], p.vz[i], rec + 10 * (size_t)orig, F);
             const double irho = 1 / fp.rhoF;
             // a uniform block's cell volume is a constant, not a gather
             const double ooUniform = fp.uniform_vol > 0 ? 1. / (fp.uniform_vol * fp.rhoF) : 0.0;
@@ -1447,6 +1504,21 @@ __global__ __launch_bounds__(kForceThreads) FY_FORCE_ATTR void k_force_gaussian(
     }
     __syncthreads();
     flush_table<kSlots, kForceThreads>(keys, vals, tmap, tb, drag_acc, uSource, nullptr);
+}
+
+template <int LAW>
+__global__ __launch_bounds__(kForceThreads) FY_FORCE_ATTR void k_force_gaussian(
+        ParticleSoA p, int64_t n, ForceParams fp, CellWindow cw, const double* __restrict__ vol, const double* __restrict__ R,
+        const double* __restrict__ vGrad, const double* __restrict__ ddtU, const double* __restrict__ rec,
+        double* __restrict__ drag_acc, double* __restrict__ uSource, double* __restrict__ force_out, TileBuckets tb) {
+    force_gaussian_body<LAW, false>(p, n, fp, cw, vol, R, vGrad, ddtU, rec, drag_acc, uSource, force_out, tb);
+}
+template <int LAW>
+__global__ __launch_bounds__(kForceThreads) void k_force_gaussian_models(
+        ParticleSoA p, int64_t n, ForceParams fp, CellWindow cw, const double* __restrict__ vol, const double* __restrict__ R,
+        const double* __restrict__ vGrad, const double* __restrict__ ddtU, const double* __restrict__ rec,
+        double* __restrict__ drag_acc, double* __restrict__ uSource, double* __restrict__ force_out, TileBuckets tb) {
+    force_gaussian_body<LAW, true>(p, n, fp, cw, vol, R, vGrad, ddtU, rec, drag_acc, uSource, force_out, tb);
 }
 
 // ---- particle migration between z-slabs: records whose containing cell now lies in a neighbour's planes are packed for
@@ -1512,6 +1584,8 @@ __device__ __forceinline__ int axis_cell(const double* __restrict__ f, int n, do
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (f[mid] <= x) lo = mid; else hi = mid; }
     return lo;
 }
+// SCHILLER_NAUMANN = false: the reference's Stokes drag; true: the same with the finite-Reynolds-number factor f (fy_set_drag_law)
+template <bool SCHILLER_NAUMANN>
 __global__ __launch_bounds__(256) void k_point_force(const double* __restrict__ rec, int64_t n, BlockGeom g, ForceParams fp, CellWindow cw,
                                                      const double* __restrict__ vol, const double* __restrict__ U,
                                                      const double* __restrict__ vGrad, double* __restrict__ uSource,
@@ -1565,9 +1639,14 @@ __global__ __launch_bounds__(256) void k_point_force(const double* __restrict__ 
     const double dia = 2 * r[9];
     const double rhoF = fp.rhoF, nu = fp.nu;
     // stokesDragForce FoamYade.C:437-444
-    const double coeff = 3 * M_PI * (dia)*nu * rhoF;
+    double coeff = 3 * M_PI * (dia)*nu * rhoF;
     const double ooCellVol = 1. / (vol[c] * rhoF);
     const double* u = U + 3 * (size_t)c;
+    if constexpr (SCHILLER_NAUMANN) {
+        const double urx = u[0] - r[3], ury = u[1] - r[4], urz = u[2] - r[5];
+        const double Re = fp.small + ((sqrt(urx * urx + ury * ury + urz * urz) * dia) / nu);
+        coeff = coeff * (Re < 1000 ? 1 + 0.15 * pow(Re, 0.687) : 0.44 * Re / 24);
+    }
     const double hx = coeff * (u[0] - r[3]), hy = coeff * (u[1] - r[4]), hz = coeff * (u[2] - r[5]);
     const double m = -1 * ooCellVol;
     atomic_add_f64(&uSource[3 * (size_t)c + 0], m * hx);
@@ -1807,7 +1886,15 @@ int launch_force_gaussian(hipStream_t s, ParticleSoA p, int64_t n, ForceParams f
                           const double* vGrad, const double* ddtU, const double* rec, double* drag_acc, double* uSource,
                           double* force_out, TileBuckets tb) {
     if (n <= 0) return FY_OK;
-    hipLaunchKernelGGL(k_force_gaussian, dim3(div_up(n, kForceThreads)), dim3(kForceThreads), 0, s, p, n, fp, cw, vol, R, vGrad, ddtU, rec, drag_acc, uSource, force_out, tb);
+    using Kernel = void (*)(ParticleSoA, int64_t, ForceParams, CellWindow, const double*, const double*, const double*, const double*, const double*, double*, double*, double*,
+                            TileBuckets);
+    static const Kernel table[4][2] = {{k_force_gaussian<FY_DRAG_REFERENCE>, k_force_gaussian_models<FY_DRAG_REFERENCE>},
+                                       {k_force_gaussian<FY_DRAG_DI_FELICE>, k_force_gaussian_models<FY_DRAG_DI_FELICE>},
+                                       {k_force_gaussian<FY_DRAG_KOCH_HILL>, k_force_gaussian_models<FY_DRAG_KOCH_HILL>},
+                                       {k_force_gaussian<FY_DRAG_BEETSTRA>, k_force_gaussian_models<FY_DRAG_BEETSTRA>}};
+    if (fp.drag_law < FY_DRAG_REFERENCE || fp.drag_law > FY_DRAG_BEETSTRA) return fail(FY_ERR_INVALID, "launch_force_gaussian: drag law %d has no Gaussian-mode kernel", fp.drag_law);
+    hipLaunchKernelGGL(table[fp.drag_law][fp.models ? 1 : 0], dim3(div_up(n, kForceThreads)), dim3(kForceThreads), 0, s, p, n, fp, cw, vol, R, vGrad, ddtU, rec, drag_acc,
+                       uSource, force_out, tb);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }
@@ -1907,7 +1994,9 @@ int launch_point_force(hipStream_t s, const double* rec, int64_t n, BlockGeom g,
                        const double* U, const double* vGrad, double* uSource, double* force_out, int32_t* found_out,
                        int32_t* incell_out, SlabOwn own) {
     if (n <= 0) return FY_OK;
-    hipLaunchKernelGGL(k_point_force, dim3(div_up(n, 256)), dim3(256), 0, s, rec, n, g, fp, cw, vol, U, vGrad, uSource, force_out, found_out, incell_out, own);
+    if (fp.drag_law != FY_DRAG_REFERENCE && fp.drag_law != FY_DRAG_SCHILLER_NAUMANN) return fail(FY_ERR_INVALID, "launch_point_force: drag law %d has no point-mode kernel", fp.drag_law);
+    hipLaunchKernelGGL(fp.drag_law == FY_DRAG_SCHILLER_NAUMANN ? k_point_force<true> : k_point_force<false>, dim3(div_up(n, 256)), dim3(256), 0, s, rec, n, g, fp, cw, vol, U,
+                       vGrad, uSource, force_out, found_out, incell_out, own);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

@@ -31,6 +31,7 @@ struct ForceParams {
     unsigned models;               // FY_FORCE_* : the reference's call-site-less models, off by default
     int torque_prezeroed;          // the torque half of every force record is already zero (and stays so): store the force half only
     double uniform_vol;            // > 0: every cell has this volume (structured block) -- the back-scatter does not gather V[c]
+    int drag_law;                  // FY_DRAG_* : the kernel instantiation the launchers pick (0 = the reference's law)
 };
 
 // sorted SoA particle arrays + per-particle stencil storage for one batch
