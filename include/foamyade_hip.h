@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 15
+#define FY_ABI_VERSION 16
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -265,6 +265,28 @@ enum { FY_PSOLVER_PCG_JACOBI = 0, FY_PSOLVER_PCG_MG = 1 };
 #define FY_BC_NUT_FIXED_VALUE 1
 #define FY_BC_NUT_CALCULATED 3          /* nut_bc: `calculated` patch = the model's expression on the boundary values of k (and epsilon); kEqn / kEpsilon */
 #define FY_BC_WALL_FUNCTION 2           /* nut_bc: nutkWallFunction (needs a model with k); eps_bc: epsilonWallFunction; k takes zeroGradient (kqRWallFunction) */
+/* fieldAverage: running means and second central moments of cell fields, updated on the device once per step (OpenFOAM's fieldAverage function object
+   [OF-6 fieldAverage, fieldAverageTemplates.C, as recalled: OpenFOAM is not at hand to pin it]).  An item is one field with its mean m and, with
+   prime2_mean, P = prime2Mean: one value per cell for a scalar, six for a vector in symmTensor order xx xy xz yy yz zz.  Per item N samples and T seconds
+   averaged; after a step of dt
+       base time:      Dt = T + dt, a = (Dt - dt) / Dt, b = dt / Dt          base iteration: Dt = N + 1, a = (Dt - 1) / Dt, b = 1 / Dt
+       per cell:       P = P + m m;  m_new = a m + b x;  P = (a P + b (x x)) - m_new m_new;  m = m_new;          then N += 1, T += dt
+   The sample is taken at the end of the step where runTime.write() stands (icoFoamYade.C:142, pimpleFoamYade.C:107): before setSourceZero, so it sees the
+   step's alpha / uSource / uParticle, with or without fy_solver_hold_sources.  (OpenFOAM executes function objects inside the next runTime.run(), after
+   setSourceZero, where alpha is 1 everywhere: a deliberate difference)  A sample is taken only while elapsed >= start_after - dt / 2 and,
+   with stop_after > 0, elapsed <= stop_after + dt / 2, elapsed being the sum of the steps' deltaT since the solver was created [OF-6 timeControl]. */
+#define FY_AVERAGE_MAX_ITEMS 8
+typedef struct fy_average_item {
+    char field[32];                 /* solver field name: U, p, alpha, uParticle, uSource, nut, k, epsilon -- where the solver has the field */
+    int32_t prime2_mean;            /* also keep P */
+    int32_t iteration_base;         /* 0: base time (weights deltaT), 1: base iteration (equal weights) */
+} fy_average_item;
+typedef struct fy_average_desc {
+    int32_t n_items;                /* 0: no averaging -- no kernel, no memory, no file */
+    fy_average_item items[FY_AVERAGE_MAX_ITEMS];
+    double start_after, stop_after; /* the window in seconds since the solver was created; stop_after 0: no end */
+} fy_average_desc;
+
 typedef struct fy_case_desc {
     int32_t solver;                 /* FY_SOLVER_ICO | FY_SOLVER_PIMPLE */
     int32_t nx, ny, nz;
@@ -336,6 +358,8 @@ typedef struct fy_case_desc {
        fy_set_drag_law / fy_set_force_models, whose refusals (a law of the other mode, models in point-force mode) then fail the create */
     int32_t drag_law;                       /* FY_DRAG_* */
     uint32_t force_models;                  /* FY_FORCE_* flags */
+    /* controlDict functions: the fieldAverage object (all zero: none), applied at fy_solver_create with fy_solver_set_field_average */
+    fy_average_desc average;
 } fy_case_desc;
 
 typedef struct fy_solver fy_solver;
@@ -367,6 +391,15 @@ int fy_solver_destroy(fy_solver*);
  * those fields in between. */
 int fy_solver_hold_sources(fy_solver*, int hold);
 
+/* fieldAverage on this solver (fy_average_desc above).  NULL or n_items 0: off, the buffers freed.  A new call starts every item from zero.  An unknown field,
+ * a field this case does not have, a duplicate or more than FY_AVERAGE_MAX_ITEMS items: FY_ERR_INVALID naming the field; a slab solver: FY_ERR_UNSUPPORTED.
+ * While it is on, "<field>Mean" [n][1|3] and "<field>Prime2Mean" [n][1|6] are names for fy_solver_field_count / _read_field_host / _write_field_host
+ * (writing is how a restart loads them, together with fy_solver_set_average_state; it touches nothing else).  One launch per step on the solver's stream,
+ * no host synchronisation; its time is the "field_average" clock of fy_solver_get_kernel_timing. */
+int fy_solver_set_field_average(fy_solver*, const fy_average_desc*);
+int fy_solver_get_average_state(fy_solver*, int item, int64_t* samples, double* time_averaged);
+int fy_solver_set_average_state(fy_solver*, int item, int64_t samples, double time_averaged);
+
 /* ---- OpenFOAM case directories (what the reference's executables get from runTime / mesh / the field constructors, createFields.H
  * of both solvers, and give back with runTime.write()).  Supported subset: ONE axis-aligned blockMesh hex block of uniform cubes whose
  * six sides are covered by `boundary` patches; velocity patches fixedValue (uniform) / noSlip / zeroGradient; pressure patches
@@ -388,6 +421,7 @@ typedef struct fy_foam_case_info {
     char patch_of_side[6][64];             /* blockMesh patch on the XMIN, XMAX, YMIN, YMAX, ZMIN, ZMAX side */
     int64_t field_cells, field_offset;     /* cells the field files (and fy_foam_case_initial_*, fy_foam_case_write_fields) hold, global number of the first:
                                               n_cells and 0, or one processor directory's slab (fy_foam_case_open_processor) */
+    int32_t n_ignored_functions;           /* controlDict functions: objects of a type other than fieldAverage -- accepted, never run (fy_foam_case_ignored_function) */
 } fy_foam_case_info;
 int fy_foam_case_open(const char* case_dir, int solver /* FY_SOLVER_ICO | FY_SOLVER_PIMPLE */, fy_foam_case** out);
 /* a DECOMPOSED case (decomposePar, simple (1 1 nranks); the reference's -parallel run, README.md:29): mesh, controls and schemes from the case, the
@@ -407,6 +441,18 @@ int fy_foam_case_write_time(const fy_foam_case*, fy_solver*, const char* time_na
    may be NULL where the case has no such field */
 int fy_foam_case_write_fields(const fy_foam_case*, const char* time_name, const double* U, const double* p, const double* alpha, const double* nut,
                               const double* k, const double* epsilon);
+/* controlDict `functions` [OF-6 functionObjectList]: ONE entry of `type fieldAverage` (not `enabled false`) becomes fy_case_desc.average / fy_ldu_case.average:
+ * fields ( <file name> { mean on|off; prime2Mean on|off; base time|iteration; } ... ) with the case's file names (U | U.<phase>, p, alpha.<phase>, nut.<phase>,
+ * k.<phase>, epsilon.<phase>, uParticle, uSource), timeStart / timeEnd (start_after = max(0, timeStart - startTime)), writeControl absent | writeTime | outputTime,
+ * executeControl absent | timeStep (interval 1), restartOnRestart.  Refused by name (FY_ERR_UNSUPPORTED): window, restartOnOutput on, periodicRestart on, an
+ * unknown field, a field the case does not have, mean off with prime2Mean on, another base, a second fieldAverage.  Objects of every other type are accepted
+ * and NOT run: the i-th one's "<name> (type <type>)" for a caller that wants to say so.
+ * fy_foam_case_write_time / _write_time_ldu of a solver with averaging on also write <file name>Mean (the base field's class, dimensions and patch entries),
+ * <file name>Prime2Mean (volScalarField | volSymmTensorField, squared dimensions, calculated patches) and <time>/uniform/<object>Properties (per field
+ * totalIter = N + 1, totalTime = T + deltaT: OpenFOAM's convention as recalled, unpinned).  fy_foam_case_restore_averages (_ldu for a general case) loads them back from the start time
+ * directory into a new solver (restartOnRestart off, and the files there); *restored = the number of items loaded, 0 = averaging starts from zero. */
+int fy_foam_case_ignored_function(const fy_foam_case*, int i, char* out, int cap);
+int fy_foam_case_restore_averages(const fy_foam_case*, fy_solver*, int* restored);
 int fy_foam_case_close(fy_foam_case*);
 
 /* ---- kernel-level entry points used by the roofline bench and the operator parity tests ------------------ */
@@ -568,12 +614,18 @@ typedef struct fy_ldu_case {
     double wf_kappa, wf_E;           /* the wall functions' constants [OF-6 nutkWallFunction]; fy_ldu_case_defaults: 0.41, 9.8 */
     int32_t drag_law;                /* constant/couplingProperties as in fy_case_desc: FY_DRAG_* and FY_FORCE_* flags, zero = the reference's behaviour */
     uint32_t force_models;
+    fy_average_desc average;         /* controlDict functions: the fieldAverage object as in fy_case_desc (all zero: none), applied at fy_ldu_solver_create */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */
 int fy_ldu_solver_create(const fy_poly_mesh*, const fy_ldu_case*, const fy_transport* transport /* or NULL */, int device_ordinal, fy_ldu_solver** out);
 int fy_ldu_solver_step(fy_ldu_solver*);                                     /* one pass of icoFoamYade.C:65-149 */
 int fy_ldu_solver_get_stats(fy_ldu_solver*, fy_step_stats* out);
+/* fieldAverage as on fy_solver (fy_solver_set_field_average): alpha, uParticle with pimpleFoamYade; uSource is what the coupling left (+ an external source
+   with pimpleFoamYade, as the equations saw it); the same "<field>Mean" / "<field>Prime2Mean" field names */
+int fy_ldu_solver_set_field_average(fy_ldu_solver*, const fy_average_desc*);
+int fy_ldu_solver_get_average_state(fy_ldu_solver*, int item, int64_t* samples, double* time_averaged);
+int fy_ldu_solver_set_average_state(fy_ldu_solver*, int item, int64_t samples, double time_averaged);
 int fy_ldu_solver_hold_sources(fy_ldu_solver*, int on);                    /* as fy_solver_hold_sources: setSourceZero deferred to the next step's start (runTime.write() sees alpha / uSource) */
 fy_ctx* fy_ldu_solver_coupling(fy_ldu_solver*);                              /* FoamYade on this mesh (point force); fy_set_particles_* as usual */
 /* fields by name, host copies: "U" [nc][3], "p", "phi" [n_faces], "uSource" [nc][3] (added to what the coupling leaves: an external momentum source),
@@ -599,6 +651,7 @@ int fy_foam_case_poly_mesh(const fy_foam_case*, fy_poly_mesh* out);             
 int fy_foam_case_ldu_desc(const fy_foam_case*, fy_ldu_case* out);                 /* ready for fy_ldu_solver_create (patch arrays point into the case object) */
 int fy_foam_case_patch_name(const fy_foam_case*, int patch, char* out, int cap); /* the boundary file's order = fy_poly_mesh's patch numbers */
 int fy_foam_case_write_time_ldu(const fy_foam_case*, fy_ldu_solver*, const char* time_name);     /* runTime.write() (icoFoamYade.C:142): <time>/U, p */
+int fy_foam_case_restore_averages_ldu(const fy_foam_case*, fy_ldu_solver*, int* restored);         /* fy_foam_case_restore_averages for a general case */
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,65 @@ class Transport(C.Structure):
                 ("send_reserve", C.c_void_p), ("send_commit", C.c_void_p), ("view_region", C.c_void_p)]
 
 
+AVERAGE_MAX_ITEMS = 8
+
+
+class AverageItem(C.Structure):
+    _fields_ = [("field", C.c_char * 32), ("prime2_mean", C.c_int32), ("iteration_base", C.c_int32)]
+
+
+class AverageDesc(C.Structure):
+    """fy_average_desc: the fieldAverage items of a solver (all zero: none)"""
+    _fields_ = [("n_items", C.c_int32), ("items", AverageItem * AVERAGE_MAX_ITEMS), ("start_after", C.c_double), ("stop_after", C.c_double)]
+
+    def as_list(self):
+        """[(field, prime2_mean, base)] of the items"""
+        return [(self.items[q].field.decode(), bool(self.items[q].prime2_mean), "iteration" if self.items[q].iteration_base else "time") for q in range(self.n_items)]
+
+
+def average_desc(items, start_after=0.0, stop_after=0.0):
+    """items: field names, or (field, prime2_mean[, base "time" | "iteration"]) tuples -> AverageDesc.  More than AVERAGE_MAX_ITEMS items are the library's to refuse:
+    the count is passed on as it is, the first AVERAGE_MAX_ITEMS entries filled"""
+    d = AverageDesc()
+    items = [(it,) if isinstance(it, str) else tuple(it) for it in (items or [])]
+    d.n_items = len(items)
+    for q, it in enumerate(items[:AVERAGE_MAX_ITEMS]):
+        d.items[q].field = it[0].encode()
+        d.items[q].prime2_mean = int(bool(it[1])) if len(it) > 1 else 0
+        d.items[q].iteration_base = int(it[2] == "iteration") if len(it) > 2 else 0
+    d.start_after, d.stop_after = float(start_after), float(stop_after)
+    return d
+
+
+class _Averages:
+    """fieldAverage on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*): running means and second central moments on the device"""
+    _AVG_PREFIX = "fy_solver"
+
+    def _avg_fn(self, what):
+        f = getattr(lib(), f"{self._AVG_PREFIX}_{what}")
+        f.argtypes = {"set_field_average": [C.c_void_p, C.POINTER(AverageDesc)], "get_average_state": [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _dp],
+                      "set_average_state": [C.c_void_p, C.c_int, C.c_int64, C.c_double]}[what]
+        return f
+
+    def set_field_average(self, items, start_after=0.0, stop_after=0.0):
+        """items: field names or (field, prime2_mean[, "time" | "iteration"]) tuples; None or []: off.  Afterwards get("<field>Mean") / get("<field>Prime2Mean")"""
+        if not items:
+            _check(self._avg_fn("set_field_average")(self._h, None))
+        else:
+            d = average_desc(items, start_after, stop_after)
+            _check(self._avg_fn("set_field_average")(self._h, C.byref(d)))
+
+    def average_state(self, item):
+        """(samples taken, simulated time averaged) of item `item`"""
+        n = C.c_int64(0); t = C.c_double(0.0)
+        _check(self._avg_fn("get_average_state")(self._h, int(item), C.byref(n), C.byref(t)))
+        return n.value, t.value
+
+    def set_average_state(self, item, samples, time_averaged):
+        """a restart: the state that goes with means written through set("<field>Mean", ...)"""
+        _check(self._avg_fn("set_average_state")(self._h, int(item), int(samples), float(time_averaged)))
+
+
 class PolyMesh(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("points", _dp), ("n_faces", C.c_int32), ("n_internal_faces", C.c_int32), ("face_offsets", _ip), ("face_points", _ip),
                 ("owner", _ip), ("neighbour", _ip), ("n_cells", C.c_int32), ("n_patches", C.c_int32), ("patch_start", _ip), ("patch_size", _ip), ("patch_neighbour", _ip)]
@@ -98,7 +157,7 @@ class LduCase(C.Structure):
                 ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double), ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double),
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
                 ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32)]
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc)]
 
 
 class ParticleTimings(C.Structure):
@@ -130,7 +189,7 @@ class CaseDesc(C.Structure):
                 ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double), ("eps_max_iter", C.c_int32),
                 ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32)]
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc)]
 
 
 BC_WALL_FUNCTION, BC_NUT_CALCULATED = 2, 3
@@ -141,7 +200,7 @@ NUT_ZERO_GRADIENT, NUT_FIXED_VALUE = 0, 1
 class FoamCaseInfo(C.Structure):
     _fields_ = [("start_time", C.c_double), ("end_time", C.c_double), ("delta_t", C.c_double), ("write_interval_steps", C.c_int32),
                 ("n_cells", C.c_int64), ("u_name", C.c_char * 64), ("phase", C.c_char * 32), ("start_name", C.c_char * 32),
-                ("patch_of_side", (C.c_char * 64) * 6), ("field_cells", C.c_int64), ("field_offset", C.c_int64)]
+                ("patch_of_side", (C.c_char * 64) * 6), ("field_cells", C.c_int64), ("field_offset", C.c_int64), ("n_ignored_functions", C.c_int32)]
 
 
 class StepStats(C.Structure):
@@ -586,7 +645,7 @@ def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 
     return c
 
 
-class Solver:
+class Solver(_Averages):
     """the icoFoamYade / pimpleFoamYade executables' time loop (icoFoamYade.C:65-149, pimpleFoamYade.C:60-114): step() is one
     pass of the loop body, including yadeCoupling.setParticleAction and setSourceZero."""
 
@@ -913,6 +972,13 @@ class FoamCase:
         self.write_interval_steps, self.n_cells = info.write_interval_steps, info.n_cells
         self.field_cells, self.field_offset = info.field_cells, info.field_offset
         self.u_name, self.phase, self.start_name = info.u_name.decode(), info.phase.decode(), info.start_name.decode()
+        L = lib()
+        L.fy_foam_case_ignored_function.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+        self.ignored_functions = []                # controlDict functions of a type other than fieldAverage: "<name> (type <type>)", accepted and not run
+        for q in range(info.n_ignored_functions):
+            buf = C.create_string_buffer(256)
+            _check(L.fy_foam_case_ignored_function(self._h, q, buf, 256))
+            self.ignored_functions.append(buf.value.decode())
         return info
 
     def initial_fields(self):
@@ -937,6 +1003,16 @@ class FoamCase:
 
     def write(self, solver, time_name):
         _check(lib().fy_foam_case_write_time(self._h, solver._h, str(time_name).encode()))
+
+    _RESTORE = "fy_foam_case_restore_averages"
+
+    def restore_averages(self, solver):
+        """load the start time directory's averages into a solver made from this case (restartOnRestart off, and the files there); returns the items restored"""
+        f = getattr(lib(), self._RESTORE)
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        n = C.c_int(0)
+        _check(f(self._h, solver._h, C.byref(n)))
+        return n.value
 
     def write_fields(self, time_name, U, p, alpha=None, nut=None, k=None, epsilon=None):
         """runTime.write() from host arrays holding this case's (or processor directory's) cells: fy_foam_case_write_fields"""
@@ -986,6 +1062,8 @@ class GeneralFoamCase(FoamCase):
         self.p_bc = [int(self.ldu_case.p_bc[q]) for q in range(m.n_patches)]
         self.u_value = np.array([[self.ldu_case.u_value[3 * q + a] for a in range(3)] for q in range(m.n_patches)])
         self.p_value = np.array([self.ldu_case.p_value[q] for q in range(m.n_patches)])
+
+    _RESTORE = "fy_foam_case_restore_averages_ldu"
 
     def write(self, solver, time_name):
         _check(lib().fy_foam_case_write_time_ldu(self._h, solver._h, str(time_name).encode()))
@@ -1105,10 +1183,12 @@ class VirtualSlabs:
         self.solvers, self.comms = [], []
 
 
-class LduSolver:
+class LduSolver(_Averages):
     """icoFoamYade's loop body on a general polyhedral mesh in OpenFOAM's addressing (fy_ldu_solver, include/foamyade_hip.h).  mesh: dict with points (n,3),
     face_offsets, face_points, owner, neighbour, n_cells, patch_start, patch_size (tests/poly_meshes.py builds them); u_bc / p_bc / values per patch; the
     controls are fy_ldu_case's (defaults: the icoFoam cavity tutorial's)"""
+
+    _AVG_PREFIX = "fy_ldu_solver"
 
     @staticmethod
     def _bind():

@@ -73,6 +73,12 @@ struct fy_foam_case {
     std::vector<std::string> g_patch_name;
     std::vector<int32_t> g_patch_neighbour;      // per patch: its cyclic partner, or -1
     std::vector<std::string> g_patch_class;      // the boundary file's `type` per patch (wall | patch | symmetryPlane | symmetry | cyclic)
+    // controlDict functions: the fieldAverage object (desc.average carries its items in this order) and the names of the objects of other types
+    struct AvgField { std::string file; int F; std::string solver_name; int ncomp; bool prime2; };      // F: F_U .. F_ALPHA, or -1 (uParticle, uSource: no start-time file)
+    std::string avg_name;
+    std::vector<AvgField> avg_fields;
+    bool avg_restart_on_restart = false;
+    std::vector<std::string> ignored_functions;
 };
 
 namespace {
@@ -843,7 +849,93 @@ int read_coupling_properties(fy_foam_case* c) {
     return FY_OK;
 }
 
+// controlDict `functions` [OF-6 functionObjectList; fieldAverage / fieldAverageItem as recalled]: one fieldAverage object -> desc.average (solver field names)
+// and c->avg_fields (file names); objects of other types are accepted and not run, their names kept.  Everything fieldAverage offers beyond the plain running
+// mean / prime2Mean is refused by name.  Called last in read_controls: which fields the case has depends on the solver and the turbulence model.
+int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) {
+    c->desc.average = fy_average_desc{};
+    c->avg_name.clear(); c->avg_fields.clear(); c->ignored_functions.clear(); c->avg_restart_on_restart = false;
+    const FoamDict* fn = d.subdict("functions");
+    if (!fn) return FY_OK;
+    for (const std::string& name : fn->order) {
+        const FoamDict* o = fn->subdict(name);
+        if (!o) continue;
+        std::string ty;
+        o->word("type", &ty);
+        if (ty != "fieldAverage") { c->ignored_functions.push_back(name + " (type " + (ty.empty() ? "?" : ty) + ")"); continue; }
+        bool enabled = true;
+        if (o->boolean("enabled", &enabled) && !enabled) continue;
+        const std::string where = path + ": functions." + name;
+        const char* w = where.c_str();
+        if (!c->avg_name.empty())
+            return fail(FY_ERR_UNSUPPORTED, "%s: a second object of type fieldAverage (the first is '%s'); accepted: one enabled fieldAverage object, with all fields in its list", w, c->avg_name.c_str());
+        if (c->proc_count > 1)
+            return fail(FY_ERR_UNSUPPORTED, "%s: type fieldAverage is not available in a decomposed (-parallel) run; accepted: an undecomposed case on one domain, or 'enabled false'", w);
+        c->avg_name = name;
+        if (o->has("window")) return fail(FY_ERR_UNSUPPORTED, "%s: window is not supported; accepted: no window (the average runs from timeStart on)", w);
+        for (const char* key : {"restartOnOutput", "periodicRestart"}) {
+            bool on = false;
+            std::string word;
+            o->word(key, &word);
+            if (o->has(key) && (!o->boolean(key, &on) || on)) return fail(FY_ERR_UNSUPPORTED, "%s: %s %s is not supported; accepted: off", w, key, word.c_str());
+        }
+        std::string word;
+        if (o->word("writeControl", &word) && word != "writeTime" && word != "outputTime")
+            return fail(FY_ERR_UNSUPPORTED, "%s: writeControl %s is not supported; accepted: writeTime, outputTime (the averages are written with the time directory)", w, word.c_str());
+        if (o->word("executeControl", &word) && word != "timeStep")
+            return fail(FY_ERR_UNSUPPORTED, "%s: executeControl %s is not supported; accepted: timeStep with executeInterval 1 (a sample every step)", w, word.c_str());
+        double iv = 1;
+        if (o->scalar("executeInterval", &iv) && iv != 1) return fail(FY_ERR_UNSUPPORTED, "%s: executeInterval %g is not supported; accepted: 1 (a sample every step)", w, iv);
+        if (o->has("restartOnRestart") && !o->boolean("restartOnRestart", &c->avg_restart_on_restart)) return fail(FY_ERR_INVALID, "%s: restartOnRestart must be on or off", w);
+        double t0 = c->start_time, t1 = 0;
+        if (o->scalar("timeStart", &t0)) c->desc.average.start_after = std::max(0.0, t0 - c->start_time);
+        if (o->scalar("timeEnd", &t1)) c->desc.average.stop_after = t1 > c->start_time ? t1 - c->start_time : 1e-300;      // (an end at or before the start: never a sample)
+        const auto* ft = o->tokens("fields");
+        if (!ft) return fail(FY_ERR_INVALID, "%s: no 'fields ( <name> { mean ..; prime2Mean ..; base ..; } ... )' list", w);
+        std::vector<std::pair<std::string, FoamDict> > fields;
+        FY_TRY(named_dicts(*ft, where + ".fields", &fields));
+        const std::string ph = c->phase.empty() ? std::string("<phase>") : c->phase;
+        const std::string accepted = c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource";
+        for (const auto& fd : fields) {
+            const std::string& file = fd.first;
+            const std::string fw = where + ".fields." + file;
+            if (fd.second.has("window") || fd.second.has("windowName"))
+                return fail(FY_ERR_UNSUPPORTED, "%s: window is not supported; accepted: no window (the average runs from timeStart on)", fw.c_str());
+            bool mean = false, prime2 = false;
+            if (!fd.second.boolean("mean", &mean) || !fd.second.boolean("prime2Mean", &prime2)) return fail(FY_ERR_INVALID, "%s: needs 'mean on|off;' and 'prime2Mean on|off;'", fw.c_str());
+            std::string base;
+            if (!fd.second.word("base", &base) || (base != "time" && base != "iteration"))
+                return fail(FY_ERR_UNSUPPORTED, "%s: base %s is not supported; accepted: time, iteration", fw.c_str(), base.empty() ? "(absent)" : base.c_str());
+            // the file name -> the case's field
+            static const struct { const char* stem; int F; const char* solver_name; int ncomp; } known[] = {
+                {"U", F_U, "U", 3}, {"p", F_P, "p", 1}, {"alpha", F_ALPHA, "alpha", 1}, {"nut", F_NUT, "nut", 1}, {"k", F_K, "k", 1}, {"epsilon", F_EPS, "epsilon", 1},
+                {"uParticle", -1, "uParticle", 3}, {"uSource", -1, "uSource", 3}};
+            const std::string stem = file.substr(0, file.find('.'));
+            const auto* kf = &known[0];
+            bool is_known = false;
+            for (const auto& k : known) if (stem == k.stem) { kf = &k; is_known = true; }
+            if (!is_known) return fail(FY_ERR_UNSUPPORTED, "%s: unknown field '%s'; accepted: %s", fw.c_str(), file.c_str(), accepted.c_str());
+            const bool has = kf->F >= 0 ? (has_field(c, kf->F) && file == field_name(c, kf->F))
+                                        : (file == kf->stem && (stem != "uParticle" || c->solver == FY_SOLVER_PIMPLE));
+            if (!has) return fail(FY_ERR_UNSUPPORTED, "%s: this case has no field '%s' (%s, %s); accepted: %s", fw.c_str(), file.c_str(),
+                                  c->solver == FY_SOLVER_PIMPLE ? "pimpleFoamYade" : "icoFoamYade", c->desc.turbulence_model == FY_TURBULENCE_LAMINAR ? "laminar" : "with a turbulence model", accepted.c_str());
+            if (!mean && prime2) return fail(FY_ERR_UNSUPPORTED, "%s: prime2Mean on needs mean on (OpenFOAM refuses it too); accepted: mean on with prime2Mean on|off, or both off", fw.c_str());
+            if (!mean) continue;                       // mean off; prime2Mean off: nothing to keep
+            for (const auto& a : c->avg_fields) if (a.file == file) return fail(FY_ERR_INVALID, "%s: the field is listed twice", fw.c_str());
+            fy_average_desc& av = c->desc.average;
+            if (av.n_items >= FY_AVERAGE_MAX_ITEMS) return fail(FY_ERR_UNSUPPORTED, "%s: more than %d averaged fields; accepted: at most %d", fw.c_str(), FY_AVERAGE_MAX_ITEMS, FY_AVERAGE_MAX_ITEMS);
+            fy_average_item& it = av.items[av.n_items++];
+            std::snprintf(it.field, sizeof(it.field), "%s", kf->solver_name);
+            it.prime2_mean = prime2 ? 1 : 0; it.iteration_base = base == "iteration" ? 1 : 0;
+            c->avg_fields.push_back({file, kf->F, kf->solver_name, kf->ncomp, prime2});
+        }
+        if (c->desc.average.n_items == 0) { c->desc.average = fy_average_desc{}; }      // (every field switched off: nothing is averaged)
+    }
+    return FY_OK;
+}
+
 int read_controls(fy_foam_case* c) {
+    FoamDict control_dict;
     {
         const std::string path = join(c->dir, "system/controlDict");
         FoamDict d;
@@ -896,6 +988,7 @@ int read_controls(fy_foam_case* c) {
             d.scalar("maxCo", &c->desc.max_co);
             d.scalar("maxDeltaT", &c->desc.max_delta_t);
         }
+        control_dict = d;
     }
     {
         const std::string path = join(c->dir, "constant/transportProperties");
@@ -1118,7 +1211,7 @@ int read_controls(fy_foam_case* c) {
             }
         }
     }
-    return FY_OK;
+    return read_functions(c, control_dict, join(c->dir, "system/controlDict"));
 }
 
 int write_field(const fy_foam_case* c, const std::string& tdir, const std::string& tname, const std::string& name, const char* cls, const char* dims, int ncomp,
@@ -1130,7 +1223,7 @@ int write_field(const fy_foam_case* c, const std::string& tdir, const std::strin
     std::fprintf(f, "FoamFile\n{\n    version     2.0;\n    format      %s;\n", c->write_binary ? "binary" : "ascii");
     if (c->write_binary) std::fprintf(f, "    arch        \"LSB;label=32;scalar=64\";\n");
     std::fprintf(f, "    class       %s;\n    location    \"%s\";\n    object      %s;\n}\n\n", cls, tname.c_str(), name.c_str());
-    std::fprintf(f, "dimensions      %s;\n\ninternalField   nonuniform List<%s> %zu\n(", dims, ncomp == 3 ? "vector" : "scalar", n);
+    std::fprintf(f, "dimensions      %s;\n\ninternalField   nonuniform List<%s> %zu\n(", dims, ncomp == 6 ? "symmTensor" : ncomp == 3 ? "vector" : "scalar", n);
     std::vector<double> vf;                                // lattice order -> the mesh's cell numbers
     if (!c->file_cell.empty() && n == c->file_cell.size()) {
         vf.resize(v.size());
@@ -1145,6 +1238,7 @@ int write_field(const fy_foam_case* c, const std::string& tdir, const std::strin
         std::fputc('\n', f);
         for (size_t q = 0; q < n; ++q) {
             if (ncomp == 3) std::fprintf(f, "(%.*g %.*g %.*g)\n", pr, v_out[3 * q], pr, v_out[3 * q + 1], pr, v_out[3 * q + 2]);
+            else if (ncomp == 6) std::fprintf(f, "(%.*g %.*g %.*g %.*g %.*g %.*g)\n", pr, v_out[6 * q], pr, v_out[6 * q + 1], pr, v_out[6 * q + 2], pr, v_out[6 * q + 3], pr, v_out[6 * q + 4], pr, v_out[6 * q + 5]);
             else std::fprintf(f, "%.*g\n", pr, v_out[q]);
         }
     }
@@ -1173,6 +1267,114 @@ int write_solver_fields(const fy_foam_case* c, const char* time_name, std::initi
         if (has_field(c, F)) { v[F].resize((F == F_U ? 3 : 1) * c->fcells); FY_TRY(read(solver_name[F], v[F].data())); }
     auto ptr = [&](int F) { return v[F].empty() ? nullptr : v[F].data(); };
     return fy_foam_case_write_fields(c, time_name, ptr(F_U), ptr(F_P), ptr(F_ALPHA), ptr(F_NUT), ptr(F_K), ptr(F_EPS));
+}
+
+// the dimension sets of the case's fields, and their squares for prime2Mean
+const int* field_dims(int F, const std::string& solver_name) {
+    static const int U[7] = {0, 1, -1, 0, 0, 0, 0}, p[7] = {0, 2, -2, 0, 0, 0, 0}, none[7] = {0, 0, 0, 0, 0, 0, 0}, nut[7] = {0, 2, -1, 0, 0, 0, 0}, eps[7] = {0, 2, -3, 0, 0, 0, 0},
+                     acc[7] = {0, 1, -2, 0, 0, 0, 0};
+    switch (F) {
+        case F_U: return U;
+        case F_P: case F_K: return p;
+        case F_NUT: return nut;
+        case F_EPS: return eps;
+        case F_ALPHA: return none;
+        default: return solver_name == "uSource" ? acc : U;      // volSource, uParticle (createFields.H of both solvers)
+    }
+}
+std::string dims_text(const int* d, int power) {
+    std::string t = "[";
+    for (int q = 0; q < 7; ++q) t += std::to_string(power * d[q]) + (q < 6 ? " " : "]");
+    return t;
+}
+
+// fieldAverage's part of runTime.write(): the case's object, when the solver averages its fields (a solver made from this case's descriptor: item i = avg_fields[i]).
+// count(name, &n) / read(name, host) / state(i, &N, &T) are the solver's accessors; dt the deltaT of the step just finished
+template <class Count, class Read, class State>
+int write_averages(const fy_foam_case* c, const char* time_name, double dt, Count count, Read read, State state) {
+    if (c->avg_fields.empty()) return FY_OK;
+    for (const auto& a : c->avg_fields) {             // averaging off on this solver (or other items than the case's): nothing beyond the fields
+        int64_t n = 0;
+        if (count((a.solver_name + "Mean").c_str(), &n) != FY_OK || (size_t)n != c->fcells * (size_t)a.ncomp) return FY_OK;
+        if (a.prime2 && count((a.solver_name + "Prime2Mean").c_str(), &n) != FY_OK) return FY_OK;
+    }
+    const std::string tdir = join(c->fdir, time_name);
+    const std::vector<std::pair<std::string, std::string> > none;
+    std::string props = "FoamFile\n{\n    version     2.0;\n    format      ascii;\n    class       dictionary;\n    location    \"" + std::string(time_name) + "/uniform\";\n    object      " +
+                        c->avg_name + "Properties;\n}\n\n";
+    for (size_t i = 0; i < c->avg_fields.size(); ++i) {
+        const auto& a = c->avg_fields[i];
+        const int* dims = field_dims(a.F, a.solver_name);
+        std::vector<double> v(c->fcells * (size_t)a.ncomp);
+        FY_TRY(read((a.solver_name + "Mean").c_str(), v.data()));
+        const PatchField* r = a.F >= 0 && a.F != F_ALPHA ? &c->bcs[a.F] : nullptr;
+        FY_TRY(write_field(c, tdir, time_name, a.file + "Mean", a.ncomp == 3 ? "volVectorField" : "volScalarField", dims_text(dims, 1).c_str(), a.ncomp, v, r,
+                           "        type            zeroGradient;\n", r ? r->extra : none));
+        if (a.prime2) {
+            const int pc = a.ncomp == 3 ? 6 : 1;
+            v.assign(c->fcells * (size_t)pc, 0.0);
+            FY_TRY(read((a.solver_name + "Prime2Mean").c_str(), v.data()));
+            FY_TRY(write_field(c, tdir, time_name, a.file + "Prime2Mean", pc == 6 ? "volSymmTensorField" : "volScalarField", dims_text(dims, 2).c_str(), pc, v, nullptr,
+                               pc == 6 ? "        type            calculated;\n        value           uniform (0 0 0 0 0 0);\n" : "        type            calculated;\n        value           uniform 0;\n", none));
+        }
+        int64_t N = 0; double T = 0.0;
+        FY_TRY(state((int)i, &N, &T));
+        // totalIter / totalTime: OpenFOAM's convention as recalled (N + 1, T + deltaT; unpinned); samples / timeAveraged: this library's own N and T,
+        // written with 17 digits so that a restart continues exactly (T + deltaT - deltaT need not give T back)
+        char buf[512];
+        std::snprintf(buf, sizeof(buf), "%s\n{\n    totalIter       %lld;\n    totalTime       %.17g;\n    samples         %lld;\n    timeAveraged    %.17g;\n}\n\n", a.file.c_str(),
+                      (long long)(N + 1), T + dt, (long long)N, T);
+        props += buf;
+    }
+    const std::string udir = join(tdir, "uniform");
+    if (mkdir(udir.c_str(), 0777) != 0) {
+        struct stat st;
+        if (stat(udir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return fail(FY_ERR_INVALID, "cannot create %s", udir.c_str());
+    }
+    const std::string ppath = join(udir, c->avg_name + "Properties");
+    FILE* f = std::fopen(ppath.c_str(), "wb");
+    if (!f) return fail(FY_ERR_INVALID, "cannot write %s", ppath.c_str());
+    std::fputs(props.c_str(), f);
+    std::fclose(f);
+    return FY_OK;
+}
+
+// the start time directory's averages -> a new solver: per item, when the Properties file has its entry and its mean (and prime2Mean) file is there
+template <class Write, class SetState>
+int restore_averages(const fy_foam_case* c, double dt, int* restored, Write write, SetState set_state) {
+    if (restored) *restored = 0;
+    if (c->avg_fields.empty() || c->avg_restart_on_restart) return FY_OK;
+    const std::string sdir = join(c->fdir, c->start_name);
+    const std::string ppath = join(sdir, "uniform/" + c->avg_name + "Properties");
+    if (!file_exists(ppath)) return FY_OK;
+    FoamDict props;
+    FY_TRY(need_file(ppath, &props));
+    for (size_t i = 0; i < c->avg_fields.size(); ++i) {
+        const auto& a = c->avg_fields[i];
+        const FoamDict* pd = props.subdict(a.file);
+        const std::string mpath = join(sdir, a.file + "Mean"), qpath = join(sdir, a.file + "Prime2Mean");
+        if (!pd || !file_exists(mpath) || (a.prime2 && !file_exists(qpath))) continue;
+        double N = 0, T = 0;
+        if (!(pd->scalar("samples", &N) && pd->scalar("timeAveraged", &T))) {      // a directory OpenFOAM wrote: its convention, inverted
+            if (!pd->scalar("totalIter", &N) || !pd->scalar("totalTime", &T)) return fail(FY_ERR_INVALID, "%s: %s needs totalIter and totalTime", ppath.c_str(), a.file.c_str());
+            N -= 1; T -= dt;
+        }
+        if (N < 0 || T < 0) return fail(FY_ERR_INVALID, "%s: %s: totalIter / totalTime below one step", ppath.c_str(), a.file.c_str());
+        std::vector<double> v;
+        FoamDict mf;
+        FY_TRY(need_file(mpath, &mf));
+        FY_TRY(read_internal(mf, mpath, a.ncomp, c->fcells, &v, c->general ? nullptr : &c->file_cell));
+        FY_TRY(write((a.solver_name + "Mean").c_str(), v.data()));
+        if (a.prime2) {
+            FoamDict qf;
+            FY_TRY(need_file(qpath, &qf));
+            FY_TRY(read_internal(qf, qpath, a.ncomp == 3 ? 6 : 1, c->fcells, &v, c->general ? nullptr : &c->file_cell));
+            FY_TRY(write((a.solver_name + "Prime2Mean").c_str(), v.data()));
+        }
+        FY_TRY(set_state((int)i, (int64_t)std::llround(N), T));
+        if (restored) ++*restored;
+    }
+    return FY_OK;
 }
 
 }  // namespace
@@ -1248,6 +1450,7 @@ int fy_foam_case_info_get(const fy_foam_case* c, fy_foam_case_info* out) {
     std::snprintf(out->phase, sizeof(out->phase), "%s", c->phase.c_str());
     std::snprintf(out->start_name, sizeof(out->start_name), "%s", c->start_name.c_str());
     for (int s = 0; s < 6; ++s) std::snprintf(out->patch_of_side[s], sizeof(out->patch_of_side[s]), "%s", c->patch_of_side[s].c_str());
+    out->n_ignored_functions = (int32_t)c->ignored_functions.size();
     return FY_OK;
 }
 
@@ -1318,7 +1521,14 @@ int fy_foam_case_write_fields(const fy_foam_case* c, const char* time_name, cons
             if (DIR* dd = opendir(old.c_str())) {
                 while (struct dirent* de = readdir(dd)) {
                     const std::string nm = de->d_name;
-                    if (nm != "." && nm != "..") ::unlink(join(old, nm).c_str());
+                    if (nm == "." || nm == "..") continue;
+                    if (nm == "uniform") {                               // <time>/uniform/<object>Properties of a fieldAverage object
+                        if (DIR* ud = opendir(join(old, nm).c_str())) {
+                            while (struct dirent* ue = readdir(ud)) if (std::strcmp(ue->d_name, ".") != 0 && std::strcmp(ue->d_name, "..") != 0) ::unlink(join(join(old, nm), ue->d_name).c_str());
+                            closedir(ud);
+                        }
+                        ::rmdir(join(old, nm).c_str());
+                    } else ::unlink(join(old, nm).c_str());
                 }
                 closedir(dd);
                 ::rmdir(old.c_str());
@@ -1333,7 +1543,26 @@ int fy_foam_case_write_time(const fy_foam_case* c, fy_solver* s, const char* tim
     int64_t cnt = 0;
     FY_TRY(fy_solver_field_count(s, "p", &cnt));
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_UNSUPPORTED, "fy_foam_case_write_time: the solver holds %lld cells, the case's field files %zu (a slab of an undecomposed case: gather the slabs and use fy_foam_case_write_fields)", (long long)cnt, c->fcells);
-    return write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_EPS, F_K}, [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); });
+    FY_TRY(write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_EPS, F_K}, [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); }));
+    fy_step_stats st;
+    FY_TRY(fy_solver_get_stats(s, &st));
+    return write_averages(c, time_name, st.delta_t > 0 ? st.delta_t : c->desc.dt, [s](const char* nm, int64_t* n) { return fy_solver_field_count(s, nm, n); },
+                          [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); },
+                          [s](int i, int64_t* N, double* T) { return fy_solver_get_average_state(s, i, N, T); });
+}
+
+int fy_foam_case_restore_averages(const fy_foam_case* c, fy_solver* s, int* restored) {
+    if (!c || !s) return fail(FY_ERR_INVALID, "fy_foam_case_restore_averages: null argument");
+    if (c->general) return fail(FY_ERR_INVALID, "fy_foam_case_restore_averages: the case holds a general mesh (fy_foam_case_restore_averages_ldu)");
+    return restore_averages(c, c->desc.dt, restored, [s](const char* nm, const double* v) { return fy_solver_write_field_host(s, nm, v); },
+                            [s](int i, int64_t N, double T) { return fy_solver_set_average_state(s, i, N, T); });
+}
+
+int fy_foam_case_ignored_function(const fy_foam_case* c, int i, char* out, int cap) {
+    if (!c || !out || cap < 1) return fail(FY_ERR_INVALID, "fy_foam_case_ignored_function: null argument");
+    if (i < 0 || (size_t)i >= c->ignored_functions.size()) return fail(FY_ERR_INVALID, "fy_foam_case_ignored_function: object %d of %zu", i, c->ignored_functions.size());
+    std::snprintf(out, (size_t)cap, "%s", c->ignored_functions[(size_t)i].c_str());
+    return FY_OK;
 }
 
 int fy_foam_case_open_general(const char* case_dir, int solver, fy_foam_case** out) {
@@ -1393,6 +1622,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->eps_convection_scheme = d.eps_convection_scheme; out->eps_tol = d.eps_tol; out->eps_rel_tol = d.eps_rel_tol; out->eps_max_iter = d.eps_max_iter; out->eps_relax = d.eps_relax;
     out->wf_kappa = d.wf_kappa; out->wf_E = d.wf_E;
     out->drag_law = d.drag_law; out->force_models = d.force_models;
+    out->average = d.average;
     out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
     return FY_OK;
 }
@@ -1412,7 +1642,19 @@ int fy_foam_case_write_time_ldu(const fy_foam_case* c, fy_ldu_solver* s, const c
     FY_TRY(fy_ldu_solver_field_count(s, "p", &cnt));
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_INVALID, "fy_foam_case_write_time_ldu: the solver holds %lld cells, the case %zu", (long long)cnt, c->fcells);
     // (alpha: with fy_ldu_solver_hold_sources, before setSourceZero)
-    return write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_K, F_EPS}, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); });
+    FY_TRY(write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_K, F_EPS}, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); }));
+    fy_step_stats st;
+    FY_TRY(fy_ldu_solver_get_stats(s, &st));
+    return write_averages(c, time_name, st.delta_t > 0 ? st.delta_t : c->desc.dt, [s](const char* nm, int64_t* n) { return fy_ldu_solver_field_count(s, nm, n); },
+                          [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); },
+                          [s](int i, int64_t* N, double* T) { return fy_ldu_solver_get_average_state(s, i, N, T); });
+}
+
+int fy_foam_case_restore_averages_ldu(const fy_foam_case* c, fy_ldu_solver* s, int* restored) {
+    if (!c || !s) return fail(FY_ERR_INVALID, "fy_foam_case_restore_averages_ldu: null argument");
+    if (!c->general) return fail(FY_ERR_INVALID, "fy_foam_case_restore_averages_ldu: the case was opened as a block (fy_foam_case_restore_averages)");
+    return restore_averages(c, c->desc.dt, restored, [s](const char* nm, const double* v) { return fy_ldu_solver_write_field_host(s, nm, v); },
+                            [s](int i, int64_t N, double T) { return fy_ldu_solver_set_average_state(s, i, N, T); });
 }
 
 int fy_foam_case_close(fy_foam_case* c) {

@@ -51,6 +51,21 @@ static void print_coupling(int drag_law, unsigned force_models) {
                 (force_models & FY_FORCE_GAUSSIAN_TORQUE) ? "on" : "off");
 }
 
+// controlDict functions: what is averaged (the solver's create applies it), and one line per function object of another type -- opened, never run
+static void print_functions(const fy_foam_case* fc, const fy_average_desc& av) {
+    fy_foam_case_info info;
+    if (fy_foam_case_info_get(fc, &info) != FY_OK) return;
+    for (int i = 0; i < info.n_ignored_functions; ++i) {
+        char name[256];
+        if (fy_foam_case_ignored_function(fc, i, name, (int)sizeof(name)) == FY_OK) std::printf("functions: %s is not run (only fieldAverage is implemented)\n", name);
+    }
+    if (av.n_items > 0) {
+        std::printf("fieldAverage:");
+        for (int i = 0; i < av.n_items; ++i) std::printf(" %.32s%s", av.items[i].field, av.items[i].prime2_mean ? " (mean, prime2Mean)" : " (mean)");
+        std::printf("\n");
+    }
+}
+
 // icoFoamYade on a general mesh: the same loop around fy_ldu_solver (one domain)
 static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     fy_poly_mesh pm;
@@ -59,6 +74,7 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     if (fy_foam_case_poly_mesh(fc, &pm) != FY_OK || fy_foam_case_ldu_desc(fc, &lc) != FY_OK || fy_foam_case_info_get(fc, &info) != FY_OK) return die("reading the case");
     std::printf("             %d points, %d faces (%d internal), %d cells, %d patches\n", pm.n_points, pm.n_faces, pm.n_internal_faces, pm.n_cells, pm.n_patches);
     print_coupling(lc.drag_law, lc.force_models);
+    print_functions(fc, lc.average);
     fy_ldu_solver* s = nullptr;
     if (fy_ldu_solver_create(&pm, &lc, trp, device, &s) != FY_OK) return die("fy_ldu_solver_create");
     fy_ldu_solver_hold_sources(s, 1);                   // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147, pimpleFoamYade.C:107-109)
@@ -72,6 +88,9 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
             if (fy_foam_case_initial_k(fc, p.data()) != FY_OK || fy_ldu_solver_write_field_host(s, "k", p.data()) != FY_OK) return die("initial k");
         if (lc.turbulence_model == FY_TURBULENCE_KEPSILON)
             if (fy_foam_case_initial_epsilon(fc, p.data()) != FY_OK || fy_ldu_solver_write_field_host(s, "epsilon", p.data()) != FY_OK) return die("initial epsilon");
+        int restored = 0;
+        if (fy_foam_case_restore_averages_ldu(fc, s, &restored) != FY_OK) return die("restoring the averages");
+        if (restored) std::printf("fieldAverage: %d averages continue from time %s\n", restored, info.start_name);
     }
     std::printf("\nStarting time loop\n\n");
     const long n_steps = std::lround((info.end_time - info.start_time) / info.delta_t);
@@ -207,7 +226,7 @@ int main(int argc, char** argv) {
     if (master)
         std::printf("Create mesh: %d x %d x %d cells of %g m, %s on the six sides x- x+ y- y+ z- z+: %s %s %s %s %s %s\n", cd.nx, cd.ny, cd.nz, cd.dx,
                     "patches", info.patch_of_side[0], info.patch_of_side[1], info.patch_of_side[2], info.patch_of_side[3], info.patch_of_side[4], info.patch_of_side[5]);
-    if (master) print_coupling(cd.drag_law, cd.force_models);
+    if (master) { print_coupling(cd.drag_law, cd.force_models); print_functions(fc, cd.average); }
     fy_solver* s = nullptr;
     if ((comm ? fy_solver_create_slab(&cd, trp, device, comm, &s) : fy_solver_create(&cd, trp, device, &s)) != FY_OK) return die("fy_solver_create");
     // a slab owns the z-planes [srank nz / ssize, (srank + 1) nz / ssize): a contiguous run of the block's cells, `first` cells in
@@ -225,6 +244,11 @@ int main(int argc, char** argv) {
                 (fy_foam_case_initial_k(fc, nut.data()) != FY_OK || fy_solver_write_field_host(s, "k", nut.data() + first) != FY_OK)) return die("initial k");
             if (cd.turbulence_model == FY_TURBULENCE_KEPSILON &&
                 (fy_foam_case_initial_epsilon(fc, nut.data()) != FY_OK || fy_solver_write_field_host(s, "epsilon", nut.data() + first) != FY_OK)) return die("initial epsilon");
+        }
+        if (cd.average.n_items > 0) {                                    // (one domain: a slab's create has refused the averages above)
+            int restored = 0;
+            if (fy_foam_case_restore_averages(fc, s, &restored) != FY_OK) return die("restoring the averages");
+            if (restored && master) std::printf("fieldAverage: %d averages continue from time %s\n", restored, info.start_name);
         }
     }
     // runTime.write(): one rank writes its solver's fields; slabs are gathered to the first solver rank, which writes the whole block

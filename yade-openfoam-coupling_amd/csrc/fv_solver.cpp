@@ -325,7 +325,26 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     FY_TRY(halo_U());
     FY_TRY(FVK(launch_flux_of, stream, g, U.p, F3(phi)));                     // createPhi
     FY_HIP(hipStreamSynchronize(stream));
+    if (c->average.n_items) FY_TRY(set_field_average(&c->average));           // controlDict functions: fieldAverage
     return FY_OK;
+}
+
+const double* Solver::avg_source(const std::string& name, int* comp) const {
+    const struct { const char* nm; const double* p; int comp; } tab[] = {{"U", U.p, 3}, {"p", p.p, 1}, {"alpha", alpha.p, 1}, {"uParticle", uParticle.p, 3},
+                                                                         {"uSource", uSource.p, 3}, {"nut", nut.p, 1}, {"k", kturb.p, 1}, {"epsilon", epsturb.p, 1}};
+    for (const auto& e : tab)
+        if (name == e.nm && e.p) { *comp = e.comp; return e.p + (size_t)e.comp * g.c0; }      // (the owned cells: Solver::field)
+    return nullptr;
+}
+
+int Solver::set_field_average(const fy_average_desc* d) {
+    FY_HIP(hipSetDevice(device));
+    if (d && d->n_items != 0 && comm->size > 1) {
+        avg.off();
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_set_field_average: fieldAverage is not available on z-slabs (fy_solver_create_slab over %d ranks, foamYadeHip_mpi -parallel): "
+                                        "run the case on one domain", comm->size);
+    }
+    return avg.configure(d, (size_t)Nc, stream, "fy_solver_set_field_average", [this](const std::string& nm, int* comp) { return avg_source(nm, comp); });
 }
 
 // fold the block partials, all-reduce over the slabs, read back
@@ -781,6 +800,8 @@ int Solver::step() {
         if (g.nut && final_outer) FY_TRY(turbulence_correct());        // pimple.turbCorr(): on the final outer iteration only (the default) -- pimpleFoamYade.C:101-104
     }
     FY_TRY(cpl->c.finish_results());                                                      // the answers still on their way, then the dt handshake (FoamYade.C:537-553)
+    avg.elapsed += cs.dt;
+    if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));      // where runTime.write() stands
     if (hold_sources) sources_pending = true;                                              // reset deferred to the next step (fy_solver_hold_sources)
     else FY_TRY(cpl->c.set_source_zero());                                                // icoFoamYade.C:147, pimpleFoamYade.C:109
     if (timing) tim[3].stop(stream);
@@ -801,6 +822,7 @@ int Solver::step() {
         st.ms_total = tim[3].ms();
         st.ms_other = st.ms_total - st.ms_particle - st.ms_momentum - st.ms_pressure;
         for (auto& k : kc) k.collect();
+        avg.clock.collect();
     }
     if (xwait_timing) {
         for (auto& k : clk_xwait) k.collect();
@@ -831,6 +853,7 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
     MgLev& L = *mg[0];
     const struct { const char* nm; double* p; } pm[] = {{"p_diag", L.diag.p}, {"p_ux", L.ux.p}, {"p_uy", L.uy.p}, {"p_uz", L.uz.p}};
     for (auto& e : pm) if (s == e.nm) { *ptr = e.p + L.A.c0; *count = n; return FY_OK; }
+    if (avg.lookup(s, ptr, count)) return FY_OK;                 // <field>Mean, <field>Prime2Mean
     return fail(FY_ERR_INVALID, "unknown solver field '%s'", s.c_str());
 }
 

@@ -12,6 +12,7 @@
 
 #include "comm.hpp"
 #include "coupling.hpp"
+#include "field_average.hpp"
 #include "fv_kernels.hpp"
 
 // geometry-dependent launchers exist per geometry model (fv_kernels.hpp): the uniform block's in fy, the graded block's in fy::gr
@@ -274,6 +275,11 @@ struct Solver {
     int st_k_iters = 0;
 
     int step();                    // one pass of the while (runTime.loop()) body
+    // fieldAverage (field_average.hpp): sampled once per step where runTime.write() stands -- after the last corrector, turbulence_correct and
+    // finish_results, before setSourceZero or its deferral -- so the averages see the step's alpha / uSource / uParticle whatever hold_sources says
+    FieldAverage avg;
+    const double* avg_source(const std::string& name, int* comp) const;      // the field's owned cells as they lie NOW (the buffers trade places), or nullptr
+    int set_field_average(const fy_average_desc* d);
     // field lookup; cell fields are returned/accepted as the OWNED part only (ghost planes are an implementation detail)
     int field(const char* name, double** ptr, size_t* count);
 };

@@ -132,6 +132,13 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
     FY_TRY(s->s.field(name, &p, &n));
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
+    {
+        double* ap; size_t an;
+        if (s->s.avg.lookup(name ? name : "", &ap, &an)) {      // a restart loading an average: not a solver field -- the flux, the carried sums and the halos stay
+            FY_HIP(hipStreamSynchronize(s->s.stream));
+            return FY_OK;
+        }
+    }
     s->s.carry_valid = false;                 // whatever was written, the carried Courant sums may no longer describe phi
     s->s.p_sum_valid = false; s->s.p_ghosts_fresh = false;
     if (std::string(name) == "U") {           // createPhi (collective when there are several slabs)
@@ -147,6 +154,10 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
 }
 
 int fy_solver_destroy(fy_solver* s) { delete s; return FY_OK; }
+
+int fy_solver_set_field_average(fy_solver* s, const fy_average_desc* d) { FY_S(s); return s->s.set_field_average(d); }
+int fy_solver_get_average_state(fy_solver* s, int item, int64_t* samples, double* time_averaged) { FY_S(s); return s->s.avg.get_state(item, samples, time_averaged); }
+int fy_solver_set_average_state(fy_solver* s, int item, int64_t samples, double time_averaged) { FY_S(s); return s->s.avg.set_state(item, samples, time_averaged); }
 
 int fy_solver_apply_p_matrix_host(fy_solver* s, const double* x, double* y) {
     FY_S(s);
@@ -194,6 +205,7 @@ int fy_solver_time_p_apply(fy_solver* s, int reps, double* avg_ms) {
 int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     FY_S(s);
     for (auto& k : s->s.kc) { k.reset(); k.on = on != 0; }
+    s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
     return FY_OK;
 }
 
@@ -214,6 +226,7 @@ int fy_solver_get_exchange_wait(fy_solver* s, double ms[4], int64_t waits[4]) {
 int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
     FY_S(s);
     const std::string k = kernel ? kernel : "";
+    if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }
     int idx = k == "mg_smooth_l0" ? fy::Solver::KC_MG_SMOOTH0 : k == "p_apply_dot" ? fy::Solver::KC_P_APPLY_DOT : k == "mom_pass" ? fy::Solver::KC_MOM_PASS : -1;
     if (idx < 0 || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s'", k.c_str());
     *total_ms = s->s.kc[idx].total_ms; *launches = s->s.kc[idx].launches;

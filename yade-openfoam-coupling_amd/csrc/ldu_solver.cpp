@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "coupling.hpp"
+#include "field_average.hpp"
 #include "fv_kernels.hpp"
 #include "ldu.hpp"
 #include "ldu_amg.hpp"
@@ -68,6 +69,20 @@ struct LduSolver {
     fy_step_stats st{};
     double cumulative = 0.0, total_volume = 0.0;
     EventTimer tim[2];
+    // fieldAverage (field_average.hpp), sampled where runTime.write() stands: after the last corrector and the turbulence correction, before setSourceZero
+    FieldAverage avg;
+    const double* avg_source(const std::string& name, int* comp) const {      // the field as it lies NOW (U and its scratch buffer trade places)
+        const struct { const char* nm; const double* p; int comp; bool have; } tab[] = {
+            {"U", U.p, 3, true}, {"p", p.p, 1, true}, {"alpha", alpha.p, 1, pimple}, {"uParticle", uParticle.p, 3, pimple}, {"uSource", uSource.p, 3, true},
+            {"nut", nut.p, 1, les}, {"k", kturb.p, 1, keqn || keps}, {"epsilon", epsturb.p, 1, keps}};
+        for (const auto& e : tab)
+            if (name == e.nm && e.have && e.p) { *comp = e.comp; return e.p; }
+        return nullptr;
+    }
+    int set_field_average(const fy_average_desc* d) {
+        FY_HIP(hipSetDevice(device));
+        return avg.configure(d, (size_t)nc, stream, "fy_ldu_solver_set_field_average", [this](const std::string& nm, int* comp) { return avg_source(nm, comp); });
+    }
 
     ~LduSolver() {
         if (cpl) fy_destroy(cpl);
@@ -249,6 +264,7 @@ struct LduSolver {
         }
         FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                    // createPhi
         FY_HIP(hipStreamSynchronize(stream));
+        if (c->average.n_items) FY_TRY(set_field_average(&c->average));       // controlDict functions: fieldAverage
         return FY_OK;
     }
 
@@ -530,6 +546,8 @@ struct LduSolver {
             }
             for (int corr = 0; corr < cs.n_correctors; ++corr) FY_TRY(corrector(corr == cs.n_correctors - 1));         // :97-140
         }
+        avg.elapsed += cs.dt;
+        if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));
         if (hold_sources) sources_pending = true;                                                                 // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147)
         else FY_TRY(cpl->c.set_source_zero());                                                                    // :147
         tim[1].stop(stream);
@@ -555,6 +573,7 @@ struct LduSolver {
                          {"divT", divT.p, pimple ? 3 * n : 0}, {"ddtU", ddtU.p, pimple ? 3 * n : 0}, {"phiForces", phiForces.p, pimple ? (size_t)nf : 0}, {"alphaf", alphaf.p, pimple ? (size_t)nf : 0},
                          {"rAUf", rAUf.p, (size_t)nf}, {"uSourceCoupling", uSource.p, 3 * n}, {"nut", nut.p, les ? n : 0}, {"k", kturb.p, (keqn || keps) ? n : 0}, {"epsilon", epsturb.p, keps ? n : 0}};
         for (const E& e : tab) if (s == e.nm) { *ptr = e.p; *count = e.c; return FY_OK; }
+        if (avg.lookup(s, ptr, count)) return FY_OK;                           // <field>Mean, <field>Prime2Mean
         if (s == "nut_boundary") {                                                 // formed on request: nut_b as ldu_nut_b gives it now
             *count = les ? (size_t)(nf - ni) : 0;
             if (*count) {
@@ -634,6 +653,15 @@ int fy_ldu_solver_write_field_host(fy_ldu_solver* s, const char* name, const dou
     double* p; size_t n; const std::vector<double>* h;
     FY_TRY(s->s.field(name, &p, &n, &h));
     const std::string nm = name;
+    {
+        double* ap; size_t an;
+        if (!h && s->s.avg.lookup(nm, &ap, &an)) {             // a restart loading an average: a plain copy, nothing of the solver's state follows from it
+            FY_HIP(hipSetDevice(s->s.device));
+            FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
+            FY_HIP(hipStreamSynchronize(s->s.stream));
+            return FY_OK;
+        }
+    }
     const bool pim_in = (s->s.pimple && (nm == "alpha" || nm == "uSourceDrag")) || (s->s.les && nm == "nut") || ((s->s.keqn || s->s.keps) && nm == "k") || (s->s.keps && nm == "epsilon");      // (what setParticleAction would leave: for tests that feed the equations a given void fraction)
     if (h || (nm != "U" && nm != "p" && nm != "uSource" && !pim_in)) return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_write_field_host: '%s' cannot be written (U, p, uSource; alpha, uSourceDrag with pimpleFoamYade)", nm.c_str());
     FY_HIP(hipSetDevice(s->s.device));
@@ -664,6 +692,9 @@ int fy_ldu_solver_apply(fy_ldu_solver* s, const char* op, const double* in, doub
     FY_HIP(hipStreamSynchronize(S.stream));
     return FY_OK;
 }
+int fy_ldu_solver_set_field_average(fy_ldu_solver* s, const fy_average_desc* d) { FY_LS(s); return s->s.set_field_average(d); }
+int fy_ldu_solver_get_average_state(fy_ldu_solver* s, int item, int64_t* samples, double* time_averaged) { FY_LS(s); return s->s.avg.get_state(item, samples, time_averaged); }
+int fy_ldu_solver_set_average_state(fy_ldu_solver* s, int item, int64_t samples, double time_averaged) { FY_LS(s); return s->s.avg.set_state(item, samples, time_averaged); }
 int fy_ldu_solver_hold_sources(fy_ldu_solver* s, int on) { FY_LS(s); s->s.hold_sources = on != 0; return FY_OK; }
 int fy_ldu_solver_mg_levels(fy_ldu_solver* s, int cap, int32_t* cells, int32_t* slots, int* n_levels) {
     FY_LS(s);
