@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 16
+#define FY_ABI_VERSION 17
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -461,6 +461,16 @@ int fy_solver_apply_p_matrix_host(fy_solver*, const double* x, double* y);
 /* solve  A x = rhs  with the pressure solver of the case (PCG + multigrid / Jacobi, pFinal tolerances) and the pressure matrix the last
    step assembled; x holds the start vector on entry.  For known-answer tests of the solver itself (manufactured Poisson problems). */
 int fy_solver_solve_p_host(fy_solver*, const double* rhs, double* x, int* iterations);
+/* z = M^-1 r on the owned cells with the preconditioner of the case's p_solver and the pressure matrix the last step assembled: one multigrid V-cycle
+   (FY_PSOLVER_PCG_MG), or r / diag (FY_PSOLVER_PCG_JACOBI); r, z host arrays.  On z-slabs the call is collective and takes the route the solve takes (the
+   communication-avoiding cycle where the slabs carry its ghost planes).  The solver is left as it was found -- p, the residual, the carried sum of p, the
+   levels' buffer roles: a run with calls between its steps gives the bits of a run without.  For tests that hold the cycle to a reference as an operation. */
+int fy_solver_precondition_host(fy_solver*, const double* r, double* z);
+/* the multigrid hierarchy of FY_PSOLVER_PCG_MG, finest first (one level with the Jacobi preconditioner): edge lengths, nz_owned = this rank's planes of a
+   distributed level or every plane of a replicated one, distributed = 1 | 0; fills the first `cap` levels, *n_levels = how many there are.  The operators of
+   level l >= 1 are read by name through fy_solver_read_field_host: mg<l>_diag | mg<l>_ux | mg<l>_uy | mg<l>_uz (nx ny nz_owned values; read-only), beside
+   level 0's p_diag | p_ux | p_uy | p_uz. */
+int fy_solver_mg_levels(fy_solver*, int cap, int32_t* nx, int32_t* ny, int32_t* nz_owned, int32_t* distributed, int* n_levels);
 /* time `reps` launches of the pEqn Laplacian apply (the roofline kernel) with HIP events on the solver stream; returns avg ms */
 int fy_solver_time_p_apply(fy_solver*, int reps, double* avg_ms);
 

@@ -1302,6 +1302,12 @@ int orc_fv_solve_p(void* h, const double* rhs, double* x) {
     std::memcpy(x, f->p.data(), (size_t)f->Nc * sizeof(double));
     return it;
 }
+// z = M^-1 r with the preconditioner of the case's p_solver (one V-cycle, or r / diag) and the operators of the last step
+void orc_fv_precondition(void* h, const double* r, double* z) {
+    Fv* f = (Fv*)h; vec rv(r, r + f->Nc), zv(f->Nc);
+    f->precondition(rv, zv);
+    std::memcpy(z, zv.data(), zv.size() * sizeof(double));
+}
 // y = A x with the current pressure matrix (level 0)
 void orc_fv_apply_p(void* h, const double* x, double* y) {
     Fv* f = (Fv*)h; vec xv(x, x + f->Nc), yv(f->Nc);

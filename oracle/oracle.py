@@ -343,6 +343,8 @@ def _fv_lib():
         L.orc_fv_step_end.argtypes = [C.c_void_p]
         L.orc_fv_get_stats.argtypes = [C.c_void_p, C.POINTER(FvStats)]
         L.orc_fv_apply_p.argtypes = [C.c_void_p, _dp, _dp]
+        L.orc_fv_precondition.argtypes = [C.c_void_p, _dp, _dp]
+        L.orc_fv_precondition.restype = None
         L.orc_fv_solve_p.argtypes = [C.c_void_p, _dp, _dp]
         L.orc_fv_solve_p.restype = C.c_int
         _fv_ready = True
@@ -424,6 +426,13 @@ class FvSolver:
         y = np.empty_like(x)
         self.L.orc_fv_apply_p(self.h, _d(x), _d(y))
         return y
+
+    def precondition(self, r):
+        """z = M^-1 r: one V-cycle (p_solver 1) or r / diag, with the operators of the last step"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.empty_like(r)
+        self.L.orc_fv_precondition(self.h, _d(r), _d(z))
+        return z
 
     def solve_p(self, rhs, x0=None):
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)

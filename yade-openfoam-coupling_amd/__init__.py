@@ -304,6 +304,8 @@ def lib():
     L.fy_solver_apply_p_matrix_host.argtypes = [vp, _dp, _dp]
     L.fy_solver_time_p_apply.argtypes = [vp, C.c_int, _dp]
     L.fy_solver_solve_p_host.argtypes = [vp, _dp, _dp, C.POINTER(C.c_int)]
+    L.fy_solver_precondition_host.argtypes = [vp, _dp, _dp]
+    L.fy_solver_mg_levels.argtypes = [vp, C.c_int, _ip, _ip, _ip, _ip, C.POINTER(C.c_int)]
     L.fy_rccl_unique_id.argtypes = [C.c_void_p]
     L.fy_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(vp)]
     L.fy_comm_create_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(vp)]
@@ -787,6 +789,20 @@ class Solver(_Averages):
         _check(lib().fy_solver_solve_p_host(self._h, _d(rhs), _d(x), C.byref(it)))
         return x, it.value
 
+    def precondition(self, r):
+        """z = M^-1 r with the case's preconditioner (one V-cycle, or r / diag) and the matrix of the last step; leaves the solver as it found it"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.empty_like(r)
+        _check(lib().fy_solver_precondition_host(self._h, _d(r), _d(z)))
+        return z
+
+    def mg_levels(self):
+        """[(nx, ny, nz_owned, distributed)] of the pressure multigrid hierarchy, finest first; get("mg<l>_diag" | "_ux" | "_uy" | "_uz") reads level l >= 1"""
+        a = [np.zeros(32, np.int32) for _ in range(4)]
+        n = C.c_int(0)
+        _check(lib().fy_solver_mg_levels(self._h, 32, _i(a[0]), _i(a[1]), _i(a[2]), _i(a[3]), C.byref(n)))
+        return [(int(a[0][q]), int(a[1][q]), int(a[2][q]), bool(a[3][q])) for q in range(n.value)]
+
     def time_p_apply(self, reps=50):
         ms = C.c_double()
         _check(lib().fy_solver_time_p_apply(self._h, int(reps), C.byref(ms)))
@@ -1119,6 +1135,33 @@ class VirtualSlabs:
         assert name != "phi_z" and sum(sizes) == arr.size
         offs = np.concatenate([[0], np.cumsum(sizes)])
         self._each(lambda r: self.solvers[r].set(name, arr[offs[r]:offs[r + 1]]))
+
+    def _split_cells(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        n = self.case.nx * self.case.ny * self.nz_local
+        assert x.size == n * self.n
+        return [x[r * n:(r + 1) * n] for r in range(self.n)]
+
+    def apply_p(self, x):
+        """A x over the whole block (collective; cell vectors are split and concatenated by owned planes, like set / get)"""
+        parts, out = self._split_cells(x), [None] * self.n
+        self._each(lambda r: out.__setitem__(r, self.solvers[r].apply_p(parts[r])))
+        return np.concatenate(out)
+
+    def precondition(self, r):
+        """M^-1 r over the whole block (collective)"""
+        parts, out = self._split_cells(r), [None] * self.n
+        self._each(lambda q: out.__setitem__(q, self.solvers[q].precondition(parts[q])))
+        return np.concatenate(out)
+
+    def solve_p(self, rhs, x0=None):
+        """A x = rhs over the whole block (collective); returns (x, iterations)"""
+        b = self._split_cells(rhs)
+        x = self._split_cells(np.zeros_like(rhs) if x0 is None else x0)
+        out = [None] * self.n
+        self._each(lambda r: out.__setitem__(r, self.solvers[r].solve_p(b[r], x[r])))
+        assert len({it for _, it in out}) == 1
+        return np.concatenate([o[0] for o in out]), out[0][1]
 
     def set_particles(self, records):
         """split the records by the slab their z lies in (every rank gets exactly the particles inside its own slab)"""

@@ -32,6 +32,7 @@ struct Options {
     int locate_stack;            // FOAMYADE_LOCATE_STACK=n      explicit tree: the walk's LDS stack depth (0: the full depth; unset, -1: measured per step)
     bool locate_wide;            // FOAMYADE_LOCATE_WIDE=1       explicit tree: the 16-byte stack entries of 2^25 cells and more on any tree
     bool no_deep_vcycle;         // FOAMYADE_NO_DEEP_VCYCLE=1    slab multigrid: one exchange per sweep instead of one per level and cycle
+    long long mg_replicate_below; // FOAMYADE_MG_REPLICATE_BELOW=n  slab multigrid: levels of <= n global cells are replicated (0, unset: kMgReplicateBelow)
     bool localcomm_stream;       // FOAMYADE_LOCALCOMM_STREAM=1  in-process slab groups: collectives as event waits on the ranks' streams
     bool no_fused_corrector;     // FOAMYADE_NO_FUSED_CORRECTOR=1  the corrector as five sweeps instead of the two fused ones
     bool faces_from_arrays;      // FOAMYADE_FACES_FROM_ARRAYS=1   the fused sweeps stream rAUf / alphacf from their face arrays instead of re-forming them

@@ -331,4 +331,36 @@ int Solver::solve_pressure(bool final_iter, bool init_done) {
     return FY_OK;
 }
 
+// The preconditioner alone, for the tests that hold it to a reference: the cycle solve_pressure runs on its residual, here on a right-hand side
+// from the host.  The right-hand side travels in pzj (with the V-cycle: a buffer solve_pressure never touches; with Jacobi: its output, and pw its
+// input -- both scratch between two solves), so pr keeps what the last solve left; the levels' iterate / right-hand side roles are put back.
+int Solver::precondition(const double* r_host, double* z_host) {
+    Comm::Tag tag(comm, "vcycle");
+    MgLev& L = *mg[0];
+    const size_t bytes = (size_t)Nc * sizeof(double);
+    const double* u;
+    if (cs.p_solver == FY_PSOLVER_PCG_MG) {
+        struct Roles { double* xcur; double* xalt; const double* bptr; };
+        std::vector<Roles> keep;
+        for (auto& M : mg) keep.push_back(Roles{M->xcur, M->xalt, M->bptr});
+        const bool want = want_vcycle_dot, done = vcycle_dot_done;
+        FY_HIP(hipMemcpyAsync(pzj.p + g.c0, r_host, bytes, hipMemcpyHostToDevice, stream));
+        L.bptr = pzj.p;
+        int rc;
+        if (mg_deep) rc = vcycle_deep(0, 1);
+        else { want_vcycle_dot = true; rc = vcycle(0); }
+        u = L.xcur;
+        if (rc == FY_OK && hipMemcpyAsync(z_host, u + g.c0, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess) rc = fail(FY_ERR_HIP, "fy_solver_precondition_host: copy to the host failed");
+        want_vcycle_dot = want; vcycle_dot_done = done;
+        for (size_t l = 0; l < mg.size(); ++l) { mg[l]->xcur = keep[l].xcur; mg[l]->xalt = keep[l].xalt; mg[l]->bptr = keep[l].bptr; }
+        FY_TRY(rc);
+    } else {
+        FY_HIP(hipMemcpyAsync(pw.p + g.c0, r_host, bytes, hipMemcpyHostToDevice, stream));
+        FY_TRY(launch_jacobi_precond(stream, L.A, pw.p, pzj.p));
+        FY_HIP(hipMemcpyAsync(z_host, pzj.p + g.c0, bytes, hipMemcpyDeviceToHost, stream));
+    }
+    FY_HIP(hipStreamSynchronize(stream));
+    return FY_OK;
+}
+
 }  // namespace fy

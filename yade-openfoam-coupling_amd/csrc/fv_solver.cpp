@@ -222,6 +222,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
         int ax = g.nx, ay = g.ny, az_loc = g.nz, az_glob = c->nz;
         bool dist = S > 1;
         size_t lvl = 0;
+        const int64_t replicate_below = opt.mg_replicate_below > 0 ? (int64_t)opt.mg_replicate_below : (int64_t)kMgReplicateBelow;
         mg_rep = (size_t)-1;
         for (;;) {
             std::unique_ptr<MgLev> L(new MgLev());
@@ -254,7 +255,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
                 const int64_t nNg = (int64_t)nax * nay * naz_glob;
                 if (az_loc % 2 != 0) return fail(FY_ERR_UNSUPPORTED, "slab plane count %d cannot be aggregated", az_loc);
                 az_loc /= 2;                                         // the slice of the next level this rank's cells aggregate to
-                if (az_loc % 2 != 0 || az_loc < 2 || nNg <= kMgReplicateBelow) dist = false;   // next level: replicated
+                if (az_loc % 2 != 0 || az_loc < 2 || nNg <= replicate_below) dist = false;   // next level: replicated
             }
             ax = nax; ay = nay; az_glob = naz_glob;
             ++lvl;
@@ -853,6 +854,19 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
     MgLev& L = *mg[0];
     const struct { const char* nm; double* p; } pm[] = {{"p_diag", L.diag.p}, {"p_ux", L.ux.p}, {"p_uy", L.uy.p}, {"p_uz", L.uz.p}};
     for (auto& e : pm) if (s == e.nm) { *ptr = e.p + L.A.c0; *count = n; return FY_OK; }
+    // mg<l>_diag | _ux | _uy | _uz, l >= 1: a coarse pressure operator (the owned planes of a distributed level, the whole of a replicated one)
+    if (s.size() > 2 && s.compare(0, 2, "mg") == 0 && s[2] >= '1' && s[2] <= '9') {
+        size_t q = 2, lvl = 0;
+        while (q < s.size() && s[q] >= '0' && s[q] <= '9' && lvl < 1000) lvl = 10 * lvl + (size_t)(s[q++] - '0');
+        const std::string arr = s.substr(q);
+        if (lvl < mg.size() && (arr == "_diag" || arr == "_ux" || arr == "_uy" || arr == "_uz")) {
+            MgLev& M = *mg[lvl];
+            double* base = arr == "_diag" ? M.diag.p : arr == "_ux" ? M.ux.p : arr == "_uy" ? M.uy.p : M.uz.p;
+            *ptr = base + M.A.c0; *count = (size_t)M.A.N;
+            return FY_OK;
+        }
+        return fail(FY_ERR_INVALID, "unknown solver field '%s' (the multigrid hierarchy has %zu levels)", s.c_str(), mg.size());
+    }
     if (avg.lookup(s, ptr, count)) return FY_OK;                 // <field>Mean, <field>Prime2Mean
     return fail(FY_ERR_INVALID, "unknown solver field '%s'", s.c_str());
 }

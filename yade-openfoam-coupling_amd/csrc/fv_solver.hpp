@@ -26,6 +26,7 @@ constexpr int kMgCoarsest = kMgDirectMax, kMgCoarsestEdge = 8;      // the coars
 constexpr int kMgDeepGhost = 5;               // ghost planes of a distributed level that runs the communication-avoiding V-cycle (fv_pressure.cpp: E + 3 <= 5)
 constexpr int kMgReplicateBelow = 1 << 20;    // a distributed hierarchy hands over to the replicated one at <= this many GLOBAL cells: every
                                               // distributed level costs 4 neighbour exchanges per V-cycle, a replicated 1 M-cell level ~15 us per kernel
+                                              // (the default of FOAMYADE_MG_REPLICATE_BELOW, with which a small test case carries several distributed levels)
 
 struct MgLev {
     PMat A{};
@@ -248,6 +249,8 @@ struct Solver {
     bool p_sum_valid = false;
     // init_done: r0 = b - A p and its two sums are already in pr / partials (the fused corrector sweep formed them: prepare_p_init + launch_corr_front)
     int solve_pressure(bool final_iter, bool init_done = false);      // OpenFOAM PCG.C with lduMatrix::solver::normFactor; preconditioner = MG V-cycle or Jacobi
+    // z = M^-1 r on the owned cells by the route solve_pressure takes (fy_solver_precondition_host); leaves p, pr, p_sum_valid and the levels' buffer roles alone
+    int precondition(const double* r_host, double* z_host);
     int prepare_p_init(bool with_halo = true);          // sum(p) for the norm factor's xbar where the last PCG update did not leave it, and p's ghost planes
     bool fused_corrector = true;   // the corrector as two fused sweeps (FOAMYADE_NO_FUSED_CORRECTOR=1: the five sweeps of rounds 1 - 4; identical results)
     bool hbya_ready = false;       // HbyA already holds rAU H(U) of the current U (written by the momentum predictor's last pass)

@@ -121,6 +121,7 @@ int fy_solver_read_field_host(fy_solver* s, const char* name, double* out) {
     double* p; size_t n;
     FY_TRY(s->s.field(name, &p, &n));
     FY_HIP(hipSetDevice(s->s.device));
+    if (name && std::strncmp(name, "mg", 2) == 0) FY_TRY(s->s.wait_coarse());      // (a single domain builds the coarse operators beside the solve, on the second stream)
     FY_HIP(hipMemcpyAsync(out, p, n * sizeof(double), hipMemcpyDeviceToHost, s->s.stream));
     FY_HIP(hipStreamSynchronize(s->s.stream));
     return FY_OK;
@@ -130,6 +131,7 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
     FY_S(s);
     double* p; size_t n;
     FY_TRY(s->s.field(name, &p, &n));
+    if (name && std::strncmp(name, "mg", 2) == 0) return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (rebuilt from the pressure matrix at every assembly)", name);
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
     {
@@ -144,7 +146,8 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
     if (std::string(name) == "U") {           // createPhi (collective when there are several slabs)
         s->s.U_ghosts_fresh = false;
         FY_TRY(s->s.halo_U());
-        FY_TRY(fy::launch_flux_of(s->s.stream, s->s.g, s->s.U.p, s->s.F3(s->s.phi)));
+        // (per geometry model, like Solver::create's: on a graded block the uniform launcher would take every face for a dx x dx square midway between its cells)
+        FY_TRY(s->s.g.graded ? fy::gr::launch_flux_of(s->s.stream, s->s.g, s->s.U.p, s->s.F3(s->s.phi)) : fy::launch_flux_of(s->s.stream, s->s.g, s->s.U.p, s->s.F3(s->s.phi)));
     }
     if (std::string(name) == "nut") FY_TRY(s->s.halo_cells(s->s.nut, 1, 1));
     if (std::string(name) == "k") FY_TRY(s->s.halo_cells(s->s.kturb, 1, 1));
@@ -184,6 +187,27 @@ int fy_solver_solve_p_host(fy_solver* s, const double* rhs, double* x, int* iter
     FY_HIP(hipMemcpyAsync(x, S.p.p + S.g.c0, (size_t)S.Nc * sizeof(double), hipMemcpyDeviceToHost, S.stream));
     FY_HIP(hipStreamSynchronize(S.stream));
     if (iterations) *iterations = S.st.p_iters_total - before;
+    return FY_OK;
+}
+
+int fy_solver_precondition_host(fy_solver* s, const double* r, double* z) {
+    FY_S(s);
+    if (!r || !z) return fy::fail(FY_ERR_INVALID, "fy_solver_precondition_host: null argument");
+    FY_HIP(hipSetDevice(s->s.device));
+    return s->s.precondition(r, z);
+}
+
+int fy_solver_mg_levels(fy_solver* s, int cap, int32_t* nx, int32_t* ny, int32_t* nz_owned, int32_t* distributed, int* n_levels) {
+    FY_S(s);
+    if (!n_levels) return fy::fail(FY_ERR_INVALID, "fy_solver_mg_levels: null n_levels");
+    *n_levels = (int)s->s.mg.size();
+    for (int l = 0; l < *n_levels && l < cap; ++l) {
+        const fy::MgLev& L = *s->s.mg[(size_t)l];
+        if (nx) nx[l] = L.A.nx;
+        if (ny) ny[l] = L.A.ny;
+        if (nz_owned) nz_owned[l] = L.A.nz;
+        if (distributed) distributed[l] = L.distributed ? 1 : 0;
+    }
     return FY_OK;
 }
 
