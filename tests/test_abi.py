@@ -3,6 +3,7 @@ fails loudly without a GPU, and the product never reaches into oracle/."""
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 
 import pytest
@@ -26,6 +27,33 @@ def test_library_exports_every_declared_symbol(product):
     import re
     hdr = open(os.path.join(ROOT, "include", "foamyade_hip.h")).read()
     assert L.fy_abi_version() == int(re.search(r"#define FY_ABI_VERSION (\d+)", hdr).group(1))      # the library was built from this header
+
+
+# the launchers of fv_linalg_kernels.hip (and its two host helpers): none takes an FvGeo
+GEOMETRY_FREE = """launch_reduce_finalize launch_sum3 launch_p_apply launch_p_apply_dot launch_p_init launch_dot launch_pcg_cg_update
+launch_jacobi_precond launch_mg_coarsen launch_mg_ref_term launch_mg_smooth_first launch_mg_smooth_two_from_zero launch_mg_smooth
+launch_mg_smooth_dot launch_mg_residual_restrict launch_mg_prolong_add launch_mg_prolong_add_planes launch_mg_smooth_prolong
+launch_mg_coarse_factor launch_mg_coarse_solve launch_mg_tail launch_copy_f64 launch_relax_field launch_mg_coarsen_ghost launch_add_f64
+mg_coarse_direct_ok mg_coarse_factor_doubles""".split()
+
+
+def test_geometry_free_launchers_are_built_once(product):
+    """fv_kernels.hip is compiled once per geometry model (fy, fy::gr); what reads no geometry -- pressure solver, multigrid, vector kernels --
+    is fv_linalg_kernels.hip, compiled once: fy::gr holds launchers that take an FvGeo and nothing else."""
+    if shutil.which("nm") is None:
+        pytest.skip("no nm on this host")
+    product.build()
+    out = subprocess.run(["nm", "-DC", "--defined-only", product.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    syms = [ln.split(None, 2)[2] for ln in out.splitlines() if len(ln.split(None, 2)) == 3]
+    graded = [x for x in syms if x.startswith("fy::gr::launch_")]
+    assert graded, "no fy::gr::launch_* symbol exported"
+    no_geo = [x for x in graded if "fy::FvGeo" not in x]
+    assert not no_geo, f"{len(no_geo)} geometry-free launchers were built a second time in fy::gr: {no_geo}"
+    assert not [x for x in syms if x.startswith("fy::gr::mg_coarse_")]
+    assert len(GEOMETRY_FREE) == 27
+    for name in GEOMETRY_FREE:
+        hits = [x for x in syms if re.match(rf"fy::(\w+::)*{name}\(", x)]
+        assert len(hits) == 1 and hits[0].startswith(f"fy::{name}("), (name, hits)
 
 
 def test_no_cpu_fallback_without_device(product):

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "fv_linalg_kernels.hpp"
+
 namespace fy {
 
 // geometry + boundary conditions, passed by value to every kernel
@@ -70,30 +72,16 @@ struct CFace3 { const double* a[3]; };
 // such internalCoeffs apart from the scalar lduMatrix diagonal: solve adds them per component, A() their component average, H() the rest)
 struct Mom7 { double* diag; double* an[6]; double* bd; };
 
-// symmetric 7-point pressure matrix of one multigrid level: (A x)_c = diag_c x_c - sum u_f x_nb, u_* stored at the owner (low) cell
-struct PMat {
-    int nx, ny, nz, N;      // owned extent of this level
-    int c0, ntot;           // storage index of the first owned cell, storage size (owned + ghost planes)
-    double *diag, *ux, *uy, *uz;
-};
-
-// reducing kernels emit one partial per 256-cell block; the count is rounded up to a multiple of 8 for the XCD-aware block order
-inline int red_blocks(int n) { return (((n + 255) / 256) + 7) & ~7; }
-
 inline size_t fv_fsize(const FvGeo& g, int d) {
     return d == 0 ? (size_t)(g.nx + 1) * g.ny * g.nz : d == 1 ? (size_t)g.nx * (g.ny + 1) * g.nz : (size_t)g.nx * g.ny * (g.nz + 1);
 }
 
 struct TurbEqn { int mode; double ck, ce, delta, c1, c2, c3, sigma, xmin, relax; int upwind; int bc[6]; double val[6]; int wall[6]; double cmu75, cmu25, kappa; };
-constexpr int kMgDirectMax = 128, kMgDirectBand = 64;
-constexpr int kMgTailMax = 6;
-constexpr int kMgTailCells = 1024;   // measured: at 8000 cells one workgroup (137 us) is SLOWER than the ~20 separate launches it replaces
-struct MgWeights { int n; double w[4]; };      // the smoother's Jacobi weights per sweep (pre-smoothing order; post-smoothing runs them backwards)
 
-// The launchers exist twice: fy::launch_* for the uniform block (dx, Af, V constants in every kernel) and fy::gr::launch_* for a graded block
-// (per-axis cell sizes, linear-interpolation weights, |Sf| / |d| per face) -- ONE source, fv_kernels.hip, compiled once per geometry model
-// (fv_kernels_graded.hip), so that the uniform block's kernels carry no trace of the general one.  The geometry-free launchers (linear
-// algebra, multigrid) are the same code in both.
+// The launchers that take an FvGeo exist twice: fy::launch_* for the uniform block (dx, Af, V constants in every kernel) and fy::gr::launch_* for a
+// graded block (per-axis cell sizes, linear-interpolation weights, |Sf| / |d| per face) -- ONE source, fv_kernels.hip, compiled once per geometry
+// model (fv_kernels_graded.hip), so that the uniform block's kernels carry no trace of the general one.  The launchers that take none (pressure
+// solver, multigrid, vector kernels: fv_linalg_kernels.hpp) exist once, in fy, and serve both.
 #include "fv_kernels_api.inc"
 namespace gr {
 #include "fv_kernels_api.inc"

@@ -9,19 +9,14 @@
 #include <memory>
 #include <numeric>
 
-#include "fv_kernels.hpp"
+#include "device_util.hpp"
+#include "fv_linalg_kernels.hpp"
 #include "ldu_amg.hpp"
 
 namespace fy {
 namespace {
 
 constexpr double kWa = 1.7318685872766142, kWb = 0.5695012757370842;      // fv_solver.hpp: the degree-2 Chebyshev pair of D^-1 A on [1/3, 2]
-
-#define FY_LAUNCH_CHECK()                                                                                     \
-    do {                                                                                                      \
-        hipError_t _e = hipGetLastError();                                                                    \
-        if (_e != hipSuccess) return fail(FY_ERR_HIP, "kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 __device__ __forceinline__ double ell_offdiag(const EllMat& A, const double* __restrict__ x, int c) {
     // (a row's entries come first, its padding -- the cell itself with coefficient 0 -- after them: the loop ends at the first pad, so a mesh with a few many-faced cells

@@ -5,7 +5,8 @@
 // general mesh costs.  The arithmetic is OpenFOAM-6's, restated [OF-6]; oracle/ldu_oracle.cpp is the CPU restatement the tests compare with.
 #include <hip/hip_runtime.h>
 
-#include "fv_kernels.hpp"
+#include "device_util.hpp"
+#include "fv_linalg_kernels.hpp"
 #include "ldu.hpp"
 
 namespace fy {
@@ -62,29 +63,6 @@ __device__ __forceinline__ double pbv(const LduGeo& g, const double* p, int f) {
 #define FY_CELL_FACES(g, c, f, nb)                                                                                                     \
     for (int _k = 0, f = 0, nb = 0; _k < (g).Wall && (f = (g).ef[(size_t)_k * (g).nCells + (c)]) >= 0 && ((nb = (g).en[(size_t)_k * (g).nCells + (c)]), true); ++_k)
 
-template <int N>
-__device__ __forceinline__ void block_reduce_store(double (&v)[N], const int (&is_max)[N], double* partials) {
-    __shared__ double sh[4][N];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        double x = v[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double y = __shfl_down(x, o, 64);
-            x = is_max[q] ? fmax(x, y) : x + y;
-        }
-        if (lane == 0) sh[wv][q] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        const int q = threadIdx.x;
-        double x = sh[0][q];
-        for (int w = 1; w < 4; ++w) x = is_max[q] ? fmax(x, sh[w][q]) : x + sh[w][q];
-        partials[(size_t)q * gridDim.x + blockIdx.x] = x;
-    }
-}
-
 // fvc::flux(F) = linearInterpolate(F) & Sf (createPhi; boundary: the patch value)
 __global__ __launch_bounds__(256) void k_ldu_flux_of(LduGeo g, const double* __restrict__ F, double* __restrict__ phi) {
     const int f = blockIdx.x * 256 + threadIdx.x;
@@ -103,7 +81,7 @@ __global__ __launch_bounds__(256) void k_ldu_courant(LduGeo g, const double* __r
         v[0] = s / g.V[c]; v[1] = s;
     }
     const int mx[2] = {1, 0};
-    block_reduce_store<2>(v, mx, partials);
+    block_reduce_store<2>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 
 // fvc::grad(F), Gauss linear: T[3 i + j] = (1/V) sum_f (+-Sf_i) F_f,j -- through the slot coefficients: gG0_i F_c,j + sum_k gB_k,i F_(neighbour or patch value),j
@@ -340,7 +318,7 @@ __global__ __launch_bounds__(256) void k_ldu_mom_pass(LduGeo g, LduMom M, const 
         st3(xn, c, D3{o[0], o[1], o[2]});
     }
     const int mx[6] = {0, 0, 0, 0, 0, 0};
-    block_reduce_store<6>(v, mx, partials);
+    block_reduce_store<6>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 
 // rAU = 1 / A, HbyA = rAU H (icoFoamYade.C:99-100; constrainHbyA acts on the boundary values, formed where they are used)
@@ -404,7 +382,7 @@ __global__ __launch_bounds__(256) void k_ldu_adjust_sums(LduGeo g, const double*
         else v[2] = fl;
     }
     const int mx[4] = {0, 0, 0, 0};
-    block_reduce_store<4>(v, mx, partials);
+    block_reduce_store<4>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 __global__ __launch_bounds__(256) void k_ldu_adjust_apply(LduGeo g, const double* __restrict__ sums, double* __restrict__ phiHbyA, int* __restrict__ err) {
     const int f = g.nInt + blockIdx.x * 256 + threadIdx.x;
@@ -477,7 +455,7 @@ __global__ __launch_bounds__(256) void k_ldu_p_init(LduGeo g, const double* __re
         v[0] = fabs(rr); v[1] = fabs(Ax - Aref) + fabs(b[c] - Aref);
     }
     const int mx[2] = {0, 0};
-    block_reduce_store<2>(v, mx, partials);
+    block_reduce_store<2>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 // phi = phiHbyA - pEqn.flux() (icoFoamYade.C:127-130): the matrix's flux c_f (p_N - p_P) and the explicit non-orthogonal flux it was assembled with
 __global__ __launch_bounds__(256) void k_ldu_flux_correct(LduGeo g, const double* __restrict__ p, const double* __restrict__ phiHbyA, const double* __restrict__ pcoef,
@@ -507,7 +485,7 @@ __global__ __launch_bounds__(256) void k_ldu_U_correct(LduGeo g, const double* _
         v[0] = fabs(dv); v[1] = dv;
     }
     const int mx[2] = {0, 0};
-    block_reduce_store<2>(v, mx, partials);
+    block_reduce_store<2>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 
 
@@ -969,7 +947,7 @@ __global__ __launch_bounds__(256) void k_ldu_pim_continuity(LduGeo g, const doub
         v[0] = fabs(ce) * g.V[c]; v[1] = ce * g.V[c];
     }
     const int mx[2] = {0, 0};
-    block_reduce_store<2>(v, mx, partials);
+    block_reduce_store<2>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 
 __global__ __launch_bounds__(256) void k_ldu_sum(const double* __restrict__ x, int n, int ncomp, double* __restrict__ partials) {
@@ -977,7 +955,7 @@ __global__ __launch_bounds__(256) void k_ldu_sum(const double* __restrict__ x, i
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c < n) for (int q = 0; q < ncomp; ++q) v[q] = x[(size_t)ncomp * c + q];
     const int mx[3] = {0, 0, 0};
-    block_reduce_store<3>(v, mx, partials);
+    block_reduce_store<3>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 
 // mesh.findCell (FoamYade.C:251) on a general mesh of convex cells: from the cell whose centre is nearest, step across the face the point lies
@@ -1023,13 +1001,6 @@ __global__ __launch_bounds__(256) void k_ldu_positions(const double* __restrict_
     const double* r = rec + (size_t)rec_len * (size_t)i;
     pos3[3 * (size_t)i] = r[0]; pos3[3 * (size_t)i + 1] = r[1]; pos3[3 * (size_t)i + 2] = r[2];
 }
-
-#define FY_LAUNCH_CHECK()                                                                                     \
-    do {                                                                                                      \
-        hipError_t _e = hipGetLastError();                                                                    \
-        if (_e != hipSuccess) return fail(FY_ERR_HIP, "kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-inline int div_up(long long a, int b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 

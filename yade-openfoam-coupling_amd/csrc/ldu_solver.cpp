@@ -11,7 +11,7 @@
 
 #include "coupling.hpp"
 #include "field_average.hpp"
-#include "fv_kernels.hpp"
+#include "fv_linalg_kernels.hpp"
 #include "ldu.hpp"
 #include "ldu_amg.hpp"
 

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "device_util.hpp"
 
 namespace fy {
 namespace {
@@ -1691,12 +1692,6 @@ __global__ __launch_bounds__(256) void k_set_source_zero(int32_t n_cells, int ga
         u[0] = 0.0; u[1] = 0.0; u[2] = 0.0;
     }
 }
-
-#define FY_LAUNCH_CHECK()                                                                                     \
-    do {                                                                                                      \
-        hipError_t _e = hipGetLastError();                                                                    \
-        if (_e != hipSuccess) return fail(FY_ERR_HIP, "kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 }  // namespace
 
