@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 17
+#define FY_ABI_VERSION 18
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -287,6 +287,33 @@ typedef struct fy_average_desc {
     double start_after, stop_after; /* the window in seconds since the solver was created; stop_after 0: no end */
 } fy_average_desc;
 
+/* Fluid temperature with particle-fluid heat exchange (a capability the reference does not have; DESIGN.md section 3 "heat exchange", DESIGN_FV.md "T equation").
+   Fluid: cp [J/kg/K], kappa [W/m/K], D = kappa / (rho_f cp), Pr = nu rho_f cp / kappa, Deff = D + nut / prt (nut = 0 when laminar).  A particle of diameter d and
+   temperature Tp, with the force pass's stencil (cells c, normalised weights w; point-force mode: the containing cell, w = 1, eps = 1):
+       eps = sum w alpha_c, u_f = sum w U_c, Re = small + |u_f - v_p| d / nu
+       FY_NUSSELT_RANZ_MARSHALL   Nu = 2 + 0.6 Re^1/2 Pr^1/3                                                                  (both solvers)
+       FY_NUSSELT_GUNN            Nu = (7 - 10 eps + 5 eps^2)(1 + 0.7 Res^0.2 Pr^1/3) + (1.33 - 2.4 eps + 1.2 eps^2) Res^0.7 Pr^1/3,  Res = eps Re     (pimpleFoamYade only)
+       hA = Nu kappa pi d;  Sp_c += w hA,  Su_c += w hA Tp      [W/K, W]
+   once per step, after the last corrector and the turbulence model's correct(), with the step's final flux F_f = alpha_f phi_f (outward) and alphaOld = alpha:
+       alpha_c V_c (T - T_old) / dt + sum_f F_f T_f - T_c sum_f F_f - sum_f alpha_f Deff_f |S_f| / |d_f| (T_N - T_c) = (Su_c - Sp_c T_c) / (rho_f cp)
+   (implicit; T_f linear | upwind; a Jacobi solve with T_tol / T_rel_tol / T_max_iter), and then q_p = hA (sum w T_c - Tp) [W into the particle]: sum_p q_p =
+   sum_c (Sp_c T_c - Su_c) identically.  All zero: off -- nothing is allocated or launched.  Single domain only (fy_solver_create_slab refuses it), no fibre coupling. */
+#define FY_NUSSELT_RANZ_MARSHALL 0
+#define FY_NUSSELT_GUNN 1
+#define FY_BC_T_ZERO_GRADIENT 0
+#define FY_BC_T_FIXED_VALUE 1
+typedef struct fy_thermal_desc {
+    int32_t on;
+    double cp, kappa;               /* > 0 */
+    double prt;                     /* turbulent Prandtl number (> 0 with a turbulence model; 0: 1) */
+    int32_t nusselt_law;            /* FY_NUSSELT_* */
+    double T_initial;               /* uniform internalField of 0/T (fy_solver_write_field_host("T") for a non-uniform one) */
+    int32_t T_bc[6]; double T_value[6];      /* FY_BC_T_* per side */
+    int32_t T_convection_scheme;    /* div(phi,T) / div(alphaPhic,T): FY_CONVECTION_LINEAR | FY_CONVECTION_UPWIND */
+    double T_tol, T_rel_tol; int32_t T_max_iter;      /* solvers.T: not both tolerances zero, T_max_iter >= 1 */
+    double particle_temperature;    /* Tp of every particle of a batch nobody gave temperatures (fy_solver_set_particle_temperatures_*) */
+} fy_thermal_desc;
+
 typedef struct fy_case_desc {
     int32_t solver;                 /* FY_SOLVER_ICO | FY_SOLVER_PIMPLE */
     int32_t nx, ny, nz;
@@ -360,6 +387,8 @@ typedef struct fy_case_desc {
     uint32_t force_models;                  /* FY_FORCE_* flags */
     /* controlDict functions: the fieldAverage object (all zero: none), applied at fy_solver_create with fy_solver_set_field_average */
     fy_average_desc average;
+    /* constant/couplingProperties heatTransfer + 0/T: the fluid temperature equation and the particle-fluid heat exchange (all zero: off) */
+    fy_thermal_desc thermal;
 } fy_case_desc;
 
 typedef struct fy_solver fy_solver;
@@ -400,6 +429,17 @@ int fy_solver_set_field_average(fy_solver*, const fy_average_desc*);
 int fy_solver_get_average_state(fy_solver*, int item, int64_t* samples, double* time_averaged);
 int fy_solver_set_average_state(fy_solver*, int item, int64_t samples, double time_averaged);
 
+/* Heat exchange (fy_case_desc.thermal.on; FY_ERR_INVALID on a solver without it).  The caller owns the particle temperatures: Tp[n] in the batch's wire order for the
+ * n particles the batch holds now, host or device memory (copied), or NULL = thermal.particle_temperature for all of them; they stand until the next call for that
+ * batch or until the batch's particle count changes (then the uniform value again).  q[n]: W into each particle over the last step, wire order, 0 for a particle
+ * nobody located.  Stats of the last step: Jacobi passes and initial residual of the T solve, heat_to_particles_W = sum of q over all batches (summed on the device when asked for: pass NULL to skip it).
+ * While thermal is on, "T" [n], "heatSp" [n] (W/K) and "heatSu" [n] (W) are field names of fy_solver_read/write_field_host (the sources: the last step's), "T" one that
+ * fieldAverage accepts, and "heat_coeff", "heat_flux", "T_assemble" kernel clocks of fy_solver_get_kernel_timing. */
+int fy_solver_set_particle_temperatures_host(fy_solver*, int batch, const double* Tp);
+int fy_solver_set_particle_temperatures_device(fy_solver*, int batch, const double* d_Tp);
+int fy_solver_get_particle_heat_host(fy_solver*, int batch, double* q);
+int fy_solver_get_thermal_stats(fy_solver*, int32_t* iterations, double* initial_residual, double* heat_to_particles_W);
+
 /* ---- OpenFOAM case directories (what the reference's executables get from runTime / mesh / the field constructors, createFields.H
  * of both solvers, and give back with runTime.write()).  Supported subset: ONE axis-aligned blockMesh hex block of uniform cubes whose
  * six sides are covered by `boundary` patches; velocity patches fixedValue (uniform) / noSlip / zeroGradient; pressure patches
@@ -435,6 +475,12 @@ int fy_foam_case_initial_fields(const fy_foam_case*, double* U /* [n][3] or NULL
 int fy_foam_case_initial_nut(const fy_foam_case*, double* nut /* [n] */);
 int fy_foam_case_initial_k(const fy_foam_case*, double* k /* [n] */);          /* start-time k.<phase> of a kEqn / kEpsilon case */
 int fy_foam_case_initial_epsilon(const fy_foam_case*, double* eps /* [n] */);  /* start-time epsilon.<phase> of a kEpsilon case */
+/* heat transfer: constant/couplingProperties `heatTransfer { active on; nusseltModel RanzMarshall | Gunn; Cp; kappa; Prt; particleTemperature; }` (Gunn: pimpleFoamYade)
+   becomes fy_case_desc.thermal, completed by <startTime>/T | T.<phase> (internalField uniform | nonuniform; patches zeroGradient | fixedValue uniform), divSchemes
+   div(phi,T) | div(alphaPhic,T) = [bounded] Gauss linear | upwind and fvSolution solvers.T | T.<phase>.  Refused by name (FY_ERR_UNSUPPORTED): an unknown model or
+   entry, Gunn with icoFoamYade, a missing Cp / kappa / temperature file / solvers entry, another patch type, a general-mesh or decomposed case.  fy_foam_case_write_time
+   writes the solver's T beside the other fields; fy_foam_case_initial_T hands out the start time's (for fy_solver_write_field_host(s, "T", ...)) */
+int fy_foam_case_initial_T(const fy_foam_case*, double* T /* [n] */);
 /* runTime.write(): <case>/<time_name>/{U | U.<phase>, p [, alpha.<phase>]} as ASCII volFields with the case's own patch entries */
 int fy_foam_case_write_time(const fy_foam_case*, fy_solver*, const char* time_name);
 /* the same from host arrays over the WHOLE block (a slab run gathers its ranks' owned cells first: foamYadeHip_mpi -parallel); alpha / nut / k / epsilon

@@ -1,0 +1,485 @@
+"""The fluid temperature equation and the particle-fluid heat exchange (fy_case_desc.thermal) on the device against tests/heat_transfer_ref.py -- the numpy
+restatement written from the formulas, itself held to closed forms in tests/test_heat_transfer_ref.py -- and against the closed forms directly.  Every solver run
+here uses T_tol 1e-14, T_rel_tol 0 and a T_max_iter the case's diffusion number reaches; the bar against the restatement is 1e-10 of the field's range (the bar
+tests/test_drag_laws.py holds the force laws to), against a closed form 1e-12 of its amplitude."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import field_average_ref as far
+import heat_transfer_ref as ht
+from test_heat_transfer_case import heat_case
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-10
+WATER = dict(cp=4180.0, kappa=0.6)
+
+
+def thermal(product, max_iter, **kw):
+    d = dict(T_tol=1e-14, T_rel_tol=0.0, T_max_iter=max_iter)
+    d.update(kw)
+    return product.thermal_desc(**d)
+
+
+def assert_field(a, b, what, bar=BAR, scale=None):
+    """a within bar of b, in units of b's range (a constant field: of its magnitude)"""
+    if scale is None:
+        scale = np.ptp(b) if np.ptp(b) > 0 else max(np.abs(b).max(), 1e-300)
+    err = np.abs(a - b).max()
+    print(f"{what}: |device - restatement| = {err:.3e}, range {scale:.3e}, ratio {err / scale:.2e}")
+    assert err <= bar * scale, (what, err, scale)
+
+
+def cloud(n, lo, hi, radius, seed, speed=0.05, outside=0):
+    rs = np.random.RandomState(seed)
+    lo, hi = np.asarray(lo, float), np.asarray(hi, float)
+    rec = np.zeros((n, 10))
+    rec[:, 0:3] = lo + (hi - lo) * rs.random_sample((n, 3))
+    rec[:, 3:6] = speed * rs.standard_normal((n, 3))
+    rec[:, 9] = radius * (0.6 + 0.8 * rs.random_sample(n)) if outside else radius
+    if outside:
+        rec[:outside, 0] = hi[0] + (hi[0] - lo[0]) * (1.0 + rs.random_sample(outside))
+    return rec
+
+
+def one_per_cell(nx, ny, nz, dx, count, seed):
+    """`count` particles in distinct cells: every per-cell sum of a point-force step then has one term, so the run is reproducible bit for bit"""
+    rs = np.random.RandomState(seed)
+    cells = rs.choice(nx * ny * nz, count, replace=False)
+    i, j, k = cells % nx, (cells // nx) % ny, cells // (nx * ny)
+    rec = np.zeros((count, 10))
+    rec[:, 0:3] = (np.stack([i, j, k], axis=1) + 0.2 + 0.6 * rs.random_sample((count, 3))) * dx
+    rec[:, 3:6] = 0.1 * rs.standard_normal((count, 3))
+    rec[:, 9] = 0.05 * dx
+    return rec
+
+
+BOX = (12, 10, 9)
+
+
+def bed_case(product, th=None, **kw):
+    """the moving coupled pimple box: 12 x 10 x 9 cells of 1 cm (2 x 2 x 2 tiles of 8^3, so the bucket flush crosses tile borders)"""
+    extra = dict(kw)
+    if th is not None:
+        extra["thermal"] = th
+    return product.make_case(1, *BOX, 0.01, 2e-4, 1e-5, g=(0, 0, -9.81), p_bc=[2] * 6, **extra)
+
+
+def bed_cloud(n=3000, seed=3, **kw):
+    return cloud(n, (0.004, 0.004, 0.004), (0.116, 0.096, 0.07), 0.002, seed, **kw)
+
+
+# ---- 1. thermal on changes nothing else ------------------------------------------------------------------------------------------------------------------------
+def test_ico_cavity_is_bitwise_unchanged_by_thermal(product):
+    n, dx = 8, 0.1 / 8
+    u_val = [(0, 0, 0)] * 6
+    u_val[3] = (1.0, 0, 0)
+    rec = one_per_cell(n, n, n, dx, 200, 11)
+    out = []
+    for on in (False, True):
+        kw = dict(thermal=thermal(product, 50, T_initial=300.0, particle_temperature=350.0, **WATER)) if on else {}
+        s = product.Solver(product.make_case(0, n, n, n, dx, 1e-3, 1e-2, u_val=u_val, **kw))
+        s.enable_kernel_timing(True)
+        for _ in range(3):
+            s.set_particles(rec)
+            s.step()
+        out.append((s.get("U"), s.get("p"), s.forces(), s.found()))
+        if on:
+            assert s.get("T").size == n ** 3 and np.abs(s.get("T") - 300.0).max() > 0
+            assert s.kernel_timing("heat_coeff")[1] == 3 and s.kernel_timing("heat_flux")[1] == 3 and s.kernel_timing("T_assemble")[1] == 3
+        else:
+            with pytest.raises(product.FoamYadeError):
+                s._size("T")                                 # fy_solver_field_count
+            with pytest.raises(product.FoamYadeError):
+                s.particle_heat()
+            for clock in ("heat_coeff", "heat_flux", "T_assemble"):
+                assert s.kernel_timing(clock) == (0.0, 0)
+        s.close()
+    for a, b, nm in zip(out[0], out[1], ("U", "p", "forces", "found")):
+        np.testing.assert_array_equal(a, b, err_msg=nm)
+    assert (out[0][3] == 1).all() and np.abs(out[0][2]).max() > 0
+
+
+def test_pimple_box_is_unchanged_by_thermal(product):
+    rec = bed_cloud()
+    out = []
+    for on in (False, True):
+        s = product.Solver(bed_case(product, thermal(product, 40, T_initial=300.0, particle_temperature=350.0, **WATER) if on else None))
+        for _ in range(3):
+            s.set_particles(rec)
+            s.step()
+        out.append((s.get("U"), s.get("p"), s.forces(), s.found().astype(float)))
+        s.close()
+    for a, b, nm in zip(out[0], out[1], ("U", "p", "forces", "found")):
+        assert_field(b, a, nm, scale=np.abs(a).max())        # (the Gaussian scatters add through atomics: two runs of the same code differ in the last bits)
+    assert np.abs(out[0][0]).max() > 0 and (out[0][3] == 1).mean() > 0.9
+
+
+# ---- 2. conduction, no particles, fluid at rest ----------------------------------------------------------------------------------------------------------------
+def test_cosine_mode_decays_by_the_closed_form(product):
+    """diffusion number D dt / dx^2 = 0.5: the Jacobi iteration contracts by ~0.75 per pass, 400 passes reach the rounding floor"""
+    nx, ny, nz, dx, dt = 16, 4, 4, 0.01, 0.05
+    D = 0.5 * dx * dx / dt
+    rho, cp = 1.0, 1000.0
+    th = thermal(product, 400, cp=cp, kappa=D * rho * cp)
+    s = product.Solver(product.make_case(0, nx, ny, nz, dx, dt, 1e-2, rho_f=rho, thermal=th))
+    mode = np.tile(np.cos(np.pi * (np.arange(nx) + 0.5) / nx), ny * nz)
+    lam = (2.0 / dx ** 2) * (1.0 - np.cos(np.pi / nx))
+    s.set("T", 5.0 * mode)
+    for step in range(1, 4):
+        s.step()
+        exact = 5.0 * mode / (1.0 + dt * D * lam) ** step
+        err = np.abs(s.get("T") - exact).max()
+        print(f"step {step}: |T - closed form| = {err:.3e} of amplitude 5, {s.thermal_stats()[0]} passes")
+        assert err <= 1e-12 * 5.0
+    assert np.abs(s.get("U")).max() == 0.0
+    s.close()
+
+
+GRADING = (0.01 * 1.25 ** np.arange(6), 0.012 * np.ones(5), 0.015 * 0.85 ** np.arange(4))
+
+
+def test_graded_block_between_fixed_value_walls(product):
+    nx, ny, nz = 6, 5, 4
+    dt, rho, cp, kappa = 0.02, 1.0, 1000.0, 2.0
+    bc, val = [1, 1, 0, 0, 0, 0], [300.0, 400.0, 0, 0, 0, 0]
+    th = thermal(product, 600, cp=cp, kappa=kappa, T_initial=320.0, T_bc=bc, T_value=val)
+    s = product.Solver(product.make_case(0, nx, ny, nz, 0.0, dt, 1e-2, rho_f=rho, grading=GRADING, thermal=th))
+    h = ht.block_sizes(nx, ny, nz, grading=GRADING)
+    T = s.get("T")
+    assert (T == 320.0).all()
+    for step in range(3):
+        s.step()
+        phi = [s.get(f"phi_{a}") for a in "xyz"]
+        ref = ht.solve_T(h, dt, phi, None, None, T, kappa / (rho * cp), 1.0, bc, val, ht.LINEAR)
+        T = s.get("T")
+        assert_field(T, ref, f"graded conduction, step {step}")
+    assert T.max() - T.min() > 20.0
+    s.close()
+
+
+# ---- 3. convection-diffusion in a lid-driven box --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("graded,scheme,les", [(False, "linear", False), (False, "upwind", False), (True, "linear", False), (True, "upwind", False), (True, "linear", True)])
+def test_lid_driven_box_matches_the_restatement(product, graded, scheme, les):
+    nx, ny, nz, dx, dt = 6, 5, 4, 0.1 / 6, 2e-3
+    rho, cp, kappa, prt = 1.0, 1000.0, 10.0, 0.85
+    u_val = [(0, 0, 0)] * 6
+    u_val[3] = (1.0, 0, 0)
+    bc, val = [1, 0, 0, 1, 0, 0], [280.0, 0, 0, 330.0, 0, 0]              # XMIN and the lid hold a temperature, the other four sides are adiabatic
+    upwind = scheme == "upwind"
+    th = thermal(product, 300, cp=cp, kappa=kappa, prt=prt, T_initial=300.0, T_bc=bc, T_value=val, T_convection_scheme=1 if upwind else 0)
+    kw = dict(turbulence_model=product.TURBULENCE_SMAGORINSKY) if les else {}
+    grading = [g * (0.1 / g.sum()) for g in GRADING] if graded else None
+    s = product.Solver(product.make_case(1, nx, ny, nz, dx, dt, 1e-3, rho_f=rho, u_val=u_val, p_bc=[0] * 6, grading=grading, thermal=th, **kw))
+    h = ht.block_sizes(nx, ny, nz, dx, grading)
+    s.hold_sources(True)
+    T = s.get("T")
+    for step in range(3):
+        s.step()
+        phi = [s.get(f"phi_{a}") for a in "xyz"]
+        nut = s.get("nut") if les else None
+        ref = ht.solve_T(h, dt, phi, s.get("alpha"), nut, T, kappa / (rho * cp), prt, bc, val, ht.UPWIND if upwind else ht.LINEAR)
+        T = s.get("T")
+        assert_field(T, ref, f"lid box graded={graded} {scheme} les={les}, step {step}")
+    assert max(np.abs(p).max() for p in phi) > 0 and T.max() - T.min() > 1.0
+    if les:
+        assert nut.max() > 0
+    s.close()
+
+
+# ---- 4. uniform T0 = Tp stays uniform --------------------------------------------------------------------------------------------------------------------------
+def test_uniform_temperature_stays_uniform_in_a_moving_bed(product):
+    T0 = 300.0
+    s = product.Solver(bed_case(product, thermal(product, 60, T_initial=T0, particle_temperature=T0, nusselt_law=product.NUSSELT_GUNN, **WATER)))
+    rec = bed_cloud()
+    for step in range(4):
+        s.set_particles(rec)
+        s.step()
+        T = s.get("T")
+        print(f"step {step}: max |T / T0 - 1| = {np.abs(T / T0 - 1).max():.3e}")
+        assert np.abs(T - T0).max() <= 1e-12 * T0
+    assert np.abs(s.get("U")).max() > 0 and s.get("heatSp").max() > 0
+    assert np.abs(s.particle_heat()).max() <= 1e-12 * T0 * s.get("heatSp").sum()        # q = hA (sum w T - Tp) with hA <= sum hA = sum Sp: zero to rounding
+    s.close()
+
+
+# ---- 5. lumped relaxation in point-force mode -----------------------------------------------------------------------------------------------------------------
+def test_lumped_relaxation_in_point_mode(product):
+    n, dx, dt = 4, 0.01, 0.02
+    nu, rho, cp, kappa, Tp = 1e-2, 1.0, 1000.0, 0.6, 50.0
+    th = thermal(product, 200, cp=cp, kappa=kappa, T_initial=0.0, particle_temperature=Tp)
+    s = product.Solver(product.make_case(0, n, n, n, dx, dt, nu, rho_f=rho, thermal=th))
+    N = n ** 3
+    c = np.arange(N)
+    rec = np.zeros((N, 10))
+    rec[:, 0:3] = (np.stack([c % n, (c // n) % n, c // (n * n)], axis=1) + 0.5) * dx
+    rec[:, 9] = 0.1 * dx
+    hA = float(ht.nusselt(ht.RANZ_MARSHALL, 1.0, ht.SMALL, ht.prandtl(nu, rho, cp, kappa)) * kappa * np.pi * 0.2 * dx)
+    beta = dt * hA / (rho * cp * dx ** 3)
+    assert 0.1 < beta < 0.2
+    for step in range(1, 6):
+        s.set_particles(rec)
+        s.step()
+        exact = Tp * (1.0 - 1.0 / (1.0 + beta) ** step)
+        T = s.get("T")
+        print(f"step {step}: |T - closed form| = {np.abs(T - exact).max():.3e} of {Tp}")
+        assert np.abs(T - exact).max() <= 1e-12 * Tp
+        assert np.abs(s.particle_heat() - hA * (exact - Tp)).max() <= 1e-12 * hA * Tp
+    assert np.abs(s.get("U")).max() == 0.0
+    s.close()
+
+
+# ---- 6. passes A and B in Gaussian mode ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("law", ["RanzMarshall", "Gunn"])
+def test_gaussian_passes_match_the_restatement(product, law):
+    """two batches, random radii, velocities and per-particle temperatures, 60 particles outside the box, two steps.  Both steps flush through the tile buckets: the
+    capacities the heat scatter uses are formed from the demand the SAME step's momentum back-scatter counted, so they stand from a population's first step on
+    (the second step's differ: the cloud has moved)"""
+    lawc = product.NUSSELT_GUNN if law == "Gunn" else product.NUSSELT_RANZ_MARSHALL
+    nu, rho = 1e-5, 1000.0
+    s = product.Solver(bed_case(product, thermal(product, 40, T_initial=300.0, nusselt_law=lawc, particle_temperature=111.0, **WATER)))
+    Nc = BOX[0] * BOX[1] * BOX[2]
+    rs = np.random.RandomState(17)
+    s.set("U", 0.05 * rs.standard_normal((Nc, 3)))
+    s.set("T", 300.0 + 50.0 * rs.random_sample(Nc))
+    rec = bed_cloud(3000, 5, speed=0.1, outside=60)
+    batches = [rec[:1700], rec[1700:]]
+    Tp = [280.0 + 90.0 * rs.random_sample(b.shape[0]) for b in batches]
+    Pr = ht.prandtl(nu, rho, WATER["cp"], WATER["kappa"])
+    s.hold_sources(True)
+    for step in range(2):
+        for b in batches:
+            b[:, 0:3] += 1e-4 * rs.standard_normal(b[:, 0:3].shape)
+        s.set_particle_batches(batches)
+        for bi in range(2):
+            s.set_particle_temperatures(Tp[bi], bi)
+        U = s.get("U").reshape(Nc, 3)                       # what the force pass will gather: the step's opening U
+        s.step()
+        alpha, T = s.get("alpha"), s.get("T")
+        Sp, Su, qs, qr = np.zeros(Nc), np.zeros(Nc), [], []
+        for bi, b in enumerate(batches):
+            k, ids, w, chain = s.stencils_of(bi)
+            hA, sp, su = ht.pass_a(lawc, b, ids, w, U, alpha, Tp[bi], nu, WATER["kappa"], Pr, Nc)
+            Sp += sp; Su += su
+            qr.append(ht.pass_b(hA, ids, w, T, Tp[bi])); qs.append(s.particle_heat(bi))
+            assert (qs[-1][k == 0] == 0.0).all()
+        assert (np.concatenate(qs)[:60] == 0.0).all()       # the particles outside the box
+        assert alpha.min() < 0.97
+        assert_field(s.get("heatSp"), Sp, f"{law} heatSp, step {step}")
+        assert_field(s.get("heatSu"), Su, f"{law} heatSu, step {step}")
+        assert_field(np.concatenate(qs), np.concatenate(qr), f"{law} q, step {step}")
+        it, res0, total = s.thermal_stats()
+        assert abs(total - np.concatenate(qs).sum()) <= 1e-12 * np.abs(np.concatenate(qs)).sum()
+    # a batch whose temperatures are taken back falls to the case's uniform value: 111 K, below the fluid everywhere, so every located particle is heated
+    assert np.concatenate(qs).min() < 0 < np.concatenate(qs).max()
+    s.set_particle_batches(batches)
+    s.set_particle_temperatures(None, 0)
+    s.step()
+    k, ids, w, chain = s.stencils_of(0)
+    assert s.particle_heat(0)[k > 0].min() > 0
+    s.close()
+
+
+def test_sparse_cloud_matches_the_restatement(product):
+    """16 384 particles at 0.5 per cell on 32^3 cells: a workgroup's 512 particles reach more distinct cells than its 1 024-slot LDS table holds, so part of the
+    scatter leaves the kernel as direct global atomics (the crowded-table branch) beside the bucket flush of the full tables.  Whatever route an entry takes, the
+    sums must be the restatement's.  (Whether a bucket also overflows here -- full tables ask for 2.5 entries per particle + 135 per tile where the pool holds 2.25 +
+    136 -- cannot be seen from outside and is not claimed.)"""
+    n, dx = 32, 0.01
+    nu, rho = 1e-5, 1000.0
+    s = product.Solver(product.make_case(1, n, n, n, dx, 2e-4, nu, g=(0, 0, -9.81), p_bc=[2] * 6, thermal=thermal(product, 40, T_initial=300.0, **WATER)))
+    Nc = n ** 3
+    rs = np.random.RandomState(29)
+    s.set("U", 0.05 * rs.standard_normal((Nc, 3)))
+    s.set("T", 300.0 + 50.0 * rs.random_sample(Nc))
+    rec = cloud(16384, (0.002, 0.002, 0.002), (0.318, 0.318, 0.318), 0.001, 31, speed=0.1)
+    Tp = 280.0 + 90.0 * rs.random_sample(rec.shape[0])
+    Pr = ht.prandtl(nu, rho, WATER["cp"], WATER["kappa"])
+    s.hold_sources(True)
+    s.set_particles(rec)
+    s.set_particle_temperatures(Tp)
+    U = s.get("U").reshape(Nc, 3)
+    s.step()
+    k, ids, w, chain = s.stencils()
+    assert (k > 0).all() and np.unique(ids[ids >= 0]).size > 16 * 1024
+    hA, Sp, Su = ht.pass_a(ht.RANZ_MARSHALL, rec, ids, w, U, s.get("alpha"), Tp, nu, WATER["kappa"], Pr, Nc)
+    assert_field(s.get("heatSp"), Sp, "sparse heatSp")
+    assert_field(s.get("heatSu"), Su, "sparse heatSu")
+    assert_field(s.particle_heat(), ht.pass_b(hA, ids, w, s.get("T"), Tp), "sparse q")
+    s.close()
+
+
+def test_point_mode_scatter_with_shared_cells(product):
+    """icoFoamYade, 600 particles in 512 cells: several particles per cell, so the point-mode scatter's atomics on Sp / Su meet in a cell"""
+    n, dx, nu, rho = 8, 0.1 / 8, 1e-2, 1000.0
+    u_val = [(0, 0, 0)] * 6
+    u_val[3] = (1.0, 0, 0)
+    s = product.Solver(product.make_case(0, n, n, n, dx, 1e-3, nu, rho_f=rho, u_val=u_val, thermal=thermal(product, 50, T_initial=300.0, **WATER)))
+    rs = np.random.RandomState(41)
+    rec = cloud(600, (0.0, 0.0, 0.0), (0.1, 0.1, 0.1), 0.05 * dx, 43, speed=0.2, outside=20)
+    Tp = 280.0 + 90.0 * rs.random_sample(600)
+    Pr = ht.prandtl(nu, rho, WATER["cp"], WATER["kappa"])
+    s.set("T", 300.0 + 50.0 * rs.random_sample(n ** 3))
+    for step in range(2):
+        s.set_particles(rec)
+        s.set_particle_temperatures(Tp)
+        U = s.get("U").reshape(-1, 3)
+        s.step()
+        ijk = np.floor(rec[:, 0:3] / dx).astype(int)
+        inside = ((rec[:, 0:3] >= 0) & (rec[:, 0:3] <= 0.1)).all(axis=1)
+        cell = np.where(inside, np.minimum(ijk, n - 1) @ np.array([1, n, n * n]), -1)
+        assert (s.found() == np.where(inside, 1, -1)).all() and np.bincount(cell[inside]).max() >= 3
+        ids, w = ht.point_stencils(cell)
+        hA, Sp, Su = ht.pass_a(ht.RANZ_MARSHALL, rec, ids, w, U, None, Tp, nu, WATER["kappa"], Pr, n ** 3)
+        assert_field(s.get("heatSp"), Sp, f"point heatSp, step {step}")
+        assert_field(s.get("heatSu"), Su, f"point heatSu, step {step}")
+        q = s.particle_heat()
+        assert_field(q, ht.pass_b(hA, ids, w, s.get("T"), Tp), f"point q, step {step}")
+        assert (q[~inside] == 0).all()
+    s.close()
+
+
+# ---- 7. energy balance ---------------------------------------------------------------------------------------------------------------------------------------
+def test_energy_balance_in_a_closed_box_at_rest(product):
+    """zeroGradient walls, g = 0, particles and fluid at rest: what the particles give is what the fluid's heat content gains, rho cp sum alpha V (T - T_old) = -dt sum q"""
+    nx, ny, nz, dx, dt = 8, 6, 5, 0.01, 0.05
+    rho, cp = 1000.0, 4180.0
+    th = thermal(product, 100, T_initial=0.0, particle_temperature=50.0, nusselt_law=product.NUSSELT_GUNN, **WATER)
+    s = product.Solver(product.make_case(1, nx, ny, nz, dx, dt, 1e-6, rho_f=rho, p_bc=[2] * 6, thermal=th))
+    rec = cloud(300, (0.01, 0.01, 0.01), (0.07, 0.05, 0.04), 0.002, 23, speed=0.0)
+    s.hold_sources(True)
+    Told = s.get("T")
+    for step in range(3):
+        s.set_particles(rec)
+        s.step()
+        T, alpha, q = s.get("T"), s.get("alpha"), s.particle_heat()
+        gain, given = rho * cp * (alpha * dx ** 3 * (T - Told)).sum(), -dt * q.sum()
+        print(f"step {step}: fluid gains {gain:.12e} J, particles give {given:.12e} J, relative difference {abs(gain - given) / abs(given):.2e}")
+        assert abs(gain - given) <= BAR * abs(given)
+        assert given > 0 and alpha.min() < 1.0
+        Told = T
+    assert np.abs(s.get("U")).max() <= 1e-12
+    s.close()
+
+
+def test_exchange_identity_in_the_moving_bed(product):
+    s = product.Solver(bed_case(product, thermal(product, 40, T_initial=300.0, particle_temperature=350.0, **WATER)))
+    rec = bed_cloud()
+    s.hold_sources(True)
+    for step in range(4):
+        s.set_particles(rec)
+        s.step()
+        q, T, Sp, Su = s.particle_heat(), s.get("T"), s.get("heatSp"), s.get("heatSu")
+        lhs, rhs = q.sum(), (Sp * T - Su).sum()
+        print(f"step {step}: sum q = {lhs:.12e} W, sum (Sp T - Su) = {rhs:.12e} W")
+        # Sp T and Su are each ~T / (Tp - T) times their difference: the identity holds to the rounding of those sums
+        assert abs(lhs - rhs) <= BAR * np.abs(q).sum()
+    assert q.sum() < 0 and T.max() > 300.0                  # hot particles heat the fluid
+    s.close()
+
+
+# ---- 8. fieldAverage takes T -----------------------------------------------------------------------------------------------------------------------------------
+def test_field_average_of_T(product):
+    s = product.Solver(bed_case(product, thermal(product, 40, T_initial=300.0, particle_temperature=350.0, **WATER)))
+    s.set_field_average([("T", True)])
+    Nc = BOX[0] * BOX[1] * BOX[2]
+    item = far.Item((Nc,), True, "time")
+    rec = bed_cloud(1000, 9)
+    s.hold_sources(True)
+    for step in range(4):
+        s.set_particles(rec)
+        s.step()
+        item.add(s.get("T"), s.stats()["delta_t"])
+    np.testing.assert_array_equal(s.get("TMean"), item.m)
+    np.testing.assert_array_equal(s.get("TPrime2Mean"), item.P)
+    assert item.m.max() > 300.0 and item.P.max() > 0
+    s.close()
+    cold = product.Solver(bed_case(product))
+    with pytest.raises(product.FoamYadeError) as e:
+        cold.set_field_average([("T", False)])               # no thermal: no T to average
+    assert "'T'" in str(e.value)
+    cold.close()
+
+
+# ---- 9. the executable ---------------------------------------------------------------------------------------------------------------------------------------
+def test_executable_writes_T_and_restarts_from_it(product, tmp_path):
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "yade-openfoam-coupling_amd", "bin", "foamYadeHip")
+    if not os.path.exists(exe):
+        pytest.fail("foamYadeHip has not been built: run __graft_entry__.build()")
+    dst = heat_case(tmp_path, "bed_pimple", coupling="heatTransfer { active on; nusseltModel Gunn; Cp 1000; kappa 50; particleTemperature 350; }\n",
+                    entries={"bottom": "type fixedValue; value uniform 320;", "top": "type fixedValue; value uniform 290;"})
+    # the same ten steps in this process: what the files must hold at 0.001 (step 5) and 0.002 (step 10)
+    fc = product.FoamCase(dst, product.FY_SOLVER_PIMPLE)
+    s = product.Solver(fc.case)
+    U, p = fc.initial_fields()
+    s.set("p", p); s.set("U", U); s.set("T", fc.initial_T())
+    s.hold_sources(True)
+    mine = {}
+    for step in range(1, 11):
+        s.step()
+        if step % 5 == 0:
+            mine["0.001" if step == 5 else "0.002"] = s.get("T")
+    s.close(); fc.close()
+    assert np.ptp(mine["0.002"]) > 1e-3
+    out = subprocess.run([exe, "-solver", "pimple", "-case", str(dst)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("Heat transfer:")]
+    assert len(lines) == 1 and "Gunn" in lines[0] and "kappa 50" in lines[0] and "upwind" in lines[0], out.stdout
+    for t in ("0.001", "0.002"):
+        assert os.path.exists(dst / t / "T.water")
+        text = (dst / t / "T.water").read_text()
+        assert "fixedValue" in text and "uniform 320" in text and "[0 0 0 1 0 0 0]" in text      # the start time's patch entries, the temperature's dimensions
+        # a restart from the written time reads the field back
+        ctl = dst / "system/controlDict"
+        ctl.write_text(re.sub(r"startTime\s+[0-9.]+;", f"startTime       {t};", ctl.read_text()))
+        back = product.FoamCase(dst, product.FY_SOLVER_PIMPLE)
+        assert back.start_name == t
+        np.testing.assert_array_equal(back.initial_T(), mine[t], err_msg=t)
+        back.close()
+
+
+# ---- 10. refusals ------------------------------------------------------------------------------------------------------------------------------------------------
+def test_slabs_refuse_thermal_by_name(product):
+    case = product.make_case(1, 8, 8, 20, 0.01, 2e-4, 1e-5, p_bc=[2] * 6, thermal=thermal(product, 40, T_initial=300.0, **WATER))
+    with pytest.raises(product.FoamYadeError) as e:
+        product.VirtualSlabs(case, 2)
+    assert "error 5" in str(e.value) and "slab" in str(e.value) and "thermal" in str(e.value)
+
+
+def test_create_refuses_what_it_cannot_run(product):
+    mk = lambda solver, **kw: product.Solver(product.make_case(solver, 4, 4, 4, 0.01, 1e-3, 1e-2, thermal=thermal(product, 10, **kw)))
+    with pytest.raises(product.FoamYadeError) as e:
+        mk(0, nusselt_law=product.NUSSELT_GUNN, **WATER)     # Gunn needs the void fraction
+    assert "error 5" in str(e.value) and "GUNN" in str(e.value) and "RANZ_MARSHALL" in str(e.value)
+    with pytest.raises(product.FoamYadeError) as e:
+        mk(0, cp=4180.0, kappa=0.0)
+    assert "kappa" in str(e.value)
+    with pytest.raises(product.FoamYadeError) as e:
+        mk(0, T_bc=[0, 0, 7, 0, 0, 0], **WATER)
+    assert "T_bc" in str(e.value) and "FY_BC_T_FIXED_VALUE" in str(e.value)
+    # a solve that could never report convergence, or never run
+    for kw in (dict(T_tol=0.0, T_rel_tol=0.0), dict(T_max_iter=0)):
+        with pytest.raises(product.FoamYadeError) as e:
+            mk(1, **kw, **WATER)
+        assert "T_tol" in str(e.value) and "T_max_iter" in str(e.value)
+
+
+def test_fibre_coupling_refuses_the_step_before_it_starts(product):
+    s = product.Solver(bed_case(product, thermal(product, 40, T_initial=300.0, **WATER)))
+    s.set_particles(bed_cloud(200, 7))
+    s.step()
+    before = s.get("T"), s.get("U")
+    product._check(product.lib().fy_set_fibre_coupling(s._cpl, 1))
+    with pytest.raises(product.FoamYadeError) as e:
+        s.step()
+    assert "error 5" in str(e.value) and "fibre" in str(e.value) and "thermal" in str(e.value)
+    np.testing.assert_array_equal(s.get("T"), before[0])     # nothing was scattered, nothing solved
+    np.testing.assert_array_equal(s.get("U"), before[1])
+    product._check(product.lib().fy_set_fibre_coupling(s._cpl, 0))
+    s.set_particles(bed_cloud(200, 7))
+    s.step()
+    s.close()

@@ -167,6 +167,29 @@ class ParticleTimings(C.Structure):
                 ("wire_send", C.c_double), ("bytes_in", C.c_int64), ("bytes_out", C.c_int64), ("fold", C.c_double)]
 
 
+class ThermalDesc(C.Structure):
+    """fy_thermal_desc: the fluid temperature equation and the particle-fluid heat exchange of a solver (all zero: off)"""
+    _fields_ = [("on", C.c_int32), ("cp", C.c_double), ("kappa", C.c_double), ("prt", C.c_double), ("nusselt_law", C.c_int32),
+                ("T_initial", C.c_double), ("T_bc", C.c_int32 * 6), ("T_value", C.c_double * 6), ("T_convection_scheme", C.c_int32),
+                ("T_tol", C.c_double), ("T_rel_tol", C.c_double), ("T_max_iter", C.c_int32), ("particle_temperature", C.c_double)]
+
+
+NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
+BC_T_ZERO_GRADIENT, BC_T_FIXED_VALUE = 0, 1
+
+
+def thermal_desc(cp, kappa, T_initial=0.0, T_bc=(0,) * 6, T_value=(0.0,) * 6, nusselt_law=NUSSELT_RANZ_MARSHALL, prt=1.0, T_convection_scheme=0,
+                 T_tol=1e-8, T_rel_tol=0.0, T_max_iter=1000, particle_temperature=0.0):
+    """a switched-on fy_thermal_desc (assign it to CaseDesc.thermal, or pass it to make_case as thermal=...)"""
+    d = ThermalDesc()
+    d.on, d.cp, d.kappa, d.prt, d.nusselt_law, d.T_initial = 1, cp, kappa, prt, int(nusselt_law), T_initial
+    for q in range(6):
+        d.T_bc[q] = int(T_bc[q])
+        d.T_value[q] = float(T_value[q])
+    d.T_convection_scheme, d.T_tol, d.T_rel_tol, d.T_max_iter, d.particle_temperature = int(T_convection_scheme), T_tol, T_rel_tol, int(T_max_iter), particle_temperature
+    return d
+
+
 class CaseDesc(C.Structure):
     _fields_ = [("solver", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("dx", C.c_double),
                 ("origin", C.c_double * 3), ("dt", C.c_double), ("nu", C.c_double), ("rho_fluid", C.c_double),
@@ -189,7 +212,7 @@ class CaseDesc(C.Structure):
                 ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double), ("eps_max_iter", C.c_int32),
                 ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc)]
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc)]
 
 
 BC_WALL_FUNCTION, BC_NUT_CALCULATED = 2, 3
@@ -297,6 +320,7 @@ def lib():
     L.fy_foam_case_initial_nut.argtypes = [vp, _dp]
     L.fy_foam_case_initial_k.argtypes = [vp, _dp]
     L.fy_foam_case_initial_epsilon.argtypes = [vp, _dp]
+    L.fy_foam_case_initial_T.argtypes = [vp, _dp]
     L.fy_foam_case_write_time.argtypes = [vp, vp, C.c_char_p]
     L.fy_foam_case_close.argtypes = [vp]
     L.fy_solver_write_field_host.argtypes = [vp, C.c_char_p, _dp]
@@ -322,6 +346,10 @@ def lib():
     L.fy_solver_get_kernel_timing.argtypes = [vp, C.c_char_p, _dp, C.POINTER(C.c_int64)]
     L.fy_solver_enable_exchange_timing.argtypes = [vp, C.c_int]
     L.fy_solver_get_exchange_wait.argtypes = [vp, _dp, C.POINTER(C.c_int64)]
+    L.fy_solver_set_particle_temperatures_host.argtypes = [vp, C.c_int, _dp]
+    L.fy_solver_set_particle_temperatures_device.argtypes = [vp, C.c_int, vp]
+    L.fy_solver_get_particle_heat_host.argtypes = [vp, C.c_int, _dp]
+    L.fy_solver_get_thermal_stats.argtypes = [vp, C.POINTER(C.c_int32), _dp, _dp]
     _lib = L
     return L
 
@@ -742,6 +770,47 @@ class Solver(_Averages):
         _check(L.fy_set_particles_host(self._cpl, 0, _d(rec) if rec.size else None, rec.shape[0]))
         self._batch_n = [rec.shape[0]]
 
+    def set_particle_batches(self, batches):
+        """direct mode with several "Yade procs": one (n,10) host array per batch, coupled in this order"""
+        L = lib()
+        recs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 10) for r in batches]
+        _check(L.fy_set_num_batches(self._cpl, len(recs)))
+        for bi, rec in enumerate(recs):
+            _check(L.fy_set_particles_host(self._cpl, bi, _d(rec) if rec.size else None, rec.shape[0]))
+        self._batch_n = [r.shape[0] for r in recs]
+
+    def stencils_of(self, batch):
+        """stencils() of batch `batch`"""
+        n = self._batch_n[batch]
+        k = np.zeros(n, np.int32); ids = np.full((n, MAXK), -1, np.int32); w = np.zeros((n, MAXK)); chain = np.zeros(n, np.int32)
+        _check(lib().fy_get_stencils_host(self._cpl, int(batch), _i(k), _i(ids), _d(w), _i(chain)))
+        return k, ids, w, chain
+
+    def set_particle_temperatures(self, Tp, batch=0):
+        """heat exchange: the temperatures of the batch's particles in wire order (host array or torch device tensor), or None for the case's uniform particle_temperature"""
+        L = lib()
+        if Tp is None:
+            _check(L.fy_solver_set_particle_temperatures_host(self._h, int(batch), None))
+        elif _is_device(Tp):
+            assert Tp.numel() == self._batch_n[batch]
+            _check(L.fy_solver_set_particle_temperatures_device(self._h, int(batch), C.c_void_p(Tp.data_ptr())))
+        else:
+            Tp = np.ascontiguousarray(Tp, dtype=np.float64).ravel()
+            assert Tp.size == self._batch_n[batch]
+            _check(L.fy_solver_set_particle_temperatures_host(self._h, int(batch), _d(Tp)))
+
+    def particle_heat(self, batch=0):
+        """W into each particle of the batch over the last step, wire order"""
+        q = np.zeros(self._batch_n[batch])
+        _check(lib().fy_solver_get_particle_heat_host(self._h, int(batch), _d(q) if q.size else None))
+        return q
+
+    def thermal_stats(self):
+        """(Jacobi passes, initial residual, heat to the particles [W]) of the last step's T solve"""
+        it = C.c_int32(0); r = C.c_double(0); h = C.c_double(0)
+        _check(lib().fy_solver_get_thermal_stats(self._h, C.byref(it), C.byref(r), C.byref(h)))
+        return it.value, r.value, h.value
+
     def set_particles_device(self, rec):
         L = lib()
         _check(L.fy_set_num_batches(self._cpl, 1))
@@ -1016,6 +1085,12 @@ class FoamCase:
         e = np.zeros(self.field_cells)
         _check(lib().fy_foam_case_initial_epsilon(self._h, _d(e)))
         return e
+
+    def initial_T(self):
+        """the start time's T | T.<phase> of a case with heatTransfer active"""
+        T = np.zeros(self.field_cells)
+        _check(lib().fy_foam_case_initial_T(self._h, _d(T)))
+        return T
 
     def write(self, solver, time_name):
         _check(lib().fy_foam_case_write_time(self._h, solver._h, str(time_name).encode()))

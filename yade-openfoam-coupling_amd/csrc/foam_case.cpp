@@ -27,7 +27,7 @@
 #include "foam_dict.hpp"
 
 // a case's fields (the order of fy_case_desc's and fy_ldu_case's condition arrays); alpha is written only, it has no start-time file
-enum { F_U, F_P, F_NUT, F_K, F_EPS, F_ALPHA };
+enum { F_U, F_P, F_NUT, F_K, F_EPS, F_ALPHA, F_T };      // (F_T: the temperature of a case with heatTransfer active)
 
 // one field's boundary conditions, indexed by the case's patch list (field_patches): per patch the FY_BC_* code, the value (U: three), and the
 // boundaryField entry as read, re-emitted on write; extra: a block case's entries of other names (a decomposed case's processor patches), as read
@@ -49,7 +49,8 @@ struct fy_foam_case {
     std::vector<double> grading[3];             // graded block: cell sizes per axis (fy_case_desc.hx / hy / hz point here)
     std::vector<std::string> patch_order;       // patch names in blockMeshDict order (one side each here)
     std::vector<double> U0, p0, nut0, k0, eps0; // internalField of the start time (nut0, k0, eps0: turbulence cases only)
-    PatchField bcs[5];                          // per field (U, p, nut, k, epsilon): the start time's boundary conditions
+    std::vector<double> T0;                     // ... of T | T.<phase> (heatTransfer active)
+    PatchField bcs[7];                          // per field (U, p, nut, k, epsilon; F_ALPHA unused; T): the start time's boundary conditions
     // controlDict's output settings [OF-6 Time::readDict]: writeFormat ascii | binary, writePrecision (ASCII digits; absent: 17, lossless --
     // OpenFOAM's own default of 6 would not restart a run where it stopped), purgeWrite N (keep the N newest time directories this run wrote)
     bool write_binary = false;
@@ -545,12 +546,14 @@ bool has_field(const fy_foam_case* c, int F) {
         case F_K: return tm == FY_TURBULENCE_KEQN || tm == FY_TURBULENCE_KEPSILON;
         case F_EPS: return tm == FY_TURBULENCE_KEPSILON;
         case F_ALPHA: return c->solver == FY_SOLVER_PIMPLE;
+        case F_T: return c->desc.thermal.on != 0;
         default: return true;
     }
 }
 
 std::string field_name(const fy_foam_case* c, int F) {
     static const char* const group[] = {"", "", "nut.", "k.", "epsilon.", "alpha."};
+    if (F == F_T) return c->phase.empty() ? std::string("T") : "T." + c->phase;       // (named with the velocity's group, like the turbulence fields)
     return F == F_U ? c->u_name : F == F_P ? std::string("p") : group[F] + c->phase;
 }
 
@@ -580,6 +583,15 @@ int patch_condition(fy_foam_case* c, int F, const std::string& path, size_t pa, 
     // [OF-6 nutWallFunctionFvPatchScalarField::checkType]: a wall function sits on a wall patch
     if (g && (F == F_NUT || F == F_EPS) && ty.find("WallFunction") != std::string::npos && cls != "wall")
         return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s is a wall function, but the patch is of type '%s' (constant/polyMesh/boundary), not wall", path.c_str(), pn, ty.c_str(), cls.c_str());
+    if (F == F_T) {
+        if (ty == "fixedValue") {
+            *bc = FY_BC_T_FIXED_VALUE;
+            if (!uniform_scalar(pd, val)) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform <T>'", path.c_str(), pn);
+            return FY_OK;
+        }
+        if (ty == "zeroGradient" || ty == "symmetryPlane" || ty == "symmetry") { *bc = FY_BC_T_ZERO_GRADIENT; return FY_OK; }
+        return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': temperature boundary type '%s' is not supported (zeroGradient, fixedValue)", path.c_str(), pn, ty.c_str());
+    }
     switch (F) {
         case F_U:
             if (ty == "fixedValue") {
@@ -691,6 +703,15 @@ int read_fields(fy_foam_case* c) {
     if (has_field(c, F_NUT)) FY_TRY(read_field(c, F_NUT, &c->nut0, &c->desc.nut_initial));
     if (has_field(c, F_K)) FY_TRY(read_field(c, F_K, &c->k0, &c->desc.k_initial));
     if (has_field(c, F_EPS)) FY_TRY(read_field(c, F_EPS, &c->eps0, &c->desc.eps_initial));
+    if (has_field(c, F_T)) {
+        const std::string path = join(c->fdir, c->start_name + "/" + field_name(c, F_T));
+        if (!file_exists(path))
+            return fail(FY_ERR_UNSUPPORTED, "%s: no such file, but constant/couplingProperties has heatTransfer active: the temperature field of the start time is needed "
+                                            "(volScalarField, internalField uniform | nonuniform, patches zeroGradient | fixedValue)", path.c_str());
+        FY_TRY(read_field(c, F_T, &c->T0, &c->desc.thermal.T_initial));
+        std::copy(c->bcs[F_T].bc.begin(), c->bcs[F_T].bc.end(), c->desc.thermal.T_bc);
+        std::copy(c->bcs[F_T].val.begin(), c->bcs[F_T].val.end(), c->desc.thermal.T_value);
+    }
     fy_case_desc& d = c->desc;
     const struct { int F; int32_t* bc; double* val; } to[] = {{F_U, d.u_bc, &d.u_value[0][0]}, {F_P, d.p_bc, d.p_value}, {F_NUT, d.nut_bc, d.nut_value},
                                                              {F_K, d.k_bc, d.k_value}, {F_EPS, d.eps_bc, d.eps_value}};
@@ -817,6 +838,7 @@ int check_general_schemes(const fy_foam_case* c) {
 // general cases; a missing file or entry leaves the reference's behaviour, a word the case's solver cannot take is refused here
 int read_coupling_properties(fy_foam_case* c) {
     c->desc.drag_law = FY_DRAG_REFERENCE; c->desc.force_models = 0;
+    c->desc.thermal = fy_thermal_desc{};
     const std::string path = join(c->dir, "constant/couplingProperties");
     if (!file_exists(path)) return FY_OK;
     FoamDict d;
@@ -845,6 +867,35 @@ int read_coupling_properties(fy_foam_case* c) {
         if (!d.boolean(sw.key, &on) || (on && !gaussian))
             return fail(FY_ERR_UNSUPPORTED, "%s: %s %s; %s accepts %s", path.c_str(), sw.key, w.c_str(), solver, gaussian ? "on | off" : "off");
         if (on) c->desc.force_models |= sw.flag;
+    }
+    // heatTransfer { active; nusseltModel; Cp; kappa; Prt; particleTemperature; }: the fluid temperature equation and the particles' heat exchange
+    // (fy_thermal_desc); 0/T, div(phi,T) | div(alphaPhic,T) and solvers.T complete it (read_controls, read_fields)
+    if (d.has("heatTransfer")) {
+        const FoamDict* h = d.subdict("heatTransfer");
+        if (!h) return fail(FY_ERR_INVALID, "%s: heatTransfer must be a dictionary { active; nusseltModel; Cp; kappa; Prt; particleTemperature; }", path.c_str());
+        for (const std::string& k : h->order)
+            if (k != "active" && k != "nusseltModel" && k != "Cp" && k != "kappa" && k != "Prt" && k != "particleTemperature")
+                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.%s is not an entry this reader knows (active, nusseltModel, Cp, kappa, Prt, particleTemperature)", path.c_str(), k.c_str());
+        bool active = true;
+        if (h->has("active") && !h->boolean("active", &active)) { h->word("active", &w); return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.active %s; accepts on | off", path.c_str(), w.c_str()); }
+        if (active) {
+            fy_thermal_desc& t = c->desc.thermal;
+            if (c->general) return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.active on: heat transfer runs on the structured block only, and this case holds a general mesh; accepts off", path.c_str());
+            if (c->proc_count > 0) return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.active on: heat transfer is not available on z-slabs (a decomposed case, -parallel); accepts off", path.c_str());
+            t.on = 1;
+            t.nusselt_law = FY_NUSSELT_RANZ_MARSHALL;
+            if (h->word("nusseltModel", &w)) {
+                if (w == "Gunn" && gaussian) t.nusselt_law = FY_NUSSELT_GUNN;
+                else if (w != "RanzMarshall") return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.nusseltModel %s; %s accepts %s", path.c_str(), w.c_str(), solver, gaussian ? "RanzMarshall | Gunn" : "RanzMarshall");
+            }
+            if (!h->scalar("Cp", &t.cp) || !(t.cp > 0)) return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.Cp is missing or not positive; accepts a specific heat in J/kg/K", path.c_str());
+            if (!h->scalar("kappa", &t.kappa) || !(t.kappa > 0)) return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.kappa is missing or not positive; accepts a conductivity in W/m/K", path.c_str());
+            t.prt = 1.0;
+            if (h->has("Prt") && (!h->scalar("Prt", &t.prt) || !(t.prt > 0))) return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.Prt must be a positive number", path.c_str());
+            if (h->has("particleTemperature") && !h->scalar("particleTemperature", &t.particle_temperature))
+                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.particleTemperature must be a number (the uniform temperature of the particles, K)", path.c_str());
+            t.T_convection_scheme = FY_CONVECTION_LINEAR;
+        }
     }
     return FY_OK;
 }
@@ -895,7 +946,7 @@ int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) 
         std::vector<std::pair<std::string, FoamDict> > fields;
         FY_TRY(named_dicts(*ft, where + ".fields", &fields));
         const std::string ph = c->phase.empty() ? std::string("<phase>") : c->phase;
-        const std::string accepted = c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource";
+        const std::string accepted = c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource" + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string());
         for (const auto& fd : fields) {
             const std::string& file = fd.first;
             const std::string fw = where + ".fields." + file;
@@ -909,11 +960,11 @@ int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) 
             // the file name -> the case's field
             static const struct { const char* stem; int F; const char* solver_name; int ncomp; } known[] = {
                 {"U", F_U, "U", 3}, {"p", F_P, "p", 1}, {"alpha", F_ALPHA, "alpha", 1}, {"nut", F_NUT, "nut", 1}, {"k", F_K, "k", 1}, {"epsilon", F_EPS, "epsilon", 1},
-                {"uParticle", -1, "uParticle", 3}, {"uSource", -1, "uSource", 3}};
+                {"uParticle", -1, "uParticle", 3}, {"uSource", -1, "uSource", 3}, {"T", F_T, "T", 1}};
             const std::string stem = file.substr(0, file.find('.'));
             const auto* kf = &known[0];
             bool is_known = false;
-            for (const auto& k : known) if (stem == k.stem) { kf = &k; is_known = true; }
+            for (const auto& k : known) if (stem == k.stem && (k.F != F_T || c->desc.thermal.on)) { kf = &k; is_known = true; }      // (T is a field of a case with heat transfer only)
             if (!is_known) return fail(FY_ERR_UNSUPPORTED, "%s: unknown field '%s'; accepted: %s", fw.c_str(), file.c_str(), accepted.c_str());
             const bool has = kf->F >= 0 ? (has_field(c, kf->F) && file == field_name(c, kf->F))
                                         : (file == kf->stem && (stem != "uParticle" || c->solver == FY_SOLVER_PIMPLE));
@@ -1073,6 +1124,7 @@ int read_controls(fy_foam_case* c) {
                               {"interpolationSchemes", "linear", nullptr, "pwind"},
                               {"snGradSchemes", "corrected", "orthogonal", nullptr}};   // corrected == uncorrected == orthogonal on this mesh
         int n_div = 0;
+        bool t_div_named = false, t_div_default = false;      // div(phi,T) | div(alphaPhic,T) given by name; a usable `default`
         for (const Want& w : wants) {
             const FoamDict* sd = d.subdict(w.dict);
             if (!sd) return fail(FY_ERR_INVALID, "%s: %s missing", path.c_str(), w.dict);
@@ -1118,6 +1170,12 @@ int read_controls(fy_foam_case* c) {
                         c->desc.eps_convection_scheme = sch;
                         continue;
                     }
+                    if (k == "div(phi,T)" || k == "div(alphaPhic,T)" || k == "div(alphaPhi." + c->phase + ",T." + c->phase + ")") {      // the temperature equation's convection (heatTransfer)
+                        if (sch >= FY_CONVECTION_LINEAR_UPWIND) return fail(FY_ERR_UNSUPPORTED, "%s: divSchemes.%s = '%s': [bounded] Gauss linear | upwind for T", path.c_str(), k.c_str(), joined.c_str());
+                        if (c->desc.thermal.on) c->desc.thermal.T_convection_scheme = sch;
+                        t_div_named = true;
+                        continue;
+                    }
                     if (k_convection) {                                  // fvm::div(alphaRhoPhi, k) of the kEqn / kEpsilon models
                         if (sch >= FY_CONVECTION_LINEAR_UPWIND) return fail(FY_ERR_UNSUPPORTED, "%s: divSchemes.%s = '%s': Gauss linear or Gauss upwind for k", path.c_str(), k.c_str(), joined.c_str());
                         c->desc.k_convection_scheme = sch;
@@ -1127,13 +1185,16 @@ int read_controls(fy_foam_case* c) {
                         if (sch != FY_CONVECTION_LINEAR) return fail(FY_ERR_UNSUPPORTED, "%s: divSchemes.%s = '%s': only the convection terms may be upwinded, this one must be Gauss linear", path.c_str(), k.c_str(), joined.c_str());
                         continue;
                     }
-                    if (k == "default") { if (!n_div) { c->desc.convection_scheme = sch; c->desc.convection_limiter_k = lim_k; } c->desc.k_convection_scheme = c->desc.eps_convection_scheme = sch == FY_CONVECTION_LINEAR ? sch : FY_CONVECTION_UPWIND; continue; }      // a named convection entry overrides it
+                    if (k == "default") { if (!n_div) { c->desc.convection_scheme = sch; c->desc.convection_limiter_k = lim_k; } c->desc.k_convection_scheme = c->desc.eps_convection_scheme = sch == FY_CONVECTION_LINEAR ? sch : FY_CONVECTION_UPWIND; t_div_default = true; if (c->desc.thermal.on && !t_div_named) c->desc.thermal.T_convection_scheme = c->desc.k_convection_scheme; continue; }      // a named convection entry overrides it
                     if (n_div++ && sch != c->desc.convection_scheme) return fail(FY_ERR_UNSUPPORTED, "%s: divSchemes mixes different convection schemes", path.c_str());
                     c->desc.convection_scheme = sch;
                     c->desc.convection_limiter_k = lim_k;
                 }
             }
         }
+        if (c->desc.thermal.on && !t_div_named && !t_div_default)      // (`default none;` and no entry for T: OpenFOAM stops at the first fvm::div of T)
+            return fail(FY_ERR_UNSUPPORTED, "%s: divSchemes has no entry for %s and `default none`, but constant/couplingProperties has heatTransfer active; accepted: [bounded] Gauss linear | upwind",
+                        path.c_str(), c->solver == FY_SOLVER_PIMPLE ? "div(alphaPhic,T)" : "div(phi,T)");
     }
     {
         const std::string path = join(c->dir, "system/fvSolution");
@@ -1183,6 +1244,17 @@ int read_controls(fy_foam_case* c) {
                     if (key.find(kn) != std::string::npos || key.find("|k|") != std::string::npos || key.find("|k)") != std::string::npos) { ks = sv->subdict(key); if (ks) break; }
             if (!ks) return fail(FY_ERR_INVALID, "%s: solvers has no entry for %s (kEqn solves a transport equation for it)", path.c_str(), kn.c_str());
             ks->scalar("tolerance", &c->desc.k_tol); ks->scalar("relTol", &c->desc.k_rel_tol); ks->integer("maxIter", &c->desc.k_max_iter);
+        }
+        if (c->desc.thermal.on) {                                      // solvers.T | T.<phase> (or a pattern naming it)
+            const std::string tn = field_name(c, F_T);
+            const FoamDict* ts = sv->subdict(tn);
+            if (!ts) ts = sv->subdict("T");
+            if (!ts)
+                for (const std::string& key : sv->order)
+                    if (key.find(tn) != std::string::npos || key.find("|T|") != std::string::npos || key.find("|T)") != std::string::npos || key.find("(T|") != std::string::npos) { ts = sv->subdict(key); if (ts) break; }
+            if (!ts) return fail(FY_ERR_UNSUPPORTED, "%s: solvers has no entry for %s, but constant/couplingProperties has heatTransfer active (tolerance, relTol, maxIter of the Jacobi solve)", path.c_str(), tn.c_str());
+            c->desc.thermal.T_tol = c->desc.u_tol; c->desc.thermal.T_rel_tol = c->desc.u_rel_tol; c->desc.thermal.T_max_iter = c->desc.u_max_iter;
+            ts->scalar("tolerance", &c->desc.thermal.T_tol); ts->scalar("relTol", &c->desc.thermal.T_rel_tol); ts->integer("maxIter", &c->desc.thermal.T_max_iter);
         }
         // relaxationFactors: equations { <U>; <U>Final; ".*" } for UcEqn.relax() (UcEqn.H:12), fields { p; pFinal } for p.relax() (pEqn.H:41).
         // No entry = the call does nothing [OF-6 fvMatrix::relax(), GeometricField::relax()]; icoFoamYade relaxes nothing.
@@ -1279,6 +1351,7 @@ const int* field_dims(int F, const std::string& solver_name) {
         case F_NUT: return nut;
         case F_EPS: return eps;
         case F_ALPHA: return none;
+        case F_T: { static const int temp[7] = {0, 0, 0, 1, 0, 0, 0}; return temp; }
         default: return solver_name == "uSource" ? acc : U;      // volSource, uParticle (createFields.H of both solvers)
     }
 }
@@ -1482,6 +1555,13 @@ int fy_foam_case_initial_epsilon(const fy_foam_case* c, double* eps) {
     return FY_OK;
 }
 
+int fy_foam_case_initial_T(const fy_foam_case* c, double* T) {
+    if (!c || !T) return fail(FY_ERR_INVALID, "fy_foam_case_initial_T: null argument");
+    if (c->T0.empty()) return fail(FY_ERR_INVALID, "fy_foam_case_initial_T: the case has no heat transfer");
+    std::memcpy(T, c->T0.data(), c->T0.size() * sizeof(double));
+    return FY_OK;
+}
+
 int fy_foam_case_write_fields(const fy_foam_case* c, const char* time_name, const double* U, const double* p, const double* alpha, const double* nut,
                               const double* k, const double* epsilon) {
     if (!c || !time_name || !*time_name || !U || !p) return fail(FY_ERR_INVALID, "fy_foam_case_write_fields: null argument");
@@ -1544,6 +1624,12 @@ int fy_foam_case_write_time(const fy_foam_case* c, fy_solver* s, const char* tim
     FY_TRY(fy_solver_field_count(s, "p", &cnt));
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_UNSUPPORTED, "fy_foam_case_write_time: the solver holds %lld cells, the case's field files %zu (a slab of an undecomposed case: gather the slabs and use fy_foam_case_write_fields)", (long long)cnt, c->fcells);
     FY_TRY(write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_EPS, F_K}, [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); }));
+    if (has_field(c, F_T)) {                              // T | T.<phase> beside them, with the start time's patch entries
+        std::vector<double> T(c->fcells);
+        FY_TRY(fy_solver_read_field_host(s, "T", T.data()));
+        FY_TRY(write_field(c, join(c->fdir, time_name), time_name, field_name(c, F_T), "volScalarField", "[0 0 0 1 0 0 0]", 1, T, &c->bcs[F_T], "        type            zeroGradient;\n",
+                           c->bcs[F_T].extra));
+    }
     fy_step_stats st;
     FY_TRY(fy_solver_get_stats(s, &st));
     return write_averages(c, time_name, st.delta_t > 0 ? st.delta_t : c->desc.dt, [s](const char* nm, int64_t* n) { return fy_solver_field_count(s, nm, n); },

@@ -216,6 +216,7 @@ int main(int argc, char** argv) {
 #endif
             return rc;
         }
+        std::fprintf(stderr, "foamYadeHip: the block reader said: %s\n", why.c_str());      // (what follows is the general reader's refusal)
     }
     if (open_rc != FY_OK) return die("reading the case");
     if (master && ssize > 1) std::printf("Case: %s\n", decomposed ? "decomposed (processor directories)" : "undecomposed (gathered on write)");
@@ -227,6 +228,9 @@ int main(int argc, char** argv) {
         std::printf("Create mesh: %d x %d x %d cells of %g m, %s on the six sides x- x+ y- y+ z- z+: %s %s %s %s %s %s\n", cd.nx, cd.ny, cd.nz, cd.dx,
                     "patches", info.patch_of_side[0], info.patch_of_side[1], info.patch_of_side[2], info.patch_of_side[3], info.patch_of_side[4], info.patch_of_side[5]);
     if (master) { print_coupling(cd.drag_law, cd.force_models); print_functions(fc, cd.average); }
+    if (master && cd.thermal.on)
+        std::printf("Heat transfer: nusseltModel %s, Cp %g, kappa %g, Prt %g, particleTemperature %g, div(T) %s\n", cd.thermal.nusselt_law == FY_NUSSELT_GUNN ? "Gunn" : "RanzMarshall",
+                    cd.thermal.cp, cd.thermal.kappa, cd.thermal.prt, cd.thermal.particle_temperature, cd.thermal.T_convection_scheme == FY_CONVECTION_UPWIND ? "upwind" : "linear");
     fy_solver* s = nullptr;
     if ((comm ? fy_solver_create_slab(&cd, trp, device, comm, &s) : fy_solver_create(&cd, trp, device, &s)) != FY_OK) return die("fy_solver_create");
     // a slab owns the z-planes [srank nz / ssize, (srank + 1) nz / ssize): a contiguous run of the block's cells, `first` cells in
@@ -244,6 +248,10 @@ int main(int argc, char** argv) {
                 (fy_foam_case_initial_k(fc, nut.data()) != FY_OK || fy_solver_write_field_host(s, "k", nut.data() + first) != FY_OK)) return die("initial k");
             if (cd.turbulence_model == FY_TURBULENCE_KEPSILON &&
                 (fy_foam_case_initial_epsilon(fc, nut.data()) != FY_OK || fy_solver_write_field_host(s, "epsilon", nut.data() + first) != FY_OK)) return die("initial epsilon");
+        }
+        if (cd.thermal.on) {                                             // T | T.<phase> of the start time (a restart: of the time it was written at)
+            std::vector<double> T((size_t)info.field_cells);
+            if (fy_foam_case_initial_T(fc, T.data()) != FY_OK || fy_solver_write_field_host(s, "T", T.data() + first) != FY_OK) return die("initial T");
         }
         if (cd.average.n_items > 0) {                                    // (one domain: a slab's create has refused the averages above)
             int restored = 0;

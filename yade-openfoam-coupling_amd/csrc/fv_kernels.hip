@@ -906,6 +906,75 @@ __global__ __launch_bounds__(256) void k_turb_finish(FvGeo g, TurbEqn e, const d
     else if (nut_mode == 2) nut[c] = cmu * (xb * xb) / ef[c];
 }
 
+// The fluid temperature equation (fy_thermal_desc; a capability the reference does not have -- DESIGN_FV.md "T equation"), next to the turbulence transport
+// equations and assembled like them into the momentum matrix's storage as the {X, 0, 0} system:
+//   alpha V (T - T_old) / dt + sum_f F_f T_f - T sum_f F_f - sum_f alpha_f Deff_f |S_f| / |d_f| (T_N - T) = (Su - Sp T) / (rho_f cp)
+// F_f = alpha_f phi_f outward (alpha == nullptr: icoFoamYade, alpha = 1), the convection in its bounded form, T_f linear | upwind, alpha_f and Deff_f = D + nut / Prt
+// the linear interpolates (alpha_f = 1 on a boundary face: the calculated patch's value, as in UcEqn), alpha.oldTime() == alpha (quirk F-Q1).  fixedValue side: half-cell
+// distance and F_b T_b; zeroGradient side: T_b = T.  Sp, Su: what the particles' heat exchange scattered (W/K, W; nullptr: none)
+__global__ __launch_bounds__(256) void k_assemble_scalar(FvGeo g, ScalarEqn e, const double* __restrict__ Tf, const double* __restrict__ alpha, CFace3 phi,
+                                                         const double* __restrict__ Sp, const double* __restrict__ Su, Mom7 M, double* __restrict__ b3,
+                                                         double* __restrict__ x3) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= g.Nc) return;
+    int i, j, k; ijk_of(g, t, i, j, k);
+    const int c = t + g.c0;
+    const double dt = g.dt, V = geo_V(g, i, j, k);
+    const double aP = alpha ? alpha[c] : 1.0;
+    const double dP = e.D + (g.nut ? g.nut[c] * e.rPrt : 0.0);
+    const double xc = Tf[c];
+    double dg = aP * V / dt;                                    // fvm::ddt(alpha, T)
+    double src = aP * V * xc / dt;
+    double sumF = 0.0, an[6];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int f = cface(g, d, s, i, j, k);
+            const double pv = (s ? 1.0 : -1.0) * phi.a[d][f];
+            if (onb(g, d, s, i, j, k)) {
+                an[2 * d + s] = 0.0;
+                const int patch = 2 * d + s;
+                const double F = pv;                              // alpha_f = 1 on the boundary
+                sumF += F;
+                if (e.bc[patch] == 1) {
+                    const double db = e.D + (g.nut ? nut_boundary(g, patch, c) * e.rPrt : 0.0);
+                    const double gb = kBfac * (db * geo_sfd(g, d, s, i, j, k));
+                    dg += gb;
+                    src += (gb - F) * e.val[patch];
+                } else {
+                    dg += F;
+                }
+            } else {
+                const int nbc = c + (s ? stride_of(g, d) : -stride_of(g, d));
+                const int qc = d == 0 ? i : d == 1 ? j : k;
+                const double af = geo_lerp_side(g, d, s, qc, aP, alpha ? alpha[nbc] : 1.0);
+                const double df = geo_lerp_side(g, d, s, qc, dP, e.D + (g.nut ? g.nut[nbc] * e.rPrt : 0.0));
+                const double gam = (af * df) * geo_sfd(g, d, s, i, j, k);
+                const double F = af * pv;
+                sumF += F;
+                const double wP = geo_wown(g, d, s, qc);
+                const double cP = e.upwind ? fmax(F, 0.0) : wP * F, cN = e.upwind ? fmin(F, 0.0) : (1.0 - wP) * F;
+                dg += cP + gam;
+                an[2 * d + s] = cN - gam;
+            }
+        }
+    dg -= sumF;                                                 // bounded convection: - T div(F)
+    if (Sp) { dg += Sp[c] * e.rRhoCp; src += Su[c] * e.rRhoCp; }
+    M.diag[c] = dg;
+    for (int q = 0; q < 6; ++q) M.an[q][c] = an[q];
+    b3[3 * (size_t)c] = src; b3[3 * (size_t)c + 1] = 0.0; b3[3 * (size_t)c + 2] = 0.0;
+    x3[3 * (size_t)c] = xc; x3[3 * (size_t)c + 1] = 0.0; x3[3 * (size_t)c + 2] = 0.0;
+}
+// component 0 of the solved {X, 0, 0} system -> the scalar field
+__global__ __launch_bounds__(256) void k_scalar_finish(FvGeo g, const double* __restrict__ x3, double* __restrict__ X) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= g.Nc) return;
+    const int c = t + g.c0;
+    X[c] = x3[3 * (size_t)c];
+}
+
+
 // UEqn (icoFoamYade.C:79-85) / UcEqn + relax (UcEqn.H:3-12): diag, 6 neighbour coefficients, source (no pressure term), rAU = 1/A
 // ---- NVD / TVD limited convection schemes for div(phi,U) [OF-6 LimitedScheme<vector, Limiter<NVDTVD>, limitFuncs::magSqr>, NVDTVD.H]: one
 // limiter per face from the scalar lPhi = magSqr(U): r = 2 (d . grad(lPhi)_C) / (lPhi_N - lPhi_P) - 1, C the upwind cell of the face flux, grad
@@ -1687,6 +1756,19 @@ int launch_assemble_turb(hipStream_t s, FvGeo g, TurbEqn e, const double* k, con
 
 int launch_turb_finish(hipStream_t s, FvGeo g, TurbEqn e, const double* x3, double* X, int nut_mode, double cmu, const double* eps, double* nut) {
     hipLaunchKernelGGL(k_turb_finish, dim3(fv_grid(g)), dim3(256), 0, s, g, e, x3, X, nut_mode, cmu, eps, nut);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_assemble_scalar(hipStream_t s, FvGeo g, ScalarEqn e, const double* T, const double* alpha, CFace3 phi, const double* Sp, const double* Su, Mom7 M,
+                           double* b3, double* x3) {
+    hipLaunchKernelGGL(k_assemble_scalar, dim3(fv_grid(g)), dim3(256), 0, s, g, e, T, alpha, phi, Sp, Su, M, b3, x3);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_scalar_finish(hipStream_t s, FvGeo g, const double* x3, double* X) {
+    hipLaunchKernelGGL(k_scalar_finish, dim3(fv_grid(g)), dim3(256), 0, s, g, x3, X);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

@@ -76,6 +76,8 @@ inline size_t fv_fsize(const FvGeo& g, int d) {
     return d == 0 ? (size_t)(g.nx + 1) * g.ny * g.nz : d == 1 ? (size_t)g.nx * (g.ny + 1) * g.nz : (size_t)g.nx * g.ny * (g.nz + 1);
 }
 
+// the fluid temperature equation (launch_assemble_scalar): D = kappa / (rho_f cp), rPrt = 1 / Prt, rRhoCp = 1 / (rho_f cp); bc 0 zeroGradient | 1 fixedValue
+struct ScalarEqn { int upwind; int bc[6]; double val[6]; double D, rPrt, rRhoCp; };
 struct TurbEqn { int mode; double ck, ce, delta, c1, c2, c3, sigma, xmin, relax; int upwind; int bc[6]; double val[6]; int wall[6]; double cmu75, cmu25, kappa; };
 
 // The launchers that take an FvGeo exist twice: fy::launch_* for the uniform block (dx, Af, V constants in every kernel) and fy::gr::launch_* for a

@@ -34,6 +34,12 @@ int launch_assemble_turb(hipStream_t s, FvGeo g, TurbEqn e, const double* k, con
 // bound(X, xmin) [OF-6 bound.C] on the solved component 0 of x3 -> X; nut_mode 1: nut = Ck sqrt(k) delta (kEqn::correctNut, X = k),
 // 2: nut = Cmu k^2 / eps (kEpsilon::correctNut, X = k, eps given), 0: leave nut alone (the epsilon equation)
 int launch_turb_finish(hipStream_t s, FvGeo g, TurbEqn e, const double* x3, double* X, int nut_mode, double cmu, const double* eps, double* nut);
+// The fluid temperature equation (fy_thermal_desc), assembled like the turbulence transport equations into the momentum matrix's storage (x3 = {T, 0, 0}, b3 = {source, 0, 0}):
+//   alpha V (T - T_old) / dt + sum_f F_f T_f - T sum_f F_f - sum_f alpha_f Deff_f |S_f| / |d_f| (T_N - T) = (Su - Sp T) / (rho_f cp),  F_f = alpha_f phi_f, Deff = D + nut / Prt
+// alpha == nullptr: alpha = 1 (icoFoamYade); Sp == nullptr: no particle sources.  launch_scalar_finish copies the solved component 0 back to the field
+int launch_assemble_scalar(hipStream_t s, FvGeo g, ScalarEqn e, const double* T, const double* alpha, CFace3 phi, const double* Sp, const double* Su, Mom7 M,
+                           double* b3, double* x3);
+int launch_scalar_finish(hipStream_t s, FvGeo g, const double* x3, double* X);
 int launch_smagorinsky_nut(hipStream_t s, FvGeo g, const double* vGrad, double ck, double ce, double delta, double* nut);
 // alphaf.a[0] == nullptr: alphacf is re-formed from alpha (no face array kept)
 int launch_assemble_momentum(hipStream_t s, FvGeo g, const double* U, const double* Uold, const double* alpha, const double* alphaOld,

@@ -24,6 +24,9 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
         const int nn[3] = {c->nx, c->ny, c->nz};
         for (int a = 0; a < 3; ++a) for (int q = 0; q < nn[a]; ++q) if (!(hh[a][q] > 0)) return fail(FY_ERR_INVALID, "fy_solver_create: graded block with a non-positive cell size");
     }
+    if (c->thermal.on && cm && cm->size > 1)        // (before anything collective: every rank leaves here)
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_create_slab: heat transfer (fy_case_desc.thermal.on) is not available on z-slabs (%d ranks; foamYadeHip_mpi -parallel): "
+                                        "run the case on one domain", cm->size);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FY_ERR_NO_DEVICE, "no HIP device visible: libfoamyade_hip has no CPU path");
     if (dev < 0 || dev >= ndev) return fail(FY_ERR_INVALID, "device ordinal out of range");
@@ -326,13 +329,14 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     FY_TRY(halo_U());
     FY_TRY(FVK(launch_flux_of, stream, g, U.p, F3(phi)));                     // createPhi
     FY_HIP(hipStreamSynchronize(stream));
+    if (c->thermal.on) FY_TRY(thermal_create(c));                             // couplingProperties heatTransfer + 0/T (before fieldAverage, which may ask for T)
     if (c->average.n_items) FY_TRY(set_field_average(&c->average));           // controlDict functions: fieldAverage
     return FY_OK;
 }
 
 const double* Solver::avg_source(const std::string& name, int* comp) const {
     const struct { const char* nm; const double* p; int comp; } tab[] = {{"U", U.p, 3}, {"p", p.p, 1}, {"alpha", alpha.p, 1}, {"uParticle", uParticle.p, 3},
-                                                                         {"uSource", uSource.p, 3}, {"nut", nut.p, 1}, {"k", kturb.p, 1}, {"epsilon", epsturb.p, 1}};
+                                                                         {"uSource", uSource.p, 3}, {"nut", nut.p, 1}, {"k", kturb.p, 1}, {"epsilon", epsturb.p, 1}, {"T", th.T.p, 1}};
     for (const auto& e : tab)
         if (name == e.nm && e.p) { *comp = e.comp; return e.p + (size_t)e.comp * g.c0; }      // (the owned cells: Solver::field)
     return nullptr;
@@ -409,7 +413,7 @@ int Solver::reduce_to_device(double* dst) {          // one slot, stays on the d
 
 // Jacobi sweeps on the 7-point matrix in M7() for a 3-component field X (in place; xscr is the other buffer), lduMatrix-style L1
 // residual control per component
-int Solver::solve_vec3(DevBuf<double>& X, const double* rhs, double tol, double rel_tol, int max_iter, int* iters, bool momentum) {
+int Solver::solve_vec3(DevBuf<double>& X, const double* rhs, double tol, double rel_tol, int max_iter, int* iters, bool momentum, double* res0_out) {
     Comm::Tag tag(comm, momentum ? "momentum_solve" : "turbulence_solve");
     double h[6];
     // sum(X) per component for xbar = average(X): folded (and all-reduced) on the device, divided where it is used
@@ -457,6 +461,7 @@ int Solver::solve_vec3(DevBuf<double>& X, const double* rhs, double tol, double 
     // the pass that found the iterate converged had just exchanged that iterate's ghost planes (or they were fresh): they still are
     if (&X == &U) U_ghosts_fresh = true;
     *iters = it;
+    if (res0_out) *res0_out = res0[0];
     return FY_OK;
 }
 
@@ -624,6 +629,8 @@ int Solver::step() {
     FY_HIP(hipSetDevice(device));
     st = fy_step_stats{}; st.cont_err_cumulative = cumulative_cont_err;
     clk_mom.on = clk_pres.on = timing; clk_mom.per_collect = clk_pres.per_collect = 1024; clk_mom.reset(); clk_pres.reset();
+    if (th.on && cpl->c.fibre)          // (before the particle phase: a refused step leaves nothing half done)
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_step: heat transfer (fy_case_desc.thermal.on) is not available with fibre coupling (fy_set_fibre_coupling): switch one of them off");
     if (timing) tim[3].start(stream);
     if (sources_pending) { FY_TRY(cpl->c.set_source_zero()); sources_pending = false; }   // the previous step's deferred setSourceZero
     double h[2];
@@ -738,6 +745,7 @@ int Solver::step() {
         FY_TRY(rc);
     }
     if (timing) { tim[0].stop(stream); }
+    if (th.on) FY_TRY(heat_coefficients());       // the stencils, the cell records and U are still what the force pass saw
     comm->tag = "momentum";
 
     // alphac.oldTime() is captured lazily by OpenFOAM at alphac.correctBoundaryConditions() (pimpleFoamYade.C:83), i.e. after
@@ -800,6 +808,7 @@ int Solver::step() {
         for (int corr = 0; corr < cs.n_correctors; ++corr) FY_TRY(corrector(outer == nOuter - 1 && corr == cs.n_correctors - 1));
         if (g.nut && final_outer) FY_TRY(turbulence_correct());        // pimple.turbCorr(): on the final outer iteration only (the default) -- pimpleFoamYade.C:101-104
     }
+    if (th.on) { FY_TRY(solve_temperature()); FY_TRY(heat_fluxes()); }                    // the step's final phi and nut; Sp implicit, then the particles' share
     FY_TRY(cpl->c.finish_results());                                                      // the answers still on their way, then the dt handshake (FoamYade.C:537-553)
     avg.elapsed += cs.dt;
     if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));      // where runTime.write() stands
@@ -824,6 +833,7 @@ int Solver::step() {
         st.ms_other = st.ms_total - st.ms_particle - st.ms_momentum - st.ms_pressure;
         for (auto& k : kc) k.collect();
         avg.clock.collect();
+        if (th.on) { th.clk_coeff.collect(); th.clk_flux.collect(); th.clk_asm.collect(); }
     }
     if (xwait_timing) {
         for (auto& k : clk_xwait) k.collect();
@@ -840,11 +850,19 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
                      {"rAU", rAU.p, n, 1}, {"HbyA", HbyA.p, 3 * n, 3}, {"p_rhs", prhs.p, n, 1}, {"mom_diag", mdiag.p, n, 1}, {"mom_src", src.p, 3 * n, 3},
                      {"alpha", alpha.p, n, 1}, {"uSource", uSource.p, 3 * n, 3}, {"uSourceDrag", uSourceDrag.p, n, 1}, {"uParticle", uParticle.p, 3 * n, 3},
                      {"gradP", gradP.p, 3 * n, 3}, {"divT", divT.p, 3 * n, 3}, {"vGrad", vGrad.p, 9 * n, 9}, {"ddtU", ddtU.p, 3 * n, 3}, {"nut", nut.p, n, 1}, {"k", kturb.p, n, 1}, {"epsilon", epsturb.p, n, 1}};
+    if (s == "T" || s == "heatSp" || s == "heatSu") {
+        if (!th.on) return fail(FY_ERR_INVALID, "solver field '%s' does not exist in this case (fy_case_desc.thermal is off)", s.c_str());
+        *ptr = (s == "T" ? th.T.p : s == "heatSp" ? th.Sp.p : th.Su.p) + g.c0;
+        *count = n;
+        return FY_OK;
+    }
     for (const E& e : tab) if (s == e.nm) {
         if (!e.p) return fail(FY_ERR_INVALID, "solver field '%s' does not exist in this case (no turbulence model)", s.c_str());
         // kEqn / kEpsilon assemble and solve their transport equations in the momentum matrix's storage after the last corrector
         // (turbulence_correct): these three diagnostics would then return transport-equation data beside a momentum rAU
         const bool transport = cs.turbulence_model == FY_TURBULENCE_KEQN || cs.turbulence_model == FY_TURBULENCE_KEPSILON;
+        if (th.on && (s == "HbyA" || s == "mom_diag"))
+            return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is overwritten by the temperature solve in this case (the T equation reuses the momentum matrix's storage)", s.c_str());
         if (transport && (s == "HbyA" || s == "mom_diag" || s == "mom_src"))
             return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is overwritten by the turbulence transport solve in this case (kEqn / kEpsilon reuse the momentum matrix's storage)", s.c_str());
         *ptr = e.p + (size_t)e.comp * g.c0;          // skip the ghost planes below the owned range (comp = 0: face array)

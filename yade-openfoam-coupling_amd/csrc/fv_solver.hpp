@@ -39,6 +39,31 @@ struct MgLev {
     const double* bptr = nullptr;
 };
 
+// Fluid temperature and particle-fluid heat exchange (fy_thermal_desc; fv_thermal.cpp).  Off: nothing allocated, nothing launched.  Three phases in Solver::step():
+//   heat_coefficients()  after setParticleAction: Sp / Su cleared, then per batch hA and the scatter (k_heat_coeff_*), from the stencils and cell records the force pass used
+//   solve_temperature()  after the last corrector and turbulence_correct(): k_assemble_scalar into the momentum matrix's storage, solve_vec3, T
+//   heat_fluxes()        per batch q = hA (sum w T - Tp) with the new T (k_heat_flux_*)
+struct Thermal {
+    bool on = false;
+    fy_thermal_desc d{};
+    ScalarEqn eq{};
+    HeatParams hp{};
+    DevBuf<double> T, Sp, Su;            // storage cells; Sp [W/K], Su [W]: what the last step's particles scattered
+    DevBuf<double> red;                  // block partials + result of the device-side sum of q (thermal_stats)
+    struct PerBatch {
+        DevBuf<double> hA, Tp, q;        // wire order
+        int64_t n = 0;                   // particles hA / q were formed for (the last step's count)
+        bool has_tp = false;             // Tp holds the caller's temperatures for tp_n particles; otherwise d.particle_temperature
+        int64_t tp_n = 0;
+    };
+    std::vector<std::unique_ptr<PerBatch> > pb;
+    KernelClock clk_coeff, clk_flux, clk_asm;      // "heat_coeff", "heat_flux", "T_assemble" of fy_solver_get_kernel_timing
+    int iters = 0;
+    double res0 = 0.0;
+    PerBatch& batch(size_t bi) { while (pb.size() <= bi) pb.emplace_back(new PerBatch()); return *pb[bi]; }
+    ~Thermal() { clk_coeff.destroy(); clk_flux.destroy(); clk_asm.destroy(); }
+};
+
 struct Solver {
     fy_case_desc cs{};
     std::vector<double> h_host[3];       // graded block: cell sizes per axis (host copy) and their device arrays (FvGeo::h)
@@ -215,7 +240,7 @@ struct Solver {
 
     // ---- momentum predictor: Jacobi sweeps with lduMatrix-style L1 residual control (stand-in for smoothSolver)
     int solve_momentum(int* iters) { return solve_vec3(U, bmom.p, cs.u_tol, cs.u_rel_tol, cs.u_max_iter, iters, true); }
-    int solve_vec3(DevBuf<double>& X, const double* rhs, double tol, double rel_tol, int max_iter, int* iters, bool momentum = false);
+    int solve_vec3(DevBuf<double>& X, const double* rhs, double tol, double rel_tol, int max_iter, int* iters, bool momentum = false, double* res0_out = nullptr);
 
     // ---- pressure solver (fv_pressure.cpp): multigrid V(2,2) with Chebyshev-weighted Jacobi pairs as the PCG preconditioner
     int smooth(size_t l, MgLev& L, double w, bool with_dot = false);
@@ -283,6 +308,14 @@ struct Solver {
     FieldAverage avg;
     const double* avg_source(const std::string& name, int* comp) const;      // the field's owned cells as they lie NOW (the buffers trade places), or nullptr
     int set_field_average(const fy_average_desc* d);
+    Thermal th;
+    int thermal_create(const fy_case_desc* c);          // validation + allocation, from create()
+    int heat_coefficients();
+    int solve_temperature();
+    int heat_fluxes();
+    int set_particle_temperatures(int batch, const double* tp, bool on_device);
+    int get_particle_heat(int batch, double* q);
+    int thermal_stats(int32_t* iterations, double* initial_residual, double* heat_to_particles_W);
     // field lookup; cell fields are returned/accepted as the OWNED part only (ghost planes are an implementation detail)
     int field(const char* name, double** ptr, size_t* count);
 };

@@ -141,6 +141,10 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
             return FY_OK;
         }
     }
+    if (name && (std::strcmp(name, "T") == 0 || std::strcmp(name, "heatSp") == 0 || std::strcmp(name, "heatSu") == 0)) {      // the temperature equation's fields: nothing of the flow depends on them
+        FY_HIP(hipStreamSynchronize(s->s.stream));
+        return FY_OK;
+    }
     s->s.carry_valid = false;                 // whatever was written, the carried Courant sums may no longer describe phi
     s->s.p_sum_valid = false; s->s.p_ghosts_fresh = false;
     if (std::string(name) == "U") {           // createPhi (collective when there are several slabs)
@@ -161,6 +165,14 @@ int fy_solver_destroy(fy_solver* s) { delete s; return FY_OK; }
 int fy_solver_set_field_average(fy_solver* s, const fy_average_desc* d) { FY_S(s); return s->s.set_field_average(d); }
 int fy_solver_get_average_state(fy_solver* s, int item, int64_t* samples, double* time_averaged) { FY_S(s); return s->s.avg.get_state(item, samples, time_averaged); }
 int fy_solver_set_average_state(fy_solver* s, int item, int64_t samples, double time_averaged) { FY_S(s); return s->s.avg.set_state(item, samples, time_averaged); }
+
+int fy_solver_set_particle_temperatures_host(fy_solver* s, int batch, const double* Tp) { FY_S(s); return s->s.set_particle_temperatures(batch, Tp, false); }
+int fy_solver_set_particle_temperatures_device(fy_solver* s, int batch, const double* d_Tp) { FY_S(s); return s->s.set_particle_temperatures(batch, d_Tp, true); }
+int fy_solver_get_particle_heat_host(fy_solver* s, int batch, double* q) { FY_S(s); return s->s.get_particle_heat(batch, q); }
+int fy_solver_get_thermal_stats(fy_solver* s, int32_t* iterations, double* initial_residual, double* heat_to_particles_W) {
+    FY_S(s);
+    return s->s.thermal_stats(iterations, initial_residual, heat_to_particles_W);
+}
 
 int fy_solver_apply_p_matrix_host(fy_solver* s, const double* x, double* y) {
     FY_S(s);
@@ -230,6 +242,7 @@ int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     FY_S(s);
     for (auto& k : s->s.kc) { k.reset(); k.on = on != 0; }
     s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
+    for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
     return FY_OK;
 }
 
@@ -251,6 +264,11 @@ int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_
     FY_S(s);
     const std::string k = kernel ? kernel : "";
     if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }
+    if ((k == "heat_coeff" || k == "heat_flux" || k == "T_assemble") && total_ms && launches) {
+        const fy::KernelClock& c = k == "heat_coeff" ? s->s.th.clk_coeff : k == "heat_flux" ? s->s.th.clk_flux : s->s.th.clk_asm;
+        *total_ms = c.total_ms; *launches = c.launches;
+        return FY_OK;
+    }
     int idx = k == "mg_smooth_l0" ? fy::Solver::KC_MG_SMOOTH0 : k == "p_apply_dot" ? fy::Solver::KC_P_APPLY_DOT : k == "mom_pass" ? fy::Solver::KC_MOM_PASS : -1;
     if (idx < 0 || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s'", k.c_str());
     *total_ms = s->s.kc[idx].total_ms; *launches = s->s.kc[idx].launches;

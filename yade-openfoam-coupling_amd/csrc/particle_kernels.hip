@@ -774,6 +774,7 @@ __global__ __launch_bounds__(1024) void k_tile_caps(TileBuckets s0, TileBuckets 
 constexpr int kTileMap = 128;
 struct TileMapLds { uint32_t tile[kTileMap], cnt[kTileMap], base[kTileMap]; };
 
+// (flush_table2, further down, repeats this logic for two-sum entries: a fix here belongs there too)
 template <int NSLOTS, int NTHREADS>
 __device__ __forceinline__ void flush_table(const uint32_t* keys, const double* vals, TileMapLds& m, const TileBuckets& tb, double* __restrict__ dst0,
                                             double* __restrict__ dst3, unsigned char* __restrict__ touched) {
@@ -1693,6 +1694,205 @@ __global__ __launch_bounds__(256) void k_set_source_zero(int32_t n_cells, int ga
     }
 }
 
+// ------------------------------------------------------------------------------------------------ particle-fluid heat exchange (fy_thermal_desc)
+// Not in the reference.  Pass A (k_heat_coeff_*): per particle the Nusselt number from the stencil the force pass used -- eps = sum w alpha_c and u_f = sum w U_c from
+// the SAME cell records, Re = small + |u_f - v_p| d / nu --, hA = Nu kappa pi d kept per particle (wire order), and the scatter Sp_c += w hA, Su_c += w hA Tp.
+// Pass B (k_heat_flux_*), after the fluid's T equation was solved with Sp implicit: q = hA (sum w T_c - Tp).  With sum_c w = 1 the particles receive exactly what the
+// cells lose.  The scatter has the force pass's (workgroup, cell) pattern -- same workgroup size, same table -- so it goes through the same LDS table and, where the
+// momentum back-scatter's bucket capacities are at hand, through the tile buckets (two of an entry's four value slots); what finds no room goes out as global atomics.
+__device__ __forceinline__ double nusselt(const HeatParams& hp, double eps, double Re) {
+    if (hp.law == FY_NUSSELT_GUNN) {
+        const double Res = eps * Re;
+        return (7.0 - 10.0 * eps + 5.0 * (eps * eps)) * (1.0 + 0.7 * pow(Res, 0.2) * hp.pr13) + (1.33 - 2.4 * eps + 1.2 * (eps * eps)) * pow(Res, 0.7) * hp.pr13;
+    }
+    return 2.0 + 0.6 * sqrt(Re) * hp.pr13;
+}
+
+// flush_table for a table whose entries carry two sums (component 0 -> dst0, component 1 -> dst1).  A COPY of flush_table's map / claim / store logic (that function
+// serves the shipped scatters and is left as it is): a fix to either belongs in both
+template <int NSLOTS, int NTHREADS>
+__device__ __forceinline__ void flush_table2(const uint32_t* keys, const double* vals, TileMapLds& m, const TileBuckets& tb, double* __restrict__ dst0,
+                                             double* __restrict__ dst1) {
+    static_assert(NSLOTS % NTHREADS == 0, "table slots per thread");
+    constexpr int R = NSLOTS / NTHREADS;
+    uint32_t pr[R];                                         // map slot << 16 | rank; 0xffffffff: empty table slot; 0xfffffffe: no room in the map
+#pragma unroll
+    for (int r = 0; r < R; ++r) pr[r] = keys[threadIdx.x + r * NTHREADS] == kAggEmpty ? 0xffffffffu : 0xfffffffeu;
+    if (tb.cell) {                                          // (uniform)
+        for (int q = threadIdx.x; q < kTileMap; q += NTHREADS) { m.tile[q] = kAggEmpty; m.cnt[q] = 0; }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (pr[r] == 0xffffffffu) continue;
+            uint32_t tile, local;
+            tile_of(tb.tg, keys[threadIdx.x + r * NTHREADS], &tile, &local);
+            uint32_t h = (tile * 2654435761u) >> 25;        // 7 bits
+#pragma unroll 1
+            for (int probe = 0; probe < kTileMap; ++probe) {
+                const uint32_t old = atomicCAS(&m.tile[h], kAggEmpty, tile);
+                if (old == kAggEmpty || old == tile) { pr[r] = (h << 16) | atomicAdd(&m.cnt[h], 1u); break; }
+                h = (h + 1) & (kTileMap - 1);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < kTileMap && m.tile[threadIdx.x] != kAggEmpty)
+            m.base[threadIdx.x] = atomicAdd(&tb.fill[m.tile[threadIdx.x]], m.cnt[threadIdx.x]);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (pr[r] == 0xffffffffu) continue;
+        const int q = threadIdx.x + r * NTHREADS;
+        const uint32_t c = keys[q];
+        const double v0 = vals[agg_at<NSLOTS>(q, 0)], v1 = vals[agg_at<NSLOTS>(q, 1)];
+        bool placed = false;
+        if (pr[r] != 0xfffffffeu) {
+            const uint32_t slot = pr[r] >> 16, rank = pr[r] & 0xffffu;
+            const uint32_t tile = m.tile[slot], pos = m.base[slot] + rank;
+            if (pos < tb.cap[tile]) {
+                uint32_t t2, local;
+                tile_of(tb.tg, c, &t2, &local);
+                const size_t at = (size_t)tb.off[tile] + pos;
+                tb.cell[at] = local;
+                *reinterpret_cast<double2*>(tb.val + 4 * at) = make_double2(v0, v1);
+                placed = true;
+            }
+        }
+        if (!placed) {
+            atomic_add_f64(&dst0[c], v0);
+            atomic_add_f64(&dst1[c], v1);
+        }
+    }
+}
+
+// one workgroup per tile, the tile's only writer: the bucket's two sums per entry into Sp / Su; the tile's demand counter goes back to zero (the buckets are the
+// momentum back-scatter's, which counts its own demand from zero in the next step)
+__global__ __launch_bounds__(256) void k_heat_tile_reduce(TileBuckets tb, double* __restrict__ Sp, double* __restrict__ Su) {
+    __shared__ double acc[kTileCells * 2];
+    const uint32_t tile = blockIdx.x;
+    uint32_t cnt = tb.fill[tile];
+    const uint32_t cap = tb.cap[tile];
+    if (cnt > cap) cnt = cap;
+    __syncthreads();                                        // (every thread has read the counter)
+    if (threadIdx.x == 0) tb.fill[tile] = 0;
+    if (cnt == 0) return;
+    for (int q = threadIdx.x; q < kTileCells * 2; q += 256) acc[q] = 0.0;
+    __syncthreads();
+    const size_t off = tb.off[tile];
+    for (uint32_t j = threadIdx.x; j < cnt; j += 256) {
+        const uint32_t l = tb.cell[off + j];
+        const double2 v = *reinterpret_cast<const double2*>(tb.val + 4 * (off + j));
+        lds_add_f64(&acc[agg_at<kTileCells>(l, 0)], v.x); lds_add_f64(&acc[agg_at<kTileCells>(l, 1)], v.y);
+    }
+    __syncthreads();
+    const TileGrid& tg = tb.tg;
+    const int ti = (int)(tile % (uint32_t)tg.ntx), tj = (int)((tile / (uint32_t)tg.ntx) % (uint32_t)tg.nty), tk = (int)(tile / (uint32_t)(tg.ntx * tg.nty));
+    for (int l = threadIdx.x; l < kTileCells; l += 256) {
+        const int i = ti * 8 + (l & 7), j = tj * 8 + ((l >> 3) & 7), k = tk * 8 + (l >> 6);
+        if (i >= tg.nx || j >= tg.ny || k >= tg.nzs) continue;
+        const double a0 = acc[agg_at<kTileCells>(l, 0)], a1 = acc[agg_at<kTileCells>(l, 1)];
+        if (a0 == 0.0 && a1 == 0.0) continue;
+        const size_t c = (size_t)i + (size_t)tg.nx * ((size_t)j + (size_t)tg.ny * (size_t)k);
+        Sp[c] += a0; Su[c] += a1;
+    }
+}
+
+__global__ __launch_bounds__(kForceThreads) void k_heat_coeff_gaussian(ParticleSoA p, int64_t n, HeatParams hp, CellWindow cw, const double* __restrict__ R,
+                                                                       const double* __restrict__ Tp, double* __restrict__ hA_out, double* __restrict__ Sp,
+                                                                       double* __restrict__ Su, TileBuckets tb) {
+    constexpr int kSlots = 1 << kForceLog2;
+    __shared__ uint32_t keys[kSlots];
+    __shared__ double vals[kSlots * 2];
+    __shared__ TileMapLds tmap;
+    for (int q = threadIdx.x; q < kSlots; q += kForceThreads) { keys[q] = kAggEmpty; vals[q] = 0.0; vals[q + kSlots] = 0.0; }
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * kForceThreads + threadIdx.x;
+    if (i < n) {
+        const int chain = p.chain_len[i];
+        const int k = chain < kMaxK ? chain : kMaxK;
+        const int first = chain - k;                          // the k newest entries, oldest first: the force pass's order
+        const int32_t orig = p.orig[i];
+        if (k == 0) {
+            hA_out[orig] = 0.0;                               // nobody located it: no deposit, q = 0
+        } else {
+            double eps = 0.0, ux = 0.0, uy = 0.0, uz = 0.0;
+            for (int t = 0; t < k; ++t) {
+                const size_t slot = (size_t)((first + t) & (kMaxK - 1)) * p.cap + (size_t)i;
+                const int64_t cl = (int64_t)p.ids[slot] - cw.base;
+                if (cl < 0 || cl >= cw.n_field) continue;
+                const double w = p.w[slot];
+                const double2* r = reinterpret_cast<const double2*>(R + kRecDoubles * (size_t)cl);
+                const double2 r0 = r[0], r1 = r[1];
+                ux += (r0.x * w); uy += (r0.y * w); uz += (r1.x * w);
+                eps += (r1.y * w);
+            }
+            const double dia = 2 * p.rad[i];
+            const double rx = ux - p.vx[i], ry = uy - p.vy[i], rz = uz - p.vz[i];
+            const double Re = hp.small + ((sqrt(rx * rx + ry * ry + rz * rz) * dia) / hp.nu);
+            const double hA = ((nusselt(hp, eps, Re) * hp.kappa) * M_PI) * dia;
+            const double tp = Tp ? Tp[orig] : hp.tp_uniform;
+            hA_out[orig] = hA;
+            for (int t = 0; t < k; ++t) {
+                const size_t slot = (size_t)((first + t) & (kMaxK - 1)) * p.cap + (size_t)i;
+                const int64_t cl = (int64_t)p.ids[slot] - cw.base;
+                if (cl < 0 || cl >= cw.n_field) continue;
+                const int32_t c = (int32_t)cl;
+                const double c0 = p.w[slot] * hA, c1 = c0 * tp;
+                const int h = agg_slot<kForceLog2>(keys, (uint32_t)c);
+                if (h >= 0) { lds_add_f64(&vals[agg_at<kSlots>(h, 0)], c0); lds_add_f64(&vals[agg_at<kSlots>(h, 1)], c1); }
+                else { atomic_add_f64(&Sp[c], c0); atomic_add_f64(&Su[c], c1); }
+            }
+        }
+    }
+    __syncthreads();
+    flush_table2<kSlots, kForceThreads>(keys, vals, tmap, tb, Sp, Su);
+}
+
+__global__ __launch_bounds__(256) void k_heat_flux_gaussian(ParticleSoA p, int64_t n, CellWindow cw, const double* __restrict__ T, double tp_uniform,
+                                                            const double* __restrict__ Tp, const double* __restrict__ hA, double* __restrict__ q_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int chain = p.chain_len[i];
+    const int k = chain < kMaxK ? chain : kMaxK;
+    const int first = chain - k;
+    const int32_t orig = p.orig[i];
+    double tf = 0.0;
+    for (int t = 0; t < k; ++t) {
+        const size_t slot = (size_t)((first + t) & (kMaxK - 1)) * p.cap + (size_t)i;
+        const int64_t cl = (int64_t)p.ids[slot] - cw.base;
+        if (cl < 0 || cl >= cw.n_field) continue;
+        tf += (T[cl] * p.w[slot]);
+    }
+    q_out[orig] = k == 0 ? 0.0 : hA[orig] * (tf - (Tp ? Tp[orig] : tp_uniform));
+}
+
+// point-force mode: the containing cell (k_point_force's incell, -1: not found), w = 1, eps = 1, the cell's U
+__global__ __launch_bounds__(256) void k_heat_coeff_point(const double* __restrict__ rec, int64_t n, const int32_t* __restrict__ incell, HeatParams hp, CellWindow cw,
+                                                          const double* __restrict__ U, const double* __restrict__ Tp, double* __restrict__ hA_out,
+                                                          double* __restrict__ Sp, double* __restrict__ Su) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t cl = incell[i] < 0 ? -1 : (int64_t)incell[i] - cw.base;
+    if (cl < 0 || cl >= cw.n_field) { hA_out[i] = 0.0; return; }
+    const double* r = rec + 10 * i;
+    const double* u = U + 3 * (size_t)cl;
+    const double dia = 2 * r[9];
+    const double rx = u[0] - r[3], ry = u[1] - r[4], rz = u[2] - r[5];
+    const double Re = hp.small + ((sqrt(rx * rx + ry * ry + rz * rz) * dia) / hp.nu);
+    const double hA = ((nusselt(hp, 1.0, Re) * hp.kappa) * M_PI) * dia;
+    hA_out[i] = hA;
+    atomic_add_f64(&Sp[cl], hA);
+    atomic_add_f64(&Su[cl], hA * (Tp ? Tp[i] : hp.tp_uniform));
+}
+
+__global__ __launch_bounds__(256) void k_heat_flux_point(int64_t n, const int32_t* __restrict__ incell, CellWindow cw, const double* __restrict__ T, double tp_uniform,
+                                                         const double* __restrict__ Tp, const double* __restrict__ hA, double* __restrict__ q_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t cl = incell[i] < 0 ? -1 : (int64_t)incell[i] - cw.base;
+    q_out[i] = (cl < 0 || cl >= cw.n_field) ? 0.0 : hA[i] * (T[cl] - (Tp ? Tp[i] : tp_uniform));
+}
+
 }  // namespace
 
 int launch_bin_count(hipStream_t s, const double* rec, int64_t n, BinGrid g, uint32_t* key, uint32_t* rank, uint32_t* hist) {
@@ -2013,6 +2213,40 @@ int launch_fill_f64(hipStream_t s, double* p, size_t n, double v) {
 int launch_set_source_zero(hipStream_t s, int32_t n_cells, int gaussian, double* uSourceDrag, double* alpha, double* uSource,
                            double* uParticle) {
     hipLaunchKernelGGL(k_set_source_zero, dim3(div_up(n_cells, 256)), dim3(256), 0, s, n_cells, gaussian, uSourceDrag, alpha, uSource, uParticle);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_heat_coeff_gaussian(hipStream_t s, ParticleSoA p, int64_t n, HeatParams hp, CellWindow cw, const double* R, const double* Tp, double* hA, double* Sp, double* Su,
+                               TileBuckets tb) {
+    if (n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_heat_coeff_gaussian, dim3(div_up(n, kForceThreads)), dim3(kForceThreads), 0, s, p, n, hp, cw, R, Tp, hA, Sp, Su, tb);
+    FY_LAUNCH_CHECK();
+    if (tb.cell) {                           // (the solver always hands buckets over; without them the flush above went out as atomics)
+        hipLaunchKernelGGL(k_heat_tile_reduce, dim3((unsigned)tb.tg.n_tiles()), dim3(256), 0, s, tb, Sp, Su);
+        FY_LAUNCH_CHECK();
+    }
+    return FY_OK;
+}
+
+int launch_heat_flux_gaussian(hipStream_t s, ParticleSoA p, int64_t n, CellWindow cw, const double* T, double tp_uniform, const double* Tp, const double* hA, double* q) {
+    if (n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_heat_flux_gaussian, dim3(div_up(n, 256)), dim3(256), 0, s, p, n, cw, T, tp_uniform, Tp, hA, q);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_heat_coeff_point(hipStream_t s, const double* rec, int64_t n, const int32_t* incell, HeatParams hp, CellWindow cw, const double* U, const double* Tp, double* hA,
+                            double* Sp, double* Su) {
+    if (n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_heat_coeff_point, dim3(div_up(n, 256)), dim3(256), 0, s, rec, n, incell, hp, cw, U, Tp, hA, Sp, Su);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_heat_flux_point(hipStream_t s, int64_t n, const int32_t* incell, CellWindow cw, const double* T, double tp_uniform, const double* Tp, const double* hA, double* q) {
+    if (n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_heat_flux_point, dim3(div_up(n, 256)), dim3(256), 0, s, n, incell, cw, T, tp_uniform, Tp, hA, q);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }
