@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 18
+#define FY_ABI_VERSION 19
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -696,6 +696,11 @@ int fy_ldu_solver_write_field_host(fy_ldu_solver*, const char* name, const doubl
 int fy_ldu_solver_apply(fy_ldu_solver*, const char* op, const double* in, double* out);
 /* the multigrid hierarchy of FY_PSOLVER_PCG_MG: cells and matrix slots (neighbours per row, padded) per level, finest first; n_levels = 0 without one */
 int fy_ldu_solver_mg_levels(fy_ldu_solver*, int cap, int32_t* cells, int32_t* slots, int* n_levels);
+/* one array of one level of that hierarchy, as doubles, copied from the device on the solver's stream (a diagnostic: nothing on the step's path reads it):
+ * "diag" [cells] (level 0: the solver's p_diag), "coef" and "nbr" [slots * cells] slot-major (padding: the cell itself with coefficient 0, after the row's
+ * entries), "agg" [cells]: this level's cell -> the next level's (count 0 on the last level), "inv" [cells * cells]: the last level's dense inverse (count 0
+ * elsewhere).  out = NULL: only *count is set.  "diag", "coef", "inv" are those of the last pressure assembly (step first) */
+int fy_ldu_solver_mg_level_read(fy_ldu_solver*, int level, const char* what, int64_t cap, double* out, int64_t* count);
 int fy_ldu_solver_destroy(fy_ldu_solver*);
 
 /* An OpenFOAM case directory whose constant/polyMesh is ANY mesh of wall / patch boundaries (ASCII), for icoFoamYade or (laminar, fixed time step)

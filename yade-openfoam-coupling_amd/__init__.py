@@ -1415,6 +1415,21 @@ class LduSolver(_Averages):
         _check(L.fy_ldu_solver_mg_levels(self._h, 32, _i(cells), _i(slots), C.byref(n)))
         return [(int(cells[q]), int(slots[q])) for q in range(n.value)]
 
+    def mg_level(self, level, what):
+        """one array of one level of the multigrid hierarchy (fy_ldu_solver_mg_level_read): "diag", "coef" [slots, cells], "inv" [cells, cells] as float64;
+        "nbr" [slots, cells], "agg" as int64"""
+        L = lib()
+        L.fy_ldu_solver_mg_level_read.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
+        cnt = C.c_int64(0)
+        _check(L.fy_ldu_solver_mg_level_read(self._h, int(level), what.encode(), 0, None, C.byref(cnt)))
+        out = np.zeros(cnt.value)
+        if cnt.value:
+            _check(L.fy_ldu_solver_mg_level_read(self._h, int(level), what.encode(), cnt.value, _d(out), C.byref(cnt)))
+        if what in ("nbr", "agg"):
+            out = out.astype(np.int64)
+        cells = self.mg_levels()[level][0]
+        return out.reshape(-1, cells) if what in ("coef", "nbr", "inv") and out.size else out
+
     def apply(self, op, x):
         """"p_matrix": A x; "p_precondition": M^-1 x -- the pressure equation's operators as the last step left them"""
         L = lib()

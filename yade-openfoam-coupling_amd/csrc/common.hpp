@@ -16,7 +16,7 @@
 namespace fy {
 
 // Run-time switches: environment variables, read here and nowhere else, when an object is created.  None changes a
-// result.  Deployment options and test aids only -- an A/B timing experiment is a build variant (tools/build_variant.sh), never a shipped switch.
+// result (amg_passes: the preconditioner, so the path to the converged solution).  Deployment options and test aids only -- an A/B timing experiment is a build variant (tools/build_variant.sh), never a shipped switch.
 struct Options {
     // deployment
     std::string tree_cache_dir;  // FOAMYADE_TREE_CACHE_DIR      ranks of one node share the k-d build through this directory ("" = off)
@@ -33,6 +33,7 @@ struct Options {
     bool locate_wide;            // FOAMYADE_LOCATE_WIDE=1       explicit tree: the 16-byte stack entries of 2^25 cells and more on any tree
     bool no_deep_vcycle;         // FOAMYADE_NO_DEEP_VCYCLE=1    slab multigrid: one exchange per sweep instead of one per level and cycle
     long long mg_replicate_below; // FOAMYADE_MG_REPLICATE_BELOW=n  slab multigrid: levels of <= n global cells are replicated (0, unset: kMgReplicateBelow)
+    int amg_passes;              // FOAMYADE_AMG_PASSES=1..3     general-mesh multigrid: pairwise matching passes per level (unset: 3), so that a small case carries many levels
     bool localcomm_stream;       // FOAMYADE_LOCALCOMM_STREAM=1  in-process slab groups: collectives as event waits on the ranks' streams
     bool no_fused_corrector;     // FOAMYADE_NO_FUSED_CORRECTOR=1  the corrector as five sweeps instead of the two fused ones
     bool faces_from_arrays;      // FOAMYADE_FACES_FROM_ARRAYS=1   the fused sweeps stream rAUf / alphacf from their face arrays instead of re-forming them

@@ -45,6 +45,7 @@ Options options() {
     q.locate_wide = num("FOAMYADE_LOCATE_WIDE", 0) != 0;
     q.no_deep_vcycle = on("FOAMYADE_NO_DEEP_VCYCLE");
     q.mg_replicate_below = std::max(0LL, num("FOAMYADE_MG_REPLICATE_BELOW", 0));
+    q.amg_passes = (int)std::min(3LL, std::max(1LL, num("FOAMYADE_AMG_PASSES", 3)));
     const char* ls = getenv("FOAMYADE_LOCALCOMM_STREAM");
     q.localcomm_stream = ls != nullptr && ls[0] == '1';
     q.no_fused_corrector = on("FOAMYADE_NO_FUSED_CORRECTOR");

@@ -242,6 +242,7 @@ struct LduSolver {
         }
         for (auto& t : tim) FY_TRY(t.init());
         if (cs.convection_scheme >= FY_CONVECTION_LIMITED_LINEAR) { FY_TRY(gradL.alloc_exact(3 * n)); FY_TRY(zero(gradL)); g.gradL = gradL.p; }
+        amg.passes = options().amg_passes;
         FY_TRY(amg.build(stream, nc, ni, hm.own.data(), hm.nei.data(), hm.cf_off, hm.cf_face, hm.magSf.data(), need_ref ? cs.p_ref_cell : -1, cs.p_solver == FY_PSOLVER_PCG_MG));
         // the coupling object on this mesh (icoFoamYade.C:54: point force): its tree over the cell centres, its fields the solver's device arrays
         {
@@ -702,6 +703,38 @@ int fy_ldu_solver_mg_levels(fy_ldu_solver* s, int cap, int32_t* cells, int32_t* 
     const fy::LduAmg& A = s->s.amg;
     *n_levels = A.has_hierarchy() ? (int)A.lev.size() : 0;
     for (int l = 0; l < *n_levels && l < cap; ++l) { if (cells) cells[l] = A.lev[(size_t)l]->n; if (slots) slots[l] = A.lev[(size_t)l]->W; }
+    return FY_OK;
+}
+int fy_ldu_solver_mg_level_read(fy_ldu_solver* s, int level, const char* what, int64_t cap, double* out, int64_t* count) {
+    FY_LS(s);
+    if (!what || !count) return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_mg_level_read: null argument");
+    fy::LduSolver& S = s->s;
+    const fy::LduAmg& A = S.amg;
+    if (!A.has_hierarchy() || level < 0 || (size_t)level >= A.lev.size()) return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_mg_level_read: no level %d (the hierarchy has %d)", level, A.has_hierarchy() ? (int)A.lev.size() : 0);
+    const fy::AmgLevel& L = *A.lev[(size_t)level];
+    const bool last = (size_t)level + 1 == A.lev.size();
+    const std::string w = what;
+    const double* dp = nullptr; const int32_t* ip = nullptr; size_t n = 0;
+    if (w == "diag") { dp = level == 0 ? S.pdiag.p : L.diag.p; n = (size_t)L.n; }
+    else if (w == "coef") { dp = L.coef.p; n = (size_t)L.W * L.n; }
+    else if (w == "inv") { dp = A.coarse_inv.p; n = last ? (size_t)L.n * L.n : 0; }
+    else if (w == "nbr") { ip = L.nbr.p; n = (size_t)L.W * L.n; }
+    else if (w == "agg") { ip = L.agg.p; n = last ? 0 : (size_t)L.n; }
+    else return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_mg_level_read: unknown array '%s' (diag, coef, nbr, agg, inv)", what);
+    *count = (int64_t)n;
+    if (!out || n == 0) return FY_OK;
+    if (cap < (int64_t)n) return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_mg_level_read: '%s' of level %d holds %lld values, the buffer %lld", what, level, (long long)n, (long long)cap);
+    if (dp && !A.diag0_) return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_mg_level_read: no pressure matrix yet (step first)");
+    FY_HIP(hipSetDevice(S.device));
+    if (dp) {
+        FY_HIP(hipMemcpyAsync(out, dp, n * sizeof(double), hipMemcpyDeviceToHost, S.stream));
+        FY_HIP(hipStreamSynchronize(S.stream));
+    } else {
+        std::vector<int32_t> h(n);
+        FY_HIP(hipMemcpyAsync(h.data(), ip, n * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
+        FY_HIP(hipStreamSynchronize(S.stream));
+        for (size_t q = 0; q < n; ++q) out[q] = (double)h[q];
+    }
     return FY_OK;
 }
 int fy_ldu_solver_destroy(fy_ldu_solver* s) { delete s; return FY_OK; }
