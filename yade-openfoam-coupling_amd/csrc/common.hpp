@@ -136,6 +136,50 @@ struct HostBuf {
     }
 };
 
+// Read-back of a folded reduction through MAPPED pinned host memory (both solvers' reduce_read): the fold (launch_reduce_finalize) writes its results straight into `host`
+// through the device alias `dev` and stores a sequence number behind each in one of eight arrival flags; the host spins on the flags -- in-order stream: everything
+// enqueued before the fold has completed by then -- so a read-back costs neither a device-to-host blit nor a stream synchronisation.  init() never fails: without mapped
+// memory (!mapped()) the owner folds on the device and copies, without flags (!flagged()) it synchronises the stream before it reads `host`.
+struct MappedReadback {
+    static constexpr int kFlags = 8;
+    double *host = nullptr, *dev = nullptr;    // `ndoubles` doubles: the first kFlags are wait()'s landing zone, the rest the owner's (the block solver's deferred slots)
+    unsigned long long *flag = nullptr, *flag_dev = nullptr;
+    unsigned long long seq = 0;                // what the latest fold stores into its flags
+    MappedReadback() = default;
+    MappedReadback(const MappedReadback&) = delete;
+    MappedReadback& operator=(const MappedReadback&) = delete;
+    ~MappedReadback() { if (host) (void)hipHostFree(host); if (flag) (void)hipHostFree(flag); }
+    void init(size_t ndoubles) {
+        if (hipHostMalloc((void**)&host, ndoubles * sizeof(double), hipHostMallocMapped) != hipSuccess) host = nullptr;
+        if (host && hipHostGetDevicePointer((void**)&dev, host, 0) != hipSuccess) { (void)hipHostFree(host); host = nullptr; }
+        if (!host) return;
+        if (hipHostMalloc((void**)&flag, kFlags * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) flag = nullptr;
+        if (flag && hipHostGetDevicePointer((void**)&flag_dev, flag, 0) != hipSuccess) { (void)hipHostFree(flag); flag = nullptr; }
+        if (flag) for (int q = 0; q < kFlags; ++q) flag[q] = 0;
+    }
+    bool mapped() const { return host != nullptr; }
+    bool flagged(int nslots) const { return flag && nslots <= kFlags; }
+    double* slot(int i) { return host + i; }                   // (and dev + i on the device)
+    // the fold was launched on `stream` with ++seq: wait for its `nslots` flags and take the results.  idle(): what the host does meanwhile, every 1024 spins
+    template <class Idle>
+    int wait(hipStream_t stream, int nslots, double* out, Idle&& idle) {
+        for (int q = 0; q < nslots; ++q) {
+            unsigned long spins = 0;
+            while (__atomic_load_n(&flag[q], __ATOMIC_ACQUIRE) != seq) {
+                if ((++spins & 0x3ffu) == 0) FY_TRY(idle());
+                if ((spins & 0xfffu) == 0) {                        // every 4096 polls: is the stream still alive?
+                    const hipError_t e = hipStreamQuery(stream);
+                    if (e == hipSuccess) { if (__atomic_load_n(&flag[q], __ATOMIC_ACQUIRE) == seq) break; return fail(FY_ERR_HIP, "reduction flag never arrived"); }
+                    if (e != hipErrorNotReady) return fail(FY_ERR_HIP, "stream failed while waiting for a reduction: %s", hipGetErrorString(e));
+                }
+            }
+            out[q] = host[q];
+        }
+        return FY_OK;
+    }
+    int wait(hipStream_t stream, int nslots, double* out) { return wait(stream, nslots, out, [] { return FY_OK; }); }
+};
+
 struct EventTimer {
     hipEvent_t a = nullptr, b = nullptr;
     bool armed = false;
@@ -215,6 +259,22 @@ struct KernelClock {
 };
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// setDeltaT.H [OF-6] (pimpleFoamYade.C:64): the next deltaT from the Courant number of the current flux at the old one
+inline double next_delta_t(double dt, double courant_max, double max_co, double max_delta_t) {
+    const double maxDeltaTFact = max_co / (courant_max + 1e-15);
+    const double deltaTFact = std::min(std::min(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
+    return std::min(deltaTFact * dt, max_delta_t);
+}
+
+// lduMatrix::solver's L1 residual control per component of a three-component Jacobi solve (both solve_vec3): h = {sum |b - A x| x 3, the normalisation sums x 3} of pass
+// `pass`; the first pass fixes the normalisation and the initial residuals.  Converged when every component is below tol, or below rel_tol times its initial residual
+inline bool vec3_converged(int pass, const double (&h)[6], double tol, double rel_tol, double (&norm)[3], double (&res0)[3]) {
+    if (pass == 0) for (int q = 0; q < 3; ++q) { norm[q] = h[3 + q] + 1e-20; res0[q] = h[q] / norm[q]; }
+    bool conv = true;
+    for (int q = 0; q < 3; ++q) { const double res = h[q] / norm[q]; conv = conv && (res < tol || (rel_tol > 0 && res < rel_tol * res0[q])); }
+    return conv;
+}
 
 // nutWallFunction::yPlusLam [OF-6 nutWallFunctionFvPatchScalarField.C]: ten fixed-point sweeps of y+ = ln(E y+) / kappa from 11 (both solvers' wall functions)
 inline double wall_yplus_lam(double kappa, double E) {

@@ -1,5 +1,6 @@
 // Device-side helpers that more than one kernel source needs (fv_kernels.hip in both its builds, fv_linalg_kernels.hip, ldu_kernels.hip,
 // ldu_amg.hip, particle_kernels.hip).  Everything here is inlined into its caller: including this header adds no symbol to an object.
+// Launch plumbing only (block order, reductions, the launch check); the physics that fv_kernels.hip (both builds) and ldu_kernels.hip share is in fv_closures.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -5,12 +5,14 @@
 // This source is compiled TWICE: as it stands (FY_FVK_GRADED 0: the uniform block of cubes, every kernel works with the constants dx, Af, V --
 // namespace fy) and through fv_kernels_graded.hip (FY_FVK_GRADED 1: a graded, rectilinear block with per-axis cell sizes -- namespace fy::gr).
 // Every geometric quantity goes through the geo_* functions below; in the uniform build they ARE the constants, in the expressions the
-// kernels were written and measured with.  What reads no geometry -- the pressure solver on the assembled PMat, the multigrid, the fold of the
+// kernels were written and measured with.  The closures that do not depend on the mesh at all -- limiters, turbulence sources, wall functions, bound --
+// are fv_closures.hpp's, shared with ldu_kernels.hip.  What reads no geometry -- the pressure solver on the assembled PMat, the multigrid, the fold of the
 // block partials -- is not here but in fv_linalg_kernels.hip, compiled once.
 #include "fv_kernels.hpp"
 
 #include "common.hpp"
 #include "device_util.hpp"
+#include "fv_closures.hpp"
 
 #ifndef FY_FVK_GRADED
 #define FY_FVK_GRADED 0
@@ -164,17 +166,13 @@ __device__ __forceinline__ double pbv(const FvGeo& g, const double* p, const CFa
 __device__ __forceinline__ double nut_boundary(const FvGeo& g, int patch, int c) {
     const int t = g.nut_bc[patch];
     if (t == 1 || ((t == 2 || t == 3) && !g.nut_wall_live)) return g.nut_val[patch];
-    if (t == 3) {                                       // calculated: the model's expression on the boundary values
+    if (t == 3) {                                       // calculated: correctNut()'s expression on the boundary values (fv_closures.hpp: nut_keqn, nut_kepsilon)
         const double kb = g.k_bc[patch] == 1 ? g.k_val[patch] : g.kturb[c];
-        if (g.turb_model == 2) return g.turb_ck * sqrt(kb) * geo_delta(g, g.turb_delta, c);
+        if (g.turb_model == 2) return nut_keqn(g.turb_ck, kb, geo_delta(g, g.turb_delta, c));
         const double eb = g.eps_bc[patch] == 1 ? g.eps_val[patch] : g.epsturb[c];
-        return g.turb_cmu * (kb * kb) / eb;
+        return nut_kepsilon(g.turb_cmu, kb, eb);
     }
-    if (t == 2) {
-        const double y = geo_ywall(g, patch >> 1, c);
-        const double yPlus = g.wf_cmu25 * y * sqrt(g.kturb[c]) / g.nu;
-        return yPlus > g.wf_yPlusLam ? g.nu * (yPlus * g.wf_kappa / log(g.wf_E * yPlus) - 1.0) : 0.0;
-    }
+    if (t == 2) return nutk_wall_nut(g.wf_cmu25, geo_ywall(g, patch >> 1, c), g.kturb[c], g.nu, g.wf_yPlusLam, g.wf_kappa, g.wf_E);
     return g.nut[c];
 }
 // Value held by the previous / next lane of the wave (undefined in lane 0 / 63): one DPP move per dword.  A wave's lanes are consecutive
@@ -683,9 +681,8 @@ __global__ __launch_bounds__(256) void k_div_G(FvGeo g, const double* __restrict
     for (int q = 0; q < 3; ++q) divG[3 * (size_t)c + q] = acc[q];
 }
 
-// continuousPhaseTurbulence->correct() (pimpleFoamYade.C:101-104) for LESModel Smagorinsky (DPMTurbulenceModels.C:73-74) [OF-6
-// Smagorinsky.C: k(gradU), correctNut()]: D = symm(grad U); a = Ce/delta; b = (2/3) tr(D); c = 2 Ck delta (dev(D) && D);
-// k = sqr((-b + sqrt(sqr(b) + 4 a c)) / (2 a)); nut = Ck delta sqrt(k).  grad U is the Gauss-linear gradient k_pre_coupling just wrote.
+// continuousPhaseTurbulence->correct() (pimpleFoamYade.C:101-104) for LESModel Smagorinsky (DPMTurbulenceModels.C:73-74; fv_closures.hpp: smagorinsky_nut).
+// grad U is the Gauss-linear gradient k_pre_coupling just wrote.
 __global__ __launch_bounds__(256) void k_smagorinsky_nut(FvGeo g, const double* __restrict__ vGrad, double ck, double ce, double delta, double* __restrict__ nut) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= g.Nc) return;
@@ -694,22 +691,11 @@ __global__ __launch_bounds__(256) void k_smagorinsky_nut(FvGeo g, const double* 
     double T[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) T[q] = vGrad[9 * (size_t)c + q];
-    const double Dxx = T[0], Dyy = T[4], Dzz = T[8];
-    const double Dxy = 0.5 * (T[1] + T[3]), Dxz = 0.5 * (T[2] + T[6]), Dyz = 0.5 * (T[5] + T[7]);
-    const double trD = Dxx + Dyy + Dzz;
-    const double a = ce / delta;
-    const double b = (2.0 / 3.0) * trD;
-    const double third = (1.0 / 3.0) * trD;
-    // dev(D) && D over the nine components of the symmetric tensors
-    const double dd = (Dxx - third) * Dxx + (Dyy - third) * Dyy + (Dzz - third) * Dzz + 2.0 * (Dxy * Dxy) + 2.0 * (Dxz * Dxz) + 2.0 * (Dyz * Dyz);
-    const double cc = 2.0 * ck * delta * dd;
-    const double r = (-b + sqrt(b * b + 4.0 * a * cc)) / (2.0 * a);
-    const double kk = r * r;
-    nut[c] = ck * delta * sqrt(kk);
+    nut[c] = smagorinsky_nut(T, ck, ce, delta);
 }
 
-// epsilonWallFunction [OF-6 epsilonWallFunctionFvPatchScalarField::calculate]: the value imposed on a cell with wall faces is the average over
-// them of Cmu^3/4 k^3/2 / (kappa y_w) (cornerWeights = 1 / number of wall faces); on the uniform block every y_w is dx / 2
+// epsilonWallFunction: the value imposed on a cell with wall faces is the average over them of the faces' terms (fv_closures.hpp: wall_epsilon_term); on the
+// uniform block every y_w is dx / 2
 __device__ __forceinline__ double wall_epsilon(const FvGeo& g, const TurbEqn& e, double kc, int c, int i, int j, int k) {
 #if FY_FVK_GRADED
     double sum = 0.0;
@@ -718,10 +704,10 @@ __device__ __forceinline__ double wall_epsilon(const FvGeo& g, const TurbEqn& e,
     for (int d = 0; d < 3; ++d)
 #pragma unroll
         for (int s = 0; s < 2; ++s)
-            if (e.wall[2 * d + s] && onb(g, d, s, i, j, k)) { sum += e.cmu75 * pow(kc, 1.5) / (e.kappa * geo_ywall(g, d, c)); ++W; }
+            if (e.wall[2 * d + s] && onb(g, d, s, i, j, k)) { sum += wall_epsilon_term(e.cmu75, kc, e.kappa, geo_ywall(g, d, c)); ++W; }
     return sum / (double)W;
 #else
-    return e.cmu75 * pow(kc, 1.5) / (e.kappa * geo_ywall(g, 0, c));
+    return wall_epsilon_term(e.cmu75, kc, e.kappa, geo_ywall(g, 0, c));
 #endif
 }
 
@@ -780,17 +766,7 @@ __global__ __launch_bounds__(256) void k_assemble_turb(FvGeo g, TurbEqn e, const
                 an[2 * d + s] = cN - gam;
             }
         }
-    // G = nut (gradU && dev(twoSymm(gradU)))
-    double T[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) T[q] = vGrad[9 * (size_t)c + q];
-    const double tr2 = 2.0 * (T[0] + T[4] + T[8]);              // tr(twoSymm(T))
-    double GG = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) GG += T[3 * a + b] * ((T[3 * a + b] + T[3 * b + a]) - (a == b ? (1.0 / 3.0) * tr2 : 0.0));
-    double G = nutc * GG;
+    double G = nutc * production_tensor(vGrad + 9 * (size_t)c);      // G = nut (gradU && dev(twoSymm(gradU)))
     // epsilonWallFunction: wall value of G, and (in the epsilon equation) the imposed cell value
     int Wc = 0;
     double Gw = 0.0;
@@ -804,26 +780,24 @@ __global__ __launch_bounds__(256) void k_assemble_turb(FvGeo g, TurbEqn e, const
                     double ub[3];
                     Ub(g, U, c, patch, ub);
                     const double ywall = geo_ywall(g, d, c);
+                    // snGrad U = (U_b - U_P) / y: the general mesh multiplies by deltaCoeffs
                     const double d0 = (ub[0] - U[3 * (size_t)c]) / ywall, d1 = (ub[1] - U[3 * (size_t)c + 1]) / ywall, d2 = (ub[2] - U[3 * (size_t)c + 2]) / ywall;
-                    const double magGradUw = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-                    Gw += (nut_boundary(g, patch, c) + nu) * magGradUw * e.cmu25 * sqrt(kf[c]) / (e.kappa * ywall);
+                    Gw += wall_G_term(nut_boundary(g, patch, c), nu, sqrt(d0 * d0 + d1 * d1 + d2 * d2), e.cmu25, kf[c], e.kappa, ywall);
                     ++Wc;
                 }
         if (Wc) G = Gw / (double)Wc;
     }
     const double divU = sumPhi * geo_rV(g, i, j, k);
-    double Su, c1, c2;
-    if (e.mode == 0) { Su = aP * G; c1 = (2.0 / 3.0) * aP * divU; c2 = e.ce * aP * sqrt(xc) / geo_delta(g, e.delta, c); }
-    else if (e.mode == 1) { const double kc = kf[c]; Su = e.c1 * aP * G * xc / kc; c1 = ((2.0 / 3.0) * e.c1 - e.c3) * aP * divU; c2 = e.c2 * aP * xc / kc; }
-    else { Su = aP * G; c1 = (2.0 / 3.0) * aP * divU; c2 = aP * ef[c] / xc; }
-    dg += V * (fmax(c1, 0.0) + c2);                             // fvm::SuSp (implicit where it stabilises) + fvm::Sp
-    src += V * Su - V * fmin(c1, 0.0) * xc;
+    // the sources by e.mode: 0 kEqn's k, 1 epsilon, 2 kEpsilon's k (fv_closures.hpp); each branch reads only its own fields -- ef is null without kEpsilon
+    TurbSource S;
+    if (e.mode == 0) S = keqn_k_source(aP, G, divU, e.ce, geo_delta(g, e.delta, c), xc);
+    else if (e.mode == 1) S = kepsilon_eps_source(aP, G, divU, e.c1, e.c2, e.c3, xc, kf[c]);
+    else S = kepsilon_k_source(aP, G, divU, ef[c], xc);
+    add_turb_source(S, V, xc, dg, src);                         // fvm::SuSp + fvm::Sp
     if (e.relax > 0) {                                          // fvMatrix::relax as in UcEqn
         double so = 0.0;
         for (int q = 0; q < 6; ++q) so += fabs(an[q]);
-        const double dn = fmax(fabs(dg), so) / e.relax;
-        src += (dn - dg) * xc;
-        dg = dn;
+        relax_scalar_row(e.relax, so, xc, dg, src);
     }
     double x0 = xc;
     if (e.mode == 1) {
@@ -859,8 +833,8 @@ __global__ __launch_bounds__(256) void k_assemble_turb(FvGeo g, TurbEqn e, const
     x3[3 * (size_t)c] = x0; x3[3 * (size_t)c + 1] = 0.0; x3[3 * (size_t)c + 2] = 0.0;
 }
 
-// bound(X, XMin) [OF-6 finiteVolume/cfdTools/general/bound/bound.C]: X = max(max(X, fvc::average(max(X, XMin)) pos0(-X)), XMin) -- the
-// identity where X >= XMin, so it is applied without the global min test OpenFOAM guards it with -- then correctNut (see launch_turb_finish)
+// bound(X, XMin) (fv_closures.hpp: bound_value) -- the identity where X >= XMin, so it is applied without the global min test OpenFOAM guards it
+// with -- then correctNut (see launch_turb_finish)
 __global__ __launch_bounds__(256) void k_turb_finish(FvGeo g, TurbEqn e, const double* __restrict__ x3, double* __restrict__ Xf, int nut_mode, double cmu,
                                                      const double* __restrict__ ef, double* __restrict__ nut) {
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -868,7 +842,7 @@ __global__ __launch_bounds__(256) void k_turb_finish(FvGeo g, TurbEqn e, const d
     int i, j, k; ijk_of(g, t, i, j, k);
     const int c = t + g.c0;
     const double xc = x3[3 * (size_t)c];
-    double xb = xc;
+    double avg = xc;
     if (!(xc > 0.0)) {                                          // pos0(-X) = 1: the face-area average of the bounded neighbourhood
         const double mP = fmax(xc, e.xmin);
         double av = 0.0;
@@ -895,15 +869,15 @@ __global__ __launch_bounds__(256) void k_turb_finish(FvGeo g, TurbEqn e, const d
 #endif
             }
 #if FY_FVK_GRADED
-        xb = fmax(xc, av / asum);
+        avg = av / asum;
 #else
-        xb = fmax(xc, av / 6.0);
+        avg = av / 6.0;                                         // (six equal faces)
 #endif
     }
-    xb = fmax(xb, e.xmin);
+    const double xb = bound_value(xc, avg, e.xmin);
     Xf[c] = xb;
-    if (nut_mode == 1) nut[c] = e.ck * sqrt(xb) * geo_delta(g, e.delta, c);
-    else if (nut_mode == 2) nut[c] = cmu * (xb * xb) / ef[c];
+    if (nut_mode == 1) nut[c] = nut_keqn(e.ck, xb, geo_delta(g, e.delta, c));
+    else if (nut_mode == 2) nut[c] = nut_kepsilon(cmu, xb, ef[c]);
 }
 
 // The fluid temperature equation (fy_thermal_desc; a capability the reference does not have -- DESIGN_FV.md "T equation"), next to the turbulence transport
@@ -976,10 +950,9 @@ __global__ __launch_bounds__(256) void k_scalar_finish(FvGeo g, const double* __
 
 
 // UEqn (icoFoamYade.C:79-85) / UcEqn + relax (UcEqn.H:3-12): diag, 6 neighbour coefficients, source (no pressure term), rAU = 1/A
-// ---- NVD / TVD limited convection schemes for div(phi,U) [OF-6 LimitedScheme<vector, Limiter<NVDTVD>, limitFuncs::magSqr>, NVDTVD.H]: one
-// limiter per face from the scalar lPhi = magSqr(U): r = 2 (d . grad(lPhi)_C) / (lPhi_N - lPhi_P) - 1, C the upwind cell of the face flux, grad
-// the Gauss-linear gradient (boundary value magSqr(U_b)); the weight of the OWNER's value is limiter * w_linear + (1 - limiter) * pos0(faceFlux)
-// [limitedSurfaceInterpolationScheme::weights], used implicitly in the matrix.
+// ---- NVD / TVD limited convection schemes for div(phi,U) (fv_closures.hpp: nvd_r, nvd_limiter): one limiter per face from the scalar lPhi = magSqr(U), C the
+// upwind cell of the face flux, grad the Gauss-linear gradient (boundary value magSqr(U_b)); the weight of the OWNER's value is limiter * w_linear +
+// (1 - limiter) * pos0(faceFlux), used implicitly in the matrix.
 __device__ __forceinline__ double magsqr3(const double* __restrict__ F, int c) {
     const double a = F[3 * (size_t)c], b = F[3 * (size_t)c + 1], e = F[3 * (size_t)c + 2];
     return (a * a + b * b) + e * e;
@@ -1001,28 +974,12 @@ __global__ __launch_bounds__(256) void k_grad_magsqr(FvGeo g, const double* __re
         gradL[3 * (size_t)c + d] = (fv[1] - fv[0]) * geo_rh(g, d, d == 0 ? i : d == 1 ? j : k);
     }
 }
-__device__ __forceinline__ double limiter_fn(int scheme, double twoByk, double r) {
-    switch (scheme) {
-        case 3: return fmax(fmin(twoByk * r, 1.0), 0.0);                                   // limitedLinear k: twoByk = 2 / max(k, small)
-        case 4: return (r + fabs(r)) / (1.0 + fabs(r));                                    // vanLeer
-        case 5: return fmax(fmin(fmin(2.0 * r, 0.5 * r + 0.5), 2.0), 0.0);                 // MUSCL
-        case 6: return fmax(fmin(fmin(r, 1.0), 2.0), 0.0);                                 // Minmod
-        case 7: return fmax(fmax(fmin(2.0 * r, 1.0), fmin(r, 2.0)), 0.0);                  // SuperBee
-        // QUICK (8) [OF-6 QUICK.H]: QLimiter = (phif - phiU) / (phiCD - phiU) with phif = (phiCD + phiU + (1 - w) d.grad(phi)_U) / 2, which is
-        // (3 + r) / 4 whatever the linear weight w; limited "between upwind and downwind" only -- max(min(., 2), 0) -- so NOT a TVD limiter: it stays
-        // positive down to r = -3 and has no 2 r bound (rounds 2 - 3 had min(2 r, .) here: another scheme under QUICK's name)
-        default: return fmax(fmin((3.0 + r) / 4.0, 2.0), 0.0);
-    }
-}
 // weight of the owner's (low cell's) value on the interior face between own and nei (axis d; qn = the neighbour's index along d); flux: owner -> neighbour
 __device__ __forceinline__ double limited_weight(const FvGeo& g, const double* __restrict__ U, const double* __restrict__ gradL, int d, int qn, int own,
                                                  int nei, double flux) {
     const double gradf = magsqr3(U, nei) - magsqr3(U, own);
     const double gradcf = (1.0 / geo_rdelta(g, d, qn)) * gradL[3 * (size_t)(flux > 0 ? own : nei) + d];
-    double r;
-    if (fabs(gradcf) >= 1000.0 * fabs(gradf)) r = 2.0 * 1000.0 * (gradcf >= 0 ? 1.0 : -1.0) * (gradf >= 0 ? 1.0 : -1.0) - 1.0;
-    else r = 2.0 * (gradcf / gradf) - 1.0;
-    const double lim = limiter_fn(g.upwind, g.lim_twoByk, r);
+    const double lim = nvd_limiter(g.upwind, g.lim_twoByk, nvd_r(gradcf, gradf));
 #if FY_FVK_GRADED
     const double wl = geo_wlow(g, d, qn);
 #else

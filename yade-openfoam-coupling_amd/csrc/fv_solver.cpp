@@ -202,17 +202,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     FY_TRY(partials.alloc_exact(8 * (size_t)red_blocks(Nc))); FY_TRY(red_out.alloc_exact(8)); FY_TRY(sc.alloc_exact(8)); FY_TRY(xbar3.alloc_exact(3));
     FY_TRY(zero(partials)); FY_TRY(zero(sc)); FY_TRY(zero(red_out));
     if (adjust_phi) { FY_TRY(adj_sums.alloc_exact(4)); FY_TRY(adj_err.alloc_exact(1)); FY_HIP(hipMemsetAsync(adj_err.p, 0, sizeof(int), stream)); }
-    if (hipHostMalloc((void**)&red_host, (kDeferBase + kDeferMax) * sizeof(double), hipHostMallocMapped) == hipSuccess) {
-        if (hipHostGetDevicePointer((void**)&red_host_dev, red_host, 0) != hipSuccess) { (void)hipHostFree(red_host); red_host = nullptr; }
-    } else {
-        red_host = nullptr;              // fall back to the copy path
-    }
-    if (red_host && hipHostMalloc((void**)&red_flag, 8 * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
-        for (int q = 0; q < 8; ++q) red_flag[q] = 0;
-        if (hipHostGetDevicePointer((void**)&red_flag_dev, red_flag, 0) != hipSuccess) { (void)hipHostFree(red_flag); red_flag = nullptr; }
-    } else {
-        red_flag = nullptr;
-    }
+    rb.init(kDeferBase + kDeferMax);
     FY_TRY(ops_courant.alloc_exact(2));
     FY_TRY(ops_diag.alloc_exact(4));
     { const int h4[4] = {0, 0, 1, 0}; FY_HIP(hipMemcpyAsync(ops_diag.p, h4, sizeof(h4), hipMemcpyHostToDevice, stream)); }
@@ -275,7 +265,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     // non-orthogonal correctors), the interface coefficient of a slab without deep ghost planes, the turbulence transport equations, the stand-alone
     // continuity-error sweep; otherwise the arrays are never filled
     face_arrays = !fused_corrector || !faces_from_cells || adjust_phi || cs.n_non_orth_correctors > 0 || (S > 1 && !mg_deep) ||
-                  c->turbulence_model != FY_TURBULENCE_LAMINAR || !fuse_diag || !red_host || (pimple && !cs.momentum_predictor);
+                  c->turbulence_model != FY_TURBULENCE_LAMINAR || !fuse_diag || !rb.mapped() || (pimple && !cs.momentum_predictor);
 
     // the coupling object shares the solver's device fields and stream (icoFoamYade.C:54, pimpleFoamYade.C:54); its tree spans
     // the GLOBAL block (the improvement chain depends on the whole tree), its cell arrays are this slab's storage
@@ -355,34 +345,20 @@ int Solver::set_field_average(const fy_average_desc* d) {
 // fold the block partials, all-reduce over the slabs, read back
 int Solver::reduce_read(int nslots, bool courant, double* h) {
     if (cpl) FY_TRY(cpl->c.poll_results());
-    if (comm->size == 1 && red_host) {
-        // single domain: the fold writes straight into mapped pinned host memory -- no device-to-host blit per read-back
-        if (red_flag && nslots <= 8) {
-            // spin on the flags the fold stores behind its results; everything enqueued before it has completed by then (in-order stream)
-            const unsigned long long seq = ++red_seq;
-            FY_TRY(launch_reduce_finalize(stream, partials.p, Nc, nslots, courant ? ops_courant.p : nullptr, red_host_dev, red_flag_dev, seq));
-            for (int q = 0; q < nslots; ++q) {
-                unsigned long spins = 0;
-                while (__atomic_load_n(&red_flag[q], __ATOMIC_ACQUIRE) != seq) {
-                    if ((++spins & 0x3ffu) == 0 && cpl) FY_TRY(cpl->c.poll_results());      // (answers that have landed meanwhile go out: Coupling::poll_results)
-                    if ((spins & 0xfffu) == 0) {                        // every 4096 polls: is the stream still alive?
-                        const hipError_t e = hipStreamQuery(stream);
-                        if (e == hipSuccess) { if (__atomic_load_n(&red_flag[q], __ATOMIC_ACQUIRE) == seq) break; return fail(FY_ERR_HIP, "reduction flag never arrived"); }
-                        if (e != hipErrorNotReady) return fail(FY_ERR_HIP, "stream failed while waiting for a reduction: %s", hipGetErrorString(e));
-                    }
-                }
-                h[q] = red_host[q];
-            }
-            return FY_OK;
+    if (comm->size == 1 && rb.mapped()) {
+        // single domain: the fold writes straight into mapped pinned host memory (MappedReadback) -- no device-to-host blit per read-back
+        if (rb.flagged(nslots)) {
+            FY_TRY(launch_reduce_finalize(stream, partials.p, Nc, nslots, courant ? ops_courant.p : nullptr, rb.dev, rb.flag_dev, ++rb.seq));
+            return rb.wait(stream, nslots, h, [this] { return cpl ? cpl->c.poll_results() : FY_OK; });      // (answers that have landed meanwhile go out: Coupling::poll_results)
         }
-        FY_TRY(launch_reduce_finalize(stream, partials.p, Nc, nslots, courant ? ops_courant.p : nullptr, red_host_dev));
+        FY_TRY(launch_reduce_finalize(stream, partials.p, Nc, nslots, courant ? ops_courant.p : nullptr, rb.dev));
         FY_HIP(hipStreamSynchronize(stream));
-        for (int q = 0; q < nslots; ++q) h[q] = red_host[q];
+        for (int q = 0; q < nslots; ++q) h[q] = rb.host[q];
         return FY_OK;
     }
     FY_TRY(launch_reduce_finalize(stream, partials.p, Nc, nslots, courant ? ops_courant.p : nullptr, red_out.p));
     FY_TRY(comm->allreduce_ops(stream, red_out.p, nslots, courant ? 1u : 0u));         // Courant pair: {max, sum} in one collective
-    double* land = (red_host && nslots <= 8) ? red_host : h;          // pinned landing zone: a pageable destination makes the copy a staged, blocking one
+    double* land = (rb.mapped() && nslots <= 8) ? rb.host : h;          // pinned landing zone: a pageable destination makes the copy a staged, blocking one
     FY_HIP(hipMemcpyAsync(land, red_out.p, nslots * sizeof(double), hipMemcpyDeviceToHost, stream));
     FY_HIP(hipStreamSynchronize(stream));
     if (land != h) for (int q = 0; q < nslots; ++q) h[q] = land[q];
@@ -390,11 +366,11 @@ int Solver::reduce_read(int nslots, bool courant, double* h) {
 }
 bool Solver::reduce_deferred(int nslots, bool courant, int* slot, int* rc, const int* ops) {      // ops: ops_diag.p (sum, sum, max, sum) or none
     *rc = FY_OK;
-    if (!red_host || n_deferred + nslots > kDeferMax) return false;
+    if (!rb.mapped() || n_deferred + nslots > kDeferMax) return false;
     *slot = kDeferBase + n_deferred;
     n_deferred += nslots;
     if (comm->size == 1) {
-        *rc = launch_reduce_finalize(stream, partials.p, Nc, nslots, ops ? ops : (courant ? ops_courant.p : nullptr), red_host_dev + *slot);
+        *rc = launch_reduce_finalize(stream, partials.p, Nc, nslots, ops ? ops : (courant ? ops_courant.p : nullptr), rb.dev + *slot);
         return true;
     }
     *rc = launch_reduce_finalize(stream, partials.p, Nc, nslots, ops ? ops : (courant ? ops_courant.p : nullptr), red_out.p);
@@ -402,7 +378,7 @@ bool Solver::reduce_deferred(int nslots, bool courant, int* slot, int* rc, const
         // one collective per group: the four diagnostics of k_U_correct<true> are {sum, sum, max, sum}, the Courant pair {max, sum}
         *rc = comm->allreduce_ops(stream, red_out.p, nslots, ops ? 4u : (courant ? 1u : 0u));
     }
-    if (*rc == FY_OK && hipMemcpyAsync(red_host + *slot, red_out.p, nslots * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess)
+    if (*rc == FY_OK && hipMemcpyAsync(rb.slot(*slot), red_out.p, nslots * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess)
         *rc = fail(FY_ERR_HIP, "deferred read-back failed");
     return true;
 }
@@ -426,7 +402,7 @@ int Solver::solve_vec3(DevBuf<double>& X, const double* rhs, double tol, double 
         FY_TRY(comm->allreduce(stream, xbar3.p, 3, false));
     }
     double* xc = X.p; double* xn = xscr.p;
-    double norm[3] = {1, 1, 1}, res0[3] = {0, 0, 0}, res[3];
+    double norm[3] = {1, 1, 1}, res0[3] = {0, 0, 0};
     int it = 0;
     for (;;) {
         // (the predictor's first pass reads the ghost planes the step's opening exchange left in U)
@@ -442,13 +418,7 @@ int Solver::solve_vec3(DevBuf<double>& X, const double* rhs, double tol, double 
         if (momentum) hbya_ready = with_h;
         kc[KC_MOM_PASS].end(stream);
         FY_TRY(reduce_read(6, false, h));
-        if (it == 0) for (int q = 0; q < 3; ++q) { norm[q] = h[3 + q] + 1e-20; res0[q] = h[q] / norm[q]; }
-        bool conv = true;
-        for (int q = 0; q < 3; ++q) {
-            res[q] = h[q] / norm[q];
-            if (!(res[q] < tol || (rel_tol > 0 && res[q] < rel_tol * res0[q]))) conv = false;
-        }
-        if (conv || it >= max_iter) break;
+        if (vec3_converged(it, h, tol, rel_tol, norm, res0) || it >= max_iter) break;
         std::swap(xc, xn);
         ++it;
     }
@@ -543,7 +513,7 @@ int Solver::corrector(bool final_inner) {
     clk_pres.end(stream);
     double h[2];
     int slot = 0, rc = FY_OK;
-    const bool diag_fused = fuse_diag && red_host && n_deferred + 4 <= kDeferMax;
+    const bool diag_fused = fuse_diag && rb.mapped() && n_deferred + 4 <= kDeferMax;
     if (fused_back) {
         // flux correction + velocity correction [+ the continuity errors and the NEXT step's Courant sums] in one sweep; p.relax() (pEqn.H:41) after it:
         // the sweep works with the unrelaxed solution, as pEqn.flux() and the reconstruction do (ico reads p itself, but has no relaxation)
@@ -640,12 +610,10 @@ int Solver::step() {
     n_deferred = 0; cont_slots.clear(); courant_slot = -1;
     if (carried) note_courant(carry_h);
     if (cs.adjust_time_step) {
-        // readTimeControls.H + CourantNo.H + setDeltaT.H (pimpleFoamYade.C:62-64) [OF-6 setDeltaT.H]: the step's deltaT follows from the
+        // readTimeControls.H + CourantNo.H + setDeltaT.H (pimpleFoamYade.C:62-64; common.hpp: next_delta_t): the step's deltaT follows from the
         // Courant number of the current flux at the OLD deltaT, so the host needs that number now
         if (!carried) { FY_TRY(reduce_read(2, true, h)); note_courant(h); }
-        const double maxDeltaTFact = cs.max_co / (st.courant_max + 1e-15);
-        const double deltaTFact = std::min(std::min(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
-        cs.dt = std::min(deltaTFact * cs.dt, cs.max_delta_t);
+        cs.dt = next_delta_t(cs.dt, st.courant_max, cs.max_co, cs.max_delta_t);
         g.dt = cs.dt;
     } else if (!carried) {
         int slot = 0, rc = FY_OK;
@@ -822,9 +790,9 @@ int Solver::step() {
         if (e) return fail(FY_ERR_UNSUPPORTED, "adjustPhi: continuity error cannot be removed by adjusting the outflow (the in- and outflow through the "
                                                "fixed-value patches do not balance and no adjustable outflow is left) -- OpenFOAM stops here too");
     }
-    if (courant_slot >= 0) note_courant(red_host + courant_slot);                         // the deferred diagnostics have landed
-    for (int sl : cont_slots) note_cont_err(red_host + sl);
-    if (carry_slot >= 0) { carry_h[0] = red_host[carry_slot]; carry_h[1] = red_host[carry_slot + 1]; carry_valid = true; }
+    if (courant_slot >= 0) note_courant(rb.slot(courant_slot));                         // the deferred diagnostics have landed
+    for (int sl : cont_slots) note_cont_err(rb.slot(sl));
+    if (carry_slot >= 0) { carry_h[0] = rb.slot(carry_slot)[0]; carry_h[1] = rb.slot(carry_slot)[1]; carry_valid = true; }
     if (timing) {
         clk_mom.collect(); clk_pres.collect();
         st.ms_momentum = clk_mom.total_ms; st.ms_pressure = clk_pres.total_ms;

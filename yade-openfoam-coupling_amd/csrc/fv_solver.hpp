@@ -127,11 +127,7 @@ struct Solver {
     DevBuf<double> partials, red_out, sc, xbar3;
     bool hold_sources = false, sources_pending = false;
     bool overlap_halos = true;            // FOAMYADE_HALO_OVERLAP=0: every exchange, then its consumer (serial schedule, same results); see can_window
-    double* red_host = nullptr;           // mapped pinned host memory (+ its device alias): reduce_read's landing zone (8 doubles) + deferred slots
-    double* red_host_dev = nullptr;
-    unsigned long long* red_flag = nullptr;      // 8 arrival flags (mapped pinned) the host spins on, and their device alias
-    unsigned long long* red_flag_dev = nullptr;
-    unsigned long long red_seq = 0;
+    MappedReadback rb;                    // reduce_read's landing zone (8 doubles) + the deferred slots, and the arrival flags the host spins on
     DevBuf<int> ops_courant, ops_diag;   // per-slot fold operations (0 sum, 1 max) of the Courant pair and of k_U_correct<true>'s four diagnostics
     fy_step_stats st{};
     double cumulative_cont_err = 0.0;
@@ -162,8 +158,6 @@ struct Solver {
         if (ev_coarse) (void)hipEventDestroy(ev_coarse);
         if (ev_factor) (void)hipEventDestroy(ev_factor);
         if (comm_stream) (void)hipStreamDestroy(comm_stream);
-        if (red_host) (void)hipHostFree(red_host);
-        if (red_flag) (void)hipHostFree(red_flag);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -233,7 +227,7 @@ struct Solver {
     // Diagnostics nobody branches on (Courant number, continuity errors): same fold [+ all-reduce], but the values land in their own
     // slots of the pinned buffer and are read after the step's final synchronisation instead of stalling the stream here.
     // Returns false when there is no slot left (the caller then reads at once).
-    static constexpr int kDeferBase = 8, kDeferMax = 2 + 4 * 255; // red_host: 8 immediate doubles + Courant + 255 correctors' continuity errors
+    static constexpr int kDeferBase = 8, kDeferMax = 2 + 4 * 255; // rb: 8 immediate doubles + Courant + 255 correctors' continuity errors
     int n_deferred = 0;
     bool reduce_deferred(int nslots, bool courant, int* slot, int* rc, const int* ops = nullptr);      // ops: ops_diag.p (sum, sum, max, sum) or none
     int reduce_to_device(double* dst);          // one slot, stays on the device (PCG scalars)

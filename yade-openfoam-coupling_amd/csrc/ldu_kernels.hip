@@ -3,9 +3,12 @@
 // cell -> face lists (sums, gradients, matrix rows) -- no scatter, hence no atomics, and every sum has a fixed order.  FP64, bandwidth / latency
 // bound like the structured kernels (no MFMA: nothing here is a dense contraction); the indirection through own / nei / cf_face costs what a
 // general mesh costs.  The arithmetic is OpenFOAM-6's, restated [OF-6]; oracle/ldu_oracle.cpp is the CPU restatement the tests compare with.
+// Includes: device_util.hpp (the block reductions), fv_closures.hpp (the closures stated once for this solver and the block solver: limiters, Smagorinsky, the k / epsilon
+// sources, wall functions, bound), fv_linalg_kernels.hpp (the fold of the block partials, compiled once in fv_linalg_kernels.hip), ldu.hpp (LduGeo and the launchers).
 #include <hip/hip_runtime.h>
 
 #include "device_util.hpp"
+#include "fv_closures.hpp"
 #include "fv_linalg_kernels.hpp"
 #include "ldu.hpp"
 
@@ -176,19 +179,8 @@ __global__ __launch_bounds__(256) void k_ldu_grad_magsqr(LduGeo g, const double*
     const double rV = 1.0 / g.V[c];
     st3(gradL, c, D3{a.x * rV, a.y * rV, a.z * rV});
 }
-// NVD / TVD limited schemes [OF-6 LimitedScheme<vector, Limiter<NVDTVD>, limitFuncs::magSqr>, NVDTVD.H], as fv_kernels.hip's limiter_fn / limited weight: ONE limiter per
-// face from lPhi = magSqr(U): r = 2 (d . grad(lPhi)_C) / (lPhi_N - lPhi_P) - 1, C the upwind cell of the face flux, d = C_N - C_P; the owner's weight is
-// limiter w_linear + (1 - limiter) pos0(flux) [limitedSurfaceInterpolationScheme::weights], used implicitly
-__device__ __forceinline__ double ldu_limiter_fn(int scheme, double twoByk, double r) {
-    switch (scheme) {
-        case FY_CONVECTION_LIMITED_LINEAR: return fmax(fmin(twoByk * r, 1.0), 0.0);
-        case FY_CONVECTION_VAN_LEER: return (r + fabs(r)) / (1.0 + fabs(r));
-        case FY_CONVECTION_MUSCL: return fmax(fmin(fmin(2.0 * r, 0.5 * r + 0.5), 2.0), 0.0);
-        case FY_CONVECTION_MINMOD: return fmax(fmin(fmin(r, 1.0), 2.0), 0.0);
-        case FY_CONVECTION_SUPERBEE: return fmax(fmax(fmin(2.0 * r, 1.0), fmin(r, 2.0)), 0.0);
-        default: return fmax(fmin((3.0 + r) / 4.0, 2.0), 0.0);          // QUICK
-    }
-}
+// NVD / TVD limited schemes (fv_closures.hpp: nvd_r, nvd_limiter): ONE limiter per face from lPhi = magSqr(U), C the upwind cell of the face flux, d = C_N - C_P; the
+// owner's weight is limiter w_linear + (1 - limiter) pos0(flux), used implicitly
 // the owner's weight of the convected value on internal face f for the face flux fl, by the scheme
 __device__ __forceinline__ double ldu_conv_weight(const LduGeo& g, int f, double fl, const double* __restrict__ U) {
     if (g.upwind == 0) return g.w[f];
@@ -200,10 +192,7 @@ __device__ __forceinline__ double ldu_conv_weight(const LduGeo& g, int f, double
     D3 cn = ld3(g.C, n);
     if (g.sep) { const D3 sp = ld3(g.sep, f); cn = D3{cn.x + sp.x, cn.y + sp.y, cn.z + sp.z}; }      // (a folded cyclic face: the neighbour's image)
     const double gradcf = ((cn.x - co.x) * gl.x + (cn.y - co.y) * gl.y) + (cn.z - co.z) * gl.z;
-    double r;
-    if (fabs(gradcf) >= 1000.0 * fabs(gradf)) r = 2.0 * 1000.0 * (gradcf >= 0 ? 1.0 : -1.0) * (gradf >= 0 ? 1.0 : -1.0) - 1.0;
-    else r = 2.0 * (gradcf / gradf) - 1.0;
-    const double lim = ldu_limiter_fn(g.upwind, g.lim_two_by_k, r);
+    const double lim = nvd_limiter(g.upwind, g.lim_two_by_k, nvd_r(gradcf, gradf));
     return lim * g.w[f] + (1.0 - lim) * up;
 }
 
@@ -555,17 +544,13 @@ __device__ __forceinline__ double ldu_nut_b(const LduGeo& g, const LduPim& P, in
     const int pa = g.patch_of[f - g.nInt], c = g.own[f];
     const int t = P.nut_bc[pa];
     if (t == FY_BC_NUT_FIXED_VALUE || (t == FY_BC_NUT_CALCULATED && !(P.k && P.nut_live)) || (t == FY_BC_WALL_FUNCTION && !P.nut_live)) return P.nut_val[pa];
-    // nutkWallFunction [OF-6 nutkWallFunctionFvPatchScalarField::nut]: y+ = Cmu^1/4 y sqrt(k_P) / nu, nu (y+ kappa / ln(E y+) - 1) above yPlusLam, else 0 (fv_kernels.hip: nut_boundary)
-    if (t == FY_BC_WALL_FUNCTION) {
-        const double yPlus = P.wf_cmu25 * P.ywall[f - g.nInt] * sqrt(P.k[c]) / g.nu;
-        return yPlus > P.wf_yplam ? g.nu * (yPlus * P.wf_kappa / log(P.wf_E * yPlus) - 1.0) : 0.0;
-    }
-    // calculated [OF-6 GeometricField::operator=: nut_ = Ck sqrt(k_) delta | Cmu sqr(k_) / epsilon_ assigns the patches too]
+    if (t == FY_BC_WALL_FUNCTION) return nutk_wall_nut(P.wf_cmu25, P.ywall[f - g.nInt], P.k[c], g.nu, P.wf_yplam, P.wf_kappa, P.wf_E);
+    // calculated: correctNut()'s expression on the boundary values (fv_closures.hpp: nut_kepsilon, nut_keqn)
     if (t == FY_BC_NUT_CALCULATED && P.eps) {
         const double kb = ldu_k_b(g, P, P.k, f), eb = P.eps_bc[pa] == FY_BC_NUT_FIXED_VALUE ? P.eps_val[pa] : P.eps[c];
-        return P.cmu * (kb * kb) / eb;
+        return nut_kepsilon(P.cmu, kb, eb);
     }
-    if (t == FY_BC_NUT_CALCULATED) return P.ck * sqrt(ldu_k_b(g, P, P.k, f)) * (P.delta_coeff * cbrt(g.V[c]));
+    if (t == FY_BC_NUT_CALCULATED) return nut_keqn(P.ck, ldu_k_b(g, P, P.k, f), P.delta_coeff * cbrt(g.V[c]));
     return P.nut[c];
 }
 __global__ __launch_bounds__(256) void k_ldu_pmom_faces(LduGeo g, LduPim P, const double* __restrict__ phi, const double* __restrict__ U, const double* __restrict__ alpha, const double* __restrict__ alphaf,
@@ -664,25 +649,15 @@ __global__ __launch_bounds__(256) void k_ldu_pmom_cells(LduGeo g, LduPim P, cons
     rAU[c] = 1.0 / ((dg + (bd[0] + bd[1] + bd[2]) / 3.0) / Vc);
 }
 
-// continuousPhaseTurbulence->correct() (pimpleFoamYade.C:101-104) for LESModel Smagorinsky [OF-6 Smagorinsky.C: k(gradU), correctNut()], as fv_kernels.hip's
-// k_smagorinsky_nut: D = symm(grad U); a = Ce / delta; b = 2/3 tr D; c = 2 Ck delta (dev D && D); k = sqr((-b + sqrt(b^2 + 4 a c)) / 2a); nut = Ck delta sqrt(k);
-// delta = deltaCoeff cbrt(V) per cell (cubeRootVolDelta)
+// continuousPhaseTurbulence->correct() (pimpleFoamYade.C:101-104) for LESModel Smagorinsky (fv_closures.hpp: smagorinsky_nut); delta = deltaCoeff cbrt(V) per cell
+// (cubeRootVolDelta)
 __global__ __launch_bounds__(256) void k_ldu_smagorinsky_nut(LduGeo g, const double* __restrict__ vGrad, double ck, double ce, double delta_coeff, double* __restrict__ nut) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= g.nCells) return;
-    const double delta = delta_coeff * cbrt(g.V[c]);
-    const double* T = vGrad + 9 * (size_t)c;
-    const double Dxx = T[0], Dyy = T[4], Dzz = T[8];
-    const double Dxy = 0.5 * (T[1] + T[3]), Dxz = 0.5 * (T[2] + T[6]), Dyz = 0.5 * (T[5] + T[7]);
-    const double trD = Dxx + Dyy + Dzz;
-    const double a = ce / delta, b = (2.0 / 3.0) * trD, third = (1.0 / 3.0) * trD;
-    const double dd = (Dxx - third) * Dxx + (Dyy - third) * Dyy + (Dzz - third) * Dzz + 2.0 * (Dxy * Dxy) + 2.0 * (Dxz * Dxz) + 2.0 * (Dyz * Dyz);
-    const double cc = 2.0 * ck * delta * dd;
-    const double r = (-b + sqrt(b * b + 4.0 * a * cc)) / (2.0 * a);
-    nut[c] = ck * delta * sqrt(r * r);
+    nut[c] = smagorinsky_nut(vGrad + 9 * (size_t)c, ck, ce, delta_coeff * cbrt(g.V[c]));
 }
 
-// ---- LESModel kEqn [OF-6 LES/kEqn/kEqn.C correct()] (DPMTurbulenceModels.C:76-77), as fv_kernels.hip's transport kernel with the faces of a general mesh:
+// ---- LESModel kEqn [OF-6 LES/kEqn/kEqn.C correct()] (DPMTurbulenceModels.C:76-77), the block solver's transport equation with the faces of a general mesh:
 //   fvm::ddt(alpha, k) + fvm::div(alphaPhi, k) - fvm::laplacian(alpha DkEff, k) == alpha G - fvm::SuSp(2/3 alpha divU, k) - fvm::Sp(Ce alpha sqrt(k) / delta, k)
 //   DkEff = nut + nu; G = nut (gradU && dev(twoSymm(gradU))); divU = fvc::div(phi); Gauss linear corrected laplacian: its explicit part (alpha DkEff)_f |Sf| (k & interpolate(grad k))
 // The matrix goes into the momentum matrix's arrays (free once the correctors are done) and is solved as component 0 of a three-component system by the momentum passes
@@ -740,28 +715,16 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
             } else dg += fl;
         }
     }
-    const double* T = vGrad + 9 * (size_t)c;
-    const double tr2 = 2.0 * (T[0] + T[4] + T[8]);
-    double GG = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) GG += T[3 * a + q] * ((T[3 * a + q] + T[3 * q + a]) - (a == q ? (1.0 / 3.0) * tr2 : 0.0));
+    const double GG = production_tensor(vGrad + 9 * (size_t)c);
     const int wc = K.wall_of ? K.wall_of[c] : -1;
     const double G = wc >= 0 ? K.wall_G[wc] : P.nut[c] * GG, divU = sumPhi / Vc;      // (a wall cell's production: the wall function's, k_ldu_wall_functions)
-    // mode 0 (kEqn's k): Su = alpha G, c1 = 2/3 alpha divU, c2 = Ce alpha sqrt(k) / delta; mode 1 (epsilon): Su = C1 alpha G eps / k, c1 = (2/3 C1 - C3) alpha divU, c2 = C2 alpha eps / k;
-    // mode 2 (kEpsilon's k): Su = alpha G, c1 = 2/3 alpha divU, c2 = alpha eps / k
-    double Su, c1, c2;
-    if (K.mode == 0) { Su = ac * G; c1 = (2.0 / 3.0) * ac * divU; c2 = K.ce * ac * sqrt(xc) / (P.delta_coeff * cbrt(Vc)); }
-    else if (K.mode == 1) { const double kc = P.k[c]; Su = K.c1 * ac * G * xc / kc; c1 = ((2.0 / 3.0) * K.c1 - K.c3) * ac * divU; c2 = K.c2 * ac * xc / kc; }
-    else { Su = ac * G; c1 = (2.0 / 3.0) * ac * divU; c2 = ac * P.eps[c] / xc; }
-    dg += Vc * (fmax(c1, 0.0) + c2);                        // fvm::SuSp: the positive part implicit, the negative part on the source; fvm::Sp
-    b += Vc * Su - Vc * fmin(c1, 0.0) * xc;
-    if (K.relax > 0) {                                      // fvMatrix::relax
-        const double dn = fmax(fabs(dg), offsum) / K.relax;
-        b += (dn - dg) * xc;
-        dg = dn;
-    }
+    // the sources by K.mode: 0 kEqn's k, 1 epsilon, 2 kEpsilon's k (fv_closures.hpp); each branch reads only its own fields -- P.eps is null without kEpsilon
+    TurbSource S;
+    if (K.mode == 0) S = keqn_k_source(ac, G, divU, K.ce, P.delta_coeff * cbrt(Vc), xc);
+    else if (K.mode == 1) S = kepsilon_eps_source(ac, G, divU, K.c1, K.c2, K.c3, xc, P.k[c]);
+    else S = kepsilon_k_source(ac, G, divU, P.eps[c], xc);
+    add_turb_source(S, Vc, xc, dg, b);                      // fvm::SuSp + fvm::Sp
+    if (K.relax > 0) relax_scalar_row(K.relax, offsum, xc, dg, b);      // fvMatrix::relax
     // epsEqn.boundaryManipulate -> fvMatrix::setValues [OF-6 fvMatrix.C setValuesFromList], after relax() as on the block: a wall cell's row becomes dg x = dg eps_w
     // and it starts from eps_w; a row next to wall cells moves those coefficients times their eps_w to its source (the faces' coefficients are zeroed after this
     // kernel, k_ldu_wall_set_values: every row here still reads the assembled ones)
@@ -773,23 +736,22 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
     st3(x3, c, D3{x0, 0.0, 0.0});
 }
 
-// epsilonWallFunction::calculate [OF-6 epsilonWallFunctionFvPatchScalarField.C], one lane per wall cell over its W faces on epsilonWallFunction patches (fv_kernels.hip:
-// k_assemble_turb, wall_epsilon): eps_w = (1/W) sum Cmu^3/4 k^3/2 / (kappa y), G_w = (1/W) sum (nut_w + nu) |snGrad U| Cmu^1/4 sqrt(k) / (kappa y), snGrad U =
-// (U_b - U_P) deltaCoeffs with the boundary face's 1 / (n . (Cf - C_P)); k of the cell as this correct() found it
+// epsilonWallFunction::calculate, one lane per wall cell over its W faces on epsilonWallFunction patches: eps_w and G_w = the averages of the faces' terms (fv_closures.hpp:
+// wall_epsilon_term, wall_G_term); k of the cell as this correct() found it
 __global__ __launch_bounds__(256) void k_ldu_wall_functions(LduGeo g, LduPim P, LduWallCells W, const double* __restrict__ U, double* __restrict__ wall_eps, double* __restrict__ wall_G) {
     const int w = blockIdx.x * 256 + threadIdx.x;
     if (w >= W.n) return;
     const int c = W.cell[w], q0 = W.off[w], q1 = W.off[w + 1];
-    const double kc = P.k[c], uk = pow(kc, 1.5), sk = sqrt(kc);
+    const double kc = P.k[c];
     const D3 uc = ld3(U, c);
     double se = 0.0, sg = 0.0;
     for (int q = q0; q < q1; ++q) {
         const int f = W.face[q];
         const double y = P.ywall[f - g.nInt], dc = g.dcNO[f];
         const D3 ub = Ub(g, U, f);
-        const double d0 = (ub.x - uc.x) * dc, d1 = (ub.y - uc.y) * dc, d2 = (ub.z - uc.z) * dc;
-        se += W.cmu75 * uk / (P.wf_kappa * y);
-        sg += (ldu_nut_b(g, P, f) + g.nu) * sqrt(d0 * d0 + d1 * d1 + d2 * d2) * P.wf_cmu25 * sk / (P.wf_kappa * y);
+        const double d0 = (ub.x - uc.x) * dc, d1 = (ub.y - uc.y) * dc, d2 = (ub.z - uc.z) * dc;      // snGrad U = (U_b - U_P) deltaCoeffs, the boundary face's 1 / (n . (Cf - C_P)): the block divides by y
+        se += wall_epsilon_term(W.cmu75, kc, P.wf_kappa, y);
+        sg += wall_G_term(ldu_nut_b(g, P, f), g.nu, sqrt(d0 * d0 + d1 * d1 + d2 * d2), P.wf_cmu25, kc, P.wf_kappa, y);
     }
     wall_eps[w] = se / (double)(q1 - q0);
     wall_G[w] = sg / (double)(q1 - q0);
@@ -806,12 +768,12 @@ __global__ __launch_bounds__(256) void k_ldu_nut_boundary(LduGeo g, LduPim P, do
     if (b >= g.nFaces - g.nInt) return;
     out[b] = ldu_nut_b(g, P, g.nInt + b);
 }
-// bound(k, kMin) [OF-6 bound.C: k = max(max(k, fvc::average(max(k, kMin)) pos0(-k)), kMin), fvc::average = sum |Sf| k_f / sum |Sf|], then correctNut(): nut = Ck sqrt(k) delta
+// bound(k, kMin) (fv_closures.hpp: bound_value; fvc::average = sum |Sf| k_f / sum |Sf|, formed only where pos0(-k) = 1), then correctNut()
 __global__ __launch_bounds__(256) void k_ldu_k_bound_nut(LduGeo g, LduPim P, LduKEqn K, const double* __restrict__ x3, double* __restrict__ X, double* __restrict__ nut) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= g.nCells) return;
     const double kMin = 1e-15, xc = x3[3 * (size_t)c];
-    double xb = xc;
+    double avg = xc;
     if (!(xc > 0.0)) {
         double av = 0.0, asum = 0.0;
         FY_CELL_FACES(g, c, f, nb) {
@@ -825,12 +787,12 @@ __global__ __launch_bounds__(256) void k_ldu_k_bound_nut(LduGeo g, LduPim P, Ldu
             }
             av += g.magSf[f] * xf; asum += g.magSf[f];
         }
-        xb = fmax(xc, av / asum);
+        avg = av / asum;
     }
-    const double xn = fmax(xb, kMin);
+    const double xn = bound_value(xc, avg, kMin);
     X[c] = xn;
-    if (K.mode == 0) nut[c] = P.ck * sqrt(xn) * (P.delta_coeff * cbrt(g.V[c]));
-    else if (K.mode == 2) nut[c] = P.cmu * (xn * xn) / P.eps[c];            // correctNut() after the k equation, with the epsilon of this correct()
+    if (K.mode == 0) nut[c] = nut_keqn(P.ck, xn, P.delta_coeff * cbrt(g.V[c]));
+    else if (K.mode == 2) nut[c] = nut_kepsilon(P.cmu, xn, P.eps[c]);            // correctNut() after the k equation, with the epsilon of this correct()
 }
 
 // rAUcf = interpolate(rAUc) (boundary: the cell's), phicForces = fvc::flux(rAUc uSource) + rAUcf (g & Sf) (UcEqn.H:15-20)

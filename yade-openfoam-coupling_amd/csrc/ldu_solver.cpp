@@ -86,8 +86,6 @@ struct LduSolver {
 
     ~LduSolver() {
         if (cpl) fy_destroy(cpl);
-        if (red_host) (void)hipHostFree(red_host);
-        if (red_flag) (void)hipHostFree(red_flag);
         for (auto& t : tim) t.destroy();
         if (side) (void)hipStreamDestroy(side);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -177,15 +175,7 @@ struct LduSolver {
         FY_TRY(partials.alloc_exact(8 * (size_t)ldu_red_blocks(std::max(nc, nf)))); FY_TRY(zero(partials));
         FY_TRY(sc.alloc_exact(8)); FY_TRY(zero(sc)); FY_TRY(xsum.alloc_exact(4)); FY_TRY(zero(xsum)); FY_TRY(adj.alloc_exact(4)); FY_TRY(zero(adj));
         FY_TRY(adj_err.alloc_exact(1)); FY_HIP(hipMemsetAsync(adj_err.p, 0, sizeof(int), stream));
-        if (hipHostMalloc((void**)&red_host, 8 * sizeof(double), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&red_host_dev, red_host, 0) != hipSuccess) {
-            if (red_host) (void)hipHostFree(red_host);
-            red_host = nullptr;                              // (fall back to the copy path)
-        }
-        if (red_host && (hipHostMalloc((void**)&red_flag, 8 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&red_flag_dev, red_flag, 0) != hipSuccess)) {
-            if (red_flag) (void)hipHostFree(red_flag);
-            red_flag = nullptr;
-        }
-        if (red_flag) for (int q = 0; q < 8; ++q) red_flag[q] = 0;
+        rb.init(MappedReadback::kFlags);
         if (pimple) {
             DevBuf<double>* p3[] = {&uParticle, &gradP, &divT, &ddtU, &bmom};
             for (auto* b : p3) { FY_TRY(b->alloc_exact(3 * n)); FY_TRY(zero(*b)); }
@@ -297,27 +287,12 @@ struct LduSolver {
     }
 
     // fold `nslots` of the block partials of an n-cell reduction and read them back
-    // the fold writes straight into mapped pinned host memory and stores a sequence number behind each result; the host spins on those flags (in-order stream: everything
-    // enqueued before the fold has completed by then) -- no device-to-host blit and no stream synchronisation per read-back, as fv_solver.cpp's reduce_read
-    double* red_host = nullptr; double* red_host_dev = nullptr;
-    unsigned long long* red_flag = nullptr; unsigned long long* red_flag_dev = nullptr;
-    unsigned long long red_seq = 0;
+    // through mapped pinned host memory and its arrival flags (common.hpp: MappedReadback); without them the fold lands on the device and is copied
+    MappedReadback rb;
     int reduce_read(int n, int nslots, const int* ops_dev, double* h, double* dev_land = nullptr) {      // dev_land: where the copy path lets the fold land (default: sc)
-        if (red_flag && nslots <= 8) {
-            const unsigned long long seq = ++red_seq;
-            FY_TRY(launch_reduce_finalize(stream, partials.p, n, nslots, ops_dev, red_host_dev, red_flag_dev, seq));
-            for (int q = 0; q < nslots; ++q) {
-                unsigned long spins = 0;
-                while (__atomic_load_n(&red_flag[q], __ATOMIC_ACQUIRE) != seq) {
-                    if ((++spins & 0xfffu) == 0) {                      // every 4096 polls: is the stream still alive?
-                        const hipError_t e = hipStreamQuery(stream);
-                        if (e == hipSuccess) { if (__atomic_load_n(&red_flag[q], __ATOMIC_ACQUIRE) == seq) break; return fail(FY_ERR_HIP, "reduction flag never arrived"); }
-                        if (e != hipErrorNotReady) return fail(FY_ERR_HIP, "stream failed while waiting for a reduction: %s", hipGetErrorString(e));
-                    }
-                }
-                h[q] = red_host[q];
-            }
-            return FY_OK;
+        if (rb.flagged(nslots)) {
+            FY_TRY(launch_reduce_finalize(stream, partials.p, n, nslots, ops_dev, rb.dev, rb.flag_dev, ++rb.seq));
+            return rb.wait(stream, nslots, h);
         }
         double* land = dev_land ? dev_land : sc.p;
         FY_TRY(launch_reduce_finalize(stream, partials.p, n, nslots, ops_dev, land, nullptr, 0));
@@ -337,18 +312,12 @@ struct LduSolver {
         FY_TRY(launch_ldu_sum(stream, *x, nc, 3, partials.p));
         FY_TRY(launch_reduce_finalize(stream, partials.p, nc, 3, nullptr, xsum.p, nullptr, 0));
         double* xc = *x; double* xn = *scratch;
-        double norm[3] = {1, 1, 1}, res0[3] = {0, 0, 0}, res[3], h[6];
+        double norm[3] = {1, 1, 1}, res0[3] = {0, 0, 0}, h[6];
         int it = 0;
         for (;;) {
             FY_TRY(launch_ldu_mom_pass(stream, g, Mx, rhs, gp, xc, xn, xsum.p, partials.p));
             FY_TRY(reduce_read(nc, 6, nullptr, h));
-            if (it == 0) for (int q = 0; q < 3; ++q) { norm[q] = h[3 + q] + 1e-20; res0[q] = h[q] / norm[q]; }
-            bool conv = true;
-            for (int q = 0; q < 3; ++q) {
-                res[q] = h[q] / norm[q];
-                if (!(res[q] < tol || (rel_tol > 0 && res[q] < rel_tol * res0[q]))) conv = false;
-            }
-            if (conv || it >= max_iter) break;
+            if (vec3_converged(it, h, tol, rel_tol, norm, res0) || it >= max_iter) break;
             std::swap(xc, xn);
             ++it;
         }
@@ -519,10 +488,8 @@ struct LduSolver {
         FY_TRY(launch_ldu_courant(stream, g, phi.p, partials.p));                                                   // icoFoamYade.C:68
         FY_TRY(reduce_read(nc, 2, ops_courant.p, h));
         st.courant_max = 0.5 * h[0] * cs.dt; st.courant_mean = 0.5 * (h[1] / total_volume) * cs.dt;
-        if (cs.adjust_time_step) {                                                                                  // setDeltaT.H [OF-6] (pimpleFoamYade.C:64): Co from the current flux at the OLD step
-            const double maxDeltaTFact = cs.max_co / (st.courant_max + 1e-15);
-            const double deltaTFact = std::min(std::min(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
-            cs.dt = std::min(deltaTFact * cs.dt, cs.max_delta_t);
+        if (cs.adjust_time_step) {                                                                                  // setDeltaT.H (common.hpp: next_delta_t): Co from the current flux at the OLD step
+            cs.dt = next_delta_t(cs.dt, st.courant_max, cs.max_co, cs.max_delta_t);
             g.dt = cs.dt;
         }
         st.delta_t = cs.dt;
