@@ -284,32 +284,47 @@ def test_gaussian_passes_match_the_restatement(product, law):
     s.close()
 
 
-def test_sparse_cloud_matches_the_restatement(product):
-    """16 384 particles at 0.5 per cell on 32^3 cells: a workgroup's 512 particles reach more distinct cells than its 1 024-slot LDS table holds, so part of the
-    scatter leaves the kernel as direct global atomics (the crowded-table branch) beside the bucket flush of the full tables.  Whatever route an entry takes, the
+def tiles_reached(ids, n):
+    """distinct 8 x 8 x 8 cell tiles of an n^3 block among the stencil ids"""
+    c = ids[ids >= 0]
+    nt = (n + 7) // 8
+    return np.unique((c % n) // 8 + nt * (((c // n) % n) // 8 + nt * ((c // (n * n)) // 8))).size
+
+
+@pytest.mark.parametrize("n,npart,steps", [(32, 16384, 1), (48, 512, 2)], ids=["crowded_table", "tile_map_full"])
+def test_sparse_cloud_matches_the_restatement(product, n, npart, steps):
+    """crowded_table: 16 384 particles at 0.5 per cell on 32^3 cells: a workgroup's 512 particles reach more distinct cells than its 1 024-slot LDS table holds, so part
+    of the scatter leaves the kernel as direct global atomics (the crowded-table branch) beside the bucket flush of the full tables.  Whatever route an entry takes, the
     sums must be the restatement's.  (Whether a bucket also overflows here -- full tables ask for 2.5 entries per particle + 135 per tile where the pool holds 2.25 +
-    136 -- cannot be seen from outside and is not claimed.)"""
-    n, dx = 32, 0.01
+    136 -- cannot be seen from outside and is not claimed.)
+    tile_map_full: 512 particles -- ONE workgroup -- spread over 48^3 cells = 216 tiles reach more tiles than the flush's 128-slot tile map holds: the entries of the
+    tiles that find no map slot go out as the two-sum flush's global atomics beside the buckets of those that do; two steps, the second with capacities."""
+    dx = {32: 0.01, 48: 0.32 / 48}[n]
     nu, rho = 1e-5, 1000.0
     s = product.Solver(product.make_case(1, n, n, n, dx, 2e-4, nu, g=(0, 0, -9.81), p_bc=[2] * 6, thermal=thermal(product, 40, T_initial=300.0, **WATER)))
     Nc = n ** 3
     rs = np.random.RandomState(29)
     s.set("U", 0.05 * rs.standard_normal((Nc, 3)))
     s.set("T", 300.0 + 50.0 * rs.random_sample(Nc))
-    rec = cloud(16384, (0.002, 0.002, 0.002), (0.318, 0.318, 0.318), 0.001, 31, speed=0.1)
+    rec = cloud(npart, (0.002, 0.002, 0.002), (0.318, 0.318, 0.318), 0.001, 31, speed=0.1)
     Tp = 280.0 + 90.0 * rs.random_sample(rec.shape[0])
     Pr = ht.prandtl(nu, rho, WATER["cp"], WATER["kappa"])
     s.hold_sources(True)
-    s.set_particles(rec)
-    s.set_particle_temperatures(Tp)
-    U = s.get("U").reshape(Nc, 3)
-    s.step()
-    k, ids, w, chain = s.stencils()
-    assert (k > 0).all() and np.unique(ids[ids >= 0]).size > 16 * 1024
-    hA, Sp, Su = ht.pass_a(ht.RANZ_MARSHALL, rec, ids, w, U, s.get("alpha"), Tp, nu, WATER["kappa"], Pr, Nc)
-    assert_field(s.get("heatSp"), Sp, "sparse heatSp")
-    assert_field(s.get("heatSu"), Su, "sparse heatSu")
-    assert_field(s.particle_heat(), ht.pass_b(hA, ids, w, s.get("T"), Tp), "sparse q")
+    for step in range(steps):
+        s.set_particles(rec)
+        s.set_particle_temperatures(Tp)
+        U = s.get("U").reshape(Nc, 3)
+        s.step()
+        k, ids, w, chain = s.stencils()
+        assert (k > 0).all()
+        if npart > 512:
+            assert np.unique(ids[ids >= 0]).size > 16 * 1024
+        else:
+            assert tiles_reached(ids, n) > 128, tiles_reached(ids, n)      # kTileMap
+        hA, Sp, Su = ht.pass_a(ht.RANZ_MARSHALL, rec, ids, w, U, s.get("alpha"), Tp, nu, WATER["kappa"], Pr, Nc)
+        assert_field(s.get("heatSp"), Sp, f"sparse heatSp, step {step}")
+        assert_field(s.get("heatSu"), Su, f"sparse heatSu, step {step}")
+        assert_field(s.particle_heat(), ht.pass_b(hA, ids, w, s.get("T"), Tp), f"sparse q, step {step}")
     s.close()
 
 

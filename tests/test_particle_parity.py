@@ -169,6 +169,111 @@ def test_against_oracle_seeded(product, oracle, dims, npart, gaussian):
     fy.close()
 
 
+# ---- the scatters' flush (scatter_table.hpp: one flush_table for the four-sum deposit / back-scatter and the two-sum heat scatter): the branches an ordinary
+# cloud does not reach.  Each test asserts, from the ORACLE's ids alone, the condition that makes its branch certain, then holds every action to the oracle as
+# test_against_oracle_seeded does.  (The two-sum side: test_heat_transfer.py::test_sparse_cloud_matches_the_restatement.)
+def flush_case(n):
+    return gc.Case("flush", n, n, n, 0.3, origin=(0.1, -0.2, 0.05), gaussian=1, np_=2048, seed=78)
+
+
+def uniform_cloud(c, n, seed, x_cells=None):
+    """n records with positions uniform over the block (x_cells: over its first x_cells cell layers in x only), drawn from a seeded RandomState"""
+    rs = np.random.RandomState(seed)
+    ext = np.array([c.nx, c.ny, c.nz], dtype=np.float64) * c.dx
+    if x_cells is not None:
+        ext[0] = x_cells * c.dx
+    rec = np.empty((n, 10))
+    rec[:, 0:3] = np.array(c.origin) + (0.02 + 0.96 * rs.random_sample((n, 3))) * ext
+    rec[:, 3:6] = (rs.random_sample((n, 3)) * 2.0 - 1.0) * c.vel_scale
+    rec[:, 6:9] = (rs.random_sample((n, 3)) * 2.0 - 1.0) * 0.1
+    rec[:, 9] = c.radius_dx * c.dx
+    return rec
+
+
+def oracle_action(oracle, c, fields, rec):
+    om = oracle.Mesh(c.nx, c.ny, c.nz, c.dx, c.origin)
+    omut = oracle.fresh_mutable(c.ncells)
+    ref = oracle.particle_action(om, fields, omut, rec, np.array([0, rec.shape[0]], np.int32), 1, c.rhoP, c.rhoF, c.nu, threads=8)
+    return ref, omut
+
+
+def tiles_of(c, ids):
+    """the 8 x 8 x 8 cell tiles the stencil ids lie in"""
+    cells = ids[ids >= 0]
+    i, j, k = cells % c.nx, (cells // c.nx) % c.ny, cells // (c.nx * c.ny)
+    ntx, nty = (c.nx + 7) // 8, (c.ny + 7) // 8
+    return np.unique(i // 8 + ntx * (j // 8 + nty * (k // 8)))
+
+
+def act_and_compare(fy, mut, c, rec, ref, omut, what):
+    fy.setParticles([rec])
+    fy.setParticleAction(c.dt)
+    k, ids, w, chain = fy.stencils(0)
+    assert np.array_equal(chain, ref["chain_len"]), what
+    assert np.array_equal(k, ref["k"]), what
+    assert np.array_equal(ids, ref["ids"]), what
+    assert np.array_equal(fy.found(0), ref["found"]), what
+    assert_close(w, ref["w"], gu.RTOL_GPU, what + ": weights")
+    assert_close(fy.forces(0), ref["force"], gu.RTOL_GPU, what + ": force")
+    for nm in ("alpha", "uSource", "uSourceDrag", "uParticle"):
+        assert_close(mut[nm], omut[nm], gu.RTOL_GPU, what + ": " + nm)
+    fy.setSourceZero()                       # the sources accumulate over actions until the solver has taken them (FoamYade.C:556-564)
+
+
+def test_flush_with_a_crowded_table(product, oracle):
+    """2 048 particles on 24^3 cells = 4 workgroups of 512 with 1 024 table slots each, and the oracle's ids name more distinct cells than the four tables hold
+    together: at least one workgroup cannot hold its cells, so the direct-atomic branches of deposit_pair and of the force back-scatter run.  Two actions on the
+    same records: the first has no bucket capacities (the whole flush goes out as atomics), the second flushes through buckets sized by the first."""
+    c = flush_case(24)
+    fields = gc.fluid_fields(c)
+    rec = gc.particle_records(c, 0)
+    ref, omut = oracle_action(oracle, c, fields, rec)
+    n = rec.shape[0]
+    assert np.unique(ref["ids"][ref["ids"] >= 0]).size > 1024 * -(-n // 512)
+    mut = seeded_mutable(c.ncells)
+    mesh, fy = make_engine(product, c, fields, mut)
+    for action in ("first action (atomics)", "second action (buckets)"):
+        act_and_compare(fy, mut, c, rec, ref, omut, action)
+    fy.close()
+
+
+def test_flush_into_buckets_without_room(product, oracle):
+    """The cloud sits in the cell layers i <= 4 (with particles in layer 5 the first chain entries of a walk, up to three cells away, reach the tiles of layers 8 .. 15
+    from both places); the second action has the same records 16 dx further in x.  No tile receives entries in both actions (asserted from the oracle's ids), so
+    every entry of the second action meets a capacity of zero and leaves as atomics while the tiles that were given room stay empty; a third action at the new
+    place has buckets again."""
+    c = flush_case(24)
+    fields = gc.fluid_fields(c)
+    rec_a = uniform_cloud(c, 2048, 79, x_cells=5)
+    rec_b = rec_a.copy()
+    rec_b[:, 0] += 16 * c.dx
+    ref_a, omut_a = oracle_action(oracle, c, fields, rec_a)
+    ref_b, omut_b = oracle_action(oracle, c, fields, rec_b)
+    assert (np.floor((rec_a[:, 0] - c.origin[0]) / c.dx) <= 5).all()
+    assert np.intersect1d(tiles_of(c, ref_a["ids"]), tiles_of(c, ref_b["ids"])).size == 0
+    mut = seeded_mutable(c.ncells)
+    mesh, fy = make_engine(product, c, fields, mut)
+    act_and_compare(fy, mut, c, rec_a, ref_a, omut_a, "first place (atomics)")
+    act_and_compare(fy, mut, c, rec_b, ref_b, omut_b, "second place (no room in any bucket)")
+    act_and_compare(fy, mut, c, rec_b, ref_b, omut_b, "second place again (buckets)")
+    fy.close()
+
+
+def test_flush_with_a_full_tile_map(product, oracle):
+    """512 particles -- one workgroup -- uniform over 48^3 cells = 216 tiles: the oracle's ids reach more tiles than the flush's tile map has slots (kTileMap = 128),
+    so the entries of the tiles that find no slot go out as atomics beside the buckets of those that do.  Two actions: without and with capacities."""
+    c = flush_case(48)
+    fields = gc.fluid_fields(c)
+    rec = uniform_cloud(c, 512, 80)
+    ref, omut = oracle_action(oracle, c, fields, rec)
+    assert tiles_of(c, ref["ids"]).size > 128
+    mut = seeded_mutable(c.ncells)
+    mesh, fy = make_engine(product, c, fields, mut)
+    for action in ("first action (atomics)", "second action (buckets, tile map full)"):
+        act_and_compare(fy, mut, c, rec, ref, omut, action)
+    fy.close()
+
+
 @pytest.mark.parametrize("dims", [(96, 80, 64), (33, 47, 29)])
 def test_locate_on_lattice_positions(product, oracle, dims):
     """k_locate starts every walk at a node precomputed per CELL (k_build_locate_start).  Queries that sit exactly on cell faces,

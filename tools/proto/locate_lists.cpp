@@ -1,4 +1,4 @@
-// Host restatement of k_build_locate_lists / k_locate_lists (particle_kernels.hip): per-(cell, octant) candidate lists for the k-d
+// Host restatement of k_build_locate_lists / k_locate_lists (particle_locate.hip): per-(cell, octant) candidate lists for the k-d
 // "range" locate, checked against the plain walk on random and extreme queries.  Test infrastructure (tests/test_locate_lists_host.py).
 //   g++ -O2 -std=c++17 -I../../yade-openfoam-coupling_amd/csrc locate_lists.cpp ../../yade-openfoam-coupling_amd/csrc/kdtree.cpp -o /tmp/locate_lists -lpthread
 #include <cmath>
@@ -49,7 +49,7 @@ static std::vector<Pair> walk(double qx, double qy, double qz, double maxdist, i
 }
 
 // ---- list builder, lattice units (cell centre of index i at coordinate i)
-constexpr double EPS = 4e-6, MARGIN = 1e-8;      // = kListEps, kListMargin of particle_kernels.hip
+constexpr double EPS = 4e-6, MARGIN = 1e-8;      // = kListEps, kListMargin of particle_locate.hip
 struct Box { double lo[3], hi[3]; };
 struct Cand { int x[3]; bool noemit; };
 static inline double ax_min2(double lo, double hi, double x) { double g = x < lo ? lo - x : (x > hi ? x - hi : 0.0); return g * g; }

@@ -1,5 +1,5 @@
 // fy_ctx: MI355X-native replacement of Foam::FoamYade (FoamYade/FoamYade.{H,C}).  Host orchestration + wire protocol;
-// all arithmetic runs in the HIP kernels of particle_kernels.hip.  There is no CPU compute path: without a HIP
+// all arithmetic runs in the HIP kernels of the particle_*.hip sources.  There is no CPU compute path: without a HIP
 // device fy_create fails with FY_ERR_NO_DEVICE.
 #include "coupling.hpp"
 #include "ldu.hpp"
@@ -465,7 +465,7 @@ int Coupling::ensure_batch(Batch& b, int64_t n) {
             FY_TRY(b.soa.alloc_exact(7 * c2)); FY_TRY(b.orig.alloc_exact(c2)); FY_TRY(b.chain.alloc_exact(c2)); FY_TRY(b.scan_class.alloc_exact(c2)); FY_HIP(hipMemset(b.scan_class.p, 0, c2));
             FY_TRY(b.ids.alloc_exact((size_t)kMaxK * c2)); FY_TRY(b.w.alloc_exact((size_t)kMaxK * c2));
             FY_TRY(b.key.alloc_exact(c2)); FY_TRY(b.rank.alloc_exact(c2));
-            if (tile_flush && structured) {
+            if (structured) {
                 const size_t nt = (size_t)tile_grid().n_tiles();
                 for (int w = 0; w < 2; ++w) {
                     FY_TRY(b.tb_off[w].alloc_exact(nt)); FY_TRY(b.tb_cap[w].alloc_exact(nt)); FY_TRY(b.tb_fill[w].alloc_exact(nt));
@@ -507,7 +507,7 @@ TileGrid Coupling::tile_grid() const {
 // which = 0: the void-fraction deposit's flush, 1: the momentum-source back-scatter's
 TileBuckets Coupling::buckets_of(Batch& b, int which) {
     TileBuckets tb{};
-    if (!tile_flush || !b.tb_off[which].p || !tile_cell.p) return tb;
+    if (!b.tb_off[which].p || !tile_cell.p) return tb;
     tb.cell = tile_cell.p; tb.val = tile_val.p;
     tb.off = b.tb_off[which].p; tb.cap = b.tb_cap[which].p; tb.fill = b.tb_fill[which].p;
     tb.pool = (uint32_t)std::min<size_t>(tile_cell.n, 0xfffffff0u);

@@ -122,9 +122,8 @@ struct Coupling {
     DevBuf<uint32_t> tile_cell;          // entry pool of the tile buckets (one flush at a time uses it)
     DevBuf<double> tile_val;
     SideStream side{};                   // the walk's leftovers run here, beside the cell-record pack
-    bool tile_flush = true;              // the scatters' tables are flushed into per-tile buckets (false: global atomics, round-1 behaviour)
     TileGrid tile_grid() const;
-    TileBuckets buckets_of(Batch& b, int which);
+    TileBuckets buckets_of(Batch& b, int which);      // a structured block's scatters flush into per-tile buckets; all null (global atomics) on a general mesh
     bool rectilinear = false;            // graded block (fy_mesh_desc.xf / yf / zf): lattice indexing, explicit tree, findCell by search
     DevBuf<double> d_faces[3];
     ImplicitGeom implicit{};

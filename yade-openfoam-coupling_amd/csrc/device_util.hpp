@@ -1,5 +1,5 @@
 // Device-side helpers that more than one kernel source needs (fv_kernels.hip in both its builds, fv_linalg_kernels.hip, ldu_kernels.hip,
-// ldu_amg.hip, particle_kernels.hip).  Everything here is inlined into its caller: including this header adds no symbol to an object.
+// ldu_amg.hip, the particle_*.hip sources).  Everything here is inlined into its caller: including this header adds no symbol to an object.
 // Launch plumbing only (block order, reductions, the launch check); the physics that fv_kernels.hip (both builds) and ldu_kernels.hip share is in fv_closures.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,3 +60,24 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[N], const int (&i
         hipError_t _e = hipGetLastError();                                                                    \
         if (_e != hipSuccess) return fail(FY_ERR_HIP, "kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
+
+namespace fy {
+namespace {
+
+// The launcher most kernels have: one thread per item, nothing to do for none, the launch check.  `at` is the caller's stream; it also takes down
+// where the launcher stands, so that a failed launch is reported with the launcher's file and line as FY_LAUNCH_CHECK reports it.
+struct LaunchAt {
+    hipStream_t s; const char* file; int line;
+    LaunchAt(hipStream_t s_, const char* f = __builtin_FILE(), int l = __builtin_LINE()) : s(s_), file(f), line(l) {}
+};
+template <class Kernel, class... Args>
+int launch_n(LaunchAt at, Kernel kernel, int64_t n, int block, Args... args) {
+    if (n <= 0) return FY_OK;
+    hipLaunchKernelGGL(kernel, dim3(div_up(n, block)), dim3(block), 0, at.s, args...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FY_ERR_HIP, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e), at.file, at.line);
+    return FY_OK;
+}
+
+}  // namespace
+}  // namespace fy

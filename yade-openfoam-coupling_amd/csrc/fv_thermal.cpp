@@ -1,5 +1,5 @@
 // fy::Solver's heat exchange: the fluid temperature equation and the particles' share of it (fy_thermal_desc, Thermal in fv_solver.hpp).  Not in the
-// reference; DESIGN.md section 3 "heat exchange", DESIGN_FV.md "T equation".  Host code only sequences the kernels of particle_kernels.hip (k_heat_coeff_*,
+// reference; DESIGN.md section 3 "heat exchange", DESIGN_FV.md "T equation".  Host code only sequences the kernels of particle_heat.hip (k_heat_coeff_*,
 // k_heat_flux_*) and fv_kernels.hip (k_assemble_scalar) on the solver's stream.
 #include "fv_solver.hpp"
 

@@ -73,6 +73,7 @@ struct ImplicitGeom {
 };
 // the chain lengths of the step before, filed under the wire index (before the placement they belong to is overwritten), and the new placement's
 // runs of 512 slots put in order of them (stable): see k_order_blocks_by_chain
+constexpr int kOrderRun = 512;           // one run = one workgroup of the locate and of the force pass
 int launch_chain_by_wire(hipStream_t s, const int32_t* orig, const int32_t* chain_len, const unsigned char* scan_class /* nullable */, int64_t n, unsigned char* kwire);
 int launch_order_blocks_by_chain(hipStream_t s, int32_t* orig, const unsigned char* kwire, int64_t n);
 // re-use the placement (p.orig) of an earlier step: only gather the records into the SoA arrays
@@ -157,6 +158,7 @@ int launch_add_mark(hipStream_t s, double* y, const double* x, size_t n, unsigne
 int launch_finalize_cells(hipStream_t s, int32_t n_cells, const double* vol, double* pvol_acc, double* up_acc,
                           unsigned char* touched, double* alpha, double* uParticle, double* R /* nullable: cell records whose alpha slot follows */);
 // the force pass gathers one 64-byte record per stencil cell: {U[3], alpha, A[3] = 2 nu rho_f divT - gradP, V} (k_pack_cells)
+constexpr int kRecDoubles = 8;           // CellRec: Ux Uy Uz alpha | Ax Ay Az V
 int launch_pack_cells(hipStream_t s, int64_t n_field, const double* U, const double* alpha, const double* gradP, const double* divT, const double* vol,
                       double nu, double rhoF, double* R);
 int launch_patch_rec_alpha(hipStream_t s, int64_t c0, int64_t n, const double* alpha, double* R);    // alpha slot of cells [c0, c0 + n)
