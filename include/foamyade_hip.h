@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 19
+#define FY_ABI_VERSION 20
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -312,6 +312,13 @@ typedef struct fy_thermal_desc {
     int32_t T_convection_scheme;    /* div(phi,T) / div(alphaPhic,T): FY_CONVECTION_LINEAR | FY_CONVECTION_UPWIND */
     double T_tol, T_rel_tol; int32_t T_max_iter;      /* solvers.T: not both tolerances zero, T_max_iter >= 1 */
     double particle_temperature;    /* Tp of every particle of a batch nobody gave temperatures (fy_solver_set_particle_temperatures_*) */
+    /* The thermal loop (all three zero: off, the caller owns Tp and T is a passive scalar).
+       particle_cp > 0 [J/kg/K; needs rho_particle > 0]: the library integrates Tp per particle, m_p c_pp dTp/dt = q_p with m_p = rho_particle (4/3) pi r^3, backward Euler
+       for the particle-fluid pair: r_p = dt hA / (m_p c_pp), hA' = hA / (1 + r_p) takes hA's place in Sp / Su / q above and Tp += dt q / (m_p c_pp) after the T solve
+       (dt: the step's own delta_t).  A particle nobody located keeps its Tp.
+       beta [1/K], T_ref: Boussinesq buoyancy a_c = (-beta (T_c - T_ref)) g with the T the step found, added to uSource where the momentum equations read it (ico:
+       the assembly; pimple: phicForces and the predictor's right-hand side, beside g); field "buoyancy" [n][3], kernel clock "buoyancy".  Off with beta == 0 or g == 0. */
+    double particle_cp, beta, T_ref;
 } fy_thermal_desc;
 
 typedef struct fy_case_desc {
@@ -434,11 +441,18 @@ int fy_solver_set_average_state(fy_solver*, int item, int64_t samples, double ti
  * batch or until the batch's particle count changes (then the uniform value again).  q[n]: W into each particle over the last step, wire order, 0 for a particle
  * nobody located.  Stats of the last step: Jacobi passes and initial residual of the T solve, heat_to_particles_W = sum of q over all batches (summed on the device when asked for: pass NULL to skip it).
  * While thermal is on, "T" [n], "heatSp" [n] (W/K) and "heatSu" [n] (W) are field names of fy_solver_read/write_field_host (the sources: the last step's), "T" one that
- * fieldAverage accepts, and "heat_coeff", "heat_flux", "T_assemble" kernel clocks of fy_solver_get_kernel_timing. */
+ * fieldAverage accepts, and "heat_coeff", "heat_flux", "T_assemble" kernel clocks of fy_solver_get_kernel_timing; with thermal.beta != 0 and g != 0 also the field "buoyancy" [n][3]
+ * (the acceleration the last step added to the momentum source) and the clock "buoyancy". */
 int fy_solver_set_particle_temperatures_host(fy_solver*, int batch, const double* Tp);
 int fy_solver_set_particle_temperatures_device(fy_solver*, int batch, const double* d_Tp);
 int fy_solver_get_particle_heat_host(fy_solver*, int batch, double* q);
 int fy_solver_get_thermal_stats(fy_solver*, int32_t* iterations, double* initial_residual, double* heat_to_particles_W);
+/* The batch's particle temperatures as they stand now, Tp[n] in wire order for the n particles the batch holds (NULL: `batch` is not looked at), and the solver's count of resets (NULL: skip).
+ * With thermal.particle_cp > 0 the library owns one Tp array per batch: made at the batch's first step from thermal.particle_temperature or from what
+ * fy_solver_set_particle_temperatures_* gave (which then sets the CURRENT temperatures; NULL there re-initialises to the uniform value), advanced by every step, kept while
+ * the batch's particle count is unchanged -- a particle's identity is its place in the wire order.  When the count changes the batch falls back to the uniform value and
+ * the reset counter goes up by one.  With particle_cp == 0: what the caller set, or the uniform value.  FY_ERR_INVALID on a solver without heat transfer. */
+int fy_solver_get_particle_thermal_state(fy_solver*, int batch, double* Tp, int64_t* resets);
 
 /* ---- OpenFOAM case directories (what the reference's executables get from runTime / mesh / the field constructors, createFields.H
  * of both solvers, and give back with runTime.write()).  Supported subset: ONE axis-aligned blockMesh hex block of uniform cubes whose

@@ -171,7 +171,8 @@ class ThermalDesc(C.Structure):
     """fy_thermal_desc: the fluid temperature equation and the particle-fluid heat exchange of a solver (all zero: off)"""
     _fields_ = [("on", C.c_int32), ("cp", C.c_double), ("kappa", C.c_double), ("prt", C.c_double), ("nusselt_law", C.c_int32),
                 ("T_initial", C.c_double), ("T_bc", C.c_int32 * 6), ("T_value", C.c_double * 6), ("T_convection_scheme", C.c_int32),
-                ("T_tol", C.c_double), ("T_rel_tol", C.c_double), ("T_max_iter", C.c_int32), ("particle_temperature", C.c_double)]
+                ("T_tol", C.c_double), ("T_rel_tol", C.c_double), ("T_max_iter", C.c_int32), ("particle_temperature", C.c_double),
+                ("particle_cp", C.c_double), ("beta", C.c_double), ("T_ref", C.c_double)]
 
 
 NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
@@ -179,14 +180,16 @@ BC_T_ZERO_GRADIENT, BC_T_FIXED_VALUE = 0, 1
 
 
 def thermal_desc(cp, kappa, T_initial=0.0, T_bc=(0,) * 6, T_value=(0.0,) * 6, nusselt_law=NUSSELT_RANZ_MARSHALL, prt=1.0, T_convection_scheme=0,
-                 T_tol=1e-8, T_rel_tol=0.0, T_max_iter=1000, particle_temperature=0.0):
-    """a switched-on fy_thermal_desc (assign it to CaseDesc.thermal, or pass it to make_case as thermal=...)"""
+                 T_tol=1e-8, T_rel_tol=0.0, T_max_iter=1000, particle_temperature=0.0, particle_cp=0.0, beta=0.0, T_ref=0.0):
+    """a switched-on fy_thermal_desc (assign it to CaseDesc.thermal, or pass it to make_case as thermal=...).  particle_cp > 0: the library integrates the particle
+    temperatures; beta != 0: Boussinesq buoyancy about T_ref"""
     d = ThermalDesc()
     d.on, d.cp, d.kappa, d.prt, d.nusselt_law, d.T_initial = 1, cp, kappa, prt, int(nusselt_law), T_initial
     for q in range(6):
         d.T_bc[q] = int(T_bc[q])
         d.T_value[q] = float(T_value[q])
     d.T_convection_scheme, d.T_tol, d.T_rel_tol, d.T_max_iter, d.particle_temperature = int(T_convection_scheme), T_tol, T_rel_tol, int(T_max_iter), particle_temperature
+    d.particle_cp, d.beta, d.T_ref = particle_cp, beta, T_ref
     return d
 
 
@@ -350,6 +353,7 @@ def lib():
     L.fy_solver_set_particle_temperatures_device.argtypes = [vp, C.c_int, vp]
     L.fy_solver_get_particle_heat_host.argtypes = [vp, C.c_int, _dp]
     L.fy_solver_get_thermal_stats.argtypes = [vp, C.POINTER(C.c_int32), _dp, _dp]
+    L.fy_solver_get_particle_thermal_state.argtypes = [vp, C.c_int, _dp, C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -798,6 +802,18 @@ class Solver(_Averages):
             Tp = np.ascontiguousarray(Tp, dtype=np.float64).ravel()
             assert Tp.size == self._batch_n[batch]
             _check(L.fy_solver_set_particle_temperatures_host(self._h, int(batch), _d(Tp)))
+
+    def particle_temperatures(self, batch=0):
+        """the batch's particle temperatures as they stand now, wire order: what the library integrates (thermal particle_cp > 0), else what was set or the uniform value"""
+        Tp = np.zeros(self._batch_n[batch])
+        _check(lib().fy_solver_get_particle_thermal_state(self._h, int(batch), _d(Tp) if Tp.size else None, None))
+        return Tp
+
+    def particle_temperature_resets(self):
+        """how often a batch's temperature array was dropped because its particle count changed"""
+        n = C.c_int64(0)
+        _check(lib().fy_solver_get_particle_thermal_state(self._h, 0, None, C.byref(n)))
+        return n.value
 
     def particle_heat(self, batch=0):
         """W into each particle of the batch over the last step, wire order"""

@@ -868,14 +868,15 @@ int read_coupling_properties(fy_foam_case* c) {
             return fail(FY_ERR_UNSUPPORTED, "%s: %s %s; %s accepts %s", path.c_str(), sw.key, w.c_str(), solver, gaussian ? "on | off" : "off");
         if (on) c->desc.force_models |= sw.flag;
     }
-    // heatTransfer { active; nusseltModel; Cp; kappa; Prt; particleTemperature; }: the fluid temperature equation and the particles' heat exchange
-    // (fy_thermal_desc); 0/T, div(phi,T) | div(alphaPhic,T) and solvers.T complete it (read_controls, read_fields)
+    // heatTransfer { active; nusseltModel; Cp; kappa; Prt; particleTemperature; particleCp; beta; TRef; }: the fluid temperature equation, the particles' heat
+    // exchange and, with the last three, particle temperatures that evolve and Boussinesq buoyancy (fy_thermal_desc); 0/T, div(phi,T) | div(alphaPhic,T) and solvers.T complete it (read_controls, read_fields)
     if (d.has("heatTransfer")) {
         const FoamDict* h = d.subdict("heatTransfer");
-        if (!h) return fail(FY_ERR_INVALID, "%s: heatTransfer must be a dictionary { active; nusseltModel; Cp; kappa; Prt; particleTemperature; }", path.c_str());
+        if (!h) return fail(FY_ERR_INVALID, "%s: heatTransfer must be a dictionary { active; nusseltModel; Cp; kappa; Prt; particleTemperature; particleCp; beta; TRef; }", path.c_str());
         for (const std::string& k : h->order)
-            if (k != "active" && k != "nusseltModel" && k != "Cp" && k != "kappa" && k != "Prt" && k != "particleTemperature")
-                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.%s is not an entry this reader knows (active, nusseltModel, Cp, kappa, Prt, particleTemperature)", path.c_str(), k.c_str());
+            if (k != "active" && k != "nusseltModel" && k != "Cp" && k != "kappa" && k != "Prt" && k != "particleTemperature" && k != "particleCp" && k != "beta" && k != "TRef")
+                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.%s is not an entry this reader knows (active, nusseltModel, Cp, kappa, Prt, particleTemperature, particleCp, beta, TRef)",
+                            path.c_str(), k.c_str());
         bool active = true;
         if (h->has("active") && !h->boolean("active", &active)) { h->word("active", &w); return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.active %s; accepts on | off", path.c_str(), w.c_str()); }
         if (active) {
@@ -894,6 +895,14 @@ int read_coupling_properties(fy_foam_case* c) {
             if (h->has("Prt") && (!h->scalar("Prt", &t.prt) || !(t.prt > 0))) return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.Prt must be a positive number", path.c_str());
             if (h->has("particleTemperature") && !h->scalar("particleTemperature", &t.particle_temperature))
                 return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.particleTemperature must be a number (the uniform temperature of the particles, K)", path.c_str());
+            if (h->has("particleCp") && (!h->scalar("particleCp", &t.particle_cp) || !(t.particle_cp >= 0)))
+                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.particleCp must be a number that is not negative (the particles' specific heat in J/kg/K; 0: their temperatures stay as given)", path.c_str());
+            if (h->has("beta") && (!h->scalar("beta", &t.beta) || !std::isfinite(t.beta)))
+                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.beta must be a number (the thermal expansion coefficient in 1/K; 0: no buoyancy)", path.c_str());
+            if (h->has("TRef") && (!h->scalar("TRef", &t.T_ref) || !std::isfinite(t.T_ref)))
+                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.TRef must be a number (the temperature at which the buoyancy vanishes, K)", path.c_str());
+            if (t.beta != 0.0 && !h->has("TRef"))
+                return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.beta %g needs heatTransfer.TRef, the temperature at which the buoyancy vanishes", path.c_str(), t.beta);
             t.T_convection_scheme = FY_CONVECTION_LINEAR;
         }
     }

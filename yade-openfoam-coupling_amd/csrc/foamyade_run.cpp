@@ -229,8 +229,9 @@ int main(int argc, char** argv) {
                     "patches", info.patch_of_side[0], info.patch_of_side[1], info.patch_of_side[2], info.patch_of_side[3], info.patch_of_side[4], info.patch_of_side[5]);
     if (master) { print_coupling(cd.drag_law, cd.force_models); print_functions(fc, cd.average); }
     if (master && cd.thermal.on)
-        std::printf("Heat transfer: nusseltModel %s, Cp %g, kappa %g, Prt %g, particleTemperature %g, div(T) %s\n", cd.thermal.nusselt_law == FY_NUSSELT_GUNN ? "Gunn" : "RanzMarshall",
-                    cd.thermal.cp, cd.thermal.kappa, cd.thermal.prt, cd.thermal.particle_temperature, cd.thermal.T_convection_scheme == FY_CONVECTION_UPWIND ? "upwind" : "linear");
+        std::printf("Heat transfer: nusseltModel %s, Cp %g, kappa %g, Prt %g, particleTemperature %g, particleCp %g, beta %g, TRef %g, div(T) %s\n",
+                    cd.thermal.nusselt_law == FY_NUSSELT_GUNN ? "Gunn" : "RanzMarshall", cd.thermal.cp, cd.thermal.kappa, cd.thermal.prt, cd.thermal.particle_temperature,
+                    cd.thermal.particle_cp, cd.thermal.beta, cd.thermal.T_ref, cd.thermal.T_convection_scheme == FY_CONVECTION_UPWIND ? "upwind" : "linear");
     fy_solver* s = nullptr;
     if ((comm ? fy_solver_create_slab(&cd, trp, device, comm, &s) : fy_solver_create(&cd, trp, device, &s)) != FY_OK) return die("fy_solver_create");
     // a slab owns the z-planes [srank nz / ssize, (srank + 1) nz / ssize): a contiguous run of the block's cells, `first` cells in
@@ -291,6 +292,7 @@ int main(int argc, char** argv) {
     const long n_steps = std::lround((info.end_time - info.start_time) / info.delta_t);
     double t = info.start_time;
     double dt_now = info.delta_t;                      // Time::run(): value() < endTime - 0.5 deltaT [OF-6 Time.C], with the deltaT setDeltaT.H left
+    int64_t tp_resets = 0;                             // batches whose particle temperatures fell back to particleTemperature so far (heatTransfer.particleCp)
     for (long k = 1; cd.adjust_time_step ? t < info.end_time - 0.5 * dt_now : k <= n_steps; ++k) {
         if (fy_solver_step(s) != FY_OK) return die("fy_solver_step");
         fy_step_stats st;
@@ -303,6 +305,13 @@ int main(int argc, char** argv) {
             std::printf("Time = %s\n\nCourant Number mean: %g max: %g\n", tname, st.courant_mean, st.courant_max);
             std::printf("pressure: %d solves, %d iterations, initial residual %g, final residual %g\n", st.p_solves, st.p_iters_total, st.p_initial_residual, st.p_final_residual);
             std::printf("time step continuity errors : sum local = %g, global = %g, cumulative = %g\n\n", st.cont_err_sum_local, st.cont_err_global, st.cont_err_cumulative);
+        }
+        if (cd.thermal.on) {
+            int64_t now = tp_resets;
+            if (fy_solver_get_particle_thermal_state(s, 0, nullptr, &now) != FY_OK) return die("fy_solver_get_particle_thermal_state");
+            if (master && now > tp_resets)
+                std::printf("Particle temperatures: %lld batch(es) changed their particle count and fell back to particleTemperature\n\n", (long long)(now - tp_resets));
+            tp_resets = now;
         }
         if (info.write_interval_steps > 0 && k % info.write_interval_steps == 0)
             if (write_time(tname) != FY_OK) return die("writing the time directory");

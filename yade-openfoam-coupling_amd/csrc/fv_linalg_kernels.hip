@@ -952,7 +952,26 @@ __global__ __launch_bounds__(256) void k_add(double* __restrict__ y, const doubl
     if (i < n) y[i] += x[i];
 }
 
+// Boussinesq buoyancy (fy_thermal_desc.beta): a_c = (-beta (T_c - T_ref)) g, and the momentum equations' source uSource + a.  One thread per component of a cell
+__global__ __launch_bounds__(256) void k_buoyancy(size_t n3, const double* __restrict__ T, double beta, double T_ref, double gx, double gy, double gz,
+                                                  const double* __restrict__ uSource, double* __restrict__ a_out, double* __restrict__ sum_out) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n3) return;
+    const size_t c = e / 3;
+    const int q = (int)(e - 3 * c);
+    const double a = (-beta * (T[c] - T_ref)) * (q == 0 ? gx : q == 1 ? gy : gz);
+    a_out[e] = a;
+    sum_out[e] = uSource[e] + a;
+}
+
 }  // namespace
+
+int launch_buoyancy(hipStream_t s, size_t n_cells, const double* T, double beta, double T_ref, const double* g, const double* uSource, double* a, double* sum) {
+    if (!n_cells) return FY_OK;
+    hipLaunchKernelGGL(k_buoyancy, dim3(div_up(3 * n_cells, 256)), dim3(256), 0, s, 3 * n_cells, T, beta, T_ref, g[0], g[1], g[2], uSource, a, sum);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
 
 int launch_reduce_finalize(hipStream_t s, const double* partials, int n_cells, int nslots, const int* ops, double* out, unsigned long long* flag,
                            unsigned long long seq) {

@@ -68,5 +68,7 @@ int launch_relax_field(hipStream_t s, double* x, const double* prev, double alph
 int launch_mg_coarsen_ghost(hipStream_t s, PMat F, PMat C);
 // y += x on a contiguous range (reverse-halo accumulation)
 int launch_add_f64(hipStream_t s, double* y, const double* x, size_t n);
+// Boussinesq buoyancy: a[3 n] = (-beta (T - T_ref)) g per cell, sum[3 n] = uSource + a (g: three host doubles)
+int launch_buoyancy(hipStream_t s, size_t n_cells, const double* T, double beta, double T_ref, const double* g, const double* uSource, double* a, double* sum);
 
 }  // namespace fy

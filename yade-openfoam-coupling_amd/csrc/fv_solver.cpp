@@ -714,6 +714,8 @@ int Solver::step() {
     }
     if (timing) { tim[0].stop(stream); }
     if (th.on) FY_TRY(heat_coefficients());       // the stencils, the cell records and U are still what the force pass saw
+    if (th.buoyant) FY_TRY(buoyancy());           // uSource is what the coupling left, T what the step found
+    const double* usrc = momentum_source();       // uSource [+ the buoyant acceleration]
     comm->tag = "momentum";
 
     // alphac.oldTime() is captured lazily by OpenFOAM at alphac.correctBoundaryConditions() (pimpleFoamYade.C:83), i.e. after
@@ -749,7 +751,7 @@ int Solver::step() {
             FY_TRY(FVK(launch_grad_magsqr, stream, g, U.p, gradL.p));
             FY_TRY(halo_cells(gradL, 3, 1));
         }
-        FY_TRY(FVK(launch_assemble_momentum, stream, g, U.p, Uold.p, alpha.p, /* alphaOld */ alpha.p, face_arrays ? C3(alphaf) : CFace3{}, phi_now(), uSource.p, uSourceDrag.p,
+        FY_TRY(FVK(launch_assemble_momentum, stream, g, U.p, Uold.p, alpha.p, /* alphaOld */ alpha.p, face_arrays ? C3(alphaf) : CFace3{}, phi_now(), usrc, uSourceDrag.p,
                                         divG.p, g.upwind >= 3 ? gradL.p : vGrad.p, M7(), src.p, rAU.p));
         rAU_new = true; hbya_ready = false;
         // pimple: rAUcf, phicForces and the predictor's right-hand side in one sweep (k_bmom_faces); uSource ghosts refreshed by the coupling
@@ -759,11 +761,11 @@ int Solver::step() {
             if (cpl->c.slab.tail_pending) { FY_HIP(hipStreamWaitEvent(stream, cpl->c.slab.ev_tail, 0)); cpl->c.slab.tail_pending = false; }
             if (bmom_fused) {
                 FY_TRY(overlapped(XW_MOMENTUM, true, [&](hipStream_t on) { return halo_cells(rAU, 1, 1, on); }, [&](const FvGeo& gw) {
-                    return FVK(launch_bmom_faces, stream, gw, rAU.p, uSource.p, src.p, p.p, C3(psn), face_arrays ? F3(rAUf) : Face3{}, F3(phiForces), bmom.p);
+                    return FVK(launch_bmom_faces, stream, gw, rAU.p, usrc, src.p, p.p, C3(psn), face_arrays ? F3(rAUf) : Face3{}, F3(phiForces), bmom.p);
                 }));
             } else {
                 FY_TRY(halo_cells(rAU, 1, 1));
-                FY_TRY(FVK(launch_rAUf_phi_forces, stream, g, rAU.p, uSource.p, F3(rAUf), F3(phiForces)));
+                FY_TRY(FVK(launch_rAUf_phi_forces, stream, g, rAU.p, usrc, F3(rAUf), F3(phiForces)));
             }
         }
         if (cs.momentum_predictor) {
@@ -801,7 +803,7 @@ int Solver::step() {
         st.ms_other = st.ms_total - st.ms_particle - st.ms_momentum - st.ms_pressure;
         for (auto& k : kc) k.collect();
         avg.clock.collect();
-        if (th.on) { th.clk_coeff.collect(); th.clk_flux.collect(); th.clk_asm.collect(); }
+        if (th.on) { th.clk_coeff.collect(); th.clk_flux.collect(); th.clk_asm.collect(); th.clk_buoy.collect(); }
     }
     if (xwait_timing) {
         for (auto& k : clk_xwait) k.collect();
@@ -822,6 +824,12 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
         if (!th.on) return fail(FY_ERR_INVALID, "solver field '%s' does not exist in this case (fy_case_desc.thermal is off)", s.c_str());
         *ptr = (s == "T" ? th.T.p : s == "heatSp" ? th.Sp.p : th.Su.p) + g.c0;
         *count = n;
+        return FY_OK;
+    }
+    if (s == "buoyancy") {
+        if (!th.buoyant) return fail(FY_ERR_INVALID, "solver field 'buoyancy' does not exist in this case (fy_case_desc.thermal.beta or g is zero)");
+        *ptr = th.buoy.p + 3 * (size_t)g.c0;
+        *count = 3 * n;
         return FY_OK;
     }
     for (const E& e : tab) if (s == e.nm) {

@@ -42,7 +42,8 @@ struct MgLev {
 // Fluid temperature and particle-fluid heat exchange (fy_thermal_desc; fv_thermal.cpp).  Off: nothing allocated, nothing launched.  Three phases in Solver::step():
 //   heat_coefficients()  after setParticleAction: Sp / Su cleared, then per batch hA and the scatter (k_heat_coeff_*), from the stencils and cell records the force pass used
 //   solve_temperature()  after the last corrector and turbulence_correct(): k_assemble_scalar into the momentum matrix's storage, solve_vec3, T
-//   heat_fluxes()        per batch q = hA (sum w T - Tp) with the new T (k_heat_flux_*)
+//   heat_fluxes()        per batch q = hA (sum w T - Tp) with the new T (k_heat_flux_*); with particle_cp > 0 the same kernel advances Tp
+// and, with beta != 0 and g != 0, buoyancy() between the first and the momentum assembly
 struct Thermal {
     bool on = false;
     fy_thermal_desc d{};
@@ -53,15 +54,21 @@ struct Thermal {
     struct PerBatch {
         DevBuf<double> hA, Tp, q;        // wire order
         int64_t n = 0;                   // particles hA / q were formed for (the last step's count)
-        bool has_tp = false;             // Tp holds the caller's temperatures for tp_n particles; otherwise d.particle_temperature
+        // Tp holds temperatures for tp_n particles: the caller's, or (own_tp) the ones the library integrates; otherwise d.particle_temperature
+        bool has_tp = false;
         int64_t tp_n = 0;
     };
     std::vector<std::unique_ptr<PerBatch> > pb;
-    KernelClock clk_coeff, clk_flux, clk_asm;      // "heat_coeff", "heat_flux", "T_assemble" of fy_solver_get_kernel_timing
+    bool own_tp = false;                 // d.particle_cp > 0: k_heat_coeff_* / k_heat_flux_*<true> advance each batch's Tp
+    int64_t tp_resets = 0;               // batches whose Tp array was dropped because their particle count changed
+    // Boussinesq buoyancy (d.beta != 0 and g != 0): a [3 nstore], and uSource + a, what the momentum equations read in uSource's place
+    bool buoyant = false;
+    DevBuf<double> buoy, usrc_sum;
+    KernelClock clk_coeff, clk_flux, clk_asm, clk_buoy;      // "heat_coeff", "heat_flux", "T_assemble", "buoyancy" of fy_solver_get_kernel_timing
     int iters = 0;
     double res0 = 0.0;
     PerBatch& batch(size_t bi) { while (pb.size() <= bi) pb.emplace_back(new PerBatch()); return *pb[bi]; }
-    ~Thermal() { clk_coeff.destroy(); clk_flux.destroy(); clk_asm.destroy(); }
+    ~Thermal() { clk_coeff.destroy(); clk_flux.destroy(); clk_asm.destroy(); clk_buoy.destroy(); }
 };
 
 struct Solver {
@@ -307,7 +314,11 @@ struct Solver {
     int heat_coefficients();
     int solve_temperature();
     int heat_fluxes();
+    int buoyancy();                                     // a from the T the step found, and uSource + a (after heat_coefficients, before the first momentum assembly)
+    const double* momentum_source() const { return th.buoyant ? th.usrc_sum.p : uSource.p; }
+    void sync_particle_temperatures(size_t bi, int64_t n);      // drops a Tp array held for another particle count (counted in th.tp_resets)
     int set_particle_temperatures(int batch, const double* tp, bool on_device);
+    int get_particle_thermal_state(int batch, double* tp, int64_t* resets);
     int get_particle_heat(int batch, double* q);
     int thermal_stats(int32_t* iterations, double* initial_residual, double* heat_to_particles_W);
     // field lookup; cell fields are returned/accepted as the OWNED part only (ghost planes are an implementation detail)

@@ -141,7 +141,7 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
             return FY_OK;
         }
     }
-    if (name && (std::strcmp(name, "T") == 0 || std::strcmp(name, "heatSp") == 0 || std::strcmp(name, "heatSu") == 0)) {      // the temperature equation's fields: nothing of the flow depends on them
+    if (name && (std::strcmp(name, "T") == 0 || std::strcmp(name, "heatSp") == 0 || std::strcmp(name, "heatSu") == 0 || std::strcmp(name, "buoyancy") == 0)) {      // the temperature equation's fields: the flux and the carried sums stand
         FY_HIP(hipStreamSynchronize(s->s.stream));
         return FY_OK;
     }
@@ -169,6 +169,7 @@ int fy_solver_set_average_state(fy_solver* s, int item, int64_t samples, double 
 int fy_solver_set_particle_temperatures_host(fy_solver* s, int batch, const double* Tp) { FY_S(s); return s->s.set_particle_temperatures(batch, Tp, false); }
 int fy_solver_set_particle_temperatures_device(fy_solver* s, int batch, const double* d_Tp) { FY_S(s); return s->s.set_particle_temperatures(batch, d_Tp, true); }
 int fy_solver_get_particle_heat_host(fy_solver* s, int batch, double* q) { FY_S(s); return s->s.get_particle_heat(batch, q); }
+int fy_solver_get_particle_thermal_state(fy_solver* s, int batch, double* Tp, int64_t* resets) { FY_S(s); return s->s.get_particle_thermal_state(batch, Tp, resets); }
 int fy_solver_get_thermal_stats(fy_solver* s, int32_t* iterations, double* initial_residual, double* heat_to_particles_W) {
     FY_S(s);
     return s->s.thermal_stats(iterations, initial_residual, heat_to_particles_W);
@@ -242,7 +243,7 @@ int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     FY_S(s);
     for (auto& k : s->s.kc) { k.reset(); k.on = on != 0; }
     s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
-    for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
+    for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm, &s->s.th.clk_buoy}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
     return FY_OK;
 }
 
@@ -264,8 +265,8 @@ int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_
     FY_S(s);
     const std::string k = kernel ? kernel : "";
     if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }
-    if ((k == "heat_coeff" || k == "heat_flux" || k == "T_assemble") && total_ms && launches) {
-        const fy::KernelClock& c = k == "heat_coeff" ? s->s.th.clk_coeff : k == "heat_flux" ? s->s.th.clk_flux : s->s.th.clk_asm;
+    if ((k == "heat_coeff" || k == "heat_flux" || k == "T_assemble" || k == "buoyancy") && total_ms && launches) {
+        const fy::KernelClock& c = k == "heat_coeff" ? s->s.th.clk_coeff : k == "heat_flux" ? s->s.th.clk_flux : k == "T_assemble" ? s->s.th.clk_asm : s->s.th.clk_buoy;
         *total_ms = c.total_ms; *launches = c.launches;
         return FY_OK;
     }

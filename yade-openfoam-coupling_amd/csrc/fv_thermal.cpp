@@ -21,6 +21,10 @@ int Solver::thermal_create(const fy_case_desc* c) {
     if (!(d.T_tol >= 0) || !(d.T_rel_tol >= 0) || !(d.T_tol > 0 || d.T_rel_tol > 0) || d.T_max_iter < 1)
         return fail(FY_ERR_INVALID, "fy_solver_create: thermal needs T_tol >= 0 and T_rel_tol >= 0 with at least one of them positive, and T_max_iter >= 1 (got %g, %g, %d)", d.T_tol, d.T_rel_tol,
                     d.T_max_iter);
+    if (!(d.particle_cp >= 0)) return fail(FY_ERR_INVALID, "fy_solver_create: thermal.particle_cp must not be negative (got %g; 0: the caller owns the particle temperatures)", d.particle_cp);
+    if (d.particle_cp > 0 && !(c->rho_particle > 0))
+        return fail(FY_ERR_INVALID, "fy_solver_create: thermal.particle_cp %g needs rho_particle > 0 for the particles' heat capacity (got %g)", d.particle_cp, c->rho_particle);
+    if (!std::isfinite(d.beta) || !std::isfinite(d.T_ref)) return fail(FY_ERR_INVALID, "fy_solver_create: thermal.beta and thermal.T_ref must be finite (got %g, %g)", d.beta, d.T_ref);
     th.d = d;
     th.eq = ScalarEqn{};
     th.eq.upwind = d.T_convection_scheme == FY_CONVECTION_UPWIND ? 1 : 0;
@@ -33,10 +37,13 @@ int Solver::thermal_create(const fy_case_desc* c) {
     th.eq.rPrt = 1.0 / (d.prt > 0 ? d.prt : 1.0);
     th.eq.rRhoCp = 1.0 / (c->rho_fluid * d.cp);
     const double Pr = c->nu * c->rho_fluid * d.cp / d.kappa;
-    th.hp = HeatParams{c->nu, 1e-09, d.kappa, std::cbrt(Pr), d.particle_temperature, d.nusselt_law};      // (small: the force laws', ForceParams)
+    th.own_tp = d.particle_cp > 0;
+    th.hp = HeatParams{c->nu, 1e-09, d.kappa, std::cbrt(Pr), d.particle_temperature, d.nusselt_law, c->dt, c->rho_particle * d.particle_cp};      // (small: the force laws', ForceParams)
     DevBuf<double>* bs[] = {&th.T, &th.Sp, &th.Su};
     for (auto* b : bs) { FY_TRY(b->alloc_exact(nstore)); FY_TRY(zero(*b)); }
     FY_TRY(launch_fill_f64(stream, th.T.p, nstore, d.T_initial));
+    th.buoyant = d.beta != 0.0 && (c->g[0] != 0.0 || c->g[1] != 0.0 || c->g[2] != 0.0);
+    if (th.buoyant) { FY_TRY(th.buoy.alloc_exact(3 * nstore)); FY_TRY(zero(th.buoy)); FY_TRY(th.usrc_sum.alloc_exact(3 * nstore)); FY_TRY(zero(th.usrc_sum)); }
     FY_HIP(hipStreamSynchronize(stream));
     th.on = true;
     return FY_OK;
@@ -47,6 +54,7 @@ int Solver::heat_coefficients() {
     Coupling& C = cpl->c;
     FY_TRY(zero(th.Sp)); FY_TRY(zero(th.Su));
     const CellWindow cw{0, (int64_t)nstore};
+    th.hp.dt = cs.dt;                                          // (the step's own delta_t: adjust_time_step)
     for (size_t bi = (size_t)C.n_batches; bi < th.pb.size(); ++bi) th.pb[bi]->n = 0;      // (batches that are gone)
     th.clk_coeff.begin(stream);
     for (int bi = 0; bi < C.n_batches; ++bi) {
@@ -55,7 +63,12 @@ int Solver::heat_coefficients() {
         t.n = b.n;
         if (b.n == 0) continue;
         FY_TRY(t.hA.reserve((size_t)b.n)); FY_TRY(t.q.reserve((size_t)b.n));
-        if (t.has_tp && t.tp_n != b.n) t.has_tp = false;      // another population: the uniform temperature again
+        sync_particle_temperatures((size_t)bi, b.n);           // another population: the uniform temperature again
+        if (th.own_tp && !t.has_tp) {                          // the batch's first step: the array the library advances from here on
+            FY_TRY(t.Tp.reserve((size_t)b.n));
+            FY_TRY(launch_fill_f64(stream, t.Tp.p, (size_t)b.n, th.hp.tp_uniform));
+            t.has_tp = true; t.tp_n = b.n;
+        }
         const double* tp = t.has_tp ? t.Tp.p : nullptr;
         if (C.gaussian) {
             // the momentum back-scatter's buckets, with the capacities formed from the demand its pass has just counted (k_tile_caps on the side stream at the end of
@@ -95,11 +108,48 @@ int Solver::heat_fluxes() {
         Batch& b = *C.batches[(size_t)bi];
         Thermal::PerBatch& t = th.batch((size_t)bi);
         if (b.n == 0) continue;
-        const double* tp = t.has_tp ? t.Tp.p : nullptr;
-        if (C.gaussian) FY_TRY(launch_heat_flux_gaussian(stream, C.soa_of(b), b.n, cw, th.T.p, th.hp.tp_uniform, tp, t.hA.p, t.q.p));
-        else FY_TRY(launch_heat_flux_point(stream, b.n, b.incell.p, cw, th.T.p, th.hp.tp_uniform, tp, t.hA.p, t.q.p));
+        double* tp = t.has_tp ? t.Tp.p : nullptr;              // (own_tp: heat_coefficients made it)
+        if (th.own_tp && (!tp || t.tp_n != b.n)) return fail(FY_ERR_INVALID, "fy_solver_step: heat exchange: batch %d has no temperature array of this step", bi);
+        if (C.gaussian) FY_TRY(launch_heat_flux_gaussian(stream, C.soa_of(b), b.n, cw, th.T.p, th.hp, tp, t.hA.p, t.q.p));
+        else FY_TRY(launch_heat_flux_point(stream, b.d_rec, b.n, b.incell.p, cw, th.T.p, th.hp, tp, t.hA.p, t.q.p));
     }
     th.clk_flux.end(stream);
+    return FY_OK;
+}
+
+// Boussinesq buoyancy, once per step: a from T as the step found it, kept for all outer correctors, and the sum the momentum equations read in uSource's place
+int Solver::buoyancy() {
+    th.clk_buoy.begin(stream);
+    FY_TRY(launch_buoyancy(stream, nstore, th.T.p, th.d.beta, th.d.T_ref, cs.g, uSource.p, th.buoy.p, th.usrc_sum.p));
+    th.clk_buoy.end(stream);
+    return FY_OK;
+}
+
+void Solver::sync_particle_temperatures(size_t bi, int64_t n) {
+    Thermal::PerBatch& t = th.batch(bi);
+    if (!t.has_tp || t.tp_n == n) return;
+    t.has_tp = false;
+    ++th.tp_resets;
+}
+
+int Solver::get_particle_thermal_state(int batch, double* tp, int64_t* resets) {
+    if (!th.on) return fail(FY_ERR_INVALID, "fy_solver_get_particle_thermal_state: this solver has no heat transfer (fy_case_desc.thermal is off)");
+    Coupling& C = cpl->c;
+    if (!tp) { if (resets) *resets = th.tp_resets; return FY_OK; }      // (the counter alone: no batch is looked at)
+    if (batch < 0 || batch >= C.n_batches) return fail(FY_ERR_INVALID, "fy_solver_get_particle_thermal_state: batch %d of %d", batch, C.n_batches);
+    const int64_t n = C.batches[(size_t)batch]->n;
+    sync_particle_temperatures((size_t)batch, n);
+    if (n > 0) {
+        Thermal::PerBatch& t = th.batch((size_t)batch);
+        if (t.has_tp) {
+            FY_HIP(hipSetDevice(device));
+            FY_HIP(hipMemcpyAsync(tp, t.Tp.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+            FY_HIP(hipStreamSynchronize(stream));
+        } else {
+            std::fill(tp, tp + n, th.hp.tp_uniform);
+        }
+    }
+    if (resets) *resets = th.tp_resets;
     return FY_OK;
 }
 

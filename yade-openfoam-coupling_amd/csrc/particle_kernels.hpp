@@ -193,18 +193,19 @@ struct HeatParams {
     double kappa, pr13;            // fluid conductivity, Pr^(1/3)
     double tp_uniform;
     int law;                       // FY_NUSSELT_*
+    double dt, rho_cpp;            // the step's delta_t and rho_particle particle_cp; rho_cpp == 0: the caller owns Tp, > 0: the library integrates it (the kernels' kOwn variant)
 };
 // pass A: hA = Nu kappa pi d per particle; Sp[c] += w hA, Su[c] += w hA Tp through the LDS table and tb's tile buckets, which are reduced and whose demand counters are
 // reset here; a table entry that finds no room in its bucket goes out as two global atomics (flush_table's rule).  tb: the momentum back-scatter's buckets with capacities
 // formed AFTER that pass (demand counters at zero).  R: the force pass's cell records.  A particle without a stencil gets hA = 0
 int launch_heat_coeff_gaussian(hipStream_t s, ParticleSoA p, int64_t n, HeatParams hp, CellWindow cw, const double* R, const double* Tp, double* hA, double* Sp, double* Su,
                                TileBuckets tb);
-// pass B: q = hA (sum w T[c] - Tp)
-int launch_heat_flux_gaussian(hipStream_t s, ParticleSoA p, int64_t n, CellWindow cw, const double* T, double tp_uniform, const double* Tp, const double* hA, double* q);
+// pass B: q = hA (sum w T[c] - Tp); with hp.rho_cpp > 0 also Tp += dt q / (m c) in place (Tp then must not be null)
+int launch_heat_flux_gaussian(hipStream_t s, ParticleSoA p, int64_t n, CellWindow cw, const double* T, HeatParams hp, double* Tp, const double* hA, double* q);
 // point-force mode: the containing cell launch_point_force left in incell (-1: not found), w = 1, eps = 1
 int launch_heat_coeff_point(hipStream_t s, const double* rec, int64_t n, const int32_t* incell, HeatParams hp, CellWindow cw, const double* U, const double* Tp, double* hA,
                             double* Sp, double* Su);
-int launch_heat_flux_point(hipStream_t s, int64_t n, const int32_t* incell, CellWindow cw, const double* T, double tp_uniform, const double* Tp, const double* hA, double* q);
+int launch_heat_flux_point(hipStream_t s, const double* rec, int64_t n, const int32_t* incell, CellWindow cw, const double* T, HeatParams hp, double* Tp, const double* hA, double* q);
 
 int launch_fill_f64(hipStream_t s, double* p, size_t n, double v);
 int launch_set_source_zero(hipStream_t s, int32_t n_cells, int gaussian, double* uSourceDrag, double* alpha,
