@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 20
+#define FY_ABI_VERSION 21
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -308,7 +308,7 @@ typedef struct fy_thermal_desc {
     double prt;                     /* turbulent Prandtl number (> 0 with a turbulence model; 0: 1) */
     int32_t nusselt_law;            /* FY_NUSSELT_* */
     double T_initial;               /* uniform internalField of 0/T (fy_solver_write_field_host("T") for a non-uniform one) */
-    int32_t T_bc[6]; double T_value[6];      /* FY_BC_T_* per side */
+    int32_t T_bc[6]; double T_value[6];      /* FY_BC_T_* per side (fy_case_desc; not read on a general mesh: fy_ldu_case.T_bc / T_value per patch) */
     int32_t T_convection_scheme;    /* div(phi,T) / div(alphaPhic,T): FY_CONVECTION_LINEAR | FY_CONVECTION_UPWIND */
     double T_tol, T_rel_tol; int32_t T_max_iter;      /* solvers.T: not both tolerances zero, T_max_iter >= 1 */
     double particle_temperature;    /* Tp of every particle of a batch nobody gave temperatures (fy_solver_set_particle_temperatures_*) */
@@ -685,6 +685,14 @@ typedef struct fy_ldu_case {
     int32_t drag_law;                /* constant/couplingProperties as in fy_case_desc: FY_DRAG_* and FY_FORCE_* flags, zero = the reference's behaviour */
     uint32_t force_models;
     fy_average_desc average;         /* controlDict functions: the fieldAverage object as in fy_case_desc (all zero: none), applied at fy_ldu_solver_create */
+    /* The fluid temperature equation and the particle-fluid heat exchange as in fy_case_desc.thermal (all zero: off -- nothing allocated, nothing launched).  Everything
+     * of fy_thermal_desc applies but its six-sided T_bc[6] / T_value[6], which are NOT READ on a general mesh: the patch conditions are the two arrays below.  The
+     * diffusion term is Gauss linear corrected like every laplacian here: gam_f = alphaf_f (D + nut / prt)_f |Sf|, implicit part gam_f dcNO_f, explicit part
+     * gam_f (kvec_f . (grad T_old)_f) added to the owner and taken from the neighbour; the Gaussian scatter of Sp / Su goes out as FP64 global atomics (no tiles) */
+    fy_thermal_desc thermal;
+    const int32_t* T_bc;             /* per patch: FY_BC_T_ZERO_GRADIENT | FY_BC_T_FIXED_VALUE (NULL: zeroGradient everywhere); a symmetry / slip patch takes
+                                        FY_BC_T_ZERO_GRADIENT, folded cyclic pairs are internal faces and need nothing */
+    const double* T_value;           /* [n_patches] */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */
@@ -696,10 +704,18 @@ int fy_ldu_solver_get_stats(fy_ldu_solver*, fy_step_stats* out);
 int fy_ldu_solver_set_field_average(fy_ldu_solver*, const fy_average_desc*);
 int fy_ldu_solver_get_average_state(fy_ldu_solver*, int item, int64_t* samples, double* time_averaged);
 int fy_ldu_solver_set_average_state(fy_ldu_solver*, int item, int64_t samples, double time_averaged);
+/* Heat exchange (fy_ldu_case.thermal.on; FY_ERR_INVALID on a solver without it): the entry points of fy_solver one for one, with the same semantics.  While thermal is
+ * on, "T" [nc] (also writable: a non-uniform start), "heatSp" [nc] (W/K), "heatSu" [nc] (W) and, with thermal.beta != 0 and g != 0, "buoyancy" [nc][3] are field names
+ * of fy_ldu_solver_read_field_host, and "T" one that fieldAverage accepts. */
+int fy_ldu_solver_set_particle_temperatures_host(fy_ldu_solver*, int batch, const double* Tp);
+int fy_ldu_solver_set_particle_temperatures_device(fy_ldu_solver*, int batch, const double* d_Tp);
+int fy_ldu_solver_get_particle_heat_host(fy_ldu_solver*, int batch, double* q);
+int fy_ldu_solver_get_thermal_stats(fy_ldu_solver*, int32_t* iterations, double* initial_residual, double* heat_to_particles_W);
+int fy_ldu_solver_get_particle_thermal_state(fy_ldu_solver*, int batch, double* Tp, int64_t* resets);
 int fy_ldu_solver_hold_sources(fy_ldu_solver*, int on);                    /* as fy_solver_hold_sources: setSourceZero deferred to the next step's start (runTime.write() sees alpha / uSource) */
 fy_ctx* fy_ldu_solver_coupling(fy_ldu_solver*);                              /* FoamYade on this mesh (point force); fy_set_particles_* as usual */
 /* fields by name, host copies: "U" [nc][3], "p", "phi" [n_faces], "uSource" [nc][3] (added to what the coupling leaves: an external momentum source),
- * "rAU", "HbyA", "phiHbyA", "p_diag", "p_coef" [n_faces], "p_rhs", "vGrad" [nc][9]; geometry: "C" "V" "Cf" "Sf" "magSf" "w" "dcNO" "kvec";
+ * "rAU", "HbyA", "phiHbyA", "p_diag", "p_coef" [n_faces], "p_rhs", "vGrad" [nc][9]; with pimpleFoamYade "alpha" [nc], "alphaf" [n_faces] (the void fraction on the faces, 1 on the boundary), "uSourceDrag", "uParticle"; with heat transfer "T", "heatSp", "heatSu", "buoyancy" (below); geometry: "C" "V" "Cf" "Sf" "magSf" "w" "dcNO" "kvec";
  * "nearWallDist" [n_faces - n_internal_faces]: y of each boundary face on a patch with a wall-function nut or epsilon (0 elsewhere) [OF-6 nearWallDist::correct];
  * "nut_boundary" [n_faces - n_internal_faces]: nut on each boundary face as the equations see it now (what the last correctNut() left; the file's value before) */
 int fy_ldu_solver_field_count(fy_ldu_solver*, const char* name, int64_t* count);

@@ -2,9 +2,12 @@
 """fy_ldu_solver (icoFoamYade on a general polyhedral mesh, LDU addressing) at scale: a lid-driven cavity on n^3 hexahedra written as a polyhedral mesh,
 plain and wavy (non-orthogonal + skewed, one non-orthogonal corrector), against the structured fy_solver on the same lattice.
 usage: ldu_bench.py [n=128] [steps=10] [kind=wavy|lattice|prisms] [particles=0] [p_solver=mg|diag] [nu=1e-4] [solver=ico|pimple] [turb=laminar|kEpsilon|kEpsilonWF]
-                                                                                                                                     -> one JSON line
+             [--thermal] [--particle-cp=C] [--beta=B]                                                                                -> one JSON line
 pimple: a closed box under gravity (fixedFluxPressure walls), the cloud at rest in its lower 60 %, Gaussian 4-way coupling; turb (pimple only): RAS kEpsilon with
-zero-gradient k / epsilon / nut patches, or kEpsilonWF: with nutkWallFunction / epsilonWallFunction on every side of the box"""
+zero-gradient k / epsilon / nut patches, or kEpsilonWF: with nutkWallFunction / epsilonWallFunction on every side of the box.
+--thermal: the fluid temperature equation and the particle-fluid heat exchange (fy_ldu_case.thermal) with water's cp and kappa, the fluid at 300 K and the particles
+at 350 K, zeroGradient T patches (tools/thermal_loop_bench.py's case); --particle-cp: the library integrates the particle temperatures; --beta: Boussinesq buoyancy
+about 300 K (it needs gravity: solver=pimple).  The output then carries the T solve's Jacobi passes of the last step and the heat the particles received in the last step"""
 import json
 import os
 import sys
@@ -17,6 +20,11 @@ import numpy as np  # noqa: E402
 import __graft_entry__ as ge  # noqa: E402
 import poly_meshes as pm  # noqa: E402
 
+flags = {a.split("=")[0]: (a.split("=") + [""])[1] for a in sys.argv[1:] if a.startswith("--")}
+sys.argv = [a for a in sys.argv if not a.startswith("--")]
+if set(flags) - {"--thermal", "--particle-cp", "--beta"}:
+    sys.exit("flags: --thermal [--particle-cp=C] [--beta=B]")
+thermal_on = "--thermal" in flags
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 kind = sys.argv[3] if len(sys.argv) > 3 else "wavy"
@@ -39,6 +47,13 @@ lid[3] = (1.0, 0, 0)
 dt = 0.2 * (L / n) / 1.0
 kw = dict(n_non_orth=0 if kind == "lattice" else 1, p_tol=1e-6, p_rel_tol=0.05, p_final_tol=1e-6, u_tol=1e-5, p_max_iter=2000,
           p_solver=prod.FY_PSOLVER_PCG_MG if psolver == "mg" else prod.FY_PSOLVER_PCG_JACOBI)
+if thermal_on:
+    loop = {}
+    if flags.get("--particle-cp"):
+        loop["particle_cp"] = float(flags["--particle-cp"])
+    if flags.get("--beta"):
+        loop.update(beta=float(flags["--beta"]), T_ref=300.0)
+    kw["thermal"] = prod.thermal_desc(4180.0, 0.6, T_initial=300.0, particle_temperature=350.0, T_tol=1e-8, T_max_iter=50, **loop)
 t0 = time.time()
 if pimple:
     dt = 1e-4
@@ -71,6 +86,9 @@ wall = time.time() - t0
 out = dict(tool="ldu_bench", kind=kind, turb=turb, cells=int(mesh["n_cells"]), faces=int(len(mesh["owner"])), steps=steps, steps_per_s=steps / wall, ms_per_step_wall=1e3 * wall / steps,
            ms_per_step_stream=ms / steps, ms_particle=mp / steps, solver=solver, pcg_iters_per_step=its / steps, p_solver=psolver, nu=nu, u_sweeps_per_step=uits / steps, us_per_pcg_iter=1e3 * ms / max(its, 1), courant_max=st["courant_max"],
            cont_err=st["cont_err_sum_local"], particles=npart, mesh_build_s=t_mesh, create_s=t_create, non_orth=kw["n_non_orth"])
+if thermal_on:
+    out.update(thermal=True, particle_cp=float(flags.get("--particle-cp") or 0), beta=float(flags.get("--beta") or 0), T_passes_last_step=s.thermal_stats()[0],
+               heat_to_particles_W=s.thermal_stats()[2] if npart else 0.0)
 s.close()
 if kind == "lattice" and n % 8 == 0:
     # the structured solver on the same block with the same controls (PCG + diagonal preconditioner)

@@ -139,25 +139,70 @@ class _Averages:
         _check(self._avg_fn("set_average_state")(self._h, int(item), int(samples), float(time_averaged)))
 
 
+class _ParticleHeat:
+    """particle batches and the heat exchange's particle side on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*); the object has _h, _cpl, _batch_n"""
+    _AVG_PREFIX = "fy_solver"
+
+    def _th_fn(self, what):
+        return getattr(lib(), f"{self._AVG_PREFIX}_{what}")
+
+    def set_particle_batches(self, batches):
+        """direct mode with several "Yade procs": one (n,10) host array per batch, coupled in this order"""
+        L = lib()
+        recs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 10) for r in batches]
+        _check(L.fy_set_num_batches(self._cpl, len(recs)))
+        for bi, rec in enumerate(recs):
+            _check(L.fy_set_particles_host(self._cpl, bi, _d(rec) if rec.size else None, rec.shape[0]))
+        self._batch_n = [r.shape[0] for r in recs]
+
+    def stencils_of(self, batch):
+        """stencils() of batch `batch`"""
+        n = self._batch_n[batch]
+        k = np.zeros(n, np.int32); ids = np.full((n, MAXK), -1, np.int32); w = np.zeros((n, MAXK)); chain = np.zeros(n, np.int32)
+        _check(lib().fy_get_stencils_host(self._cpl, int(batch), _i(k), _i(ids), _d(w), _i(chain)))
+        return k, ids, w, chain
+
+    def set_particle_temperatures(self, Tp, batch=0):
+        """heat exchange: the temperatures of the batch's particles in wire order (host array or torch device tensor), or None for the case's uniform particle_temperature"""
+        L = lib()
+        if Tp is None:
+            _check(self._th_fn("set_particle_temperatures_host")(self._h, int(batch), None))
+        elif _is_device(Tp):
+            assert Tp.numel() == self._batch_n[batch]
+            _check(self._th_fn("set_particle_temperatures_device")(self._h, int(batch), C.c_void_p(Tp.data_ptr())))
+        else:
+            Tp = np.ascontiguousarray(Tp, dtype=np.float64).ravel()
+            assert Tp.size == self._batch_n[batch]
+            _check(self._th_fn("set_particle_temperatures_host")(self._h, int(batch), _d(Tp)))
+
+    def particle_temperatures(self, batch=0):
+        """the batch's particle temperatures as they stand now, wire order: what the library integrates (thermal particle_cp > 0), else what was set or the uniform value"""
+        Tp = np.zeros(self._batch_n[batch])
+        _check(self._th_fn("get_particle_thermal_state")(self._h, int(batch), _d(Tp) if Tp.size else None, None))
+        return Tp
+
+    def particle_temperature_resets(self):
+        """how often a batch's temperature array was dropped because its particle count changed"""
+        n = C.c_int64(0)
+        _check(self._th_fn("get_particle_thermal_state")(self._h, 0, None, C.byref(n)))
+        return n.value
+
+    def particle_heat(self, batch=0):
+        """W into each particle of the batch over the last step, wire order"""
+        q = np.zeros(self._batch_n[batch])
+        _check(self._th_fn("get_particle_heat_host")(self._h, int(batch), _d(q) if q.size else None))
+        return q
+
+    def thermal_stats(self):
+        """(Jacobi passes, initial residual, heat to the particles [W]) of the last step's T solve"""
+        it = C.c_int32(0); r = C.c_double(0); h = C.c_double(0)
+        _check(self._th_fn("get_thermal_stats")(self._h, C.byref(it), C.byref(r), C.byref(h)))
+        return it.value, r.value, h.value
+
+
 class PolyMesh(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("points", _dp), ("n_faces", C.c_int32), ("n_internal_faces", C.c_int32), ("face_offsets", _ip), ("face_points", _ip),
                 ("owner", _ip), ("neighbour", _ip), ("n_cells", C.c_int32), ("n_patches", C.c_int32), ("patch_start", _ip), ("patch_size", _ip), ("patch_neighbour", _ip)]
-
-
-class LduCase(C.Structure):
-    _fields_ = [("dt", C.c_double), ("nu", C.c_double), ("rho_fluid", C.c_double), ("rho_particle", C.c_double), ("n_correctors", C.c_int32),
-                ("n_non_orth_correctors", C.c_int32), ("momentum_predictor", C.c_int32), ("p_ref_cell", C.c_int32), ("p_ref_value", C.c_double),
-                ("p_tol", C.c_double), ("p_rel_tol", C.c_double), ("p_final_tol", C.c_double), ("p_final_rel_tol", C.c_double), ("p_max_iter", C.c_int32),
-                ("u_tol", C.c_double), ("u_rel_tol", C.c_double), ("u_max_iter", C.c_int32), ("p_solver", C.c_int32), ("u_bc", _ip), ("u_value", _dp), ("p_bc", _ip),
-                ("p_value", _dp), ("solver", C.c_int32), ("n_outer_correctors", C.c_int32), ("g", C.c_double * 3), ("u_relax", C.c_double), ("u_relax_final", C.c_double),
-                ("p_relax", C.c_double), ("p_relax_final", C.c_double), ("adjust_time_step", C.c_int32), ("max_co", C.c_double), ("max_delta_t", C.c_double),
-                ("turbulence_model", C.c_int32), ("les_ck", C.c_double), ("les_ce", C.c_double), ("les_delta_coeff", C.c_double), ("nut_initial", C.c_double), ("nut_bc", _ip),
-                ("nut_value", _dp), ("convection_scheme", C.c_int32), ("convection_limiter_k", C.c_double), ("k_initial", C.c_double), ("k_bc", _ip), ("k_value", _dp),
-                ("k_convection_scheme", C.c_int32), ("k_tol", C.c_double), ("k_rel_tol", C.c_double), ("k_max_iter", C.c_int32), ("k_relax", C.c_double),
-                ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double), ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double),
-                ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
-                ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc)]
 
 
 class ParticleTimings(C.Structure):
@@ -173,6 +218,22 @@ class ThermalDesc(C.Structure):
                 ("T_initial", C.c_double), ("T_bc", C.c_int32 * 6), ("T_value", C.c_double * 6), ("T_convection_scheme", C.c_int32),
                 ("T_tol", C.c_double), ("T_rel_tol", C.c_double), ("T_max_iter", C.c_int32), ("particle_temperature", C.c_double),
                 ("particle_cp", C.c_double), ("beta", C.c_double), ("T_ref", C.c_double)]
+
+
+class LduCase(C.Structure):
+    _fields_ = [("dt", C.c_double), ("nu", C.c_double), ("rho_fluid", C.c_double), ("rho_particle", C.c_double), ("n_correctors", C.c_int32),
+                ("n_non_orth_correctors", C.c_int32), ("momentum_predictor", C.c_int32), ("p_ref_cell", C.c_int32), ("p_ref_value", C.c_double),
+                ("p_tol", C.c_double), ("p_rel_tol", C.c_double), ("p_final_tol", C.c_double), ("p_final_rel_tol", C.c_double), ("p_max_iter", C.c_int32),
+                ("u_tol", C.c_double), ("u_rel_tol", C.c_double), ("u_max_iter", C.c_int32), ("p_solver", C.c_int32), ("u_bc", _ip), ("u_value", _dp), ("p_bc", _ip),
+                ("p_value", _dp), ("solver", C.c_int32), ("n_outer_correctors", C.c_int32), ("g", C.c_double * 3), ("u_relax", C.c_double), ("u_relax_final", C.c_double),
+                ("p_relax", C.c_double), ("p_relax_final", C.c_double), ("adjust_time_step", C.c_int32), ("max_co", C.c_double), ("max_delta_t", C.c_double),
+                ("turbulence_model", C.c_int32), ("les_ck", C.c_double), ("les_ce", C.c_double), ("les_delta_coeff", C.c_double), ("nut_initial", C.c_double), ("nut_bc", _ip),
+                ("nut_value", _dp), ("convection_scheme", C.c_int32), ("convection_limiter_k", C.c_double), ("k_initial", C.c_double), ("k_bc", _ip), ("k_value", _dp),
+                ("k_convection_scheme", C.c_int32), ("k_tol", C.c_double), ("k_rel_tol", C.c_double), ("k_max_iter", C.c_int32), ("k_relax", C.c_double),
+                ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double), ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double),
+                ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
+                ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp)]
 
 
 NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
@@ -349,11 +410,12 @@ def lib():
     L.fy_solver_get_kernel_timing.argtypes = [vp, C.c_char_p, _dp, C.POINTER(C.c_int64)]
     L.fy_solver_enable_exchange_timing.argtypes = [vp, C.c_int]
     L.fy_solver_get_exchange_wait.argtypes = [vp, _dp, C.POINTER(C.c_int64)]
-    L.fy_solver_set_particle_temperatures_host.argtypes = [vp, C.c_int, _dp]
-    L.fy_solver_set_particle_temperatures_device.argtypes = [vp, C.c_int, vp]
-    L.fy_solver_get_particle_heat_host.argtypes = [vp, C.c_int, _dp]
-    L.fy_solver_get_thermal_stats.argtypes = [vp, C.POINTER(C.c_int32), _dp, _dp]
-    L.fy_solver_get_particle_thermal_state.argtypes = [vp, C.c_int, _dp, C.POINTER(C.c_int64)]
+    for pre in ("fy_solver", "fy_ldu_solver"):
+        getattr(L, pre + "_set_particle_temperatures_host").argtypes = [vp, C.c_int, _dp]
+        getattr(L, pre + "_set_particle_temperatures_device").argtypes = [vp, C.c_int, vp]
+        getattr(L, pre + "_get_particle_heat_host").argtypes = [vp, C.c_int, _dp]
+        getattr(L, pre + "_get_thermal_stats").argtypes = [vp, C.POINTER(C.c_int32), _dp, _dp]
+        getattr(L, pre + "_get_particle_thermal_state").argtypes = [vp, C.c_int, _dp, C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -679,7 +741,7 @@ def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 
     return c
 
 
-class Solver(_Averages):
+class Solver(_Averages, _ParticleHeat):
     """the icoFoamYade / pimpleFoamYade executables' time loop (icoFoamYade.C:65-149, pimpleFoamYade.C:60-114): step() is one
     pass of the loop body, including yadeCoupling.setParticleAction and setSourceZero."""
 
@@ -773,59 +835,6 @@ class Solver(_Averages):
             rec = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, 10)
         _check(L.fy_set_particles_host(self._cpl, 0, _d(rec) if rec.size else None, rec.shape[0]))
         self._batch_n = [rec.shape[0]]
-
-    def set_particle_batches(self, batches):
-        """direct mode with several "Yade procs": one (n,10) host array per batch, coupled in this order"""
-        L = lib()
-        recs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 10) for r in batches]
-        _check(L.fy_set_num_batches(self._cpl, len(recs)))
-        for bi, rec in enumerate(recs):
-            _check(L.fy_set_particles_host(self._cpl, bi, _d(rec) if rec.size else None, rec.shape[0]))
-        self._batch_n = [r.shape[0] for r in recs]
-
-    def stencils_of(self, batch):
-        """stencils() of batch `batch`"""
-        n = self._batch_n[batch]
-        k = np.zeros(n, np.int32); ids = np.full((n, MAXK), -1, np.int32); w = np.zeros((n, MAXK)); chain = np.zeros(n, np.int32)
-        _check(lib().fy_get_stencils_host(self._cpl, int(batch), _i(k), _i(ids), _d(w), _i(chain)))
-        return k, ids, w, chain
-
-    def set_particle_temperatures(self, Tp, batch=0):
-        """heat exchange: the temperatures of the batch's particles in wire order (host array or torch device tensor), or None for the case's uniform particle_temperature"""
-        L = lib()
-        if Tp is None:
-            _check(L.fy_solver_set_particle_temperatures_host(self._h, int(batch), None))
-        elif _is_device(Tp):
-            assert Tp.numel() == self._batch_n[batch]
-            _check(L.fy_solver_set_particle_temperatures_device(self._h, int(batch), C.c_void_p(Tp.data_ptr())))
-        else:
-            Tp = np.ascontiguousarray(Tp, dtype=np.float64).ravel()
-            assert Tp.size == self._batch_n[batch]
-            _check(L.fy_solver_set_particle_temperatures_host(self._h, int(batch), _d(Tp)))
-
-    def particle_temperatures(self, batch=0):
-        """the batch's particle temperatures as they stand now, wire order: what the library integrates (thermal particle_cp > 0), else what was set or the uniform value"""
-        Tp = np.zeros(self._batch_n[batch])
-        _check(lib().fy_solver_get_particle_thermal_state(self._h, int(batch), _d(Tp) if Tp.size else None, None))
-        return Tp
-
-    def particle_temperature_resets(self):
-        """how often a batch's temperature array was dropped because its particle count changed"""
-        n = C.c_int64(0)
-        _check(lib().fy_solver_get_particle_thermal_state(self._h, 0, None, C.byref(n)))
-        return n.value
-
-    def particle_heat(self, batch=0):
-        """W into each particle of the batch over the last step, wire order"""
-        q = np.zeros(self._batch_n[batch])
-        _check(lib().fy_solver_get_particle_heat_host(self._h, int(batch), _d(q) if q.size else None))
-        return q
-
-    def thermal_stats(self):
-        """(Jacobi passes, initial residual, heat to the particles [W]) of the last step's T solve"""
-        it = C.c_int32(0); r = C.c_double(0); h = C.c_double(0)
-        _check(lib().fy_solver_get_thermal_stats(self._h, C.byref(it), C.byref(r), C.byref(h)))
-        return it.value, r.value, h.value
 
     def set_particles_device(self, rec):
         L = lib()
@@ -1317,7 +1326,7 @@ class VirtualSlabs:
         self.solvers, self.comms = [], []
 
 
-class LduSolver(_Averages):
+class LduSolver(_Averages, _ParticleHeat):
     """icoFoamYade's loop body on a general polyhedral mesh in OpenFOAM's addressing (fy_ldu_solver, include/foamyade_hip.h).  mesh: dict with points (n,3),
     face_offsets, face_points, owner, neighbour, n_cells, patch_start, patch_size (tests/poly_meshes.py builds them); u_bc / p_bc / values per patch; the
     controls are fy_ldu_case's (defaults: the icoFoam cavity tutorial's)"""
@@ -1337,7 +1346,9 @@ class LduSolver(_Averages):
         L.fy_ldu_solver_read_field_host.argtypes = [C.c_void_p, C.c_char_p, _dp]
         L.fy_ldu_solver_write_field_host.argtypes = [C.c_void_p, C.c_char_p, _dp]
 
-    def __init__(self, mesh, dt, nu, u_bc, u_val, p_bc, p_val=None, device=0, transport=None, nut_bc=None, nut_val=None, k_bc=None, k_val=None, eps_bc=None, eps_val=None, **controls):
+    def __init__(self, mesh, dt, nu, u_bc, u_val, p_bc, p_val=None, device=0, transport=None, nut_bc=None, nut_val=None, k_bc=None, k_val=None, eps_bc=None, eps_val=None, thermal=None,
+                 T_bc=None, T_val=None, **controls):
+        """thermal: a thermal_desc(...) (its six-sided T_bc / T_value are not read here); T_bc / T_val: FY_BC_T_* and the fixed values per patch (None: zeroGradient)"""
         L = lib()
         self._bind()
         npatch = len(mesh["patch_start"])
@@ -1372,6 +1383,11 @@ class LduSolver(_Averages):
         if eps_bc is not None:
             k["eb"], k["ev"] = i32(eps_bc), np.ascontiguousarray(eps_val if eps_val is not None else np.zeros(npatch), np.float64)
             self.case.eps_bc, self.case.eps_value = _i(k["eb"]), _d(k["ev"])
+        if thermal is not None:
+            self.case.thermal = thermal
+        if T_bc is not None:
+            k["tb"], k["tv"] = i32(T_bc), np.ascontiguousarray(T_val if T_val is not None else np.zeros(npatch), np.float64)
+            self.case.T_bc, self.case.T_value = _i(k["tb"]), _d(k["tv"])
         self._create(device, transport)
 
     def _create(self, device, transport):

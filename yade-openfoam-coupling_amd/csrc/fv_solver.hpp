@@ -14,6 +14,7 @@
 #include "coupling.hpp"
 #include "field_average.hpp"
 #include "fv_kernels.hpp"
+#include "heat_exchange.hpp"
 
 // geometry-dependent launchers exist per geometry model (fv_kernels.hpp): the uniform block's in fy, the graded block's in fy::gr
 #define FVK(fn, ...) (g.graded ? ::fy::gr::fn(__VA_ARGS__) : ::fy::fn(__VA_ARGS__))
@@ -48,26 +49,14 @@ struct Thermal {
     bool on = false;
     fy_thermal_desc d{};
     ScalarEqn eq{};
-    HeatParams hp{};
     DevBuf<double> T, Sp, Su;            // storage cells; Sp [W/K], Su [W]: what the last step's particles scattered
-    DevBuf<double> red;                  // block partials + result of the device-side sum of q (thermal_stats)
-    struct PerBatch {
-        DevBuf<double> hA, Tp, q;        // wire order
-        int64_t n = 0;                   // particles hA / q were formed for (the last step's count)
-        // Tp holds temperatures for tp_n particles: the caller's, or (own_tp) the ones the library integrates; otherwise d.particle_temperature
-        bool has_tp = false;
-        int64_t tp_n = 0;
-    };
-    std::vector<std::unique_ptr<PerBatch> > pb;
-    bool own_tp = false;                 // d.particle_cp > 0: k_heat_coeff_* / k_heat_flux_*<true> advance each batch's Tp
-    int64_t tp_resets = 0;               // batches whose Tp array was dropped because their particle count changed
+    HeatExchange part;                   // the particles' half: per-batch hA / q / Tp, the two particle passes, set and get (heat_exchange.hpp; shared with fy_ldu_solver)
     // Boussinesq buoyancy (d.beta != 0 and g != 0): a [3 nstore], and uSource + a, what the momentum equations read in uSource's place
     bool buoyant = false;
     DevBuf<double> buoy, usrc_sum;
     KernelClock clk_coeff, clk_flux, clk_asm, clk_buoy;      // "heat_coeff", "heat_flux", "T_assemble", "buoyancy" of fy_solver_get_kernel_timing
     int iters = 0;
     double res0 = 0.0;
-    PerBatch& batch(size_t bi) { while (pb.size() <= bi) pb.emplace_back(new PerBatch()); return *pb[bi]; }
     ~Thermal() { clk_coeff.destroy(); clk_flux.destroy(); clk_asm.destroy(); clk_buoy.destroy(); }
 };
 
@@ -316,7 +305,6 @@ struct Solver {
     int heat_fluxes();
     int buoyancy();                                     // a from the T the step found, and uSource + a (after heat_coefficients, before the first momentum assembly)
     const double* momentum_source() const { return th.buoyant ? th.usrc_sum.p : uSource.p; }
-    void sync_particle_temperatures(size_t bi, int64_t n);      // drops a Tp array held for another particle count (counted in th.tp_resets)
     int set_particle_temperatures(int batch, const double* tp, bool on_device);
     int get_particle_thermal_state(int batch, double* tp, int64_t* resets);
     int get_particle_heat(int batch, double* q);

@@ -113,8 +113,16 @@ struct LduKEqn {
     const int32_t* wall_of;
     const double *wall_eps, *wall_G;
 };
+// the fluid temperature equation (fy_thermal_desc): T of the old time with its per-patch conditions (FY_BC_T_*), D = kappa / (rho_f cp), 1 / Prt, 1 / (rho_f cp)
+struct LduTEqn {
+    const double* T;
+    const int32_t* bc;
+    const double* val;
+    int upwind;
+    double D, rPrt, rRhoCp;
+};
 
-int ldu_red_blocks(int n);      // partials per slot of the reducing kernels (= red_blocks(n) of fv_kernels.hpp: the folds are shared)
+int ldu_red_blocks(int n);     // partials per slot of the reducing kernels (= red_blocks(n) of fv_kernels.hpp: the folds are shared)
 
 int launch_ldu_flux_of(hipStream_t s, LduGeo g, const double* F, double* phi);
 int launch_ldu_courant(hipStream_t s, LduGeo g, const double* phi, double* partials);                    // slot 0 = max sumPhi / V, slot 1 = sum sumPhi
@@ -149,6 +157,9 @@ int launch_ldu_smagorinsky_nut(hipStream_t s, LduGeo g, const double* vGrad, dou
 int launch_ldu_grad_k(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, double* gk);
 int launch_ldu_k_assemble(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, const double* phi, const double* vGrad, const double* gk, LduMom M, double* face_corr, double* x3);
 int launch_ldu_k_bound_nut(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, const double* x3, double* X, double* nut);
+// the T equation's matrix into M in the same way (face part, then cells with the particles' Sp / Su -- null: none), x3 = (T, 0, 0); P's alpha, alphaf and nut may be null
+int launch_ldu_grad_T(hipStream_t s, LduGeo g, LduTEqn E, double* gT);
+int launch_ldu_T_assemble(hipStream_t s, LduGeo g, LduPim P, LduTEqn E, const double* phi, const double* gT, const double* Sp, const double* Su, LduMom M, double* face_corr, double* x3);
 // epsilonWallFunction::calculate before the epsilon equation: per wall cell the imposed epsilon and G (k of this correct()'s start, U of the last corrector)
 int launch_ldu_wall_functions(hipStream_t s, LduGeo g, LduPim P, LduWallCells W, const double* U, double* wall_eps, double* wall_G);
 // fvMatrix::setValues' last part on the epsilon matrix: the wall cells' faces lose their coefficients (the rows were imposed by k_ldu_k_cells)

@@ -736,6 +736,72 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
     st3(x3, c, D3{x0, 0.0, 0.0});
 }
 
+// ---- the fluid temperature equation (fy_thermal_desc; not in the reference -- DESIGN_FV.md "T equation"), the block solver's k_assemble_scalar with the faces of a
+// general mesh, in the pattern of the k equation above:
+//   alpha V (T - T_old) / dt + sum_f F_f T_f - T sum_f F_f - sum_f gam_f (dcNO_f (T_N - T) + kvec_f . (grad T)_f) = (Su - Sp T) / (rho_f cp)
+// F_f = alphaf_f phi_f outward, T_f linear | upwind, gam_f = alphaf_f (Deff)_f |Sf| with Deff = D + nut / Prt interpolated linearly (alphaf_f = 1 and nut_b by ldu_nut_b
+// on a boundary face), the non-orthogonal part explicit from the Gauss-linear gradient of T_old: + on the owner, - on the neighbour.  alpha, alphaf and nut come with P
+// and may each be null (icoFoamYade has no LduPim: 1, 1, 0).  fixedValue face: gb = Deff_b |Sf| dcNO on the diagonal, (gb - F_b) T_b in the source; zeroGradient: F_b
+__device__ __forceinline__ double ldu_T_b(const LduGeo& g, const LduTEqn& E, double tc, int f) {
+    const int pa = g.patch_of[f - g.nInt];
+    return E.bc[pa] == FY_BC_T_FIXED_VALUE ? E.val[pa] : tc;
+}
+__global__ __launch_bounds__(256) void k_ldu_grad_T(LduGeo g, LduTEqn E, double* __restrict__ gT) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= g.nCells) return;
+    const double tc = E.T[c];
+    D3 a{0, 0, 0};
+    FY_CELL_FACES(g, c, f, nb) {
+        double tf, sg = 1.0;
+        if (f < g.nInt) { const bool o = nb > c; const double tn = E.T[nb]; tf = o ? g.w[f] * tc + (1.0 - g.w[f]) * tn : g.w[f] * tn + (1.0 - g.w[f]) * tc; sg = o ? 1.0 : -1.0; }
+        else tf = ldu_T_b(g, E, tc, f);
+        const D3 S = ld3(g.Sf, f);
+        a.x += sg * S.x * tf; a.y += sg * S.y * tf; a.z += sg * S.z * tf;
+    }
+    const double rV = 1.0 / g.V[c];
+    st3(gT, c, D3{a.x * rV, a.y * rV, a.z * rV});
+}
+__global__ __launch_bounds__(256) void k_ldu_T_faces(LduGeo g, LduPim P, LduTEqn E, const double* __restrict__ phi, const double* __restrict__ gT, LduMom M, double* __restrict__ corr) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= g.nInt) return;
+    const int o = g.own[f], n = g.nei[f];
+    const double w = g.w[f], af = P.alphaf ? P.alphaf[f] : 1.0, fl = af * phi[f];
+    const double dO = E.D + (P.nut ? P.nut[o] * E.rPrt : 0.0), dN = E.D + (P.nut ? P.nut[n] * E.rPrt : 0.0);
+    const double gam = (af * (w * dO + (1.0 - w) * dN)) * g.magSf[f];
+    const double wc = E.upwind ? (fl >= 0.0 ? 1.0 : 0.0) : w;
+    double lo = -wc * fl, up = lo + fl;
+    lo -= gam * g.dcNO[f]; up -= gam * g.dcNO[f];
+    M.lower[f] = lo; M.upper[f] = up;
+    const D3 kv = ld3(g.kvec, f), go = ld3(gT, o), gn = ld3(gT, n);
+    corr[f] = gam * dot3(kv, lerp3(w, go, gn));
+}
+__global__ __launch_bounds__(256) void k_ldu_T_cells(LduGeo g, LduPim P, LduTEqn E, const double* __restrict__ phi, const double* __restrict__ Sp, const double* __restrict__ Su,
+                                                     LduMom M, const double* __restrict__ corr, double* __restrict__ x3) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= g.nCells) return;
+    const double Vc = g.V[c], ac = P.alpha ? P.alpha[c] : 1.0, tc = E.T[c];
+    double dg = ac * Vc / g.dt, b = ac * Vc / g.dt * tc, sumF = 0.0;
+    FY_CELL_FACES(g, c, f, nb) {
+        const double fl = (P.alphaf ? P.alphaf[f] : 1.0) * phi[f];
+        if (f < g.nInt) {
+            if (nb > c) { dg -= M.lower[f]; sumF += fl; b += corr[f]; }
+            else { dg -= M.upper[f]; sumF -= fl; b -= corr[f]; }
+        } else {
+            const int pa = g.patch_of[f - g.nInt];
+            sumF += fl;
+            if (E.bc[pa] == FY_BC_T_FIXED_VALUE) {
+                const double gb = (E.D + ldu_nut_b(g, P, f) * E.rPrt) * g.magSf[f] * g.dcNO[f];
+                dg += gb; b += (gb - fl) * E.val[pa];
+            } else dg += fl;
+        }
+    }
+    dg -= sumF;                                              // bounded convection: - T div(F)
+    if (Sp) { dg += Sp[c] * E.rRhoCp; b += Su[c] * E.rRhoCp; }
+    M.diag[c] = dg;
+    st3(M.b, c, D3{b, 0.0, 0.0});
+    st3(x3, c, D3{tc, 0.0, 0.0});
+}
+
 // epsilonWallFunction::calculate, one lane per wall cell over its W faces on epsilonWallFunction patches: eps_w and G_w = the averages of the faces' terms (fv_closures.hpp:
 // wall_epsilon_term, wall_G_term); k of the cell as this correct() found it
 __global__ __launch_bounds__(256) void k_ldu_wall_functions(LduGeo g, LduPim P, LduWallCells W, const double* __restrict__ U, double* __restrict__ wall_eps, double* __restrict__ wall_G) {
@@ -1077,6 +1143,17 @@ int launch_ldu_grad_k(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, double* gk) 
 int launch_ldu_k_assemble(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, const double* phi, const double* vGrad, const double* gk, LduMom M, double* face_corr, double* x3) {
     if (g.nInt > 0) hipLaunchKernelGGL(k_ldu_k_faces, dim3(div_up(g.nInt, 256)), dim3(256), 0, s, g, P, K, phi, gk, M, face_corr);
     hipLaunchKernelGGL(k_ldu_k_cells, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, P, K, phi, vGrad, M, face_corr, x3);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_grad_T(hipStream_t s, LduGeo g, LduTEqn E, double* gT) {
+    hipLaunchKernelGGL(k_ldu_grad_T, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, E, gT);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_T_assemble(hipStream_t s, LduGeo g, LduPim P, LduTEqn E, const double* phi, const double* gT, const double* Sp, const double* Su, LduMom M, double* face_corr, double* x3) {
+    if (g.nInt > 0) hipLaunchKernelGGL(k_ldu_T_faces, dim3(div_up(g.nInt, 256)), dim3(256), 0, s, g, P, E, phi, gT, M, face_corr);
+    hipLaunchKernelGGL(k_ldu_T_cells, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, P, E, phi, Sp, Su, M, face_corr, x3);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

@@ -11,7 +11,9 @@
 
 #include "coupling.hpp"
 #include "field_average.hpp"
+#include "fv_kernels.hpp"
 #include "fv_linalg_kernels.hpp"
+#include "heat_exchange.hpp"
 #include "ldu.hpp"
 #include "ldu_amg.hpp"
 
@@ -52,8 +54,21 @@ struct LduSolver {
     int n_wall_cells = 0;
     double wf_yplam = 0.0;
     LduWallCells WC() const { return LduWallCells{n_wall_cells, d_wc_cell.p, d_wc_off.p, d_wc_face.p, std::pow(cs.ras_cmu, 0.75)}; }
+    // heat exchange (fy_ldu_case.thermal; DESIGN.md section 3 "heat exchange", DESIGN_FV.md "T equation"): the fluid's T with its sources and per-patch conditions, the
+    // Gauss gradient of T_old for the explicit non-orthogonal part, the buoyancy a and uSource + a (what the momentum equations then read in uSource's place), and the
+    // particles' half, which fy_solver holds too.  Off: nothing allocated, nothing launched
+    struct Thermal {
+        bool on = false, buoyant = false;
+        fy_thermal_desc d{};
+        LduTEqn eq{};
+        DevBuf<double> T, Sp, Su, gradT, buoy, usrc_sum, d_val;
+        DevBuf<int32_t> d_bc;
+        HeatExchange part;
+        int iters = 0;
+        double res0 = 0.0;
+    } th;
     LduPim P() const {
-        return LduPim{alpha.p, alpha.p, alphaf.p, uSourceDrag.p, uSource.p, {cs.g[0], cs.g[1], cs.g[2]}, les ? nut.p : nullptr, d_nutbc.p, d_nutval.p,
+        return LduPim{alpha.p, alpha.p, alphaf.p, uSourceDrag.p, th.buoyant ? th.usrc_sum.p : uSource.p, {cs.g[0], cs.g[1], cs.g[2]}, les ? nut.p : nullptr, d_nutbc.p, d_nutval.p,
                       (keqn || keps) ? kturb.p : nullptr, d_kbc.p, d_kval.p, nut_live ? 1 : 0, cs.les_ck, cs.les_delta_coeff,
                       keps ? epsturb.p : nullptr, d_epsbc.p, d_epsval.p, cs.ras_cmu,
                       d_ywall.p, std::pow(cs.ras_cmu, 0.25), cs.wf_kappa, cs.wf_E, wf_yplam};
@@ -74,7 +89,7 @@ struct LduSolver {
     const double* avg_source(const std::string& name, int* comp) const {      // the field as it lies NOW (U and its scratch buffer trade places)
         const struct { const char* nm; const double* p; int comp; bool have; } tab[] = {
             {"U", U.p, 3, true}, {"p", p.p, 1, true}, {"alpha", alpha.p, 1, pimple}, {"uParticle", uParticle.p, 3, pimple}, {"uSource", uSource.p, 3, true},
-            {"nut", nut.p, 1, les}, {"k", kturb.p, 1, keqn || keps}, {"epsilon", epsturb.p, 1, keps}};
+            {"nut", nut.p, 1, les}, {"k", kturb.p, 1, keqn || keps}, {"epsilon", epsturb.p, 1, keps}, {"T", th.T.p, 1, th.on}};
         for (const auto& e : tab)
             if (name == e.nm && e.have && e.p) { *comp = e.comp; return e.p; }
         return nullptr;
@@ -101,6 +116,7 @@ struct LduSolver {
     LduMom M() { return LduMom{mdiag.p, mlower.p, mupper.p, mb.p, has_slip ? mbdiag.p : nullptr}; }
 
     int create(const fy_poly_mesh* m, const fy_ldu_case* c, const fy_transport* tr, int dev) {
+        th.part.who = "fy_ldu_solver"; th.part.desc = "fy_ldu_case";
         if (!c || !(c->dt > 0) || !(c->nu >= 0) || !c->u_bc || !c->u_value || !c->p_bc || !c->p_value) return fail(FY_ERR_INVALID, "fy_ldu_solver_create: bad case (dt, nu, the per-patch arrays)");
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FY_ERR_NO_DEVICE, "no HIP device visible: libfoamyade_hip has no CPU path");
@@ -141,6 +157,18 @@ struct LduSolver {
             if (pbc[(size_t)pa] == FY_BC_P_FIXED_VALUE) need_ref = false;
         }
         if (need_ref && (c->p_ref_cell < 0 || c->p_ref_cell >= nc)) return fail(FY_ERR_INVALID, "fy_ldu_solver: pRefCell out of range");
+        std::vector<int32_t> tbc((size_t)hm.nPatches, FY_BC_T_ZERO_GRADIENT);
+        std::vector<double> tval((size_t)hm.nPatches, 0.0);
+        if (c->thermal.on) {                                                  // (what Solver::thermal_create checks, with the patches of this mesh in the six sides' place)
+            FY_TRY(HeatExchange::validate(c->thermal, pimple, c->rho_particle, "fy_ldu_solver_create"));
+            for (int pa = 0; pa < hm.nPatches; ++pa) {
+                if (c->T_bc) tbc[(size_t)pa] = c->T_bc[pa];
+                if (c->T_value) tval[(size_t)pa] = c->T_value[pa];
+                if (tbc[(size_t)pa] != FY_BC_T_ZERO_GRADIENT && tbc[(size_t)pa] != FY_BC_T_FIXED_VALUE)
+                    return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver_create: unknown T_bc %d on patch %d (FY_BC_T_ZERO_GRADIENT, FY_BC_T_FIXED_VALUE)", tbc[(size_t)pa], pa);
+            }
+        }
+        cs.T_bc = nullptr; cs.T_value = nullptr;
         if (c->p_solver != FY_PSOLVER_PCG_JACOBI && c->p_solver != FY_PSOLVER_PCG_MG) return fail(FY_ERR_INVALID, "fy_ldu_solver: p_solver %d (FY_PSOLVER_PCG_JACOBI, FY_PSOLVER_PCG_MG)", c->p_solver);
         cs.u_bc = nullptr; cs.u_value = nullptr; cs.p_bc = nullptr; cs.p_value = nullptr;      // (copied; the caller's arrays are not kept)
         FY_HIP(hipSetDevice(device));
@@ -254,9 +282,47 @@ struct LduSolver {
             if (c->force_models) FY_TRY(cpl->c.set_force_models(c->force_models));
         }
         FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                    // createPhi
+        if (c->thermal.on) FY_TRY(thermal_create(c, tbc, tval));              // (before fieldAverage, which may ask for T)
         FY_HIP(hipStreamSynchronize(stream));
         if (c->average.n_items) FY_TRY(set_field_average(&c->average));       // controlDict functions: fieldAverage
         return FY_OK;
+    }
+
+    int thermal_create(const fy_ldu_case* c, const std::vector<int32_t>& tbc, const std::vector<double>& tval) {
+        const fy_thermal_desc& d = c->thermal;
+        const size_t n = (size_t)nc;
+        th.d = d;
+        FY_TRY(up(th.d_bc, tbc)); FY_TRY(up(th.d_val, tval));
+        DevBuf<double>* bs[] = {&th.T, &th.Sp, &th.Su};
+        for (auto* b : bs) { FY_TRY(b->alloc_exact(n)); FY_TRY(zero(*b)); }
+        FY_TRY(th.gradT.alloc_exact(3 * n)); FY_TRY(zero(th.gradT));
+        FY_TRY(launch_fill_f64(stream, th.T.p, n, d.T_initial));
+        th.eq = LduTEqn{th.T.p, th.d_bc.p, th.d_val.p, d.T_convection_scheme == FY_CONVECTION_UPWIND ? 1 : 0, d.kappa / (c->rho_fluid * d.cp), 1.0 / (d.prt > 0 ? d.prt : 1.0),
+                        1.0 / (c->rho_fluid * d.cp)};
+        th.part.configure(d, c->nu, c->rho_fluid, c->rho_particle, c->dt, "fy_ldu_solver", "fy_ldu_case");
+        th.buoyant = d.beta != 0.0 && (c->g[0] != 0.0 || c->g[1] != 0.0 || c->g[2] != 0.0);
+        if (th.buoyant) { FY_TRY(th.buoy.alloc_exact(3 * n)); FY_TRY(zero(th.buoy)); FY_TRY(th.usrc_sum.alloc_exact(3 * n)); FY_TRY(zero(th.usrc_sum)); }
+        th.on = true;
+        return FY_OK;
+    }
+    // pass A on the solver's stream, right after setParticleAction returned (pimpleFoamYade: and after the side stream's sweeps, whose alphaf the later kernels read): a
+    // general mesh has no tiles, so the Gaussian scatter's table flushes as global atomics
+    int heat_coefficients() {
+        FY_TRY(zero(th.Sp)); FY_TRY(zero(th.Su));
+        return th.part.coefficients(cpl->c, stream, CellWindow{0, (int64_t)nc}, U.p, th.Sp.p, th.Su.p, cs.dt, false);
+    }
+    // the T equation, once per step with the step's final phi and nut, into the momentum matrix's storage as {T, 0, 0}; then pass B with the new T
+    int solve_temperature() {
+        LduMom Mt = M();
+        Mt.bdiag = nullptr;
+        const LduPim Pt = pimple ? P() : LduPim{};                // (icoFoamYade: alpha = alphaf = 1, nut = 0)
+        FY_TRY(launch_ldu_grad_T(stream, g, th.eq, th.gradT.p));
+        FY_TRY(launch_ldu_T_assemble(stream, g, Pt, th.eq, phi.p, th.gradT.p, th.Sp.p, th.Su.p, Mt, fcorr.p, HbyA.p));
+        FY_TRY(solve_vec3(&th.iters, Mt, mb.p, nullptr, &HbyA.p, &xscr.p, th.d.T_tol, th.d.T_rel_tol, th.d.T_max_iter, &th.res0));
+        FvGeo flat{};                                             // (k_scalar_finish reads the cell count and the first cell only)
+        flat.Nc = nc; flat.c0 = 0;
+        FY_TRY(launch_scalar_finish(stream, flat, HbyA.p, th.T.p));
+        return th.part.fluxes(cpl->c, stream, CellWindow{0, (int64_t)nc}, th.T.p);
     }
 
     // nearWallDist on the patches with a wall-function nut or epsilon, and the list of the cells with epsilonWallFunction faces (what k_ldu_wall_functions runs over)
@@ -308,7 +374,7 @@ struct LduSolver {
         return FY_OK;
     }
     // Jacobi passes on a three-component system with lduMatrix::solver's L1 residual control per component; the converged iterate ends up in *x (the two buffers may trade places)
-    int solve_vec3(int* iters, LduMom Mx, const double* rhs, const double* gp, double** x, double** scratch, double tol, double rel_tol, int max_iter) {
+    int solve_vec3(int* iters, LduMom Mx, const double* rhs, const double* gp, double** x, double** scratch, double tol, double rel_tol, int max_iter, double* res0_out = nullptr) {
         FY_TRY(launch_ldu_sum(stream, *x, nc, 3, partials.p));
         FY_TRY(launch_reduce_finalize(stream, partials.p, nc, 3, nullptr, xsum.p, nullptr, 0));
         double* xc = *x; double* xn = *scratch;
@@ -323,6 +389,7 @@ struct LduSolver {
         }
         if (xc != *x) std::swap(*x, *scratch);            // the converged iterate sits in the scratch buffer: the two trade places
         *iters = it;
+        if (res0_out) *res0_out = res0[0];
         return FY_OK;
     }
 
@@ -426,7 +493,9 @@ struct LduSolver {
         tim[0].stop(stream);
         if (beside) FY_HIP(hipStreamWaitEvent(stream, ev_fields, 0));                                             // (whatever the coupling did: the sweeps below read alphaf)
         FY_TRY(launch_ldu_alphaf(stream, g, alpha.p, alphaf.p));                                                  // :83-85
+        if (th.on) FY_TRY(heat_coefficients());                                                                   // (the stencils, the cell records and U are still what the force pass saw)
         if (ext_source) FY_TRY(launch_add_f64(stream, uSource.p, uSourceExt.p, 3 * (size_t)nc));
+        if (th.buoyant) FY_TRY(launch_buoyancy(stream, (size_t)nc, th.T.p, th.d.beta, th.d.T_ref, cs.g, uSource.p, th.buoy.p, th.usrc_sum.p));      // P().uSource: the sum
         const int nOuter = std::max(cs.n_outer_correctors, 1);
         for (int outer = 0; outer < nOuter; ++outer) {                                                             // :90
             const bool final_outer = outer == nOuter - 1;
@@ -480,6 +549,8 @@ struct LduSolver {
 
     int step() {
         FY_HIP(hipSetDevice(device));
+        if (th.on && cpl->c.fibre)          // (before the particle phase: a refused step leaves nothing half done)
+            return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver_step: heat transfer (fy_ldu_case.thermal.on) is not available with fibre coupling (fy_set_fibre_coupling): switch one of them off");
         st = fy_step_stats{}; st.cont_err_cumulative = cumulative; st.delta_t = cs.dt;
         if (sources_pending) { FY_TRY(cpl->c.set_source_zero()); sources_pending = false; }      // the previous step's deferred setSourceZero
         tim[1].start(stream);
@@ -501,9 +572,11 @@ struct LduSolver {
             tim[0].start(stream);
             FY_TRY(cpl->c.set_particle_action(cs.dt));                                                                // :74
             tim[0].stop(stream);
-            // the momentum source: what the coupling left (+ an external one, fy_ldu_solver_write_field_host("uSource", ...))
+            if (th.on) FY_TRY(heat_coefficients());
+            // the momentum source: what the coupling left (+ an external one, fy_ldu_solver_write_field_host("uSource", ...)) (+ the buoyancy of the T the step found)
             const double* src = uSource.p;
             if (ext_source) { FY_TRY(launch_copy_f64(stream, uSourceSum.p, uSource.p, 3 * (size_t)nc)); FY_TRY(launch_add_f64(stream, uSourceSum.p, uSourceExt.p, 3 * (size_t)nc)); src = uSourceSum.p; }
+            if (th.buoyant) { FY_TRY(launch_buoyancy(stream, (size_t)nc, th.T.p, th.d.beta, th.d.T_ref, cs.g, src, th.buoy.p, th.usrc_sum.p)); src = th.usrc_sum.p; }
             if (g.gradL) FY_TRY(launch_ldu_grad_magsqr(stream, g, Uold.p, gradL.p));
             FY_TRY(launch_ldu_assemble_momentum(stream, g, phi.p, Uold.p, src, vGrad.p, M(), fcorr.p));                // :79-85 (grad U of the iterate it is assembled from = vGrad)
             if (cs.momentum_predictor) {
@@ -514,6 +587,7 @@ struct LduSolver {
             }
             for (int corr = 0; corr < cs.n_correctors; ++corr) FY_TRY(corrector(corr == cs.n_correctors - 1));         // :97-140
         }
+        if (th.on) FY_TRY(solve_temperature());                                                                   // after the last corrector and the turbulence model's correct()
         avg.elapsed += cs.dt;
         if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));
         if (hold_sources) sources_pending = true;                                                                 // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147)
@@ -542,6 +616,16 @@ struct LduSolver {
                          {"rAUf", rAUf.p, (size_t)nf}, {"uSourceCoupling", uSource.p, 3 * n}, {"nut", nut.p, les ? n : 0}, {"k", kturb.p, (keqn || keps) ? n : 0}, {"epsilon", epsturb.p, keps ? n : 0}};
         for (const E& e : tab) if (s == e.nm) { *ptr = e.p; *count = e.c; return FY_OK; }
         if (avg.lookup(s, ptr, count)) return FY_OK;                           // <field>Mean, <field>Prime2Mean
+        if (s == "T" || s == "heatSp" || s == "heatSu") {
+            if (!th.on) return fail(FY_ERR_INVALID, "fy_ldu_solver field '%s' does not exist in this case (fy_ldu_case.thermal is off)", s.c_str());
+            *ptr = s == "T" ? th.T.p : s == "heatSp" ? th.Sp.p : th.Su.p; *count = n;
+            return FY_OK;
+        }
+        if (s == "buoyancy") {
+            if (!th.buoyant) return fail(FY_ERR_INVALID, "fy_ldu_solver field 'buoyancy' does not exist in this case (fy_ldu_case.thermal.beta or g is zero)");
+            *ptr = th.buoy.p; *count = 3 * n;
+            return FY_OK;
+        }
         if (s == "nut_boundary") {                                                 // formed on request: nut_b as ldu_nut_b gives it now
             *count = les ? (size_t)(nf - ni) : 0;
             if (*count) {
@@ -630,8 +714,8 @@ int fy_ldu_solver_write_field_host(fy_ldu_solver* s, const char* name, const dou
             return FY_OK;
         }
     }
-    const bool pim_in = (s->s.pimple && (nm == "alpha" || nm == "uSourceDrag")) || (s->s.les && nm == "nut") || ((s->s.keqn || s->s.keps) && nm == "k") || (s->s.keps && nm == "epsilon");      // (what setParticleAction would leave: for tests that feed the equations a given void fraction)
-    if (h || (nm != "U" && nm != "p" && nm != "uSource" && !pim_in)) return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_write_field_host: '%s' cannot be written (U, p, uSource; alpha, uSourceDrag with pimpleFoamYade)", nm.c_str());
+    const bool pim_in = (s->s.pimple && (nm == "alpha" || nm == "uSourceDrag")) || (s->s.les && nm == "nut") || ((s->s.keqn || s->s.keps) && nm == "k") || (s->s.keps && nm == "epsilon") || (s->s.th.on && nm == "T");      // (what setParticleAction would leave: for tests that feed the equations a given void fraction)
+    if (h || (nm != "U" && nm != "p" && nm != "uSource" && !pim_in)) return fy::fail(FY_ERR_INVALID, "fy_ldu_solver_write_field_host: '%s' cannot be written (U, p, uSource; alpha, uSourceDrag with pimpleFoamYade; T with heat transfer on)", nm.c_str());
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
     if (nm == "uSource") s->s.ext_source = true;
@@ -663,6 +747,19 @@ int fy_ldu_solver_apply(fy_ldu_solver* s, const char* op, const double* in, doub
 int fy_ldu_solver_set_field_average(fy_ldu_solver* s, const fy_average_desc* d) { FY_LS(s); return s->s.set_field_average(d); }
 int fy_ldu_solver_get_average_state(fy_ldu_solver* s, int item, int64_t* samples, double* time_averaged) { FY_LS(s); return s->s.avg.get_state(item, samples, time_averaged); }
 int fy_ldu_solver_set_average_state(fy_ldu_solver* s, int item, int64_t samples, double time_averaged) { FY_LS(s); return s->s.avg.set_state(item, samples, time_averaged); }
+int fy_ldu_solver_set_particle_temperatures_host(fy_ldu_solver* s, int batch, const double* Tp) { FY_LS(s); return s->s.th.part.set_temperatures(s->s.cpl->c, s->s.device, s->s.stream, batch, Tp, false); }
+int fy_ldu_solver_set_particle_temperatures_device(fy_ldu_solver* s, int batch, const double* d_Tp) { FY_LS(s); return s->s.th.part.set_temperatures(s->s.cpl->c, s->s.device, s->s.stream, batch, d_Tp, true); }
+int fy_ldu_solver_get_particle_heat_host(fy_ldu_solver* s, int batch, double* q) { FY_LS(s); return s->s.th.part.get_heat(s->s.device, s->s.stream, batch, q); }
+int fy_ldu_solver_get_particle_thermal_state(fy_ldu_solver* s, int batch, double* Tp, int64_t* resets) { FY_LS(s); return s->s.th.part.get_state(s->s.cpl->c, s->s.device, s->s.stream, batch, Tp, resets); }
+int fy_ldu_solver_get_thermal_stats(fy_ldu_solver* s, int32_t* iterations, double* initial_residual, double* heat_to_particles_W) {
+    FY_LS(s);
+    fy::LduSolver& S = s->s;
+    if (!S.th.on) return S.th.part.refuse_off("get_thermal_stats");
+    if (iterations) *iterations = S.th.iters;
+    if (initial_residual) *initial_residual = S.th.res0;
+    if (heat_to_particles_W) FY_TRY(S.th.part.total_heat(S.device, S.stream, heat_to_particles_W));
+    return FY_OK;
+}
 int fy_ldu_solver_hold_sources(fy_ldu_solver* s, int on) { FY_LS(s); s->s.hold_sources = on != 0; return FY_OK; }
 int fy_ldu_solver_mg_levels(fy_ldu_solver* s, int cap, int32_t* cells, int32_t* slots, int* n_levels) {
     FY_LS(s);
