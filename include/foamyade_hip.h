@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 21
+#define FY_ABI_VERSION 22
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -287,6 +287,40 @@ typedef struct fy_average_desc {
     double start_after, stop_after; /* the window in seconds since the solver was created; stop_after 0: no end */
 } fy_average_desc;
 
+/* Run-time monitors: OpenFOAM's volFieldValue / surfaceFieldValue function objects as reductions on the device ([OF-6 fieldValue, volFieldValue.C, surfaceFieldValue.C]
+   as recalled: OpenFOAM is not at hand to pin them).  An object reduces up to 8 fields over all cells (FY_MONITOR_VOL) or over the boundary faces of
+   one patch (FY_MONITOR_SURFACE), once every `interval` steps, where fieldAverage samples: after the last corrector, the turbulence correction and the T equation, before
+   setSourceZero.  x_i = the field in cell i, or its boundary value on face i ("p_boundary" ... below; phi: the flux OUT of the domain); V_i the cell volume, A_i = |Sf_i|;
+   w_i the weight field (volume: alpha; surface: phi, outward); n the number of cells / faces.  A vector field yields three values, component by component (min and max too).
+       sum          sum_i x_i                               average            (sum_i x_i) / n                        min, max     over i
+       volIntegrate sum_i x_i V_i                           volAverage         (sum_i x_i V_i) / (sum_i V_i)           weightedVolAverage  (sum_i (w_i V_i) x_i) / (sum_i w_i V_i)
+       areaIntegrate sum_i x_i A_i                          areaAverage        (sum_i x_i A_i) / (sum_i A_i)           weightedAverage     (sum_i w_i x_i) / (sum_i w_i)
+   Every sum is formed as per-256-block partials folded in a fixed order: FP64, no atomics, the same bits from run to run.  Each sample is one row {time, values} in a
+   ring on the device; the host copies rows out only when the ring is full or when fy_solver_get_monitor_rows asks, so that sampling never waits for the device.
+   time = start_time + the sum of the steps' deltaT since the solver was created. */
+#define FY_MONITOR_MAX_OBJECTS 8
+#define FY_MONITOR_MAX_FIELDS 8
+#define FY_MONITOR_VOL 1
+#define FY_MONITOR_SURFACE 2
+enum { FY_MONITOR_SUM = 1, FY_MONITOR_AVERAGE, FY_MONITOR_VOL_AVERAGE, FY_MONITOR_VOL_INTEGRATE, FY_MONITOR_WEIGHTED_VOL_AVERAGE, FY_MONITOR_MIN, FY_MONITOR_MAX,
+       FY_MONITOR_AREA_AVERAGE, FY_MONITOR_AREA_INTEGRATE, FY_MONITOR_WEIGHTED_AVERAGE };
+typedef struct fy_monitor_object {
+    char name[32];
+    int32_t kind;                   /* FY_MONITOR_VOL | FY_MONITOR_SURFACE */
+    int32_t patch;                  /* surface, fy_ldu_solver: the patch index; fy_solver: a mask of sides, bit 2 d + s (x- x+ y- y+ z- z+) -- one patch may cover several */
+    int32_t operation;              /* FY_MONITOR_*: volume sum average volAverage volIntegrate weightedVolAverage min max; surface sum average areaAverage areaIntegrate weightedAverage min max */
+    char weight_field[32];          /* weighted operations: "alpha" (volume) | "phi" (surface); else empty */
+    int32_t interval;               /* one sample every `interval` steps, >= 1 (0 is read as 1) */
+    int32_t n_fields;
+    char fields[FY_MONITOR_MAX_FIELDS][32];      /* volume: what fieldAverage accepts on this solver; surface: phi, p, U, T */
+} fy_monitor_object;
+typedef struct fy_monitor_desc {
+    int32_t n_objects;              /* 0: no monitors -- no kernel, no memory */
+    fy_monitor_object objects[FY_MONITOR_MAX_OBJECTS];
+    int32_t ring_rows;              /* rows of the device ring per object (0: 256) */
+    double start_time;              /* the time of the solver's creation (a case's startTime) */
+} fy_monitor_desc;
+
 /* Fluid temperature with particle-fluid heat exchange (a capability the reference does not have; DESIGN.md section 3 "heat exchange", DESIGN_FV.md "T equation").
    Fluid: cp [J/kg/K], kappa [W/m/K], D = kappa / (rho_f cp), Pr = nu rho_f cp / kappa, Deff = D + nut / prt (nut = 0 when laminar).  A particle of diameter d and
    temperature Tp, with the force pass's stencil (cells c, normalised weights w; point-force mode: the containing cell, w = 1, eps = 1):
@@ -396,6 +430,8 @@ typedef struct fy_case_desc {
     fy_average_desc average;
     /* constant/couplingProperties heatTransfer + 0/T: the fluid temperature equation and the particle-fluid heat exchange (all zero: off) */
     fy_thermal_desc thermal;
+    /* controlDict functions: the volFieldValue / surfaceFieldValue objects (all zero: none), applied at fy_solver_create with fy_solver_set_monitors */
+    fy_monitor_desc monitors;
 } fy_case_desc;
 
 typedef struct fy_solver fy_solver;
@@ -436,6 +472,21 @@ int fy_solver_set_field_average(fy_solver*, const fy_average_desc*);
 int fy_solver_get_average_state(fy_solver*, int item, int64_t* samples, double* time_averaged);
 int fy_solver_set_average_state(fy_solver*, int item, int64_t samples, double time_averaged);
 
+/* Run-time monitors on this solver (fy_monitor_desc above).  NULL or n_objects 0: off, the buffers freed; a new call starts every history from empty.  FY_ERR_INVALID,
+ * naming the object and the word: an unknown field or operation, a field this case does not have, a weighted operation without its weight field, an empty side mask
+ * (a patch without faces on a general mesh), more than FY_MONITOR_MAX_OBJECTS objects or FY_MONITOR_MAX_FIELDS fields; a slab solver: FY_ERR_UNSUPPORTED.
+ * At most three launches per sampled step on the solver's stream and no host synchronisation; their time is the "monitors" clock of fy_solver_get_kernel_timing.
+ * _layout: the number of values in a row of `object` and their labels, separated by '\n': "volAverage(p)", "volAverage(U)_x" ...
+ * _get_monitor_rows: rows [first_row, first_row + max_rows) of the object's history since set_monitors: times[r], values[r][n_values]; *n_rows = how many were copied
+ * (times and values may be NULL to count: *n_rows = rows from first_row on).  Only this call waits for the device.
+ * Boundary values as the equations see them are field names of fy_solver_read_field_host / _field_count (read-only; a slab solver: FY_ERR_UNSUPPORTED):
+ * "p_boundary" [nb], "U_boundary" [nb][3], "T_boundary" [nb] (thermal on); nb = 2 (ny nz + nx nz + nx ny), the six sides in the order x- x+ y- y+ z- z+, each side's
+ * faces with the lower remaining axis fastest.  fixedValue: the value; zeroGradient: the owner cell's; slip / symmetry: the owner's, a vector without its normal
+ * component; fixedFluxPressure: p_P + snGrad / deltaCoeff with the gradient as constrainPressure last left it. */
+int fy_solver_set_monitors(fy_solver*, const fy_monitor_desc*);
+int fy_solver_monitor_layout(fy_solver*, int object, int32_t* n_values, char* labels, int cap);
+int fy_solver_get_monitor_rows(fy_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
+
 /* Heat exchange (fy_case_desc.thermal.on; FY_ERR_INVALID on a solver without it).  The caller owns the particle temperatures: Tp[n] in the batch's wire order for the
  * n particles the batch holds now, host or device memory (copied), or NULL = thermal.particle_temperature for all of them; they stand until the next call for that
  * batch or until the batch's particle count changes (then the uniform value again).  q[n]: W into each particle over the last step, wire order, 0 for a particle
@@ -475,7 +526,7 @@ typedef struct fy_foam_case_info {
     char patch_of_side[6][64];             /* blockMesh patch on the XMIN, XMAX, YMIN, YMAX, ZMIN, ZMAX side */
     int64_t field_cells, field_offset;     /* cells the field files (and fy_foam_case_initial_*, fy_foam_case_write_fields) hold, global number of the first:
                                               n_cells and 0, or one processor directory's slab (fy_foam_case_open_processor) */
-    int32_t n_ignored_functions;           /* controlDict functions: objects of a type other than fieldAverage -- accepted, never run (fy_foam_case_ignored_function) */
+    int32_t n_ignored_functions;           /* controlDict functions: objects of a type other than fieldAverage, volFieldValue, surfaceFieldValue -- accepted, never run (fy_foam_case_ignored_function) */
 } fy_foam_case_info;
 int fy_foam_case_open(const char* case_dir, int solver /* FY_SOLVER_ICO | FY_SOLVER_PIMPLE */, fy_foam_case** out);
 /* a DECOMPOSED case (decomposePar, simple (1 1 nranks); the reference's -parallel run, README.md:29): mesh, controls and schemes from the case, the
@@ -512,6 +563,18 @@ int fy_foam_case_write_fields(const fy_foam_case*, const char* time_name, const 
  * totalIter = N + 1, totalTime = T + deltaT: OpenFOAM's convention as recalled, unpinned).  fy_foam_case_restore_averages (_ldu for a general case) loads them back from the start time
  * directory into a new solver (restartOnRestart off, and the files there); *restored = the number of items loaded, 0 = averaging starts from zero. */
 int fy_foam_case_ignored_function(const fy_foam_case*, int i, char* out, int cap);
+/* controlDict `functions`, objects of `type volFieldValue` / `type surfaceFieldValue` (not `enabled false`) become fy_case_desc.monitors / fy_ldu_case.monitors, in the
+ * dictionary's order ([OF-6 fieldValue, volFieldValue, surfaceFieldValue] as recalled, unpinned).  Accepted: fields ( <file name> ... ) with the case's file names (volume: what
+ * fieldAverage takes; surface: phi, p, U | U.<phase>, T), operation (fy_monitor_desc's words), weightField alpha.<phase> (volume) | phi (surface), regionType all (volume) |
+ * regionType patch with name <patch> (surface; on a block the patch becomes its mask of sides), writeFields false, writeControl / executeControl timeStep with writeInterval /
+ * executeInterval N (one sample every N steps), enabled, libs, log.  Refused by name with the accepted words (FY_ERR_UNSUPPORTED): every other keyword (scaleFactor,
+ * postOperation, ...), regionType cellZone | faceZone | sampledSurface, writeFields true, other controls, unknown operations, fields and patches, a cyclic patch, a decomposed case.
+ * fy_foam_case_write_monitors (_ldu for a general case) appends the rows the solver has gathered since the last call to
+ * <case>/postProcessing/<object>/<start time name>/volFieldValue.dat | surfaceFieldValue.dat: '#' header lines (region type and name, number of cells | faces, total volume |
+ * area, the column labels), then one row per sample: the time and the values, a vector as (x y z), writePrecision digits.  The first call of a run creates the file: a
+ * restarted run writes into the directory of its own start time */
+int fy_foam_case_monitor_count(const fy_foam_case*);
+int fy_foam_case_write_monitors(const fy_foam_case*, fy_solver*);
 int fy_foam_case_restore_averages(const fy_foam_case*, fy_solver*, int* restored);
 int fy_foam_case_close(fy_foam_case*);
 
@@ -693,6 +756,7 @@ typedef struct fy_ldu_case {
     const int32_t* T_bc;             /* per patch: FY_BC_T_ZERO_GRADIENT | FY_BC_T_FIXED_VALUE (NULL: zeroGradient everywhere); a symmetry / slip patch takes
                                         FY_BC_T_ZERO_GRADIENT, folded cyclic pairs are internal faces and need nothing */
     const double* T_value;           /* [n_patches] */
+    fy_monitor_desc monitors;        /* controlDict functions: the volFieldValue / surfaceFieldValue objects as in fy_case_desc (all zero: none); `patch` is a patch index */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */
@@ -704,6 +768,12 @@ int fy_ldu_solver_get_stats(fy_ldu_solver*, fy_step_stats* out);
 int fy_ldu_solver_set_field_average(fy_ldu_solver*, const fy_average_desc*);
 int fy_ldu_solver_get_average_state(fy_ldu_solver*, int item, int64_t* samples, double* time_averaged);
 int fy_ldu_solver_set_average_state(fy_ldu_solver*, int item, int64_t samples, double time_averaged);
+/* Run-time monitors as on fy_solver (fy_solver_set_monitors): a surface object's `patch` is a patch index (a folded cyclic patch has no faces and is refused by name).
+ * "p_boundary" [nb], "U_boundary" [nb][3] and, with thermal on, "T_boundary" [nb] are read-only field names: nb = n_faces - n_internal_faces in the solver's
+ * boundary-face order, like "nut_boundary" */
+int fy_ldu_solver_set_monitors(fy_ldu_solver*, const fy_monitor_desc*);
+int fy_ldu_solver_monitor_layout(fy_ldu_solver*, int object, int32_t* n_values, char* labels, int cap);
+int fy_ldu_solver_get_monitor_rows(fy_ldu_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
 /* Heat exchange (fy_ldu_case.thermal.on; FY_ERR_INVALID on a solver without it): the entry points of fy_solver one for one, with the same semantics.  While thermal is
  * on, "T" [nc] (also writable: a non-uniform start), "heatSp" [nc] (W/K), "heatSu" [nc] (W) and, with thermal.beta != 0 and g != 0, "buoyancy" [nc][3] are field names
  * of fy_ldu_solver_read_field_host, and "T" one that fieldAverage accepts. */
@@ -742,6 +812,7 @@ int fy_foam_case_poly_mesh(const fy_foam_case*, fy_poly_mesh* out);             
 int fy_foam_case_ldu_desc(const fy_foam_case*, fy_ldu_case* out);                 /* ready for fy_ldu_solver_create (patch arrays point into the case object) */
 int fy_foam_case_patch_name(const fy_foam_case*, int patch, char* out, int cap); /* the boundary file's order = fy_poly_mesh's patch numbers */
 int fy_foam_case_write_time_ldu(const fy_foam_case*, fy_ldu_solver*, const char* time_name);     /* runTime.write() (icoFoamYade.C:142): <time>/U, p */
+int fy_foam_case_write_monitors_ldu(const fy_foam_case*, fy_ldu_solver*);                           /* fy_foam_case_write_monitors for a general case */
 int fy_foam_case_restore_averages_ldu(const fy_foam_case*, fy_ldu_solver*, int* restored);         /* fy_foam_case_restore_averages for a general case */
 
 #ifdef __cplusplus

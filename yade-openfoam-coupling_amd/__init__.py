@@ -139,6 +139,81 @@ class _Averages:
         _check(self._avg_fn("set_average_state")(self._h, int(item), int(samples), float(time_averaged)))
 
 
+MONITOR_MAX_OBJECTS, MONITOR_MAX_FIELDS = 8, 8
+MONITOR_VOL, MONITOR_SURFACE = 1, 2
+MONITOR_OPERATIONS = {"sum": 1, "average": 2, "volAverage": 3, "volIntegrate": 4, "weightedVolAverage": 5, "min": 6, "max": 7, "areaAverage": 8, "areaIntegrate": 9,
+                      "weightedAverage": 10}
+
+
+class MonitorObject(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("kind", C.c_int32), ("patch", C.c_int32), ("operation", C.c_int32), ("weight_field", C.c_char * 32), ("interval", C.c_int32),
+                ("n_fields", C.c_int32), ("fields", (C.c_char * 32) * MONITOR_MAX_FIELDS)]
+
+
+class MonitorDesc(C.Structure):
+    """fy_monitor_desc: the volFieldValue / surfaceFieldValue objects of a solver (all zero: none)"""
+    _fields_ = [("n_objects", C.c_int32), ("objects", MonitorObject * MONITOR_MAX_OBJECTS), ("ring_rows", C.c_int32), ("start_time", C.c_double)]
+
+
+def monitor_desc(objects, ring_rows=0, start_time=0.0):
+    """objects: dicts with name, kind ("vol" | "surface"), operation (OpenFOAM's name, or a number), fields, and optionally patch (surface: a patch index on a general
+    mesh, a mask of sides bit 2 d + s on a block), weight_field, interval -> MonitorDesc.  Counts past the limits are passed on as they are, for the library to refuse"""
+    d = MonitorDesc()
+    objects = list(objects or [])
+    d.n_objects = len(objects)
+    for q, o in enumerate(objects[:MONITOR_MAX_OBJECTS]):
+        m = d.objects[q]
+        m.name = str(o["name"]).encode()
+        m.kind = {"vol": MONITOR_VOL, "surface": MONITOR_SURFACE}.get(o["kind"], o["kind"])
+        m.patch = int(o.get("patch", 0))
+        op = o["operation"]
+        m.operation = MONITOR_OPERATIONS.get(op, -1) if isinstance(op, str) else int(op)
+        m.weight_field = str(o.get("weight_field", "")).encode()
+        m.interval = int(o.get("interval", 1))
+        fields = list(o["fields"])
+        m.n_fields = len(fields)
+        for f, nm in enumerate(fields[:MONITOR_MAX_FIELDS]):
+            m.fields[f].value = str(nm).encode()
+    d.ring_rows, d.start_time = int(ring_rows), float(start_time)
+    return d
+
+
+class _Monitors:
+    """run-time monitors on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*): volFieldValue / surfaceFieldValue reductions on the device"""
+
+    def _mon_fn(self, what):
+        f = getattr(lib(), f"{self._AVG_PREFIX}_{what}")
+        f.argtypes = {"set_monitors": [C.c_void_p, C.POINTER(MonitorDesc)], "monitor_layout": [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_int],
+                      "get_monitor_rows": [C.c_void_p, C.c_int, C.c_int64, C.c_int64, _dp, _dp, C.POINTER(C.c_int64)]}[what]
+        return f
+
+    def set_monitors(self, objects, ring_rows=0, start_time=0.0):
+        """objects: as monitor_desc takes them (or a MonitorDesc); None or []: off"""
+        if not objects:
+            _check(self._mon_fn("set_monitors")(self._h, None))
+        else:
+            d = objects if isinstance(objects, MonitorDesc) else monitor_desc(objects, ring_rows, start_time)
+            _check(self._mon_fn("set_monitors")(self._h, C.byref(d)))
+
+    def monitor_layout(self, obj):
+        """the labels of the values in a row of object `obj`: "volAverage(p)", "volAverage(U)_x" ..."""
+        n = C.c_int32(0); buf = C.create_string_buffer(4096)
+        _check(self._mon_fn("monitor_layout")(self._h, int(obj), C.byref(n), buf, 4096))
+        labels = buf.value.decode().split("\n") if n.value else []
+        assert len(labels) == n.value
+        return labels
+
+    def monitor_rows(self, obj, first_row=0):
+        """(times [rows], values [rows, n_values]) of object `obj` from row `first_row` on; this call waits for the device, sampling never does"""
+        n = C.c_int64(0)
+        _check(self._mon_fn("get_monitor_rows")(self._h, int(obj), int(first_row), 0, None, None, C.byref(n)))
+        nv = len(self.monitor_layout(obj))
+        t = np.zeros(n.value); v = np.zeros((n.value, nv))
+        if n.value:
+            _check(self._mon_fn("get_monitor_rows")(self._h, int(obj), int(first_row), n.value, _d(t), _d(v), C.byref(n)))
+        return t, v
+
+
 class _ParticleHeat:
     """particle batches and the heat exchange's particle side on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*); the object has _h, _cpl, _batch_n"""
     _AVG_PREFIX = "fy_solver"
@@ -233,7 +308,7 @@ class LduCase(C.Structure):
                 ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double), ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double),
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
                 ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp)]
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp), ("monitors", MonitorDesc)]
 
 
 NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
@@ -276,7 +351,7 @@ class CaseDesc(C.Structure):
                 ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double), ("eps_max_iter", C.c_int32),
                 ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc)]
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("monitors", MonitorDesc)]
 
 
 BC_WALL_FUNCTION, BC_NUT_CALCULATED = 2, 3
@@ -741,7 +816,7 @@ def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 
     return c
 
 
-class Solver(_Averages, _ParticleHeat):
+class Solver(_Averages, _Monitors, _ParticleHeat):
     """the icoFoamYade / pimpleFoamYade executables' time loop (icoFoamYade.C:65-149, pimpleFoamYade.C:60-114): step() is one
     pass of the loop body, including yadeCoupling.setParticleAction and setSourceZero."""
 
@@ -1120,6 +1195,14 @@ class FoamCase:
     def write(self, solver, time_name):
         _check(lib().fy_foam_case_write_time(self._h, solver._h, str(time_name).encode()))
 
+    _WRITE_MONITORS = "fy_foam_case_write_monitors"
+
+    def write_monitors(self, solver):
+        """append the rows the solver's monitors have gathered since the last call to postProcessing/<object>/<start time name>/volFieldValue.dat | surfaceFieldValue.dat"""
+        f = getattr(lib(), self._WRITE_MONITORS)
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        _check(f(self._h, solver._h))
+
     _RESTORE = "fy_foam_case_restore_averages"
 
     def restore_averages(self, solver):
@@ -1180,6 +1263,7 @@ class GeneralFoamCase(FoamCase):
         self.p_value = np.array([self.ldu_case.p_value[q] for q in range(m.n_patches)])
 
     _RESTORE = "fy_foam_case_restore_averages_ldu"
+    _WRITE_MONITORS = "fy_foam_case_write_monitors_ldu"
 
     def write(self, solver, time_name):
         _check(lib().fy_foam_case_write_time_ldu(self._h, solver._h, str(time_name).encode()))
@@ -1326,7 +1410,7 @@ class VirtualSlabs:
         self.solvers, self.comms = [], []
 
 
-class LduSolver(_Averages, _ParticleHeat):
+class LduSolver(_Averages, _Monitors, _ParticleHeat):
     """icoFoamYade's loop body on a general polyhedral mesh in OpenFOAM's addressing (fy_ldu_solver, include/foamyade_hip.h).  mesh: dict with points (n,3),
     face_offsets, face_points, owner, neighbour, n_cells, patch_start, patch_size (tests/poly_meshes.py builds them); u_bc / p_bc / values per patch; the
     controls are fy_ldu_case's (defaults: the icoFoam cavity tutorial's)"""
@@ -1425,7 +1509,7 @@ class LduSolver(_Averages, _ParticleHeat):
     def get(self, name):
         out = np.zeros(self._size(name))
         _check(lib().fy_ldu_solver_read_field_host(self._h, name.encode(), _d(out)))
-        return out.reshape(-1, 3) if name in ("C", "Cf", "Sf", "kvec", "sep") else out
+        return out.reshape(-1, 3) if name in ("C", "Cf", "Sf", "kvec", "sep", "U_boundary") else out
 
     geometry = get
 

@@ -14,6 +14,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -80,6 +81,10 @@ struct fy_foam_case {
     std::vector<AvgField> avg_fields;
     bool avg_restart_on_restart = false;
     std::vector<std::string> ignored_functions;
+    // ... and the volFieldValue / surfaceFieldValue objects (desc.monitors carries them in this order): the region's name ("all" | the patch), the fields' file
+    // names, and how many rows of the solver's history fy_foam_case_write_monitors has put into the object's .dat file
+    struct MonMeta { std::string name, region; bool vol = true; std::vector<std::string> files; std::vector<int> ncomp; mutable int64_t rows_written = 0; };
+    std::vector<MonMeta> monitors;
 };
 
 namespace {
@@ -909,12 +914,125 @@ int read_coupling_properties(fy_foam_case* c) {
     return FY_OK;
 }
 
+const char* monitor_op_word(int op) {
+    static const char* const nm[] = {"", "sum", "average", "volAverage", "volIntegrate", "weightedVolAverage", "min", "max", "areaAverage", "areaIntegrate", "weightedAverage"};
+    return op >= FY_MONITOR_SUM && op <= FY_MONITOR_WEIGHTED_AVERAGE ? nm[op] : "?";
+}
+
+// One volFieldValue / surfaceFieldValue object of controlDict `functions` [OF-6 fieldValue, volFieldValue, surfaceFieldValue as recalled] -> desc.monitors and c->monitors.
+// Accepted: fields (file names), operation, weightField, regionType all | patch with name, writeFields false, writeControl / executeControl timeStep with
+// writeInterval / executeInterval N, enabled, libs, log.  Everything else the function objects offer is refused by name
+int read_monitor(fy_foam_case* c, const std::string& name, const std::string& ty, const FoamDict* o, const std::string& where) {
+    const char* w = where.c_str();
+    const bool vol = ty == "volFieldValue";
+    static const char* const keys[] = {"type", "libs", "log", "enabled", "fields", "operation", "weightField", "regionType", "name", "writeFields", "writeControl",
+                                       "executeControl", "writeInterval", "executeInterval"};
+    for (const std::string& k : o->order) {
+        bool known = false;
+        for (const char* a : keys) known = known || k == a;
+        if (!known) return fail(FY_ERR_UNSUPPORTED, "%s: %s is not supported; accepted: type, libs, log, enabled, fields, operation, weightField, regionType, name, writeFields false, "
+                                                    "writeControl | executeControl timeStep, writeInterval | executeInterval", w, k.c_str());
+    }
+    if (c->proc_count > 1)
+        return fail(FY_ERR_UNSUPPORTED, "%s: type %s is not available in a decomposed (-parallel) run; accepted: an undecomposed case on one domain, or 'enabled false'", w, ty.c_str());
+    fy_monitor_desc& md = c->desc.monitors;
+    if (md.n_objects >= FY_MONITOR_MAX_OBJECTS)
+        return fail(FY_ERR_UNSUPPORTED, "%s: more than %d volFieldValue / surfaceFieldValue objects; accepted: at most %d", w, FY_MONITOR_MAX_OBJECTS, FY_MONITOR_MAX_OBJECTS);
+    if (name.size() >= sizeof(md.objects[0].name)) return fail(FY_ERR_UNSUPPORTED, "%s: the object's name is longer than %zu characters; accepted: a shorter name", w, sizeof(md.objects[0].name) - 1);
+    fy_monitor_object ob{};
+    fy_foam_case::MonMeta meta;
+    meta.name = name; meta.vol = vol;
+    std::snprintf(ob.name, sizeof(ob.name), "%s", name.c_str());
+    ob.kind = vol ? FY_MONITOR_VOL : FY_MONITOR_SURFACE;
+    std::string word;
+    if (!o->word("regionType", &word) || word != (vol ? "all" : "patch"))
+        return fail(FY_ERR_UNSUPPORTED, "%s: regionType %s is not supported; accepted: %s", w, word.empty() ? "(absent)" : word.c_str(), vol ? "all" : "patch (with name <patch>)");
+    meta.region = "all";
+    if (!vol) {
+        std::string pn;
+        if (!o->word("name", &pn)) return fail(FY_ERR_INVALID, "%s: regionType patch needs 'name <patch>;'", w);
+        const std::vector<std::string> patches = field_patches(c);
+        std::string all;
+        int found = -1, mask = 0;
+        for (size_t q = 0; q < patches.size(); ++q) {
+            if (patches[q] == pn) { found = (int)q; mask |= 1 << q; }
+            if (all.find(patches[q]) == std::string::npos) all += (all.empty() ? "" : ", ") + patches[q];
+        }
+        if (found < 0) return fail(FY_ERR_UNSUPPORTED, "%s: name %s: the mesh has no such patch; accepted: %s", w, pn.c_str(), all.c_str());
+        if (c->general && c->g_patch_neighbour.size() > (size_t)found && c->g_patch_neighbour[(size_t)found] >= 0)
+            return fail(FY_ERR_UNSUPPORTED, "%s: name %s is a cyclic patch, whose faces are internal faces of the solver's mesh; accepted: a patch of boundary faces", w, pn.c_str());
+        ob.patch = c->general ? found : mask;                    // (block: one patch may cover several sides -- `walls`)
+        meta.region = pn;
+    }
+    static const struct { const char* word; int op; int kinds; } ops[] = {
+        {"sum", FY_MONITOR_SUM, 3}, {"average", FY_MONITOR_AVERAGE, 3}, {"min", FY_MONITOR_MIN, 3}, {"max", FY_MONITOR_MAX, 3},
+        {"volAverage", FY_MONITOR_VOL_AVERAGE, 1}, {"volIntegrate", FY_MONITOR_VOL_INTEGRATE, 1}, {"weightedVolAverage", FY_MONITOR_WEIGHTED_VOL_AVERAGE, 1},
+        {"areaAverage", FY_MONITOR_AREA_AVERAGE, 2}, {"areaIntegrate", FY_MONITOR_AREA_INTEGRATE, 2}, {"weightedAverage", FY_MONITOR_WEIGHTED_AVERAGE, 2}};
+    word.clear();
+    o->word("operation", &word);
+    for (const auto& e : ops) if (word == e.word && (e.kinds & (vol ? 1 : 2))) ob.operation = e.op;
+    if (!ob.operation)
+        return fail(FY_ERR_UNSUPPORTED, "%s: operation %s is not supported; accepted: %s", w, word.empty() ? "(absent)" : word.c_str(),
+                    vol ? "sum, average, volAverage, volIntegrate, weightedVolAverage, min, max" : "sum, average, areaAverage, areaIntegrate, weightedAverage, min, max");
+    const bool weighted = ob.operation == FY_MONITOR_WEIGHTED_VOL_AVERAGE || ob.operation == FY_MONITOR_WEIGHTED_AVERAGE;
+    const std::string want_w = vol ? field_name(c, F_ALPHA) : std::string("phi");
+    word.clear();
+    if (o->word("weightField", &word)) {
+        if (word != want_w || (vol && !has_field(c, F_ALPHA)))
+            return fail(FY_ERR_UNSUPPORTED, "%s: weightField %s is not supported; accepted: %s", w, word.c_str(), vol ? (has_field(c, F_ALPHA) ? want_w.c_str() : "none (icoFoamYade has no void fraction)") : "phi");
+        std::snprintf(ob.weight_field, sizeof(ob.weight_field), "%s", vol ? "alpha" : "phi");
+    } else if (weighted)
+        return fail(FY_ERR_UNSUPPORTED, "%s: operation %s needs a weightField; accepted: weightField %s", w, monitor_op_word(ob.operation), want_w.c_str());
+    bool wf = false;
+    word.clear();
+    o->word("writeFields", &word);
+    if (o->has("writeFields") && (!o->boolean("writeFields", &wf) || wf)) return fail(FY_ERR_UNSUPPORTED, "%s: writeFields %s is not supported; accepted: false", w, word.c_str());
+    for (const char* key : {"writeControl", "executeControl"})
+        if (o->word(key, &word) && word != "timeStep") return fail(FY_ERR_UNSUPPORTED, "%s: %s %s is not supported; accepted: timeStep (with writeInterval N)", w, key, word.c_str());
+    double iv = 1, iv2 = 0;
+    const bool h1 = o->scalar("writeInterval", &iv), h2 = o->scalar("executeInterval", &iv2);
+    if (!h1 && h2) iv = iv2;
+    if ((h1 && h2 && iv != iv2) || !(iv >= 1) || iv != std::floor(iv) || iv > 1e9)
+        return fail(FY_ERR_UNSUPPORTED, "%s: writeInterval %g / executeInterval %g is not supported; accepted: one whole number of steps >= 1 for both", w, iv, h2 ? iv2 : iv);
+    ob.interval = (int32_t)iv;
+    const auto* ft = o->tokens("fields");
+    if (!ft) return fail(FY_ERR_INVALID, "%s: no 'fields ( <name> ... )' list", w);
+    const std::string ph = c->phase.empty() ? std::string("<phase>") : c->phase;
+    const std::string accepted = vol ? c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource" + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string())
+                                     : "phi, p, " + c->u_name + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string());
+    static const struct { const char* stem; int F; int ncomp; bool surface; } known[] = {
+        {"U", F_U, 3, true}, {"p", F_P, 1, true}, {"alpha", F_ALPHA, 1, false}, {"nut", F_NUT, 1, false}, {"k", F_K, 1, false}, {"epsilon", F_EPS, 1, false},
+        {"uParticle", -1, 3, false}, {"uSource", -1, 3, false}, {"T", F_T, 1, true}, {"phi", -2, 1, true}};
+    for (const std::string& file : *ft) {
+        double cnt;
+        if (file == "(" || file == ")" || fy::foam_tok_is_number(file, &cnt)) continue;
+        const std::string stem = file.substr(0, file.find('.'));
+        const auto* kf = &known[0];
+        bool is_known = false;
+        for (const auto& k : known)
+            if (stem == k.stem && (vol ? k.F != -2 : k.surface) && (k.F != F_T || c->desc.thermal.on)) { kf = &k; is_known = true; }
+        if (!is_known) return fail(FY_ERR_UNSUPPORTED, "%s: unknown field '%s'; accepted: %s", w, file.c_str(), accepted.c_str());
+        const bool has = kf->F >= 0 ? (has_field(c, kf->F) && file == field_name(c, kf->F)) : (file == kf->stem && (stem != "uParticle" || c->solver == FY_SOLVER_PIMPLE));
+        if (!has) return fail(FY_ERR_UNSUPPORTED, "%s: this case has no field '%s'; accepted: %s", w, file.c_str(), accepted.c_str());
+        for (const std::string& f : meta.files) if (f == file) return fail(FY_ERR_INVALID, "%s: field '%s' is listed twice", w, file.c_str());
+        if (ob.n_fields >= FY_MONITOR_MAX_FIELDS) return fail(FY_ERR_UNSUPPORTED, "%s: more than %d fields; accepted: at most %d", w, FY_MONITOR_MAX_FIELDS, FY_MONITOR_MAX_FIELDS);
+        std::snprintf(ob.fields[ob.n_fields++], sizeof(ob.fields[0]), "%s", kf->stem);
+        meta.files.push_back(file); meta.ncomp.push_back(kf->ncomp);
+    }
+    if (ob.n_fields == 0) return fail(FY_ERR_INVALID, "%s: the 'fields' list is empty", w);
+    md.objects[md.n_objects++] = ob;
+    md.start_time = c->start_time;
+    c->monitors.push_back(meta);
+    return FY_OK;
+}
+
 // controlDict `functions` [OF-6 functionObjectList; fieldAverage / fieldAverageItem as recalled]: one fieldAverage object -> desc.average (solver field names)
 // and c->avg_fields (file names); objects of other types are accepted and not run, their names kept.  Everything fieldAverage offers beyond the plain running
 // mean / prime2Mean is refused by name.  Called last in read_controls: which fields the case has depends on the solver and the turbulence model.
 int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) {
     c->desc.average = fy_average_desc{};
     c->avg_name.clear(); c->avg_fields.clear(); c->ignored_functions.clear(); c->avg_restart_on_restart = false;
+    c->desc.monitors = fy_monitor_desc{}; c->monitors.clear();
     const FoamDict* fn = d.subdict("functions");
     if (!fn) return FY_OK;
     for (const std::string& name : fn->order) {
@@ -922,10 +1040,12 @@ int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) 
         if (!o) continue;
         std::string ty;
         o->word("type", &ty);
-        if (ty != "fieldAverage") { c->ignored_functions.push_back(name + " (type " + (ty.empty() ? "?" : ty) + ")"); continue; }
+        const bool monitor = ty == "volFieldValue" || ty == "surfaceFieldValue";
+        if (ty != "fieldAverage" && !monitor) { c->ignored_functions.push_back(name + " (type " + (ty.empty() ? "?" : ty) + ")"); continue; }
         bool enabled = true;
         if (o->boolean("enabled", &enabled) && !enabled) continue;
         const std::string where = path + ": functions." + name;
+        if (monitor) { FY_TRY(read_monitor(c, name, ty, o, where)); continue; }
         const char* w = where.c_str();
         if (!c->avg_name.empty())
             return fail(FY_ERR_UNSUPPORTED, "%s: a second object of type fieldAverage (the first is '%s'); accepted: one enabled fieldAverage object, with all fields in its list", w, c->avg_name.c_str());
@@ -1461,6 +1581,61 @@ int restore_averages(const fy_foam_case* c, double dt, int* restored, Write writ
 
 }  // namespace
 
+namespace {
+// The rows the solver's monitors have gathered since the last call -> postProcessing/<object>/<start time name>/volFieldValue.dat | surfaceFieldValue.dat (the layout of
+// OpenFOAM-6's fieldValue files as recalled: '#' header lines, then one row per sample -- time, values, a vector as (x y z)).  measure(i, &n, &total): the object's
+// number of cells / faces and their total volume / area
+template <class Layout, class Rows, class Measure>
+int write_monitors(const fy_foam_case* c, Layout layout, Rows rows, Measure measure) {
+    for (size_t q = 0; q < c->monitors.size(); ++q) {
+        const fy_foam_case::MonMeta& m = c->monitors[q];
+        int32_t nv = 0;
+        FY_TRY(layout((int)q, &nv));
+        int64_t have = 0;
+        FY_TRY(rows((int)q, m.rows_written, 0, nullptr, nullptr, &have));
+        std::string dir = join(c->dir, "postProcessing");
+        for (const std::string& part : {std::string(), m.name, c->start_name}) {
+            if (!part.empty()) dir = join(dir, part);
+            if (mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) return fail(FY_ERR_INVALID, "cannot create %s", dir.c_str());
+        }
+        const std::string path = join(dir, m.vol ? "volFieldValue.dat" : "surfaceFieldValue.dat");
+        FILE* f = std::fopen(path.c_str(), m.rows_written == 0 ? "w" : "a");
+        if (!f) return fail(FY_ERR_INVALID, "cannot write %s", path.c_str());
+        const int pr = c->write_precision;
+        if (m.rows_written == 0) {
+            int64_t n = 0; double total = 0;
+            const int rc = measure((int)q, &n, &total);
+            if (rc != FY_OK) { std::fclose(f); return rc; }
+            std::fprintf(f, "# Region type : %s%s\n", m.vol ? "all" : "patch ", m.vol ? "" : m.region.c_str());
+            std::fprintf(f, "# %s       : %lld\n", m.vol ? "Cells" : "Faces", (long long)n);
+            std::fprintf(f, "# %s      : %.*g\n", m.vol ? "Volume" : "Area  ", pr, total);
+            std::fprintf(f, "# Time");
+            for (const std::string& file : m.files) std::fprintf(f, "\t%s(%s)", monitor_op_word(c->desc.monitors.objects[q].operation), file.c_str());
+            std::fprintf(f, "\n");
+        }
+        if (have > 0) {
+            std::vector<double> t((size_t)have), v((size_t)have * (size_t)nv);
+            int64_t got = 0;
+            const int rc = rows((int)q, m.rows_written, have, t.data(), v.data(), &got);
+            if (rc != FY_OK) { std::fclose(f); return rc; }
+            for (int64_t r = 0; r < got; ++r) {
+                std::fprintf(f, "%.*g", pr, t[(size_t)r]);
+                const double* x = v.data() + (size_t)r * nv;
+                for (int nc : m.ncomp) {
+                    if (nc == 3) std::fprintf(f, "\t(%.*g %.*g %.*g)", pr, x[0], pr, x[1], pr, x[2]);
+                    else std::fprintf(f, "\t%.*g", pr, x[0]);
+                    x += nc;
+                }
+                std::fprintf(f, "\n");
+            }
+            m.rows_written += got;
+        }
+        if (std::fclose(f) != 0) return fail(FY_ERR_INVALID, "cannot write %s", path.c_str());
+    }
+    return FY_OK;
+}
+}  // namespace
+
 extern "C" {
 
 static int open_case(const char* case_dir, int solver, int rank, int nranks, fy_foam_case** out) {
@@ -1718,6 +1893,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->wf_kappa = d.wf_kappa; out->wf_E = d.wf_E;
     out->drag_law = d.drag_law; out->force_models = d.force_models;
     out->average = d.average;
+    out->monitors = d.monitors;
     out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
     return FY_OK;
 }
@@ -1750,6 +1926,57 @@ int fy_foam_case_restore_averages_ldu(const fy_foam_case* c, fy_ldu_solver* s, i
     if (!c->general) return fail(FY_ERR_INVALID, "fy_foam_case_restore_averages_ldu: the case was opened as a block (fy_foam_case_restore_averages)");
     return restore_averages(c, c->desc.dt, restored, [s](const char* nm, const double* v) { return fy_ldu_solver_write_field_host(s, nm, v); },
                             [s](int i, int64_t N, double T) { return fy_ldu_solver_set_average_state(s, i, N, T); });
+}
+
+int fy_foam_case_monitor_count(const fy_foam_case* c) { return c ? (int)c->monitors.size() : 0; }
+
+int fy_foam_case_write_monitors(const fy_foam_case* c, fy_solver* s) {
+    if (!c || !s) return fail(FY_ERR_INVALID, "fy_foam_case_write_monitors: null argument");
+    if (c->general) return fail(FY_ERR_INVALID, "fy_foam_case_write_monitors: the case holds a general mesh (fy_foam_case_write_monitors_ldu)");
+    const fy_case_desc& d = c->desc;
+    auto h = [&](int a, int q) { return c->grading[a].empty() ? d.dx : c->grading[a][(size_t)q]; };
+    return write_monitors(c, [s](int q, int32_t* nv) { return fy_solver_monitor_layout(s, q, nv, nullptr, 0); },
+                          [s](int q, int64_t first, int64_t mx, double* t, double* v, int64_t* n) { return fy_solver_get_monitor_rows(s, q, first, mx, t, v, n); },
+                          [&](int q, int64_t* n, double* total) -> int {
+                              const int ext[3] = {d.nx, d.ny, d.nz};
+                              double len[3] = {0, 0, 0};
+                              for (int a = 0; a < 3; ++a) for (int k = 0; k < ext[a]; ++k) len[a] += h(a, k);
+                              if (c->monitors[(size_t)q].vol) { *n = (int64_t)d.nx * d.ny * d.nz; *total = len[0] * len[1] * len[2]; return FY_OK; }
+                              *n = 0; *total = 0;
+                              for (int side = 0; side < 6; ++side)
+                                  if (d.monitors.objects[q].patch >> side & 1) {
+                                      const int a = side / 2, b1 = (a + 1) % 3, b2 = (a + 2) % 3;
+                                      *n += (int64_t)ext[b1] * ext[b2]; *total += len[b1] * len[b2];
+                                  }
+                              return FY_OK;
+                          });
+}
+
+int fy_foam_case_write_monitors_ldu(const fy_foam_case* c, fy_ldu_solver* s) {
+    if (!c || !s) return fail(FY_ERR_INVALID, "fy_foam_case_write_monitors_ldu: null argument");
+    if (!c->general) return fail(FY_ERR_INVALID, "fy_foam_case_write_monitors_ldu: the case was opened as a block (fy_foam_case_write_monitors)");
+    return write_monitors(c, [s](int q, int32_t* nv) { return fy_ldu_solver_monitor_layout(s, q, nv, nullptr, 0); },
+                          [s](int q, int64_t first, int64_t mx, double* t, double* v, int64_t* n) { return fy_ldu_solver_get_monitor_rows(s, q, first, mx, t, v, n); },
+                          [&](int q, int64_t* n, double* total) -> int {
+                              const bool vol = c->monitors[(size_t)q].vol;
+                              int64_t cnt = 0, no = 0;
+                              FY_TRY(fy_ldu_solver_field_count(s, vol ? "V" : "magSf", &cnt));
+                              std::vector<double> m((size_t)cnt);
+                              FY_TRY(fy_ldu_solver_read_field_host(s, vol ? "V" : "magSf", m.data()));
+                              *n = 0; *total = 0;
+                              if (vol) { *n = cnt; for (double x : m) *total += x; return FY_OK; }
+                              // the solver's face f was made from the case's face orig_face[f] (a mesh with folded cyclic pairs); without such pairs the numbering is the case's
+                              FY_TRY(fy_ldu_solver_field_count(s, "orig_face", &no));
+                              std::vector<double> of((size_t)no);
+                              if (no) FY_TRY(fy_ldu_solver_read_field_host(s, "orig_face", of.data()));
+                              const int pa = c->desc.monitors.objects[q].patch;
+                              const int64_t f0 = c->g_patch_start[(size_t)pa], f1 = f0 + c->g_patch_size[(size_t)pa];
+                              for (int64_t f = 0; f < cnt; ++f) {
+                                  const int64_t orig = no ? (int64_t)of[(size_t)f] : f;
+                                  if (orig >= f0 && orig < f1) { *n += 1; *total += m[(size_t)f]; }
+                              }
+                              return FY_OK;
+                          });
 }
 
 int fy_foam_case_close(fy_foam_case* c) {

@@ -52,16 +52,22 @@ static void print_coupling(int drag_law, unsigned force_models) {
 }
 
 // controlDict functions: what is averaged (the solver's create applies it), and one line per function object of another type -- opened, never run
-static void print_functions(const fy_foam_case* fc, const fy_average_desc& av) {
+static void print_functions(const fy_foam_case* fc, const fy_average_desc& av, const fy_monitor_desc& mon) {
     fy_foam_case_info info;
     if (fy_foam_case_info_get(fc, &info) != FY_OK) return;
     for (int i = 0; i < info.n_ignored_functions; ++i) {
         char name[256];
-        if (fy_foam_case_ignored_function(fc, i, name, (int)sizeof(name)) == FY_OK) std::printf("functions: %s is not run (only fieldAverage is implemented)\n", name);
+        if (fy_foam_case_ignored_function(fc, i, name, (int)sizeof(name)) == FY_OK) std::printf("functions: %s is not run (only fieldAverage, volFieldValue and surfaceFieldValue are implemented)\n", name);
     }
     if (av.n_items > 0) {
         std::printf("fieldAverage:");
         for (int i = 0; i < av.n_items; ++i) std::printf(" %.32s%s", av.items[i].field, av.items[i].prime2_mean ? " (mean, prime2Mean)" : " (mean)");
+        std::printf("\n");
+    }
+    if (mon.n_objects > 0) {
+        std::printf("Monitors:");
+        for (int i = 0; i < mon.n_objects; ++i) std::printf(" %.32s (%s, %d field%s)", mon.objects[i].name, mon.objects[i].kind == FY_MONITOR_VOL ? "volFieldValue" : "surfaceFieldValue",
+                                                            mon.objects[i].n_fields, mon.objects[i].n_fields == 1 ? "" : "s");
         std::printf("\n");
     }
 }
@@ -74,7 +80,7 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     if (fy_foam_case_poly_mesh(fc, &pm) != FY_OK || fy_foam_case_ldu_desc(fc, &lc) != FY_OK || fy_foam_case_info_get(fc, &info) != FY_OK) return die("reading the case");
     std::printf("             %d points, %d faces (%d internal), %d cells, %d patches\n", pm.n_points, pm.n_faces, pm.n_internal_faces, pm.n_cells, pm.n_patches);
     print_coupling(lc.drag_law, lc.force_models);
-    print_functions(fc, lc.average);
+    print_functions(fc, lc.average, lc.monitors);
     fy_ldu_solver* s = nullptr;
     if (fy_ldu_solver_create(&pm, &lc, trp, device, &s) != FY_OK) return die("fy_ldu_solver_create");
     fy_ldu_solver_hold_sources(s, 1);                   // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147, pimpleFoamYade.C:107-109)
@@ -107,8 +113,9 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
         std::printf("pressure: %d solves, %d iterations, initial residual %g, final residual %g\n", st.p_solves, st.p_iters_total, st.p_initial_residual, st.p_final_residual);
         std::printf("time step continuity errors : sum local = %g, global = %g, cumulative = %g\n\n", st.cont_err_sum_local, st.cont_err_global, st.cont_err_cumulative);
         if (info.write_interval_steps > 0 && k % info.write_interval_steps == 0)
-            if (fy_foam_case_write_time_ldu(fc, s, tname) != FY_OK) return die("writing the time directory");
+            if (fy_foam_case_write_time_ldu(fc, s, tname) != FY_OK || fy_foam_case_write_monitors_ldu(fc, s) != FY_OK) return die("writing the time directory");
     }
+    if (fy_foam_case_write_monitors_ldu(fc, s) != FY_OK) return die("writing the monitors");
     std::printf("End\n");
     fy_ldu_solver_destroy(s);
     fy_foam_case_close(fc);
@@ -227,7 +234,7 @@ int main(int argc, char** argv) {
     if (master)
         std::printf("Create mesh: %d x %d x %d cells of %g m, %s on the six sides x- x+ y- y+ z- z+: %s %s %s %s %s %s\n", cd.nx, cd.ny, cd.nz, cd.dx,
                     "patches", info.patch_of_side[0], info.patch_of_side[1], info.patch_of_side[2], info.patch_of_side[3], info.patch_of_side[4], info.patch_of_side[5]);
-    if (master) { print_coupling(cd.drag_law, cd.force_models); print_functions(fc, cd.average); }
+    if (master) { print_coupling(cd.drag_law, cd.force_models); print_functions(fc, cd.average, cd.monitors); }
     if (master && cd.thermal.on)
         std::printf("Heat transfer: nusseltModel %s, Cp %g, kappa %g, Prt %g, particleTemperature %g, particleCp %g, beta %g, TRef %g, div(T) %s\n",
                     cd.thermal.nusselt_law == FY_NUSSELT_GUNN ? "Gunn" : "RanzMarshall", cd.thermal.cp, cd.thermal.kappa, cd.thermal.prt, cd.thermal.particle_temperature,
@@ -314,8 +321,9 @@ int main(int argc, char** argv) {
             tp_resets = now;
         }
         if (info.write_interval_steps > 0 && k % info.write_interval_steps == 0)
-            if (write_time(tname) != FY_OK) return die("writing the time directory");
+            if (write_time(tname) != FY_OK || (cd.monitors.n_objects > 0 && fy_foam_case_write_monitors(fc, s) != FY_OK)) return die("writing the time directory");
     }
+    if (cd.monitors.n_objects > 0 && fy_foam_case_write_monitors(fc, s) != FY_OK) return die("writing the monitors");      // (one domain: a slab's create has refused them)
     if (master) std::printf("End\n");
     fy_solver_destroy(s);
     if (comm) fy_comm_destroy(comm);

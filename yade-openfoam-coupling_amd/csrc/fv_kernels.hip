@@ -1662,6 +1662,89 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     block_reduce_store<2>(v, mx, partials, fy_lb, fy_stride);
 }
 
+// ------------------------------------------------------------------------------------------------ boundary values as fields; the monitors' face kernel
+// Boundary face b of a single-domain block in the read-outs' order: the six sides 2 d + s (x- x+ y- y+ z- z+), each side's faces with the lower remaining axis
+// fastest.  side = 2 d + s, r = the face's number on its side; false: b is past the last face
+__device__ __forceinline__ bool bface_side(const FvGeo& g, int b, int& side, int& r) {
+    const int nyz = g.ny * g.nz, nxz = g.nx * g.nz, nxy = g.nx * g.ny;
+    if (b < 2 * nyz) { side = b >= nyz; r = b - side * nyz; return true; }
+    b -= 2 * nyz;
+    if (b < 2 * nxz) { const int s = b >= nxz; side = 2 + s; r = b - s * nxz; return true; }
+    b -= 2 * nxz;
+    if (b < 2 * nxy) { const int s = b >= nxy; side = 4 + s; r = b - s * nxy; return true; }
+    return false;
+}
+// T on patch `patch` next to cell c, as k_assemble_scalar takes it: the patch value (fixedValue) or the cell's (zeroGradient).  The six conditions come as device
+// arrays (TPatch), not as the by-value ScalarEqn: the six sides' cases below would be merged into one lane-indexed read of the kernel argument, i.e. a stack copy
+__device__ __forceinline__ double Tbv(const TPatch& e, const double* T, int c, int patch) { return e.bc[patch] == 1 ? e.val[patch] : T[c]; }
+// what face r of side (D, S) carries: its area, the flux out of the domain (the +axis oriented face field negated on a low side) and the boundary values pbv / Ub / Tbv.
+// want: bit MF_* of monitors.hpp per component (phi, p, U, T) -- what is not wanted is neither read nor formed.  D and S are template arguments so that every patch
+// index into FvGeo's tables is a constant, as in the sweeps' unrolled side loops
+struct BFace { double A, phi, p, ux, uy, uz, T; };
+template <int D, int S>
+__device__ __forceinline__ void bface_values(const FvGeo& g, int r, int want, const double* __restrict__ p, const double* psn_d, const double* __restrict__ U,
+                                             const double* __restrict__ T, const TPatch& te, const double* phi_d, BFace& o) {
+    CFace3 psn{};
+    psn.a[D] = psn_d;
+    int i, j, k;
+    if (D == 0) { j = r % g.ny; k = r / g.ny; i = S ? g.nx - 1 : 0; }
+    else if (D == 1) { i = r % g.nx; k = r / g.nx; j = S ? g.ny - 1 : 0; }
+    else { i = r % g.nx; j = r / g.nx; k = S ? g.nz - 1 : 0; }
+    const int c = cidx(g, i, j, k), face = cface(g, D, S, i, j, k), patch = 2 * D + S;
+    o.A = geo_Af(g, D, i, j, k);
+    if (want & (1 << MF_PHI)) o.phi = (S ? 1.0 : -1.0) * phi_d[face];
+    if (want & (1 << MF_P)) o.p = pbv(g, p, psn, c, D, S, face);
+    if (want & (7 << MF_U)) { double u[3]; Ub(g, U, c, patch, u); o.ux = u[0]; o.uy = u[1]; o.uz = u[2]; }
+    if (want & (1 << MF_T)) o.T = Tbv(te, T, c, patch);
+}
+__device__ __forceinline__ void bface_values_of(const FvGeo& g, int side, int r, int want, const double* __restrict__ p, CFace3 psn, const double* __restrict__ U,
+                                                const double* __restrict__ T, const TPatch& te, CFace3 phi, BFace& o) {
+    switch (side) {
+        case 0: bface_values<0, 0>(g, r, want, p, psn.a[0], U, T, te, phi.a[0], o); break;
+        case 1: bface_values<0, 1>(g, r, want, p, psn.a[0], U, T, te, phi.a[0], o); break;
+        case 2: bface_values<1, 0>(g, r, want, p, psn.a[1], U, T, te, phi.a[1], o); break;
+        case 3: bface_values<1, 1>(g, r, want, p, psn.a[1], U, T, te, phi.a[1], o); break;
+        case 4: bface_values<2, 0>(g, r, want, p, psn.a[2], U, T, te, phi.a[2], o); break;
+        default: bface_values<2, 1>(g, r, want, p, psn.a[2], U, T, te, phi.a[2], o); break;
+    }
+}
+
+// "p_boundary", "U_boundary", "T_boundary" (null: not asked for) per boundary face
+__global__ __launch_bounds__(256) void k_boundary_values(FvGeo g, const double* __restrict__ p, CFace3 psn, const double* __restrict__ U, const double* __restrict__ T, TPatch te,
+                                                         double* __restrict__ pb, double* __restrict__ ub, double* __restrict__ tb) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    int side, r;
+    if (!bface_side(g, b, side, r)) return;
+    BFace v{};
+    bface_values_of(g, side, r, (pb ? 1 << MF_P : 0) | (ub ? 7 << MF_U : 0) | (tb ? 1 << MF_T : 0), p, psn, U, T, te, CFace3{}, v);
+    if (pb) pb[b] = v.p;
+    if (ub) { ub[3 * (size_t)b] = v.ux; ub[3 * (size_t)b + 1] = v.uy; ub[3 * (size_t)b + 2] = v.uz; }
+    if (tb) tb[b] = v.T;
+}
+
+// fy::Monitors' face kernel (monitors.hpp): one lane per boundary face, blockIdx.y = the surface object; a face belongs to the object when its side is in the object's
+// mask.  Side, owner, face index and area come from FvGeo.  Each wanted component leaves the block as its five partials; the others are skipped (uniform: the table
+// is a kernel argument)
+__global__ __launch_bounds__(256) void k_monitor_faces(FvGeo g, MonFaceTable t, const double* __restrict__ p, CFace3 psn, const double* __restrict__ U, const double* __restrict__ T,
+                                                       TPatch te, CFace3 phi, double* __restrict__ partials) {
+    const MonFaceObj o = t.o[blockIdx.y];
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    int side = 0, r = 0;
+    bool in = bface_side(g, b, side, r);
+    in = in && ((o.patch >> side) & 1);
+    BFace v{};
+    if (in) bface_values_of(g, side, r, o.fields | (1 << MF_PHI), p, psn, U, T, te, phi, v);
+    const double x[kMonFaceComps] = {1.0, v.phi, v.p, v.ux, v.uy, v.uz, v.T};
+    const int slot0 = (int)blockIdx.y * kMonFaceComps * kMonKinds;
+#pragma unroll
+    for (int q = 0; q < kMonFaceComps; ++q) {
+        if (!((o.fields >> q) & 1)) continue;
+        double w[kMonKinds];
+        mon_terms(in, x[q], v.A, v.phi, w);
+        mon_block_reduce_store(w, partials, slot0 + q * kMonKinds, (int)gridDim.x, (int)blockIdx.x);
+    }
+}
+
 // launch grids of the cell sweeps: the whole owned range, or the block window the geometry names (FvGeo::win_nblk: a range of z-planes, for the
 // sweeps that run beside a halo exchange)
 inline int fv_grid(const FvGeo& g) { return g.win_nblk > 0 ? g.win_nblk : div_up(g.Nc, 256); }
@@ -1877,6 +1960,20 @@ int launch_corr_front(hipStream_t s, FvGeo g, const double* HbyA, const double* 
 
 int launch_p_ghost_uz(hipStream_t s, FvGeo g, CFace3 rAUf, CFace3 alphaf, PMat A) {
     hipLaunchKernelGGL(k_p_ghost_uz, dim3(div_up((size_t)g.nx * g.ny, 256)), dim3(256), 0, s, g, rAUf, alphaf, A);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_boundary_values(hipStream_t s, FvGeo g, const double* p, CFace3 psn, const double* U, const double* T, TPatch te, double* pb, double* ub, double* tb) {
+    const size_t nb = 2 * ((size_t)g.ny * g.nz + (size_t)g.nx * g.nz + (size_t)g.nx * g.ny);
+    hipLaunchKernelGGL(k_boundary_values, dim3(div_up(nb, 256)), dim3(256), 0, s, g, p, psn, U, T, te, pb, ub, tb);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_monitor_faces(hipStream_t s, FvGeo g, MonFaceTable t, const double* p, CFace3 psn, const double* U, const double* T, TPatch te, CFace3 phi, double* partials, int nblk) {
+    if (t.n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_monitor_faces, dim3(nblk, t.n), dim3(256), 0, s, g, t, p, psn, U, T, te, phi, partials);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

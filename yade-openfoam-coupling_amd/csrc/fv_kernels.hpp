@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "fv_linalg_kernels.hpp"
+#include "monitors.hpp"
 
 namespace fy {
 
@@ -78,6 +79,8 @@ inline size_t fv_fsize(const FvGeo& g, int d) {
 
 // the fluid temperature equation (launch_assemble_scalar): D = kappa / (rho_f cp), rPrt = 1 / Prt, rRhoCp = 1 / (rho_f cp); bc 0 zeroGradient | 1 fixedValue
 struct ScalarEqn { int upwind; int bc[6]; double val[6]; double D, rPrt, rRhoCp; };
+// T's six patch conditions as device arrays (bc[6]: 0 zeroGradient | 1 fixedValue, val[6]), for the kernels that take a boundary face's side from the lane
+struct TPatch { const int* bc; const double* val; };
 struct TurbEqn { int mode; double ck, ce, delta, c1, c2, c3, sigma, xmin, relax; int upwind; int bc[6]; double val[6]; int wall[6]; double cmu75, cmu25, kappa; };
 
 // The launchers that take an FvGeo exist twice: fy::launch_* for the uniform block (dx, Af, V constants in every kernel) and fy::gr::launch_* for a

@@ -93,3 +93,8 @@ int launch_corr_front(hipStream_t s, FvGeo g, const double* HbyA, const double* 
 
 // slab interfaces: coefficient of the z-face below the first owned plane, stored at the ghost cell under it (what p_row reads as uz[c - sz])
 int launch_p_ghost_uz(hipStream_t s, FvGeo g, CFace3 rAUf, CFace3 alphaf, PMat A);
+// boundary values as the equations see them, per boundary face of a single-domain block (the six sides x- x+ y- y+ z- z+, each with the lower remaining axis
+// fastest): pb [nb], ub [nb][3], tb [nb]; a null output is skipped
+int launch_boundary_values(hipStream_t s, FvGeo g, const double* p, CFace3 psn, const double* U, const double* T, TPatch te, double* pb, double* ub, double* tb);
+// fy::Monitors' face kernel (monitors.hpp): the five partials of every wanted component of every surface object, nblk blocks per object
+int launch_monitor_faces(hipStream_t s, FvGeo g, MonFaceTable t, const double* p, CFace3 psn, const double* U, const double* T, TPatch te, CFace3 phi, double* partials, int nblk);

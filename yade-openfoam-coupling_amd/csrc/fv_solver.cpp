@@ -321,6 +321,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     FY_HIP(hipStreamSynchronize(stream));
     if (c->thermal.on) FY_TRY(thermal_create(c));                             // couplingProperties heatTransfer + 0/T (before fieldAverage, which may ask for T)
     if (c->average.n_items) FY_TRY(set_field_average(&c->average));           // controlDict functions: fieldAverage
+    if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));            // volFieldValue / surfaceFieldValue
     return FY_OK;
 }
 
@@ -340,6 +341,41 @@ int Solver::set_field_average(const fy_average_desc* d) {
                                         "run the case on one domain", comm->size);
     }
     return avg.configure(d, (size_t)Nc, stream, "fy_solver_set_field_average", [this](const std::string& nm, int* comp) { return avg_source(nm, comp); });
+}
+
+int Solver::t_patch(TPatch* out) {
+    if (th.on && !d_Tbc.p) {
+        FY_TRY(d_Tbc.alloc_exact(6)); FY_TRY(d_Tval.alloc_exact(6));
+        FY_HIP(hipMemcpy(d_Tbc.p, th.eq.bc, 6 * sizeof(int), hipMemcpyHostToDevice));
+        FY_HIP(hipMemcpy(d_Tval.p, th.eq.val, 6 * sizeof(double), hipMemcpyHostToDevice));
+    }
+    *out = TPatch{d_Tbc.p, d_Tval.p};
+    return FY_OK;
+}
+
+int Solver::set_monitors(const fy_monitor_desc* d) {
+    FY_HIP(hipSetDevice(device));
+    if (d && d->n_objects != 0 && comm->size > 1) {
+        mon.off();
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_set_monitors: monitors are not available on z-slabs (fy_solver_create_slab over %d ranks, foamYadeHip_mpi -parallel): "
+                                        "run the case on one domain", comm->size);
+    }
+    if (d && d->n_objects != 0 && g.graded && !Vcell.p) {                       // V = (hx hy) hz per cell, as geo_V forms it
+        std::vector<double> v((size_t)Nc);
+        for (int k = 0; k < g.nz; ++k)
+            for (int j = 0; j < g.ny; ++j)
+                for (int i = 0; i < g.nx; ++i) v[(size_t)i + (size_t)g.nx * ((size_t)j + (size_t)g.ny * k)] = (h_host[0][(size_t)i] * h_host[1][(size_t)j]) * h_host[2][(size_t)k];
+        FY_TRY(Vcell.alloc_exact(v.size()));
+        FY_HIP(hipMemcpy(Vcell.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    TPatch tp;
+    FY_TRY(t_patch(&tp));
+    const size_t nb = 2 * ((size_t)g.ny * g.nz + (size_t)g.nx * g.nz + (size_t)g.nx * g.ny);
+    return mon.configure(d, (size_t)Nc, nb, th.on, stream, "fy_solver_set_monitors", [this](const std::string& nm, int* comp) { return avg_source(nm, comp); },
+                         [](int mask, std::string* why) {
+                             if (mask <= 0 || mask > 63) { *why = mask == 0 ? "the side mask is empty (bit 2 d + s for the sides x- x+ y- y+ z- z+)" : "side mask " + std::to_string(mask) + " (6 bits: x- x+ y- y+ z- z+)"; return 0; }
+                             return 1;
+                         });
 }
 
 // fold the block partials, all-reduce over the slabs, read back
@@ -782,6 +818,9 @@ int Solver::step() {
     FY_TRY(cpl->c.finish_results());                                                      // the answers still on their way, then the dt handshake (FoamYade.C:537-553)
     avg.elapsed += cs.dt;
     if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));      // where runTime.write() stands
+    mon.elapsed += cs.dt;
+    if (mon.on()) FY_TRY(mon.sample(stream, Vcell.p, g.V, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); },
+                                    [this](const MonFaceTable& t, double* pf, int nblk) { return FVK(launch_monitor_faces, stream, g, t, p.p, C3(psn), U.p, th.T.p, TPatch{d_Tbc.p, d_Tval.p}, phi_now(), pf, nblk); }));
     if (hold_sources) sources_pending = true;                                              // reset deferred to the next step (fy_solver_hold_sources)
     else FY_TRY(cpl->c.set_source_zero());                                                // icoFoamYade.C:147, pimpleFoamYade.C:109
     if (timing) tim[3].stop(stream);
@@ -802,7 +841,7 @@ int Solver::step() {
         st.ms_total = tim[3].ms();
         st.ms_other = st.ms_total - st.ms_particle - st.ms_momentum - st.ms_pressure;
         for (auto& k : kc) k.collect();
-        avg.clock.collect();
+        avg.clock.collect(); mon.clock.collect();
         if (th.on) { th.clk_coeff.collect(); th.clk_flux.collect(); th.clk_asm.collect(); th.clk_buoy.collect(); }
     }
     if (xwait_timing) {
@@ -862,6 +901,20 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
         return fail(FY_ERR_INVALID, "unknown solver field '%s' (the multigrid hierarchy has %zu levels)", s.c_str(), mg.size());
     }
     if (avg.lookup(s, ptr, count)) return FY_OK;                 // <field>Mean, <field>Prime2Mean
+    if (s == "p_boundary" || s == "U_boundary" || s == "T_boundary") {      // formed on request: the boundary values as pbv / Ub / Tbv give them now (read-only: fv_solver_api.cpp)
+        if (comm->size > 1) return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is not available on z-slabs (fy_solver_create_slab over %d ranks)", s.c_str(), comm->size);
+        if (s == "T_boundary" && !th.on) return fail(FY_ERR_INVALID, "solver field 'T_boundary' does not exist in this case (fy_case_desc.thermal is off)");
+        const size_t nb = 2 * ((size_t)g.ny * g.nz + (size_t)g.nx * g.nz + (size_t)g.nx * g.ny);
+        DevBuf<double>& b = s == "p_boundary" ? bndP : s == "U_boundary" ? bndU : bndT;
+        *count = s == "U_boundary" ? 3 * nb : nb;
+        FY_HIP(hipSetDevice(device));
+        if (!b.p) FY_TRY(b.alloc_exact(*count));
+        TPatch tp;
+        FY_TRY(t_patch(&tp));
+        FY_TRY(FVK(launch_boundary_values, stream, g, p.p, C3(psn), U.p, th.T.p, tp, s == "p_boundary" ? b.p : nullptr, s == "U_boundary" ? b.p : nullptr, s == "T_boundary" ? b.p : nullptr));
+        *ptr = b.p;
+        return FY_OK;
+    }
     return fail(FY_ERR_INVALID, "unknown solver field '%s'", s.c_str());
 }
 

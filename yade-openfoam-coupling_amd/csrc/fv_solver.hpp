@@ -298,6 +298,13 @@ struct Solver {
     FieldAverage avg;
     const double* avg_source(const std::string& name, int* comp) const;      // the field's owned cells as they lie NOW (the buffers trade places), or nullptr
     int set_field_average(const fy_average_desc* d);
+    // run-time monitors (monitors.hpp), sampled where fieldAverage is; Vcell: the cell volumes of a graded block (the uniform block's kernel takes the one number);
+    // bndP / bndU / bndT: the boundary read-outs "p_boundary" / "U_boundary" / "T_boundary", formed on request
+    Monitors mon;
+    DevBuf<double> Vcell, bndP, bndU, bndT, d_Tval;
+    DevBuf<int> d_Tbc;
+    int t_patch(TPatch* out);      // T's patch conditions on the device (uploaded once; null arrays without thermal)
+    int set_monitors(const fy_monitor_desc* d);
     Thermal th;
     int thermal_create(const fy_case_desc* c);          // validation + allocation, from create()
     int heat_coefficients();

@@ -132,6 +132,8 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
     double* p; size_t n;
     FY_TRY(s->s.field(name, &p, &n));
     if (name && std::strncmp(name, "mg", 2) == 0) return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (rebuilt from the pressure matrix at every assembly)", name);
+    if (name && std::strlen(name) > 9 && std::strcmp(name + std::strlen(name) - 9, "_boundary") == 0)
+        return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (the boundary values follow from the patch conditions and the cell fields)", name);
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
     {
@@ -165,6 +167,14 @@ int fy_solver_destroy(fy_solver* s) { delete s; return FY_OK; }
 int fy_solver_set_field_average(fy_solver* s, const fy_average_desc* d) { FY_S(s); return s->s.set_field_average(d); }
 int fy_solver_get_average_state(fy_solver* s, int item, int64_t* samples, double* time_averaged) { FY_S(s); return s->s.avg.get_state(item, samples, time_averaged); }
 int fy_solver_set_average_state(fy_solver* s, int item, int64_t samples, double time_averaged) { FY_S(s); return s->s.avg.set_state(item, samples, time_averaged); }
+
+int fy_solver_set_monitors(fy_solver* s, const fy_monitor_desc* d) { FY_S(s); return s->s.set_monitors(d); }
+int fy_solver_monitor_layout(fy_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_S(s); return s->s.mon.layout(object, n_values, labels, cap); }
+int fy_solver_get_monitor_rows(fy_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
+    FY_S(s);
+    FY_HIP(hipSetDevice(s->s.device));
+    return s->s.mon.get_rows(s->s.stream, object, first_row, max_rows, times, values, n_rows);
+}
 
 int fy_solver_set_particle_temperatures_host(fy_solver* s, int batch, const double* Tp) { FY_S(s); return s->s.set_particle_temperatures(batch, Tp, false); }
 int fy_solver_set_particle_temperatures_device(fy_solver* s, int batch, const double* d_Tp) { FY_S(s); return s->s.set_particle_temperatures(batch, d_Tp, true); }
@@ -243,6 +253,7 @@ int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     FY_S(s);
     for (auto& k : s->s.kc) { k.reset(); k.on = on != 0; }
     s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
+    s->s.mon.clock.reset(); s->s.mon.clock.on = on != 0;
     for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm, &s->s.th.clk_buoy}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
     return FY_OK;
 }
@@ -264,6 +275,7 @@ int fy_solver_get_exchange_wait(fy_solver* s, double ms[4], int64_t waits[4]) {
 int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
     FY_S(s);
     const std::string k = kernel ? kernel : "";
+    if (k == "monitors" && total_ms && launches) { *total_ms = s->s.mon.clock.total_ms; *launches = s->s.mon.clock.launches; return FY_OK; }
     if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }
     if ((k == "heat_coeff" || k == "heat_flux" || k == "T_assemble" || k == "buoyancy") && total_ms && launches) {
         const fy::KernelClock& c = k == "heat_coeff" ? s->s.th.clk_coeff : k == "heat_flux" ? s->s.th.clk_flux : k == "T_assemble" ? s->s.th.clk_asm : s->s.th.clk_buoy;

@@ -11,6 +11,7 @@
 
 #include "../../include/foamyade_hip.h"
 #include "common.hpp"
+#include "monitors.hpp"
 
 namespace fy {
 
@@ -165,6 +166,10 @@ int launch_ldu_wall_functions(hipStream_t s, LduGeo g, LduPim P, LduWallCells W,
 // fvMatrix::setValues' last part on the epsilon matrix: the wall cells' faces lose their coefficients (the rows were imposed by k_ldu_k_cells)
 int launch_ldu_wall_set_values(hipStream_t s, LduGeo g, LduWallCells W, LduMom M);
 int launch_ldu_nut_boundary(hipStream_t s, LduGeo g, LduPim P, double* out);      // out[f - nInt] = nut on boundary face f as the equations see it
+// boundary values as the equations see them, per boundary face (out[f - nInt]): pb [nb] = pbv, ub [nb][3] = Ub, tb [nb] = ldu_T_b; a null output is skipped
+int launch_ldu_boundary_values(hipStream_t s, LduGeo g, const double* p, const double* U, LduTEqn E, double* pb, double* ub, double* tb);
+// fy::Monitors' face kernel (monitors.hpp): the five partials of every wanted component of every surface object, nblk blocks per object
+int launch_ldu_monitor_faces(hipStream_t s, LduGeo g, MonFaceTable t, const double* p, const double* U, LduTEqn E, const double* phi, double* partials, int nblk);
 int launch_ldu_forces(hipStream_t s, LduGeo g, LduPim P, const double* rAU, double* rAUf, double* phiForces);
 int launch_ldu_ssf_predictor(hipStream_t s, LduGeo g, const double* phiForces, const double* rAUf, const double* p, const double* gradp, double* ssf);
 int launch_ldu_reconstruct(hipStream_t s, LduGeo g, const double* ssf, const double* base, const double* scale, double* out);

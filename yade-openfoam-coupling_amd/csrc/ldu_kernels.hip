@@ -834,6 +834,43 @@ __global__ __launch_bounds__(256) void k_ldu_nut_boundary(LduGeo g, LduPim P, do
     if (b >= g.nFaces - g.nInt) return;
     out[b] = ldu_nut_b(g, P, g.nInt + b);
 }
+// "p_boundary", "U_boundary", "T_boundary" (null: not asked for): pbv / Ub / ldu_T_b per boundary face
+__global__ __launch_bounds__(256) void k_ldu_boundary_values(LduGeo g, const double* __restrict__ p, const double* __restrict__ U, LduTEqn E, double* __restrict__ pb,
+                                                             double* __restrict__ ub, double* __restrict__ tb) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= g.nFaces - g.nInt) return;
+    const int f = g.nInt + b;
+    if (pb) pb[b] = pbv(g, p, f);
+    if (ub) st3(ub, b, Ub(g, U, f));
+    if (tb) tb[b] = ldu_T_b(g, E, E.T[g.own[f]], f);
+}
+// fy::Monitors' face kernel (monitors.hpp): one lane per boundary face, blockIdx.y = the surface object; a face belongs to the object when it lies on the object's patch
+// (patch_of; its area is magSf).  phi on a boundary face is the flux out of the domain as it stands (Sf points outwards); p, U and T are the boundary values above.  Each
+// wanted component leaves the block as its five partials; the others are skipped (uniform: the table is a kernel argument)
+__global__ __launch_bounds__(256) void k_ldu_monitor_faces(LduGeo g, MonFaceTable t, const double* __restrict__ p, const double* __restrict__ U, LduTEqn E,
+                                                           const double* __restrict__ phi, double* __restrict__ partials) {
+    const MonFaceObj o = t.o[blockIdx.y];
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    const bool in = b < g.nFaces - g.nInt && g.patch_of[b] == o.patch;
+    double x[kMonFaceComps] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, A = 0.0, w = 0.0;
+    if (in) {
+        const int f = g.nInt + b;
+        A = g.magSf[f];
+        w = phi[f];
+        x[MF_PHI] = w;
+        if (o.fields & (1 << MF_P)) x[MF_P] = pbv(g, p, f);
+        if (o.fields & (7 << MF_U)) { const D3 u = Ub(g, U, f); x[MF_U] = u.x; x[MF_U + 1] = u.y; x[MF_U + 2] = u.z; }
+        if (o.fields & (1 << MF_T)) x[MF_T] = ldu_T_b(g, E, E.T[g.own[f]], f);
+    }
+    const int slot0 = (int)blockIdx.y * kMonFaceComps * kMonKinds;
+#pragma unroll
+    for (int q = 0; q < kMonFaceComps; ++q) {
+        if (!((o.fields >> q) & 1)) continue;
+        double v[kMonKinds];
+        mon_terms(in, x[q], A, w, v);
+        mon_block_reduce_store(v, partials, slot0 + q * kMonKinds, (int)gridDim.x, (int)blockIdx.x);
+    }
+}
 // bound(k, kMin) (fv_closures.hpp: bound_value; fvc::average = sum |Sf| k_f / sum |Sf|, formed only where pos0(-k) = 1), then correctNut()
 __global__ __launch_bounds__(256) void k_ldu_k_bound_nut(LduGeo g, LduPim P, LduKEqn K, const double* __restrict__ x3, double* __restrict__ X, double* __restrict__ nut) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -1177,6 +1214,18 @@ int launch_ldu_wall_set_values(hipStream_t s, LduGeo g, LduWallCells W, LduMom M
 int launch_ldu_nut_boundary(hipStream_t s, LduGeo g, LduPim P, double* out) {
     if (g.nFaces == g.nInt) return FY_OK;
     hipLaunchKernelGGL(k_ldu_nut_boundary, dim3(div_up(g.nFaces - g.nInt, 256)), dim3(256), 0, s, g, P, out);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_boundary_values(hipStream_t s, LduGeo g, const double* p, const double* U, LduTEqn E, double* pb, double* ub, double* tb) {
+    if (g.nFaces == g.nInt) return FY_OK;
+    hipLaunchKernelGGL(k_ldu_boundary_values, dim3(div_up(g.nFaces - g.nInt, 256)), dim3(256), 0, s, g, p, U, E, pb, ub, tb);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_monitor_faces(hipStream_t s, LduGeo g, MonFaceTable t, const double* p, const double* U, LduTEqn E, const double* phi, double* partials, int nblk) {
+    if (t.n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_ldu_monitor_faces, dim3(nblk, t.n), dim3(256), 0, s, g, t, p, U, E, phi, partials);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

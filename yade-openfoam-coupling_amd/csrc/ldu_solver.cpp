@@ -98,6 +98,18 @@ struct LduSolver {
         FY_HIP(hipSetDevice(device));
         return avg.configure(d, (size_t)nc, stream, "fy_ldu_solver_set_field_average", [this](const std::string& nm, int* comp) { return avg_source(nm, comp); });
     }
+    // run-time monitors (monitors.hpp), sampled where fieldAverage is; the boundary read-outs "p_boundary" / "U_boundary" / "T_boundary", formed on request
+    Monitors mon;
+    DevBuf<double> bndP, bndU, bndT;
+    int set_monitors(const fy_monitor_desc* d) {
+        FY_HIP(hipSetDevice(device));
+        return mon.configure(d, (size_t)nc, (size_t)(nf - ni), th.on, stream, "fy_ldu_solver_set_monitors", [this](const std::string& nm, int* comp) { return avg_source(nm, comp); },
+                             [this](int pa, std::string* why) {
+                                 if (pa < 0 || pa >= hm.nPatches) { *why = "patch " + std::to_string(pa) + " does not exist (the mesh has " + std::to_string(hm.nPatches) + ")"; return 0; }
+                                 if (hm.psize[(size_t)pa] == 0) *why = "patch " + std::to_string(pa) + " has no faces (a cyclic patch is folded into internal faces)";
+                                 return (int)hm.psize[(size_t)pa];
+                             });
+    }
 
     ~LduSolver() {
         if (cpl) fy_destroy(cpl);
@@ -285,6 +297,7 @@ struct LduSolver {
         if (c->thermal.on) FY_TRY(thermal_create(c, tbc, tval));              // (before fieldAverage, which may ask for T)
         FY_HIP(hipStreamSynchronize(stream));
         if (c->average.n_items) FY_TRY(set_field_average(&c->average));       // controlDict functions: fieldAverage
+        if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));        // volFieldValue / surfaceFieldValue
         return FY_OK;
     }
 
@@ -590,6 +603,9 @@ struct LduSolver {
         if (th.on) FY_TRY(solve_temperature());                                                                   // after the last corrector and the turbulence model's correct()
         avg.elapsed += cs.dt;
         if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));
+        mon.elapsed += cs.dt;
+        if (mon.on()) FY_TRY(mon.sample(stream, g.V, 0.0, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); },
+                                        [this](const MonFaceTable& t, double* pf, int nblk) { return launch_ldu_monitor_faces(stream, g, t, p.p, U.p, th.eq, phi.p, pf, nblk); }));
         if (hold_sources) sources_pending = true;                                                                 // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147)
         else FY_TRY(cpl->c.set_source_zero());                                                                    // :147
         tim[1].stop(stream);
@@ -624,6 +640,17 @@ struct LduSolver {
         if (s == "buoyancy") {
             if (!th.buoyant) return fail(FY_ERR_INVALID, "fy_ldu_solver field 'buoyancy' does not exist in this case (fy_ldu_case.thermal.beta or g is zero)");
             *ptr = th.buoy.p; *count = 3 * n;
+            return FY_OK;
+        }
+        if (s == "p_boundary" || s == "U_boundary" || s == "T_boundary") {         // formed on request: the boundary values as pbv / Ub / ldu_T_b give them now
+            if (s == "T_boundary" && !th.on) return fail(FY_ERR_INVALID, "fy_ldu_solver field 'T_boundary' does not exist in this case (fy_ldu_case.thermal is off)");
+            const size_t nb = (size_t)(nf - ni);
+            DevBuf<double>& b = s == "p_boundary" ? bndP : s == "U_boundary" ? bndU : bndT;
+            *count = s == "U_boundary" ? 3 * nb : nb;
+            FY_HIP(hipSetDevice(device));
+            if (!b.p) FY_TRY(b.alloc_exact(std::max<size_t>(*count, 1)));
+            FY_TRY(launch_ldu_boundary_values(stream, g, p.p, U.p, th.eq, s == "p_boundary" ? b.p : nullptr, s == "U_boundary" ? b.p : nullptr, s == "T_boundary" ? b.p : nullptr));
+            *ptr = b.p;
             return FY_OK;
         }
         if (s == "nut_boundary") {                                                 // formed on request: nut_b as ldu_nut_b gives it now
@@ -747,6 +774,13 @@ int fy_ldu_solver_apply(fy_ldu_solver* s, const char* op, const double* in, doub
 int fy_ldu_solver_set_field_average(fy_ldu_solver* s, const fy_average_desc* d) { FY_LS(s); return s->s.set_field_average(d); }
 int fy_ldu_solver_get_average_state(fy_ldu_solver* s, int item, int64_t* samples, double* time_averaged) { FY_LS(s); return s->s.avg.get_state(item, samples, time_averaged); }
 int fy_ldu_solver_set_average_state(fy_ldu_solver* s, int item, int64_t samples, double time_averaged) { FY_LS(s); return s->s.avg.set_state(item, samples, time_averaged); }
+int fy_ldu_solver_set_monitors(fy_ldu_solver* s, const fy_monitor_desc* d) { FY_LS(s); return s->s.set_monitors(d); }
+int fy_ldu_solver_monitor_layout(fy_ldu_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_LS(s); return s->s.mon.layout(object, n_values, labels, cap); }
+int fy_ldu_solver_get_monitor_rows(fy_ldu_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
+    FY_LS(s);
+    FY_HIP(hipSetDevice(s->s.device));
+    return s->s.mon.get_rows(s->s.stream, object, first_row, max_rows, times, values, n_rows);
+}
 int fy_ldu_solver_set_particle_temperatures_host(fy_ldu_solver* s, int batch, const double* Tp) { FY_LS(s); return s->s.th.part.set_temperatures(s->s.cpl->c, s->s.device, s->s.stream, batch, Tp, false); }
 int fy_ldu_solver_set_particle_temperatures_device(fy_ldu_solver* s, int batch, const double* d_Tp) { FY_LS(s); return s->s.th.part.set_temperatures(s->s.cpl->c, s->s.device, s->s.stream, batch, d_Tp, true); }
 int fy_ldu_solver_get_particle_heat_host(fy_ldu_solver* s, int batch, double* q) { FY_LS(s); return s->s.th.part.get_heat(s->s.device, s->s.stream, batch, q); }
