@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 22
+#define FY_ABI_VERSION 23
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -277,7 +277,7 @@ enum { FY_PSOLVER_PCG_JACOBI = 0, FY_PSOLVER_PCG_MG = 1 };
    with stop_after > 0, elapsed <= stop_after + dt / 2, elapsed being the sum of the steps' deltaT since the solver was created [OF-6 timeControl]. */
 #define FY_AVERAGE_MAX_ITEMS 8
 typedef struct fy_average_item {
-    char field[32];                 /* solver field name: U, p, alpha, uParticle, uSource, nut, k, epsilon -- where the solver has the field */
+    char field[32];                 /* solver field name: U, p, alpha, uParticle, uSource, nut, k, epsilon, T and the solid statistics' six fields -- where the solver has the field */
     int32_t prime2_mean;            /* also keep P */
     int32_t iteration_base;         /* 0: base time (weights deltaT), 1: base iteration (equal weights) */
 } fy_average_item;
@@ -432,6 +432,8 @@ typedef struct fy_case_desc {
     fy_thermal_desc thermal;
     /* controlDict functions: the volFieldValue / surfaceFieldValue objects (all zero: none), applied at fy_solver_create with fy_solver_set_monitors */
     fy_monitor_desc monitors;
+    /* constant/couplingProperties solidStatistics: the solid-phase statistics, applied at fy_solver_create with fy_solver_set_solid_statistics (0: off) */
+    int32_t solid_stats;
 } fy_case_desc;
 
 typedef struct fy_solver fy_solver;
@@ -486,6 +488,21 @@ int fy_solver_set_average_state(fy_solver*, int item, int64_t samples, double ti
 int fy_solver_set_monitors(fy_solver*, const fy_monitor_desc*);
 int fy_solver_monitor_layout(fy_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_solver_get_monitor_rows(fy_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
+
+/* Solid-phase statistics on this solver (not in the reference; DESIGN.md section 3 "Solid-phase statistics").  on != 0: once per step, after the T equation and before
+ * fieldAverage and the monitors sample, one more scatter over the stencils of every located particle of EVERY batch forms eight sums per cell c (w: the stencil
+ * weight, sum_c w = 1; point-force mode: the containing cell with w = 1; d = 2 r, Vp = pi d^3 / 6, Tp: the temperature the heat exchange holds for the particle at
+ * the end of the step, s7 = 0 without heat transfer):
+ *   s0 = sum w   s1 = sum w Vp   s2..s4 = sum (w Vp) v   s5 = sum (w Vp) |v|^2   s6 = sum w d^2   s7 = sum (w Vp) Tp
+ * and from them, with the cell volume V (zeros where s1 == 0):
+ *   nParticle = s0 / V [1/m^3]   solidFraction = s1 / V (unclamped; alpha stays what it is)   uSolid = s(2..4) / s1 [m/s]
+ *   granularTemperature = max(0, (s5 / s1 - |uSolid|^2) / 3) [m^2/s^2]   dSauter = (6 / pi) s1 / s6 [m]   TParticle = s7 / s1 [K] (heat transfer on only)
+ * While it is on, "solidMoments" [n][8] (s0 .. s7) and the six fields -- "uSolid" [n][3], the others [n] -- are names of fy_solver_field_count / _read_field_host
+ * (read-only: writing is FY_ERR_INVALID), names fieldAverage and the volume monitors accept, and the pass's launches are the "solid_stats" clock of
+ * fy_solver_get_kernel_timing.  They are zero before the first coupling call and describe the particles of the last one afterwards.  on == 0 (the default): nothing
+ * is launched or allocated, the names are unknown; switching off frees the memory (16 doubles per cell, 17 with heat transfer).  FY_ERR_UNSUPPORTED: a slab solver
+ * (fy_solver_create_slab); and fy_solver_step while fibre coupling is on. */
+int fy_solver_set_solid_statistics(fy_solver*, int on);
 
 /* Heat exchange (fy_case_desc.thermal.on; FY_ERR_INVALID on a solver without it).  The caller owns the particle temperatures: Tp[n] in the batch's wire order for the
  * n particles the batch holds now, host or device memory (copied), or NULL = thermal.particle_temperature for all of them; they stand until the next call for that
@@ -757,6 +774,7 @@ typedef struct fy_ldu_case {
                                         FY_BC_T_ZERO_GRADIENT, folded cyclic pairs are internal faces and need nothing */
     const double* T_value;           /* [n_patches] */
     fy_monitor_desc monitors;        /* controlDict functions: the volFieldValue / surfaceFieldValue objects as in fy_case_desc (all zero: none); `patch` is a patch index */
+    int32_t solid_stats;             /* the solid-phase statistics as in fy_case_desc, applied with fy_ldu_solver_set_solid_statistics (0: off) */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */
@@ -774,6 +792,12 @@ int fy_ldu_solver_set_average_state(fy_ldu_solver*, int item, int64_t samples, d
 int fy_ldu_solver_set_monitors(fy_ldu_solver*, const fy_monitor_desc*);
 int fy_ldu_solver_monitor_layout(fy_ldu_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_ldu_solver_get_monitor_rows(fy_ldu_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
+/* Solid-phase statistics as on fy_solver (fy_solver_set_solid_statistics): the same sums, fields and names; a general mesh has no tiles, so the Gaussian scatter goes
+ * out as FP64 global atomics.  The pass's launches are the "solid_stats" clock (the only one here) of fy_ldu_solver_get_kernel_timing, switched on and reset by
+ * fy_ldu_solver_enable_kernel_timing. */
+int fy_ldu_solver_set_solid_statistics(fy_ldu_solver*, int on);
+int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver*, int on);
+int fy_ldu_solver_get_kernel_timing(fy_ldu_solver*, const char* kernel, double* total_ms, int64_t* launches);
 /* Heat exchange (fy_ldu_case.thermal.on; FY_ERR_INVALID on a solver without it): the entry points of fy_solver one for one, with the same semantics.  While thermal is
  * on, "T" [nc] (also writable: a non-uniform start), "heatSp" [nc] (W/K), "heatSu" [nc] (W) and, with thermal.beta != 0 and g != 0, "buoyancy" [nc][3] are field names
  * of fy_ldu_solver_read_field_host, and "T" one that fieldAverage accepts. */

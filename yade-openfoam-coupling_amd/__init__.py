@@ -268,6 +268,13 @@ class _ParticleHeat:
         _check(self._th_fn("get_particle_heat_host")(self._h, int(batch), _d(q) if q.size else None))
         return q
 
+    def set_solid_statistics(self, on=True):
+        """solid-phase statistics (fy_solver_set_solid_statistics): while on, get("solidMoments") [n * 8] and get("nParticle" | "solidFraction" | "uSolid" |
+        "granularTemperature" | "dSauter" | "TParticle") describe the particles of the last step; the case keyword solid_stats=1 switches them on at create"""
+        f = self._th_fn("set_solid_statistics")
+        f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(self._h, 1 if on else 0))
+
     def thermal_stats(self):
         """(Jacobi passes, initial residual, heat to the particles [W]) of the last step's T solve"""
         it = C.c_int32(0); r = C.c_double(0); h = C.c_double(0)
@@ -308,7 +315,8 @@ class LduCase(C.Structure):
                 ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double), ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double),
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
                 ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp), ("monitors", MonitorDesc)]
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp), ("monitors", MonitorDesc),
+                ("solid_stats", C.c_int32)]
 
 
 NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
@@ -351,7 +359,8 @@ class CaseDesc(C.Structure):
                 ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double), ("eps_max_iter", C.c_int32),
                 ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double),
-                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("monitors", MonitorDesc)]
+                ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("monitors", MonitorDesc),
+                ("solid_stats", C.c_int32)]
 
 
 BC_WALL_FUNCTION, BC_NUT_CALCULATED = 2, 3
@@ -1517,6 +1526,19 @@ class LduSolver(_Averages, _Monitors, _ParticleHeat):
         arr = np.ascontiguousarray(arr, dtype=np.float64).ravel()
         assert arr.size == self._size(name)
         _check(lib().fy_ldu_solver_write_field_host(self._h, name.encode(), _d(arr)))
+
+    def enable_kernel_timing(self, on=True):
+        L = lib()
+        L.fy_ldu_solver_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int]
+        _check(L.fy_ldu_solver_enable_kernel_timing(self._h, int(on)))
+
+    def kernel_timing(self, name):
+        """(total_ms, launches) of one instrumented kernel since enable_kernel_timing(True); the one clock here is "solid_stats" """
+        L = lib()
+        L.fy_ldu_solver_get_kernel_timing.argtypes = [C.c_void_p, C.c_char_p, _dp, C.POINTER(C.c_int64)]
+        ms = C.c_double(0); n = C.c_int64(0)
+        _check(L.fy_ldu_solver_get_kernel_timing(self._h, name.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def hold_sources(self, on=True):
         L = lib()

@@ -56,7 +56,7 @@ struct FieldAverage {
         if (d->n_items < 0 || d->n_items > FY_AVERAGE_MAX_ITEMS)
             return fail(FY_ERR_INVALID, "%s: %d items (at most FY_AVERAGE_MAX_ITEMS = %d)", who, d->n_items, FY_AVERAGE_MAX_ITEMS);
         if (!(d->start_after >= 0) || !(d->stop_after >= 0)) return fail(FY_ERR_INVALID, "%s: start_after and stop_after must not be negative", who);
-        static const char* const known[] = {"U", "p", "alpha", "uParticle", "uSource", "nut", "k", "epsilon", "T"};
+        static const char* const known[] = {"U", "p", "alpha", "uParticle", "uSource", "nut", "k", "epsilon", "T", "nParticle", "solidFraction", "uSolid", "granularTemperature", "dSauter", "TParticle"};
         for (int q = 0; q < d->n_items; ++q) {
             char nm[sizeof(d->items[q].field) + 1] = {0};
             std::memcpy(nm, d->items[q].field, sizeof(d->items[q].field));
@@ -64,7 +64,7 @@ struct FieldAverage {
             for (const char* k : known) ok = ok || std::strcmp(k, nm) == 0;
             int comp = 0;
             if (!ok || !resolve(std::string(nm), &comp)) {
-                const int rc = fail(FY_ERR_INVALID, "%s: field '%s' %s (U, p, alpha, uParticle, uSource, nut, k, epsilon, T, where the solver has the field)", who, nm,
+                const int rc = fail(FY_ERR_INVALID, "%s: field '%s' %s (U, p, alpha, uParticle, uSource, nut, k, epsilon, T, nParticle, solidFraction, uSolid, granularTemperature, dSauter, TParticle, where the solver has the field)", who, nm,
                                     ok ? "does not exist in this case" : "cannot be averaged");
                 off();
                 return rc;

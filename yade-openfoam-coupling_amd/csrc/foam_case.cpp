@@ -844,6 +844,7 @@ int check_general_schemes(const fy_foam_case* c) {
 int read_coupling_properties(fy_foam_case* c) {
     c->desc.drag_law = FY_DRAG_REFERENCE; c->desc.force_models = 0;
     c->desc.thermal = fy_thermal_desc{};
+    c->desc.solid_stats = 0;
     const std::string path = join(c->dir, "constant/couplingProperties");
     if (!file_exists(path)) return FY_OK;
     FoamDict d;
@@ -872,6 +873,15 @@ int read_coupling_properties(fy_foam_case* c) {
         if (!d.boolean(sw.key, &on) || (on && !gaussian))
             return fail(FY_ERR_UNSUPPORTED, "%s: %s %s; %s accepts %s", path.c_str(), sw.key, w.c_str(), solver, gaussian ? "on | off" : "off");
         if (on) c->desc.force_models |= sw.flag;
+    }
+    // solidStatistics on | off: the solid-phase statistics (fy_solver_set_solid_statistics), for both solvers, block and general cases; one domain only
+    if (d.has("solidStatistics")) {
+        bool on = false;
+        d.word("solidStatistics", &w);
+        if (!d.boolean("solidStatistics", &on)) return fail(FY_ERR_UNSUPPORTED, "%s: solidStatistics %s; %s accepts on | off", path.c_str(), w.c_str(), solver);
+        if (on && c->proc_count > 0)
+            return fail(FY_ERR_UNSUPPORTED, "%s: solidStatistics on: solid statistics are not available on z-slabs (a decomposed case, -parallel); accepts off", path.c_str());
+        c->desc.solid_stats = on ? 1 : 0;
     }
     // heatTransfer { active; nusseltModel; Cp; kappa; Prt; particleTemperature; particleCp; beta; TRef; }: the fluid temperature equation, the particles' heat
     // exchange and, with the last three, particle temperatures that evolve and Boussinesq buoyancy (fy_thermal_desc); 0/T, div(phi,T) | div(alphaPhic,T) and solvers.T complete it (read_controls, read_fields)
@@ -917,6 +927,14 @@ int read_coupling_properties(fy_foam_case* c) {
 const char* monitor_op_word(int op) {
     static const char* const nm[] = {"", "sum", "average", "volAverage", "volIntegrate", "weightedVolAverage", "min", "max", "areaAverage", "areaIntegrate", "weightedAverage"};
     return op >= FY_MONITOR_SUM && op <= FY_MONITOR_WEIGHTED_AVERAGE ? nm[op] : "?";
+}
+
+// the solid statistics' fields (constant/couplingProperties solidStatistics on) as fieldAverage and volFieldValue name them: whether the case has `stem`, and the
+// words they add to an accepted-fields list
+bool has_solid_stat(const fy_foam_case* c, const std::string& stem) { return c->desc.solid_stats != 0 && (stem != "TParticle" || c->desc.thermal.on); }
+std::string solid_stats_words(const fy_foam_case* c) {
+    if (!c->desc.solid_stats) return std::string();
+    return std::string(", nParticle, solidFraction, uSolid, granularTemperature, dSauter") + (c->desc.thermal.on ? ", TParticle" : "");
 }
 
 // One volFieldValue / surfaceFieldValue object of controlDict `functions` [OF-6 fieldValue, volFieldValue, surfaceFieldValue as recalled] -> desc.monitors and c->monitors.
@@ -998,11 +1016,12 @@ int read_monitor(fy_foam_case* c, const std::string& name, const std::string& ty
     const auto* ft = o->tokens("fields");
     if (!ft) return fail(FY_ERR_INVALID, "%s: no 'fields ( <name> ... )' list", w);
     const std::string ph = c->phase.empty() ? std::string("<phase>") : c->phase;
-    const std::string accepted = vol ? c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource" + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string())
+    const std::string accepted = vol ? c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource" + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string()) + solid_stats_words(c)
                                      : "phi, p, " + c->u_name + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string());
     static const struct { const char* stem; int F; int ncomp; bool surface; } known[] = {
         {"U", F_U, 3, true}, {"p", F_P, 1, true}, {"alpha", F_ALPHA, 1, false}, {"nut", F_NUT, 1, false}, {"k", F_K, 1, false}, {"epsilon", F_EPS, 1, false},
-        {"uParticle", -1, 3, false}, {"uSource", -1, 3, false}, {"T", F_T, 1, true}, {"phi", -2, 1, true}};
+        {"uParticle", -1, 3, false}, {"uSource", -1, 3, false}, {"T", F_T, 1, true}, {"phi", -2, 1, true},
+        {"nParticle", -3, 1, false}, {"solidFraction", -3, 1, false}, {"uSolid", -3, 3, false}, {"granularTemperature", -3, 1, false}, {"dSauter", -3, 1, false}, {"TParticle", -3, 1, false}};
     for (const std::string& file : *ft) {
         double cnt;
         if (file == "(" || file == ")" || fy::foam_tok_is_number(file, &cnt)) continue;
@@ -1010,7 +1029,7 @@ int read_monitor(fy_foam_case* c, const std::string& name, const std::string& ty
         const auto* kf = &known[0];
         bool is_known = false;
         for (const auto& k : known)
-            if (stem == k.stem && (vol ? k.F != -2 : k.surface) && (k.F != F_T || c->desc.thermal.on)) { kf = &k; is_known = true; }
+            if (stem == k.stem && (vol ? k.F != -2 : k.surface) && (k.F != F_T || c->desc.thermal.on) && (k.F != -3 || has_solid_stat(c, stem))) { kf = &k; is_known = true; }
         if (!is_known) return fail(FY_ERR_UNSUPPORTED, "%s: unknown field '%s'; accepted: %s", w, file.c_str(), accepted.c_str());
         const bool has = kf->F >= 0 ? (has_field(c, kf->F) && file == field_name(c, kf->F)) : (file == kf->stem && (stem != "uParticle" || c->solver == FY_SOLVER_PIMPLE));
         if (!has) return fail(FY_ERR_UNSUPPORTED, "%s: this case has no field '%s'; accepted: %s", w, file.c_str(), accepted.c_str());
@@ -1075,7 +1094,8 @@ int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) 
         std::vector<std::pair<std::string, FoamDict> > fields;
         FY_TRY(named_dicts(*ft, where + ".fields", &fields));
         const std::string ph = c->phase.empty() ? std::string("<phase>") : c->phase;
-        const std::string accepted = c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource" + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string());
+        const std::string accepted = c->u_name + ", p, alpha." + ph + ", nut." + ph + ", k." + ph + ", epsilon." + ph + ", uParticle, uSource" + (c->desc.thermal.on ? ", " + field_name(c, F_T) : std::string()) +
+                                     solid_stats_words(c);
         for (const auto& fd : fields) {
             const std::string& file = fd.first;
             const std::string fw = where + ".fields." + file;
@@ -1089,11 +1109,13 @@ int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) 
             // the file name -> the case's field
             static const struct { const char* stem; int F; const char* solver_name; int ncomp; } known[] = {
                 {"U", F_U, "U", 3}, {"p", F_P, "p", 1}, {"alpha", F_ALPHA, "alpha", 1}, {"nut", F_NUT, "nut", 1}, {"k", F_K, "k", 1}, {"epsilon", F_EPS, "epsilon", 1},
-                {"uParticle", -1, "uParticle", 3}, {"uSource", -1, "uSource", 3}, {"T", F_T, "T", 1}};
+                {"uParticle", -1, "uParticle", 3}, {"uSource", -1, "uSource", 3}, {"T", F_T, "T", 1},
+                {"nParticle", -3, "nParticle", 1}, {"solidFraction", -3, "solidFraction", 1}, {"uSolid", -3, "uSolid", 3}, {"granularTemperature", -3, "granularTemperature", 1},
+                {"dSauter", -3, "dSauter", 1}, {"TParticle", -3, "TParticle", 1}};
             const std::string stem = file.substr(0, file.find('.'));
             const auto* kf = &known[0];
             bool is_known = false;
-            for (const auto& k : known) if (stem == k.stem && (k.F != F_T || c->desc.thermal.on)) { kf = &k; is_known = true; }      // (T is a field of a case with heat transfer only)
+            for (const auto& k : known) if (stem == k.stem && (k.F != F_T || c->desc.thermal.on) && (k.F != -3 || has_solid_stat(c, stem))) { kf = &k; is_known = true; }      // (T is a field of a case with heat transfer only)
             if (!is_known) return fail(FY_ERR_UNSUPPORTED, "%s: unknown field '%s'; accepted: %s", fw.c_str(), file.c_str(), accepted.c_str());
             const bool has = kf->F >= 0 ? (has_field(c, kf->F) && file == field_name(c, kf->F))
                                         : (file == kf->stem && (stem != "uParticle" || c->solver == FY_SOLVER_PIMPLE));
@@ -1481,13 +1503,40 @@ const int* field_dims(int F, const std::string& solver_name) {
         case F_EPS: return eps;
         case F_ALPHA: return none;
         case F_T: { static const int temp[7] = {0, 0, 0, 1, 0, 0, 0}; return temp; }
-        default: return solver_name == "uSource" ? acc : U;      // volSource, uParticle (createFields.H of both solvers)
+        default: {                                                // volSource, uParticle (createFields.H of both solvers); the solid statistics' fields
+            static const int perVol[7] = {0, -3, 0, 0, 0, 0, 0}, len[7] = {0, 1, 0, 0, 0, 0, 0}, temp[7] = {0, 0, 0, 1, 0, 0, 0};
+            if (solver_name == "nParticle") return perVol;
+            if (solver_name == "solidFraction") return none;
+            if (solver_name == "granularTemperature") return p;
+            if (solver_name == "dSauter") return len;
+            if (solver_name == "TParticle") return temp;
+            return solver_name == "uSource" ? acc : U;
+        }
     }
 }
 std::string dims_text(const int* d, int power) {
     std::string t = "[";
     for (int q = 0; q < 7; ++q) t += std::to_string(power * d[q]) + (q < 6 ? " " : "]");
     return t;
+}
+
+// the solid statistics' part of runTime.write(), when the solver forms them (count(name, &n) succeeds): nParticle, solidFraction, uSolid, granularTemperature, dSauter
+// and, with heat transfer, TParticle -- patches `calculated`, as <field>Prime2Mean is written
+template <class Count, class Read>
+int write_solid_stats(const fy_foam_case* c, const char* time_name, Count count, Read read) {
+    static const struct { const char* name; int ncomp; const char* dims; } fields[] = {
+        {"nParticle", 1, "[0 -3 0 0 0 0 0]"}, {"solidFraction", 1, "[0 0 0 0 0 0 0]"}, {"uSolid", 3, "[0 1 -1 0 0 0 0]"},
+        {"granularTemperature", 1, "[0 2 -2 0 0 0 0]"}, {"dSauter", 1, "[0 1 0 0 0 0 0]"}, {"TParticle", 1, "[0 0 0 1 0 0 0]"}};
+    const std::vector<std::pair<std::string, std::string> > none;
+    for (const auto& f : fields) {
+        int64_t n = 0;
+        if (count(f.name, &n) != FY_OK || (size_t)n != c->fcells * (size_t)f.ncomp) continue;      // statistics off on this solver, or (TParticle) no heat transfer
+        std::vector<double> v((size_t)n);
+        FY_TRY(read(f.name, v.data()));
+        FY_TRY(write_field(c, join(c->fdir, time_name), time_name, f.name, f.ncomp == 3 ? "volVectorField" : "volScalarField", f.dims, f.ncomp, v, nullptr,
+                           f.ncomp == 3 ? "        type            calculated;\n        value           uniform (0 0 0);\n" : "        type            calculated;\n        value           uniform 0;\n", none));
+    }
+    return FY_OK;
 }
 
 // fieldAverage's part of runTime.write(): the case's object, when the solver averages its fields (a solver made from this case's descriptor: item i = avg_fields[i]).
@@ -1814,6 +1863,7 @@ int fy_foam_case_write_time(const fy_foam_case* c, fy_solver* s, const char* tim
         FY_TRY(write_field(c, join(c->fdir, time_name), time_name, field_name(c, F_T), "volScalarField", "[0 0 0 1 0 0 0]", 1, T, &c->bcs[F_T], "        type            zeroGradient;\n",
                            c->bcs[F_T].extra));
     }
+    FY_TRY(write_solid_stats(c, time_name, [s](const char* nm, int64_t* n) { return fy_solver_field_count(s, nm, n); }, [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); }));
     fy_step_stats st;
     FY_TRY(fy_solver_get_stats(s, &st));
     return write_averages(c, time_name, st.delta_t > 0 ? st.delta_t : c->desc.dt, [s](const char* nm, int64_t* n) { return fy_solver_field_count(s, nm, n); },
@@ -1891,7 +1941,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->eps_initial = d.eps_initial; out->eps_bc = eps.bc.empty() ? nullptr : eps.bc.data(); out->eps_value = eps.val.empty() ? nullptr : eps.val.data();
     out->eps_convection_scheme = d.eps_convection_scheme; out->eps_tol = d.eps_tol; out->eps_rel_tol = d.eps_rel_tol; out->eps_max_iter = d.eps_max_iter; out->eps_relax = d.eps_relax;
     out->wf_kappa = d.wf_kappa; out->wf_E = d.wf_E;
-    out->drag_law = d.drag_law; out->force_models = d.force_models;
+    out->drag_law = d.drag_law; out->force_models = d.force_models; out->solid_stats = d.solid_stats;
     out->average = d.average;
     out->monitors = d.monitors;
     out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
@@ -1914,6 +1964,7 @@ int fy_foam_case_write_time_ldu(const fy_foam_case* c, fy_ldu_solver* s, const c
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_INVALID, "fy_foam_case_write_time_ldu: the solver holds %lld cells, the case %zu", (long long)cnt, c->fcells);
     // (alpha: with fy_ldu_solver_hold_sources, before setSourceZero)
     FY_TRY(write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_K, F_EPS}, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); }));
+    FY_TRY(write_solid_stats(c, time_name, [s](const char* nm, int64_t* n) { return fy_ldu_solver_field_count(s, nm, n); }, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); }));
     fy_step_stats st;
     FY_TRY(fy_ldu_solver_get_stats(s, &st));
     return write_averages(c, time_name, st.delta_t > 0 ? st.delta_t : c->desc.dt, [s](const char* nm, int64_t* n) { return fy_ldu_solver_field_count(s, nm, n); },

@@ -43,12 +43,12 @@ static int die(const char* what) {
 }
 
 // constant/couplingProperties as the case reader carried it (the solver's create applies it to the coupling object)
-static void print_coupling(int drag_law, unsigned force_models) {
+static void print_coupling(int drag_law, unsigned force_models, int solid_stats) {
     static const char* const laws[] = {"reference", "DiFelice", "KochHill", "Beetstra", "SchillerNaumann"};
-    if (drag_law == FY_DRAG_REFERENCE && !force_models) return;
-    std::printf("Coupling: dragModel %s, liftModel %s, addedMass %s, gaussianTorque %s\n", drag_law >= 0 && drag_law <= 4 ? laws[drag_law] : "?",
+    if (drag_law == FY_DRAG_REFERENCE && !force_models && !solid_stats) return;
+    std::printf("Coupling: dragModel %s, liftModel %s, addedMass %s, gaussianTorque %s, solidStatistics %s\n", drag_law >= 0 && drag_law <= 4 ? laws[drag_law] : "?",
                 (force_models & FY_FORCE_SAFFMAN_MEI_LIFT) ? "SaffmanMei" : "none", (force_models & FY_FORCE_ADDED_MASS) ? "on" : "off",
-                (force_models & FY_FORCE_GAUSSIAN_TORQUE) ? "on" : "off");
+                (force_models & FY_FORCE_GAUSSIAN_TORQUE) ? "on" : "off", solid_stats ? "on" : "off");
 }
 
 // controlDict functions: what is averaged (the solver's create applies it), and one line per function object of another type -- opened, never run
@@ -79,7 +79,7 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     fy_foam_case_info info;
     if (fy_foam_case_poly_mesh(fc, &pm) != FY_OK || fy_foam_case_ldu_desc(fc, &lc) != FY_OK || fy_foam_case_info_get(fc, &info) != FY_OK) return die("reading the case");
     std::printf("             %d points, %d faces (%d internal), %d cells, %d patches\n", pm.n_points, pm.n_faces, pm.n_internal_faces, pm.n_cells, pm.n_patches);
-    print_coupling(lc.drag_law, lc.force_models);
+    print_coupling(lc.drag_law, lc.force_models, lc.solid_stats);
     print_functions(fc, lc.average, lc.monitors);
     fy_ldu_solver* s = nullptr;
     if (fy_ldu_solver_create(&pm, &lc, trp, device, &s) != FY_OK) return die("fy_ldu_solver_create");
@@ -234,7 +234,7 @@ int main(int argc, char** argv) {
     if (master)
         std::printf("Create mesh: %d x %d x %d cells of %g m, %s on the six sides x- x+ y- y+ z- z+: %s %s %s %s %s %s\n", cd.nx, cd.ny, cd.nz, cd.dx,
                     "patches", info.patch_of_side[0], info.patch_of_side[1], info.patch_of_side[2], info.patch_of_side[3], info.patch_of_side[4], info.patch_of_side[5]);
-    if (master) { print_coupling(cd.drag_law, cd.force_models); print_functions(fc, cd.average, cd.monitors); }
+    if (master) { print_coupling(cd.drag_law, cd.force_models, cd.solid_stats); print_functions(fc, cd.average, cd.monitors); }
     if (master && cd.thermal.on)
         std::printf("Heat transfer: nusseltModel %s, Cp %g, kappa %g, Prt %g, particleTemperature %g, particleCp %g, beta %g, TRef %g, div(T) %s\n",
                     cd.thermal.nusselt_law == FY_NUSSELT_GUNN ? "Gunn" : "RanzMarshall", cd.thermal.cp, cd.thermal.kappa, cd.thermal.prt, cd.thermal.particle_temperature,

@@ -320,6 +320,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     FY_TRY(FVK(launch_flux_of, stream, g, U.p, F3(phi)));                     // createPhi
     FY_HIP(hipStreamSynchronize(stream));
     if (c->thermal.on) FY_TRY(thermal_create(c));                             // couplingProperties heatTransfer + 0/T (before fieldAverage, which may ask for T)
+    if (c->solid_stats) FY_TRY(set_solid_statistics(1));                      // couplingProperties solidStatistics (before fieldAverage and the monitors, which may ask for its fields)
     if (c->average.n_items) FY_TRY(set_field_average(&c->average));           // controlDict functions: fieldAverage
     if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));            // volFieldValue / surfaceFieldValue
     return FY_OK;
@@ -330,7 +331,18 @@ const double* Solver::avg_source(const std::string& name, int* comp) const {
                                                                          {"uSource", uSource.p, 3}, {"nut", nut.p, 1}, {"k", kturb.p, 1}, {"epsilon", epsturb.p, 1}, {"T", th.T.p, 1}};
     for (const auto& e : tab)
         if (name == e.nm && e.p) { *comp = e.comp; return e.p + (size_t)e.comp * g.c0; }      // (the owned cells: Solver::field)
-    return nullptr;
+    return ss.source(name, comp);         // (one domain only: its cells are the owned cells)
+}
+
+int Solver::set_solid_statistics(int on) {
+    FY_HIP(hipSetDevice(device));
+    if (on && comm->size > 1) {
+        (void)ss.set(false, 0, false, stream);
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_set_solid_statistics: solid statistics are not available on z-slabs (fy_solver_create_slab over %d ranks, foamYadeHip_mpi -parallel): "
+                                        "run the case on one domain", comm->size);
+    }
+    ss.who = "fy_solver";
+    return ss.set(on != 0, nstore, th.on, stream);
 }
 
 int Solver::set_field_average(const fy_average_desc* d) {
@@ -637,6 +649,8 @@ int Solver::step() {
     clk_mom.on = clk_pres.on = timing; clk_mom.per_collect = clk_pres.per_collect = 1024; clk_mom.reset(); clk_pres.reset();
     if (th.on && cpl->c.fibre)          // (before the particle phase: a refused step leaves nothing half done)
         return fail(FY_ERR_UNSUPPORTED, "fy_solver_step: heat transfer (fy_case_desc.thermal.on) is not available with fibre coupling (fy_set_fibre_coupling): switch one of them off");
+    if (ss.on && cpl->c.fibre)
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_step: solid statistics (fy_solver_set_solid_statistics) are not available with fibre coupling (fy_set_fibre_coupling): switch one of them off");
     if (timing) tim[3].start(stream);
     if (sources_pending) { FY_TRY(cpl->c.set_source_zero()); sources_pending = false; }   // the previous step's deferred setSourceZero
     double h[2];
@@ -815,6 +829,7 @@ int Solver::step() {
         if (g.nut && final_outer) FY_TRY(turbulence_correct());        // pimple.turbCorr(): on the final outer iteration only (the default) -- pimpleFoamYade.C:101-104
     }
     if (th.on) { FY_TRY(solve_temperature()); FY_TRY(heat_fluxes()); }                    // the step's final phi and nut; Sp implicit, then the particles' share
+    if (ss.on) FY_TRY(ss.pass(cpl->c, stream, CellWindow{0, (int64_t)nstore}, cpl->c.d_vol.p, th.on ? &th.part : nullptr, true));      // Tp: the end-of-step temperatures
     FY_TRY(cpl->c.finish_results());                                                      // the answers still on their way, then the dt handshake (FoamYade.C:537-553)
     avg.elapsed += cs.dt;
     if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));      // where runTime.write() stands
@@ -843,6 +858,7 @@ int Solver::step() {
         for (auto& k : kc) k.collect();
         avg.clock.collect(); mon.clock.collect();
         if (th.on) { th.clk_coeff.collect(); th.clk_flux.collect(); th.clk_asm.collect(); th.clk_buoy.collect(); }
+        if (ss.on) ss.clock.collect();
     }
     if (xwait_timing) {
         for (auto& k : clk_xwait) k.collect();
@@ -901,6 +917,10 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
         return fail(FY_ERR_INVALID, "unknown solver field '%s' (the multigrid hierarchy has %zu levels)", s.c_str(), mg.size());
     }
     if (avg.lookup(s, ptr, count)) return FY_OK;                 // <field>Mean, <field>Prime2Mean
+    if (ss.on && SolidStats::is_name(s)) {                       // solidMoments and the six fields (read-only: fv_solver_api.cpp); unknown names while the feature is off
+        FY_HIP(hipSetDevice(device));
+        return ss.field(s, stream, ptr, count);
+    }
     if (s == "p_boundary" || s == "U_boundary" || s == "T_boundary") {      // formed on request: the boundary values as pbv / Ub / Tbv give them now (read-only: fv_solver_api.cpp)
         if (comm->size > 1) return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is not available on z-slabs (fy_solver_create_slab over %d ranks)", s.c_str(), comm->size);
         if (s == "T_boundary" && !th.on) return fail(FY_ERR_INVALID, "solver field 'T_boundary' does not exist in this case (fy_case_desc.thermal is off)");

@@ -15,6 +15,7 @@
 #include "field_average.hpp"
 #include "fv_kernels.hpp"
 #include "heat_exchange.hpp"
+#include "solid_stats.hpp"
 
 // geometry-dependent launchers exist per geometry model (fv_kernels.hpp): the uniform block's in fy, the graded block's in fy::gr
 #define FVK(fn, ...) (g.graded ? ::fy::gr::fn(__VA_ARGS__) : ::fy::fn(__VA_ARGS__))
@@ -316,6 +317,9 @@ struct Solver {
     int get_particle_thermal_state(int batch, double* tp, int64_t* resets);
     int get_particle_heat(int batch, double* q);
     int thermal_stats(int32_t* iterations, double* initial_residual, double* heat_to_particles_W);
+    // solid-phase statistics (solid_stats.hpp), formed once per step after the T equation's pass B and before fieldAverage and the monitors sample
+    SolidStats ss;
+    int set_solid_statistics(int on);
     // field lookup; cell fields are returned/accepted as the OWNED part only (ghost planes are an implementation detail)
     int field(const char* name, double** ptr, size_t* count);
 };

@@ -134,6 +134,8 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
     if (name && std::strncmp(name, "mg", 2) == 0) return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (rebuilt from the pressure matrix at every assembly)", name);
     if (name && std::strlen(name) > 9 && std::strcmp(name + std::strlen(name) - 9, "_boundary") == 0)
         return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (the boundary values follow from the patch conditions and the cell fields)", name);
+    if (name && fy::SolidStats::is_name(name))
+        return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (formed from the particles of the last coupling call)", name);
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
     {
@@ -167,6 +169,8 @@ int fy_solver_destroy(fy_solver* s) { delete s; return FY_OK; }
 int fy_solver_set_field_average(fy_solver* s, const fy_average_desc* d) { FY_S(s); return s->s.set_field_average(d); }
 int fy_solver_get_average_state(fy_solver* s, int item, int64_t* samples, double* time_averaged) { FY_S(s); return s->s.avg.get_state(item, samples, time_averaged); }
 int fy_solver_set_average_state(fy_solver* s, int item, int64_t samples, double time_averaged) { FY_S(s); return s->s.avg.set_state(item, samples, time_averaged); }
+
+int fy_solver_set_solid_statistics(fy_solver* s, int on) { FY_S(s); return s->s.set_solid_statistics(on); }
 
 int fy_solver_set_monitors(fy_solver* s, const fy_monitor_desc* d) { FY_S(s); return s->s.set_monitors(d); }
 int fy_solver_monitor_layout(fy_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_S(s); return s->s.mon.layout(object, n_values, labels, cap); }
@@ -255,6 +259,7 @@ int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
     s->s.mon.clock.reset(); s->s.mon.clock.on = on != 0;
     for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm, &s->s.th.clk_buoy}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
+    s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0;
     return FY_OK;
 }
 
@@ -276,6 +281,7 @@ int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_
     FY_S(s);
     const std::string k = kernel ? kernel : "";
     if (k == "monitors" && total_ms && launches) { *total_ms = s->s.mon.clock.total_ms; *launches = s->s.mon.clock.launches; return FY_OK; }
+    if (k == "solid_stats" && total_ms && launches) { *total_ms = s->s.ss.clock.total_ms; *launches = s->s.ss.clock.launches; return FY_OK; }
     if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }
     if ((k == "heat_coeff" || k == "heat_flux" || k == "T_assemble" || k == "buoyancy") && total_ms && launches) {
         const fy::KernelClock& c = k == "heat_coeff" ? s->s.th.clk_coeff : k == "heat_flux" ? s->s.th.clk_flux : k == "T_assemble" ? s->s.th.clk_asm : s->s.th.clk_buoy;

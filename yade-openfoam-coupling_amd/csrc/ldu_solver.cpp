@@ -14,6 +14,7 @@
 #include "fv_kernels.hpp"
 #include "fv_linalg_kernels.hpp"
 #include "heat_exchange.hpp"
+#include "solid_stats.hpp"
 #include "ldu.hpp"
 #include "ldu_amg.hpp"
 
@@ -92,7 +93,15 @@ struct LduSolver {
             {"nut", nut.p, 1, les}, {"k", kturb.p, 1, keqn || keps}, {"epsilon", epsturb.p, 1, keps}, {"T", th.T.p, 1, th.on}};
         for (const auto& e : tab)
             if (name == e.nm && e.have && e.p) { *comp = e.comp; return e.p; }
-        return nullptr;
+        return ss.source(name, comp);
+    }
+    // solid-phase statistics (solid_stats.hpp), formed once per step after the T equation's pass B and before fieldAverage and the monitors sample; a general mesh has
+    // no tiles, so the Gaussian scatter's table flushes as global atomics
+    SolidStats ss;
+    int set_solid_statistics(int on) {
+        FY_HIP(hipSetDevice(device));
+        ss.who = "fy_ldu_solver";
+        return ss.set(on != 0, (size_t)nc, th.on, stream);
     }
     int set_field_average(const fy_average_desc* d) {
         FY_HIP(hipSetDevice(device));
@@ -296,6 +305,7 @@ struct LduSolver {
         FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                    // createPhi
         if (c->thermal.on) FY_TRY(thermal_create(c, tbc, tval));              // (before fieldAverage, which may ask for T)
         FY_HIP(hipStreamSynchronize(stream));
+        if (c->solid_stats) FY_TRY(set_solid_statistics(1));                  // couplingProperties solidStatistics (before fieldAverage and the monitors, which may ask for its fields)
         if (c->average.n_items) FY_TRY(set_field_average(&c->average));       // controlDict functions: fieldAverage
         if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));        // volFieldValue / surfaceFieldValue
         return FY_OK;
@@ -564,6 +574,8 @@ struct LduSolver {
         FY_HIP(hipSetDevice(device));
         if (th.on && cpl->c.fibre)          // (before the particle phase: a refused step leaves nothing half done)
             return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver_step: heat transfer (fy_ldu_case.thermal.on) is not available with fibre coupling (fy_set_fibre_coupling): switch one of them off");
+        if (ss.on && cpl->c.fibre)
+            return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver_step: solid statistics (fy_ldu_solver_set_solid_statistics) are not available with fibre coupling (fy_set_fibre_coupling): switch one of them off");
         st = fy_step_stats{}; st.cont_err_cumulative = cumulative; st.delta_t = cs.dt;
         if (sources_pending) { FY_TRY(cpl->c.set_source_zero()); sources_pending = false; }      // the previous step's deferred setSourceZero
         tim[1].start(stream);
@@ -601,6 +613,7 @@ struct LduSolver {
             for (int corr = 0; corr < cs.n_correctors; ++corr) FY_TRY(corrector(corr == cs.n_correctors - 1));         // :97-140
         }
         if (th.on) FY_TRY(solve_temperature());                                                                   // after the last corrector and the turbulence model's correct()
+        if (ss.on) FY_TRY(ss.pass(cpl->c, stream, CellWindow{0, (int64_t)nc}, d_V.p, th.on ? &th.part : nullptr, false));      // Tp: the end-of-step temperatures
         avg.elapsed += cs.dt;
         if (avg.on()) FY_TRY(avg.sample(stream, cs.dt, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); }));
         mon.elapsed += cs.dt;
@@ -616,6 +629,7 @@ struct LduSolver {
             if (e) return fail(FY_ERR_UNSUPPORTED, "adjustPhi: continuity error cannot be removed by adjusting the outflow -- OpenFOAM stops here too");
         }
         st.ms_particle = tim[0].ms(); st.ms_total = tim[1].ms();
+        if (ss.on) ss.clock.collect();
         return FY_OK;
     }
 
@@ -632,6 +646,10 @@ struct LduSolver {
                          {"rAUf", rAUf.p, (size_t)nf}, {"uSourceCoupling", uSource.p, 3 * n}, {"nut", nut.p, les ? n : 0}, {"k", kturb.p, (keqn || keps) ? n : 0}, {"epsilon", epsturb.p, keps ? n : 0}};
         for (const E& e : tab) if (s == e.nm) { *ptr = e.p; *count = e.c; return FY_OK; }
         if (avg.lookup(s, ptr, count)) return FY_OK;                           // <field>Mean, <field>Prime2Mean
+        if (ss.on && SolidStats::is_name(s)) {                                 // solidMoments and the six fields (read-only); unknown names while the feature is off
+            FY_HIP(hipSetDevice(device));
+            return ss.field(s, stream, ptr, count);
+        }
         if (s == "T" || s == "heatSp" || s == "heatSu") {
             if (!th.on) return fail(FY_ERR_INVALID, "fy_ldu_solver field '%s' does not exist in this case (fy_ldu_case.thermal is off)", s.c_str());
             *ptr = s == "T" ? th.T.p : s == "heatSp" ? th.Sp.p : th.Su.p; *count = n;
@@ -774,6 +792,15 @@ int fy_ldu_solver_apply(fy_ldu_solver* s, const char* op, const double* in, doub
 int fy_ldu_solver_set_field_average(fy_ldu_solver* s, const fy_average_desc* d) { FY_LS(s); return s->s.set_field_average(d); }
 int fy_ldu_solver_get_average_state(fy_ldu_solver* s, int item, int64_t* samples, double* time_averaged) { FY_LS(s); return s->s.avg.get_state(item, samples, time_averaged); }
 int fy_ldu_solver_set_average_state(fy_ldu_solver* s, int item, int64_t samples, double time_averaged) { FY_LS(s); return s->s.avg.set_state(item, samples, time_averaged); }
+int fy_ldu_solver_set_solid_statistics(fy_ldu_solver* s, int on) { FY_LS(s); return s->s.set_solid_statistics(on); }
+int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver* s, int on) { FY_LS(s); s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0; return FY_OK; }
+int fy_ldu_solver_get_kernel_timing(fy_ldu_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
+    FY_LS(s);
+    const std::string k = kernel ? kernel : "";
+    if (k != "solid_stats" || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats)", k.c_str());
+    *total_ms = s->s.ss.clock.total_ms; *launches = s->s.ss.clock.launches;
+    return FY_OK;
+}
 int fy_ldu_solver_set_monitors(fy_ldu_solver* s, const fy_monitor_desc* d) { FY_LS(s); return s->s.set_monitors(d); }
 int fy_ldu_solver_monitor_layout(fy_ldu_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_LS(s); return s->s.mon.layout(object, n_values, labels, cap); }
 int fy_ldu_solver_get_monitor_rows(fy_ldu_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {

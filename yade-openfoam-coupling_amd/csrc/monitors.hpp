@@ -27,7 +27,7 @@ constexpr int kMonKinds = 5;                     // partials per source componen
 enum { MK_SUM = 0, MK_MSUM, MK_WSUM, MK_MIN, MK_MAX };
 constexpr int kMonCellsPerLane = 4;              // k_monitor_cells: a block's tile is 256 x this many cells
 inline int mon_cell_blocks(int n_cells) { return red_blocks((n_cells + kMonCellsPerLane - 1) / kMonCellsPerLane); }      // its grid = partials per slot (a multiple of 8)
-constexpr int kMonCellComps = 24;                // "1" + the components of every field a volume object may name
+constexpr int kMonCellComps = 24;                // "1" + the components of every field a volume object may name: 15 of the fluid's and the coupling's fields, 8 of the solid statistics
 constexpr int kMonFaceComps = 7;                 // per surface object: "1", phi, p, U x y z, T
 enum { MF_ONE = 0, MF_PHI = 1, MF_P = 2, MF_U = 3, MF_T = 6 };
 
@@ -137,7 +137,7 @@ struct Monitors {
         ring_rows = d->ring_rows > 0 ? d->ring_rows : 256;
         n_cells = cells; n_bfaces = bfaces; start_time = d->start_time;
         nblk_c = mon_cell_blocks((int)cells); nblk_f = red_blocks((int)std::max<size_t>(bfaces, 1));
-        static const char* const cell_known[] = {"U", "p", "alpha", "uParticle", "uSource", "nut", "k", "epsilon", "T"};
+        static const char* const cell_known[] = {"U", "p", "alpha", "uParticle", "uSource", "nut", "k", "epsilon", "T", "nParticle", "solidFraction", "uSolid", "granularTemperature", "dSauter", "TParticle"};
         std::vector<MonOut> ho;
         auto str = [](const char* a, size_t cap) { char b[64] = {0}; std::memcpy(b, a, std::min<size_t>(cap, 63)); return std::string(b); };
         for (int q = 0; q < d->n_objects; ++q) {
@@ -179,7 +179,7 @@ struct Monitors {
                     bool ok = false;
                     for (const char* k : cell_known) ok = ok || nm == k;
                     if (!ok || !cell(nm, &comp))
-                        return fail(FY_ERR_INVALID, "%s: object '%s': field '%s' %s (U, p, alpha, uParticle, uSource, nut, k, epsilon, T, where the solver has the field)", who, on, nm.c_str(),
+                        return fail(FY_ERR_INVALID, "%s: object '%s': field '%s' %s (U, p, alpha, uParticle, uSource, nut, k, epsilon, T, nParticle, solidFraction, uSolid, granularTemperature, dSauter, TParticle, where the solver has the field)", who, on, nm.c_str(),
                                     ok ? "does not exist in this case" : "is unknown");
                     size_t at = 0;
                     while (at < cell_fields.size() && cell_fields[at] != nm) ++at;

@@ -207,6 +207,22 @@ int launch_heat_coeff_point(hipStream_t s, const double* rec, int64_t n, const i
                             double* Sp, double* Su);
 int launch_heat_flux_point(hipStream_t s, const double* rec, int64_t n, const int32_t* incell, CellWindow cw, const double* T, HeatParams hp, double* Tp, const double* hA, double* q);
 
+// ---- solid-phase statistics (fy_solver_set_solid_statistics; not in the reference; particle_moments.hip).  Per cell eight sums over the stencils of every located
+// particle: s0 = sum w, s1 = sum w Vp, s2..s4 = sum (w Vp) v, s5 = sum (w Vp) |v|^2, s6 = sum w d^2, s7 = sum (w Vp) Tp -- kept as the two (dst0 | dstN) halves
+// flush_table<.., 4> writes: a0[c] = s0, a3[3 c + 0..2] = s1, s5, s6; b0[c] = s7, b3[3 c + 0..2] = s2, s3, s4
+struct SolidMoments { double *a0, *a3, *b0, *b3; };
+struct SolidFields { double *nParticle, *solidFraction, *uSolid, *granularTemperature, *dSauter, *TParticle /* nullable: no heat transfer */; };
+// m += the batch's sums: two launches of one kernel, four sums each, through the LDS table and tb's tile buckets (the momentum back-scatter's, with capacities formed
+// AFTER that pass; each launch's one-writer tile reduce leaves the demand counters at zero); tb.cell == nullptr (a general mesh): the table flushes as global atomics.
+// Tp: wire order, nullptr: tp_uniform for all (0 without heat transfer: s7 stays 0)
+int launch_moments_gaussian(hipStream_t s, ParticleSoA p, int64_t n, CellWindow cw, const double* Tp, double tp_uniform, SolidMoments m, TileBuckets tb);
+// point-force mode: the containing cell launch_point_force left in incell (-1: not found), w = 1; eight global atomics per located record
+int launch_moments_point(hipStream_t s, const double* rec, int64_t n, const int32_t* incell, CellWindow cw, const double* Tp, double tp_uniform, SolidMoments m);
+// nParticle = s0 / V, solidFraction = s1 / V, uSolid = s(2..4) / s1, granularTemperature = max(0, (s5 / s1 - |uSolid|^2) / 3), dSauter = (6 / pi) s1 / s6,
+// TParticle = s7 / s1; zeros where s1 == 0
+int launch_solid_stats_cells(hipStream_t s, int64_t n_cells, SolidMoments m, const double* vol, SolidFields f);
+int launch_moments_interleave(hipStream_t s, int64_t n_cells, SolidMoments m, double* out /* [n][8]: s0 .. s7 */);
+
 int launch_fill_f64(hipStream_t s, double* p, size_t n, double v);
 int launch_set_source_zero(hipStream_t s, int32_t n_cells, int gaussian, double* uSourceDrag, double* alpha,
                            double* uSource, double* uParticle);
