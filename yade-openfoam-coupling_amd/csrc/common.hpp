@@ -37,7 +37,8 @@ struct Options {
     bool localcomm_stream;       // FOAMYADE_LOCALCOMM_STREAM=1  in-process slab groups: collectives as event waits on the ranks' streams
     bool no_fused_corrector;     // FOAMYADE_NO_FUSED_CORRECTOR=1  the corrector as five sweeps instead of the two fused ones
     bool faces_from_arrays;      // FOAMYADE_FACES_FROM_ARRAYS=1   the fused sweeps stream rAUf / alphacf from their face arrays instead of re-forming them
-    bool no_pairs;               // FOAMYADE_NO_PAIRS=1          pressure solver: one cell per thread in every sweep instead of two
+    bool no_tiled_stress;        // FOAMYADE_NO_TILED_STRESS=1   explicit stress term: the tensor through memory (two sweeps) instead of the LDS-tiled sweep
+    bool no_pairs;               // FOAMYADE_NO_PAIRS=1         pressure solver: one cell per thread in every sweep instead of two
     bool no_tail_cache;          // FOAMYADE_NO_TAIL_CACHE=1     multigrid tail: the first level from global memory instead of LDS
     int ipc_slot_kb;             // FOAMYADE_IPC_SLOT_KB         peer-store communicator: KiB per neighbour slot, overrides ipc_slot_mb (0: unset)
 };

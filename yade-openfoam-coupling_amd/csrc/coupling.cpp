@@ -50,6 +50,7 @@ Options options() {
     q.localcomm_stream = ls != nullptr && ls[0] == '1';
     q.no_fused_corrector = on("FOAMYADE_NO_FUSED_CORRECTOR");
     q.faces_from_arrays = on("FOAMYADE_FACES_FROM_ARRAYS");
+    q.no_tiled_stress = on("FOAMYADE_NO_TILED_STRESS");
     q.no_pairs = on("FOAMYADE_NO_PAIRS");
     q.no_tail_cache = on("FOAMYADE_NO_TAIL_CACHE");
     q.ipc_slot_kb = (int)num("FOAMYADE_IPC_SLOT_KB", 0);

@@ -495,6 +495,41 @@ __global__ __launch_bounds__(256) void k_courant(FvGeo g, CFace3 phi, double* __
     block_reduce_store<2>(v, mx, partials, fy_lb, fy_stride);
 }
 
+// ---- the explicit stress term G = alpha nuEff dev2(T(grad U)) and its divergence, piece by piece: stated once for the two sweeps that hand G through memory
+// (k_pre_coupling, k_div_G) and for the sweep that keeps it in LDS (k_stress_div), so that both paths form every value by the same operations in the same order
+// U at face (d, s) of a cell (qc = its index along d) from the cell's value uc and its neighbour's un: on a physical boundary Ub() on the cell's own value
+__device__ __forceinline__ void u_face_value(const FvGeo& g, int d, int s, bool on_boundary, int qc, const double (&uc)[3], const double* un, double (&fv)[3]) {
+    if (on_boundary) {
+        const int patch = 2 * d + s;
+        if (g.u_bc[patch] == 0) { fv[0] = g.u_val[patch][0]; fv[1] = g.u_val[patch][1]; fv[2] = g.u_val[patch][2]; }
+        else { fv[0] = uc[0]; fv[1] = uc[1]; fv[2] = uc[2]; }
+        if (g.u_bc[patch] == 2) fv[d] = 0.0;
+    } else {
+        for (int q = 0; q < 3; ++q) fv[q] = geo_lerp_side(g, d, s, qc, uc[q], un[q]);
+    }
+}
+// row d of T = fvc::grad(U), Gauss linear, from the two face values along d
+__device__ __forceinline__ void grad_row(const FvGeo& g, int d, int qc, const double (&fv)[2][3], double (&T)[9]) {
+    const double rhd = geo_rh(g, d, qc);
+    for (int q = 0; q < 3; ++q) T[3 * d + q] = (fv[1][q] - fv[0][q]) * rhd;
+}
+__device__ __forceinline__ double stress_trace(const double (&T)[9]) { return T[0] + T[4] + T[8]; }
+// alpha nuEff (nuEff = nut + nu [OF-6 eddyViscosity/linearViscousStress])
+__device__ __forceinline__ double stress_coeff(const FvGeo& g, const double* __restrict__ alpha, int c) { return g.nut ? alpha[c] * (g.nu + g.nut[c]) : alpha[c] * g.nu; }
+__device__ __forceinline__ double stress_entry(double an, const double (&T)[9], double tr, int a, int b) { return an * (T[3 * b + a] - (a == b ? (2.0 / 3.0) * tr : 0.0)); }
+// div G at a cell from row d of G at the cell (own[d]) and at its +-d neighbours (nbv[d][s]); a boundary face takes the cell's own row
+__device__ __forceinline__ void div_of_rows(const FvGeo& g, const bool (&bnd)[3][2], const int (&ijk)[3], const double (&own)[3][3], const double (&nbv)[3][2][3], double (&acc)[3]) {
+    acc[0] = acc[1] = acc[2] = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        double fv[2][3];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            for (int q = 0; q < 3; ++q) fv[s][q] = bnd[d][s] ? own[d][q] : geo_lerp_side(g, d, s, ijk[d], own[d][q], nbv[d][s][q]);
+        for (int q = 0; q < 3; ++q) acc[q] += (fv[1][q] - fv[0][q]) * geo_rh(g, d, ijk[d]);
+    }
+}
+
 // vGrad = fvc::grad(U) (icoFoamYade.C:71, pimpleFoamYade.C:76); pimple also gradP = fvc::grad(p) (:74) and
 // divT = 2 nu fvc::laplacian(alphac, Uc) (:75)
 // In pimple mode the only consumer of grad(U) is the explicit stress term of divDevRhoReff (the Gaussian torque that would read vGrad
@@ -558,11 +593,8 @@ __global__ __launch_bounds__(256) void k_pre_coupling(FvGeo g, const double* __r
         double fv[2][3], fp[2] = {0, 0};
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
+            u_face_value(g, d, s, bnd[d][s], ijk[d], uc, un6[d][s], fv[s]);
             if (bnd[d][s]) {
-                const int patch = 2 * d + s;                       // Ub() on the cell's own value
-                if (g.u_bc[patch] == 0) { fv[s][0] = g.u_val[patch][0]; fv[s][1] = g.u_val[patch][1]; fv[s][2] = g.u_val[patch][2]; }
-                else { fv[s][0] = uc[0]; fv[s][1] = uc[1]; fv[s][2] = uc[2]; }
-                if (g.u_bc[patch] == 2) fv[s][d] = 0.0;
                 if (pf) {
                     fp[s] = pbv(g, p, psn, c, d, s, cface(g, d, s, i, j, k));
                     for (int q = 0; q < 3; ++q) lap[q] += 1.0 * geo_Af(g, d, i, j, k) * (fv[s][q] - uc[q]) * geo_rhalf(g, d, ijk[d]);     // alphaf = 1 on the boundary
@@ -570,7 +602,6 @@ __global__ __launch_bounds__(256) void k_pre_coupling(FvGeo g, const double* __r
             } else {
                 const double* un = un6[d][s];
                 const int qc = ijk[d];
-                for (int q = 0; q < 3; ++q) fv[s][q] = geo_lerp_side(g, d, s, qc, uc[q], un[q]);
                 if (pf) {
                     fp[s] = geo_lerp_side(g, d, s, qc, pc, pn6[d][s]);
                     const double af = geo_lerp_side(g, d, s, qc, ac, an6[d][s]);
@@ -595,9 +626,8 @@ __global__ __launch_bounds__(256) void k_pre_coupling(FvGeo g, const double* __r
                     dcorr.a[d][f] = coef * (1.0 / g.dt) * phiCorr;
                 }
         }
-        const double rhd = geo_rh(g, d, ijk[d]);
-        for (int q = 0; q < 3; ++q) T[3 * d + q] = (fv[1][q] - fv[0][q]) * rhd;
-        if (pf) gp3[d] = (fp[1] - fp[0]) * rhd;
+        grad_row(g, d, ijk[d], fv, T);
+        if (pf) gp3[d] = (fp[1] - fp[0]) * geo_rh(g, d, ijk[d]);
         if (ddtU) {     // fvc::div(phic, Uc), Gauss linear: the face values are the ones the gradient just used
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
@@ -628,13 +658,13 @@ __global__ __launch_bounds__(256) void k_pre_coupling(FvGeo g, const double* __r
         }
     }
     if (Gout) {
-        const double tr = T[0] + T[4] + T[8];
-        const double an = g.nut ? alpha[c] * (g.nu + g.nut[c]) : alpha[c] * g.nu;      // alpha nuEff (nuEff = nut + nu [OF-6 eddyViscosity/linearViscousStress])
+        const double tr = stress_trace(T);
+        const double an = stress_coeff(g, alpha, c);
         // stored BY ROWS (three vec3 arrays): k_div_G takes row d from the +-d neighbours only, so it streams 24-byte records
         // instead of picking 24 bytes out of 72-byte ones (fewer lines per load instruction, and the z-planes it re-reads fit L2)
         const size_t rs = g_row_stride(g);
         for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) Gout[(size_t)a * rs + 3 * (size_t)c + b] = an * (T[3 * b + a] - (a == b ? (2.0 / 3.0) * tr : 0.0));
+            for (int b = 0; b < 3; ++b) Gout[(size_t)a * rs + 3 * (size_t)c + b] = stress_entry(an, T, tr, a, b);
     }
 }
 
@@ -669,15 +699,135 @@ __global__ __launch_bounds__(256) void k_div_G(FvGeo g, const double* __restrict
             for (int q = 0; q < 3; ++q) nbv[d][s][q] = Gd[3 * (size_t)nb + q];
         }
     }
-    double acc[3] = {0, 0, 0};
+    double acc[3];
+    div_of_rows(g, bnd, ijk, own, nbv, acc);
+    for (int q = 0; q < 3; ++q) divG[3 * (size_t)c + q] = acc[q];
+}
+
+// The two sweeps above in one, without the tensor's trip through memory (single domain, no linearUpwind: nobody else wants grad U or G).  k_div_G takes row d of G
+// from the +-d neighbours only, so a tile of cells needs G at its own cells and ONE row at the cells of its six face slabs -- no edge or corner cells.  A workgroup
+// forms G for its tile (one cell per thread, rows kept in registers and published to LDS), deals the face slabs' cells out over the same threads in a second round
+// (row d of a slab cell needs grad of U_d and the trace: the loads of the other entries fall away), and takes the divergence from LDS after one barrier.
+// LDS holds row d over the tile widened by one cell at both ends along d, one plane per component: 8-byte reads at consecutive addresses.  A cell's neighbour across
+// a boundary face is the cell itself, as everywhere in this file, so no slab cell lies outside the block; partial tiles at the block's high ends leave lanes idle.
+// Every value is formed by the functions k_pre_coupling and k_div_G form it with: the same bits.
+#ifndef FY_STRESS_TILE_X
+#define FY_STRESS_TILE_X 16
+#endif
+#ifndef FY_STRESS_TILE_Y
+#define FY_STRESS_TILE_Y 8
+#endif
+#ifndef FY_STRESS_TILE_Z
+#define FY_STRESS_TILE_Z 4
+#endif
+constexpr int kSTX = FY_STRESS_TILE_X, kSTY = FY_STRESS_TILE_Y, kSTZ = FY_STRESS_TILE_Z;
+constexpr int kStressThreads = kSTX * kSTY * kSTZ;
+constexpr int kSlabX = 2 * kSTY * kSTZ, kSlabY = 2 * kSTX * kSTZ, kSlabZ = 2 * kSTX * kSTY;
+static_assert(kStressThreads % 64 == 0 && kStressThreads <= 1024, "a tile is a whole number of waves and one workgroup");
+static_assert(((kSTX + 2) * kSTY * kSTZ + kSTX * (kSTY + 2) * kSTZ + kSTX * kSTY * (kSTZ + 2)) * 3 * sizeof(double) <= 64 * 1024, "the tile's rows fit static LDS");
+
+// rows of G at cell (i, j, k) (ROWS: bit a = row a wanted; what the others alone need is never loaded).  Gather first, as k_pre_coupling does
+template <unsigned ROWS>
+__device__ __forceinline__ void stress_rows_at(const FvGeo& g, const double* __restrict__ U, const double* __restrict__ alpha, int i, int j, int k, double (&G)[3][3]) {
+    const int c = cidx(g, i, j, k);
+    const int ijk[3] = {i, j, k};
+    const double uc[3] = {U[3 * (size_t)c], U[3 * (size_t)c + 1], U[3 * (size_t)c + 2]};
+    bool bnd[3][2];
+    double un6[3][2][3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            bnd[d][s] = onb(g, d, s, i, j, k);
+            const int nb = bnd[d][s] ? c : c + (s ? stride_of(g, d) : -stride_of(g, d));
+            un6[d][s][0] = U[3 * (size_t)nb]; un6[d][s][1] = U[3 * (size_t)nb + 1]; un6[d][s][2] = U[3 * (size_t)nb + 2];
+        }
+    double T[9];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         double fv[2][3];
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
-            for (int q = 0; q < 3; ++q) fv[s][q] = bnd[d][s] ? own[d][q] : geo_lerp_side(g, d, s, ijk[d], own[d][q], nbv[d][s][q]);
-        for (int q = 0; q < 3; ++q) acc[q] += (fv[1][q] - fv[0][q]) * geo_rh(g, d, ijk[d]);
+        for (int s = 0; s < 2; ++s) u_face_value(g, d, s, bnd[d][s], ijk[d], uc, un6[d][s], fv[s]);
+        grad_row(g, d, ijk[d], fv, T);
     }
+    const double tr = stress_trace(T);
+    const double an = stress_coeff(g, alpha, c);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        if ((ROWS >> a) & 1)
+            for (int b = 0; b < 3; ++b) G[a][b] = stress_entry(an, T, tr, a, b);
+}
+
+__global__ __launch_bounds__(kStressThreads) void k_stress_div(FvGeo g, const double* __restrict__ U, const double* __restrict__ alpha, double* __restrict__ divG, int ntx, int nty) {
+    __shared__ double sx[3][(kSTX + 2) * kSTY * kSTZ], sy[3][kSTX * (kSTY + 2) * kSTZ], sz[3][kSTX * kSTY * (kSTZ + 2)];
+    // tiles in x-fastest order, an XCD's share of them contiguous: a range of z (swz_block)
+    const int tile = swz_block(blockIdx.x, gridDim.x);
+    const int tq = tile / ntx;
+    const int i0 = (tile - tq * ntx) * kSTX, j0 = (tq % nty) * kSTY, k0 = (tq / nty) * kSTZ;
+    const int tid = threadIdx.x;
+    const int lx = tid % kSTX, ly = (tid / kSTX) % kSTY, lz = tid / (kSTX * kSTY);
+    const int i = i0 + lx, j = j0 + ly, k = k0 + lz;
+    const bool in = i < g.nx && j < g.ny && k < g.nz;
+    // a cell's slot in the three images, and the step to its +-d neighbour's
+    const int ex = (lx + 1) + (kSTX + 2) * (ly + kSTY * lz), ey = lx + kSTX * ((ly + 1) + (kSTY + 2) * lz), ez = lx + kSTX * (ly + kSTY * (lz + 1));
+    double own[3][3];
+    if (in) {
+        stress_rows_at<7u>(g, U, alpha, i, j, k, own);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { sx[q][ex] = own[0][q]; sy[q][ey] = own[1][q]; sz[q][ez] = own[2][q]; }
+    }
+    // second round: the cells of the six face slabs, one row each (x slabs first, then y, then z; with the 16 x 8 x 4 tile every wave works on one direction)
+    for (int h = tid; h < kSlabX + kSlabY + kSlabZ; h += kStressThreads) {
+        double G[3][3];
+        if (h < kSlabX) {
+            const int s = h / (kSTY * kSTZ), r = h - s * (kSTY * kSTZ), hy = r % kSTY, hz = r / kSTY;
+            const int hi = s ? i0 + kSTX : i0 - 1, hj = j0 + hy, hk = k0 + hz;
+            if (hi >= 0 && hi < g.nx && hj < g.ny && hk < g.nz) {
+                stress_rows_at<1u>(g, U, alpha, hi, hj, hk, G);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) sx[q][(s ? kSTX + 1 : 0) + (kSTX + 2) * (hy + kSTY * hz)] = G[0][q];
+            }
+        } else if (h < kSlabX + kSlabY) {
+            const int hh = h - kSlabX;
+            const int s = hh / (kSTX * kSTZ), r = hh - s * (kSTX * kSTZ), hx = r % kSTX, hz = r / kSTX;
+            const int hi = i0 + hx, hj = s ? j0 + kSTY : j0 - 1, hk = k0 + hz;
+            if (hj >= 0 && hj < g.ny && hi < g.nx && hk < g.nz) {
+                stress_rows_at<2u>(g, U, alpha, hi, hj, hk, G);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) sy[q][hx + kSTX * ((s ? kSTY + 1 : 0) + (kSTY + 2) * hz)] = G[1][q];
+            }
+        } else {
+            const int hh = h - kSlabX - kSlabY;
+            const int s = hh / (kSTX * kSTY), r = hh - s * (kSTX * kSTY), hx = r % kSTX, hy = r / kSTX;
+            const int hi = i0 + hx, hj = j0 + hy, hk = s ? k0 + kSTZ : k0 - 1;
+            if (hk >= 0 && hk < g.nz && hi < g.nx && hj < g.ny) {
+                stress_rows_at<4u>(g, U, alpha, hi, hj, hk, G);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) sz[q][hx + kSTX * (hy + kSTY * (s ? kSTZ + 1 : 0))] = G[2][q];
+            }
+        }
+    }
+    __syncthreads();
+    if (!in) return;
+    const int ijk[3] = {i, j, k};
+    bool bnd[3][2];
+    double nbv[3][2][3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) bnd[d][s] = onb(g, d, s, i, j, k);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        // (across a boundary face the cell's own slot, as k_div_G reads the cell itself: the value is not used)
+        const int nx_ = bnd[0][s] ? ex : ex + (s ? 1 : -1);
+        const int ny_ = bnd[1][s] ? ey : ey + (s ? kSTX : -kSTX);
+        const int nz_ = bnd[2][s] ? ez : ez + (s ? kSTX * kSTY : -kSTX * kSTY);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { nbv[0][s][q] = sx[q][nx_]; nbv[1][s][q] = sy[q][ny_]; nbv[2][s][q] = sz[q][nz_]; }
+    }
+    double acc[3];
+    div_of_rows(g, bnd, ijk, own, nbv, acc);
+    const int c = cidx(g, i, j, k);
     for (int q = 0; q < 3; ++q) divG[3 * (size_t)c + q] = acc[q];
 }
 
@@ -1783,6 +1933,14 @@ int launch_interp_alpha(hipStream_t s, FvGeo g, const double* alpha, Face3 af) {
 
 int launch_div_G(hipStream_t s, FvGeo g, const double* G, double* divG) {
     hipLaunchKernelGGL(k_div_G, dim3(fv_grid(g)), dim3(256), 0, s, g, G, divG);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+
+int launch_stress_div(hipStream_t s, FvGeo g, const double* U, const double* alpha, double* divG) {
+    if (g.gz != 0 || g.c0 != 0 || g.win_nblk > 0) return fail(FY_ERR_INVALID, "launch_stress_div: single domain only (a slab exchanges row z of G between the two sweeps)");
+    const int ntx = (int)div_up(g.nx, kSTX), nty = (int)div_up(g.ny, kSTY), ntz = (int)div_up(g.nz, kSTZ);
+    hipLaunchKernelGGL(k_stress_div, dim3((unsigned)(ntx * nty * ntz)), dim3(kStressThreads), 0, s, g, U, alpha, divG, ntx, nty);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

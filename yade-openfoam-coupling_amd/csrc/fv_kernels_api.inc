@@ -16,6 +16,8 @@ int launch_pre_coupling(hipStream_t s, FvGeo g, const double* U, const double* p
 int launch_interp_alpha(hipStream_t s, FvGeo g, const double* alpha, Face3 alphaf);
 // G: three vec3 fields (rows of the tensor) over the whole storage, as k_pre_coupling writes them
 int launch_div_G(hipStream_t s, FvGeo g, const double* G, double* divG);
+// the same divG straight from U and alpha (and g.nut): launch_pre_coupling(Gout) + launch_div_G in one sweep over 3-D tiles, G held in LDS.  Single domain only
+int launch_stress_div(hipStream_t s, FvGeo g, const double* U, const double* alpha, double* divG);
 // The transport equations of the two-equation / one-equation closures (DPMTurbulenceModels.C:70-71 RAS kEpsilon, :76-77 LES kEqn):
 //   fvm::ddt(alpha, X) + fvm::div(alphaPhi, X) - fvm::laplacian(alpha (nut / sigma + nu), X) == Su - fvm::SuSp(c1, X) - fvm::Sp(c2, X)
 // mode 0  kEqn      X = k:    Su = alpha G,            c1 = 2/3 alpha divU,            c2 = Ce alpha sqrt(k) / delta          (sigma = 1)

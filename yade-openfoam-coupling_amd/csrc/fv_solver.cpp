@@ -191,7 +191,9 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     if (c->turbulence_model != FY_TURBULENCE_LAMINAR) { FY_TRY(nut.alloc_exact(n)); FY_TRY(launch_fill_f64(stream, nut.p, n, c->nut_initial)); g.nut = nut.p; }
     if (c->turbulence_model == FY_TURBULENCE_KEQN || c->turbulence_model == FY_TURBULENCE_KEPSILON) { FY_TRY(kturb.alloc_exact(n)); FY_TRY(launch_fill_f64(stream, kturb.p, n, c->k_initial)); g.kturb = kturb.p; }
     if (c->turbulence_model == FY_TURBULENCE_KEPSILON) { FY_TRY(epsturb.alloc_exact(n)); FY_TRY(launch_fill_f64(stream, epsturb.p, n, c->eps_initial)); g.epsturb = epsturb.p; }
-    FY_TRY(Gt.alloc_exact(9 * n)); FY_TRY(zero(Gt));
+    // the explicit stress term: linearUpwind wants vGrad stored by the sweep that forms G, and slabs exchange row z of G between the two sweeps -- both keep them
+    tiled_stress = pimple && S == 1 && g.upwind != 2 && !opt.no_tiled_stress;
+    if (!tiled_stress) { FY_TRY(Gt.alloc_exact(9 * n)); FY_TRY(zero(Gt)); }
     for (int d = 0; d < 3; ++d) {
         DevBuf<double>* fs[] = {&phi[d], &phiOld[d], &psn[d], &alphaf[d], &phiHbyA[d], &phiForces[d], &rAUf[d], &pflux[d], &ddtc[d], &dcorr[d]};
         for (auto* b : fs) { FY_TRY(b->alloc_exact(fv_fsize(g, d))); FY_TRY(zero(*b)); }
@@ -790,10 +792,14 @@ int Solver::step() {
         if (pimple) {
             // explicit stress term of divDevRhoReff from the CURRENT U and this step's alpha (one fused stencil pass)
             if (outer > 0) FY_TRY(halo_U());
-            FY_TRY(FVK(launch_pre_coupling, stream, g, U.p, p.p, alpha.p, C3(psn), vGrad.p, gradP.p, divT.p, Gt.p, g.upwind == 2 ? 1 : 0, 0));
-            // G is stored by rows; only row z is read across the slab faces
-            FY_TRY(overlapped(XW_MOMENTUM, true, [&](hipStream_t on) { return halo(Gt.p + 2 * 3 * nstore, 3, plane, g.nz, g.gz, 1, on); },
-                              [&](const FvGeo& gw) { return FVK(launch_div_G, stream, gw, Gt.p, divG.p); }));
+            if (tiled_stress) {
+                FY_TRY(FVK(launch_stress_div, stream, g, U.p, alpha.p, divG.p));       // (G stays in LDS)
+            } else {
+                FY_TRY(FVK(launch_pre_coupling, stream, g, U.p, p.p, alpha.p, C3(psn), vGrad.p, gradP.p, divT.p, Gt.p, g.upwind == 2 ? 1 : 0, 0));
+                // G is stored by rows; only row z is read across the slab faces
+                FY_TRY(overlapped(XW_MOMENTUM, true, [&](hipStream_t on) { return halo(Gt.p + 2 * 3 * nstore, 3, plane, g.nz, g.gz, 1, on); },
+                                  [&](const FvGeo& gw) { return FVK(launch_div_G, stream, gw, Gt.p, divG.p); }));
+            }
         }
         if (g.upwind == 2) FY_TRY(halo_cells(vGrad, 9, 1));      // linearUpwind reads grad(U) of the upwind neighbour (ico: written at step start)
         if (g.upwind >= 3) {                                     // the limited schemes: gradient ratio from grad(magSqr(U)) of the current U
@@ -874,7 +880,7 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
     const E tab[] = {{"U", U.p, 3 * n, 3}, {"p", p.p, n, 1}, {"phi_x", phi[0].p, phi[0].n, 0}, {"phi_y", phi[1].p, phi[1].n, 0}, {"phi_z", phi[2].p, phi[2].n, 0},
                      {"rAU", rAU.p, n, 1}, {"HbyA", HbyA.p, 3 * n, 3}, {"p_rhs", prhs.p, n, 1}, {"mom_diag", mdiag.p, n, 1}, {"mom_src", src.p, 3 * n, 3},
                      {"alpha", alpha.p, n, 1}, {"uSource", uSource.p, 3 * n, 3}, {"uSourceDrag", uSourceDrag.p, n, 1}, {"uParticle", uParticle.p, 3 * n, 3},
-                     {"gradP", gradP.p, 3 * n, 3}, {"divT", divT.p, 3 * n, 3}, {"vGrad", vGrad.p, 9 * n, 9}, {"ddtU", ddtU.p, 3 * n, 3}, {"nut", nut.p, n, 1}, {"k", kturb.p, n, 1}, {"epsilon", epsturb.p, n, 1}};
+                     {"gradP", gradP.p, 3 * n, 3}, {"divT", divT.p, 3 * n, 3}, {"vGrad", vGrad.p, 9 * n, 9}, {"divG", divG.p, 3 * n, 3}, {"ddtU", ddtU.p, 3 * n, 3}, {"nut", nut.p, n, 1}, {"k", kturb.p, n, 1}, {"epsilon", epsturb.p, n, 1}};
     if (s == "T" || s == "heatSp" || s == "heatSu") {
         if (!th.on) return fail(FY_ERR_INVALID, "solver field '%s' does not exist in this case (fy_case_desc.thermal is off)", s.c_str());
         *ptr = (s == "T" ? th.T.p : s == "heatSp" ? th.Sp.p : th.Su.p) + g.c0;
@@ -885,6 +891,12 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
         if (!th.buoyant) return fail(FY_ERR_INVALID, "solver field 'buoyancy' does not exist in this case (fy_case_desc.thermal.beta or g is zero)");
         *ptr = th.buoy.p + 3 * (size_t)g.c0;
         *count = 3 * n;
+        return FY_OK;
+    }
+    if (s == "stress_G") {      // the tensor of the explicit stress term as the two-sweep path stores it: three row fields over the whole storage, ghost planes included
+        if (!Gt.p) return fail(FY_ERR_INVALID, "solver field 'stress_G' does not exist in this case (the tiled sweep keeps the tensor in LDS; FOAMYADE_NO_TILED_STRESS=1 stores it)");
+        *ptr = Gt.p;
+        *count = 9 * nstore;
         return FY_OK;
     }
     for (const E& e : tab) if (s == e.nm) {

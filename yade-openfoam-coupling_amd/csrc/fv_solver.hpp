@@ -271,6 +271,7 @@ struct Solver {
     bool fused_corrector = true;   // the corrector as two fused sweeps (FOAMYADE_NO_FUSED_CORRECTOR=1: the five sweeps of rounds 1 - 4; identical results)
     bool hbya_ready = false;       // HbyA already holds rAU H(U) of the current U (written by the momentum predictor's last pass)
     bool face_arrays = true;       // rAUf / alphacf are kept as face arrays (somebody streams them: see create())
+    bool tiled_stress = false;     // pimple, one domain, no linearUpwind: div G from U in one LDS-tiled sweep, Gt never allocated (FOAMYADE_NO_TILED_STRESS=1: the two sweeps; identical results)
     bool faces_from_cells = true;  // the fused sweeps re-form rAUf / alphacf from rAU / alpha (FOAMYADE_FACES_FROM_ARRAYS=1: stream the face arrays)
 
     // ---- one PISO / PIMPLE corrector (icoFoamYade.C:97-140, pEqn.H)
