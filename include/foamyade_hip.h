@@ -452,7 +452,11 @@ int fy_solver_create(const fy_case_desc* c, const fy_transport* transport, int d
 fy_ctx* fy_solver_coupling(fy_solver*);                 /* the yadeCoupling object (icoFoamYade.C:54, pimpleFoamYade.C:54) */
 int fy_solver_step(fy_solver*);                         /* one pass of the while(runTime.loop()) body */
 int fy_solver_get_stats(fy_solver*, fy_step_stats* out);
-/* names: "U" [n][3], "p" [n], "phi_x" [(nx+1)*ny*nz], "phi_y", "phi_z", "nut" [n] (with a turbulence model), "k" [n] (kEqn, kEpsilon), "epsilon" [n] (kEpsilon), plus every fy_ctx field name */
+/* names: "U" [n][3], "p" [n], "phi_x" [(nx+1)*ny*nz], "phi_y", "phi_z", "nut" [n] (with a turbulence model), "k" [n] (kEqn, kEpsilon), "epsilon" [n] (kEpsilon), plus every fy_ctx field name.
+   Diagnostics of the last step, for tests that hold the sweeps to a reference (the owned cells / faces): "rAU", "HbyA", "mom_diag", "mom_src", "p_diag", "p_ux", "p_uy",
+   "p_uz", "p_rhs", "divG"; read-only: "mom_an0" .. "mom_an5" [n] (the momentum matrix's neighbour coefficient across side 2 d + s) and "phiHbyA_x" | "_y" | "_z" (face
+   arrays like phi).  kEqn / kEpsilon and the T equation reuse the momentum matrix's storage: "HbyA", "mom_diag", "mom_an*" (and "mom_src" under a transport model) are
+   FY_ERR_UNSUPPORTED there. */
 int fy_solver_read_field_host(fy_solver*, const char* name, double* out);
 int fy_solver_write_field_host(fy_solver*, const char* name, const double* in);
 /* number of doubles fy_solver_read/write_field_host move for `name` on this rank (owned cells / local faces) */

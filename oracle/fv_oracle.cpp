@@ -21,7 +21,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 extern "C" {
@@ -72,9 +74,20 @@ struct orc_fv_stats {
 
 namespace {
 
-typedef std::vector<double> vec;
-const double SMALL = 1e-15;      // OpenFOAM `small` for double
-const double VSMALL = 1e-300;
+// The arithmetic type.  liboracle.so computes in double; liboracle_ld.so is this file alone with -DORC_REAL='long double', the reference the FV sweeps are held
+// to (tests/test_fv_sweeps_*.py).  The C interface (orc_fv_case, orc_fv_stats, every array that crosses it) is double in both.  Literals such as 2.0 / 3.0 stay
+// double-rounded in the wide build too: they are the constants the kernels use.
+#ifdef ORC_REAL
+typedef ORC_REAL real;
+#else
+typedef double real;
+#endif
+inline real rmax(real a, real b) { return (a < b) ? b : a; }      // (std::max / std::min, whose two arguments must agree in type)
+inline real rmin(real a, real b) { return (b < a) ? b : a; }
+
+typedef std::vector<real> vec;
+const real SMALL = 1e-15;      // OpenFOAM `small` for real
+const real VSMALL = 1e-300;
 const int kMgCoarsest = 128, kMgCoarsestEdge = 8, kMgCoarseSweeps = 120;    // coarsest multigrid level (same rule as the product so iteration counts are comparable):
                                                                             // solved exactly out of its dense inverse; the sweeps only stand in if that inverse cannot be formed
 
@@ -87,7 +100,7 @@ struct MgLevel {
 struct Fv {
     orc_fv_case cs;
     int nx, ny, nz, Nc, n[3], stride[3];
-    double dx, Af, V;
+    real dx, Af, V;
     bool pimple;
     // ---- geometry of a graded (rectilinear, orthogonal) block [OF-6 surfaceInterpolation::weights / deltaCoeffs on a hex mesh whose cell sizes
     // vary along the axes]: the uniform block keeps its constants (dx, Af, V) and its original expressions, `graded` switches every operator to
@@ -95,16 +108,16 @@ struct Fv {
     // centre over the centre distance; |Sf| / |d| from the face area and the centre distance (a boundary face: centre to face)
     bool graded = false;
     vec h[3];
-    double total_volume = 0.0;
+    real total_volume = 0.0;
     inline int idx_of(int d, int c) const { return (c / stride[d]) % n[d]; }
-    inline double vol(int i, int j, int k) const { return graded ? (h[0][i] * h[1][j]) * h[2][k] : V; }
-    inline double volc(int c) const { return graded ? vol(c % nx, (c / nx) % ny, c / (nx * ny)) : V; }
+    inline real vol(int i, int j, int k) const { return graded ? (h[0][i] * h[1][j]) * h[2][k] : V; }
+    inline real volc(int c) const { return graded ? vol(c % nx, (c / nx) % ny, c / (nx * ny)) : V; }
     // area of a face normal to d whose transverse indices are those of (i, j, k) (cell or face indices: the normal one is not used)
-    inline double area(int d, int i, int j, int k) const { return graded ? (d == 0 ? h[1][j] * h[2][k] : d == 1 ? h[0][i] * h[2][k] : h[0][i] * h[1][j]) : Af; }
-    inline double wlow(int d, int q) const { return graded ? h[d][q] / (h[d][q - 1] + h[d][q]) : 0.5; }
-    inline double lerp(int d, int q, double lo, double hi) const { if (!graded) return 0.5 * (lo + hi); const double w = wlow(d, q); return w * lo + (1.0 - w) * hi; }
+    inline real area(int d, int i, int j, int k) const { return graded ? (d == 0 ? h[1][j] * h[2][k] : d == 1 ? h[0][i] * h[2][k] : h[0][i] * h[1][j]) : Af; }
+    inline real wlow(int d, int q) const { return graded ? h[d][q] / (h[d][q - 1] + h[d][q]) : 0.5; }
+    inline real lerp(int d, int q, real lo, real hi) const { if (!graded) return 0.5 * (lo + hi); const real w = wlow(d, q); return w * lo + (1.0 - w) * hi; }
     // centre distance across face q of axis d (q = 0 or n[d]: cell centre to the boundary face)
-    inline double delta(int d, int q) const {
+    inline real delta(int d, int q) const {
         if (!graded) return (q == 0 || q == n[d]) ? 0.5 * dx : dx;
         if (q == 0) return 0.5 * h[d][0];
         if (q == n[d]) return 0.5 * h[d][n[d] - 1];
@@ -113,14 +126,14 @@ struct Fv {
     // face index along d of face (d, s) of cell (i, j, k)
     inline int fq(int d, int s, int i, int j, int k) const { return (d == 0 ? i : d == 1 ? j : k) + s; }
     // |Sf| / |d| of face (d, s) of cell (i, j, k).  Uniform block: dx for EVERY face -- the boundary factor 2 stays where the uniform code has it
-    inline double sfd(int d, int s, int i, int j, int k) const { return graded ? area(d, i, j, k) / delta(d, fq(d, s, i, j, k)) : dx; }
-    inline double bfac() const { return graded ? 1.0 : 2.0; }          // (gb = bfac * gamma: see sfd)
-    inline double hcell(int d, int c) const { return graded ? h[d][idx_of(d, c)] : dx; }
+    inline real sfd(int d, int s, int i, int j, int k) const { return graded ? area(d, i, j, k) / delta(d, fq(d, s, i, j, k)) : dx; }
+    inline real bfac() const { return graded ? 1.0 : 2.0; }          // (gb = bfac * gamma: see sfd)
+    inline real hcell(int d, int c) const { return graded ? h[d][idx_of(d, c)] : dx; }
     // LESdelta cubeRootVol [OF-6 cubeRootVolDelta.C]: deltaCoeff * cbrt(V) of the cell; nearWallDist: half the cell's extent along the wall normal
-    inline double les_delta(int c) const { return graded ? cs.les_delta_coeff * std::cbrt(volc(c)) : cs.les_delta_coeff * std::pow(V, 1.0 / 3.0); }
-    inline double ywall_of(int d, int c) const { return 0.5 * hcell(d, c); }
+    inline real les_delta(int c) const { return graded ? cs.les_delta_coeff * std::cbrt(volc(c)) : cs.les_delta_coeff * std::pow(V, 1.0 / 3.0); }
+    inline real ywall_of(int d, int c) const { return 0.5 * hcell(d, c); }
     // linear face interpolate of a cell pair across face (d, s) of the cell with index qc along d: own = this cell's value, nb = the neighbour's
-    inline double lerp_side(int d, int s, int qc, double own, double nb) const { return !graded ? 0.5 * (own + nb) : (s ? lerp(d, qc + 1, own, nb) : lerp(d, qc, nb, own)); }
+    inline real lerp_side(int d, int s, int qc, real own, real nb) const { return !graded ? 0.5 * (own + nb) : (s ? lerp(d, qc + 1, own, nb) : lerp(d, qc, nb, own)); }
     int threads = 1;
     // state
     vec U, Uold, p, alpha, alphaOld, uSource, uSourceDrag, uParticle, gradP, divT, vGrad, ddtU;
@@ -134,7 +147,7 @@ struct Fv {
     std::vector<MgLevel> mg;
     vec pb, pr, pw, pp, pz;
     orc_fv_stats st{};
-    double cumulativeContErr = 0.0;
+    real cumulativeContErr = 0.0;
 
     int fsize(int d) const { return d == 0 ? (nx + 1) * ny * nz : d == 1 ? nx * (ny + 1) * nz : nx * ny * (nz + 1); }
     inline int cid(int i, int j, int k) const { return i + nx * (j + ny * k); }
@@ -183,14 +196,14 @@ struct Fv {
     }
 
     // ---- boundary values ----------------------------------------------------------------------------------
-    inline void Ub(const vec& F, int c, int patch, double* out) const {          // velocity-like field with U's BCs
+    inline void Ub(const vec& F, int c, int patch, real* out) const {          // velocity-like field with U's BCs
         if (cs.u_bc[patch] == 0) { out[0] = cs.u_value[patch][0]; out[1] = cs.u_value[patch][1]; out[2] = cs.u_value[patch][2]; }
         else { out[0] = F[3 * (size_t)c]; out[1] = F[3 * (size_t)c + 1]; out[2] = F[3 * (size_t)c + 2]; }
         // symmetryPlane / slip on a planar, axis-aligned patch [OF-6 basicSymmetryFvPatchField::evaluate]: the cell value with its normal
         // component removed, (pif + transform(I - 2 nn, pif)) / 2
         if (cs.u_bc[patch] == 2) out[patch / 2] = 0.0;
     }
-    inline double pbv(int c, int d, int s, int face) const {                     // boundary value of p
+    inline real pbv(int c, int d, int s, int face) const {                     // boundary value of p
         const int patch = 2 * d + s;
         if (cs.p_bc[patch] == 1) return cs.p_value[patch];
         if (cs.p_bc[patch] == 2) return p[c] + (s ? 0.5 : -0.5) * hcell(d, c) * psn[d][face];
@@ -204,9 +217,9 @@ struct Fv {
             for (int k = 0; k < nz + (d == 2); ++k) for (int j = 0; j < ny + (d == 1); ++j) for (int i = 0; i < nx + (d == 0); ++i) {
                 const int q = d == 0 ? i : d == 1 ? j : k;
                 const int f = fid(d, i, j, k);
-                double v;
-                if (q == 0) { double b[3]; Ub(F, cid(i, j, k), 2 * d, b); v = b[d]; }
-                else if (q == n[d]) { double b[3]; const int c = cid(i - (d == 0), j - (d == 1), k - (d == 2)); Ub(F, c, 2 * d + 1, b); v = b[d]; }
+                real v;
+                if (q == 0) { real b[3]; Ub(F, cid(i, j, k), 2 * d, b); v = b[d]; }
+                else if (q == n[d]) { real b[3]; const int c = cid(i - (d == 0), j - (d == 1), k - (d == 2)); Ub(F, c, 2 * d + 1, b); v = b[d]; }
                 else { const int c = cid(i, j, k); v = lerp(d, q, F[3 * (size_t)(c - stride[d]) + d], F[3 * (size_t)c + d]); }
                 out[d][f] = v * area(d, i, j, k);
             }
@@ -218,7 +231,7 @@ struct Fv {
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
             for (int d = 0; d < 3; ++d) {
-                double fv[2];
+                real fv[2];
                 for (int s = 0; s < 2; ++s) {
                     if (onb(d, s, i, j, k)) fv[s] = pbv(c, d, s, cface(d, s, i, j, k));
                     else if (!graded) fv[s] = 0.5 * (p[c] + p[c + (s ? stride[d] : -stride[d])]);
@@ -241,35 +254,35 @@ struct Fv {
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
             for (int d = 0; d < 3; ++d) {
-                double fv[2];
+                real fv[2];
                 for (int s = 0; s < 2; ++s) {
-                    if (onb(d, s, i, j, k)) { double b[3]; Ub(F, c, 2 * d + s, b); fv[s] = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]; }
+                    if (onb(d, s, i, j, k)) { real b[3]; Ub(F, c, 2 * d + s, b); fv[s] = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]; }
                     else fv[s] = lerp_side(d, s, d == 0 ? i : d == 1 ? j : k, lphi[c], lphi[c + (s ? stride[d] : -stride[d])]);
                 }
                 gradL[3 * (size_t)c + d] = (fv[1] - fv[0]) / hcell(d, c);
             }
         }
     }
-    static double limiter_fn(int scheme, double twoByk, double r) {
+    static real limiter_fn(int scheme, real twoByk, real r) {
         switch (scheme) {
-            case 3: return std::max(std::min(twoByk * r, 1.0), 0.0);                                             // limitedLinear
+            case 3: return rmax(rmin(twoByk * r, 1.0), 0.0);                                             // limitedLinear
             case 4: return (r + std::fabs(r)) / (1.0 + std::fabs(r));                                            // vanLeer
-            case 5: return std::max(std::min(std::min(2.0 * r, 0.5 * r + 0.5), 2.0), 0.0);                       // MUSCL
-            case 6: return std::max(std::min(std::min(r, 1.0), 2.0), 0.0);                                       // Minmod
-            case 7: return std::max(std::max(std::min(2.0 * r, 1.0), std::min(r, 2.0)), 0.0);                    // SuperBee
-            default: return std::max(std::min((3.0 + r) / 4.0, 2.0), 0.0);        // QUICK (8) [OF-6 QUICK.H]: (phif - phiU) / (phiCD - phiU) = (3 + r) / 4, limited to [0, 2] only
+            case 5: return rmax(rmin(rmin(2.0 * r, 0.5 * r + 0.5), 2.0), 0.0);                       // MUSCL
+            case 6: return rmax(rmin(rmin(r, 1.0), 2.0), 0.0);                                       // Minmod
+            case 7: return rmax(rmax(rmin(2.0 * r, 1.0), rmin(r, 2.0)), 0.0);                    // SuperBee
+            default: return rmax(rmin((3.0 + r) / 4.0, 2.0), 0.0);        // QUICK (8) [OF-6 QUICK.H]: (phif - phiU) / (phiCD - phiU) = (3 + r) / 4, limited to [0, 2] only
         }
     }
     // weight of the owner's (low cell's) value on interior face q of axis d between cells own and nei, for the face flux `flux` (owner -> neighbour)
-    double limited_weight(int d, int q, int own, int nei, double flux) const {
-        const double gradf = lphi[nei] - lphi[own];
-        const double gradcf = delta(d, q) * gradL[3 * (size_t)(flux > 0 ? own : nei) + d];
-        double r;
+    real limited_weight(int d, int q, int own, int nei, real flux) const {
+        const real gradf = lphi[nei] - lphi[own];
+        const real gradcf = delta(d, q) * gradL[3 * (size_t)(flux > 0 ? own : nei) + d];
+        real r;
         if (std::fabs(gradcf) >= 1000.0 * std::fabs(gradf)) r = 2.0 * 1000.0 * (gradcf >= 0 ? 1.0 : -1.0) * (gradf >= 0 ? 1.0 : -1.0) - 1.0;
         else r = 2.0 * (gradcf / gradf) - 1.0;
-        const double kk = std::max(cs.convection_limiter_k, SMALL);            // limitedLinearLimiter: twoByk_ = 2 / max(k, small) (k = 1: min(2 r, 1), TVD conforming)
-        const double lim = limiter_fn(cs.convection_scheme, 2.0 / kk, r);
-        const double wl = graded ? wlow(d, q) : 0.5;
+        const real kk = rmax(cs.convection_limiter_k, SMALL);            // limitedLinearLimiter: twoByk_ = 2 / max(k, small) (k = 1: min(2 r, 1), TVD conforming)
+        const real lim = limiter_fn(cs.convection_scheme, 2.0 / kk, r);
+        const real wl = graded ? wlow(d, q) : 0.5;
         return lim * wl + (1.0 - lim) * (flux >= 0 ? 1.0 : 0.0);
     }
 
@@ -279,7 +292,7 @@ struct Fv {
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
             for (int d = 0; d < 3; ++d) {
-                double fv[2][3];
+                real fv[2][3];
                 for (int s = 0; s < 2; ++s) {
                     if (onb(d, s, i, j, k)) Ub(F, c, 2 * d + s, fv[s]);
                     else {
@@ -306,11 +319,11 @@ struct Fv {
 
     // CourantNo.H:32-49 (pimple) / OpenFOAM CourantNo.H (ico, icoFoamYade.C:68)
     void courant() {
-        double mx = 0.0, sum = 0.0;
+        real mx = 0.0, sum = 0.0;
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
-            double s = 0.0;
+            real s = 0.0;
             for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) s += std::fabs(phi[d][cface(d, sd, i, j, k)]);
-            mx = std::max(mx, s / vol(i, j, k)); sum += s;
+            mx = rmax(mx, s / vol(i, j, k)); sum += s;
         }
         st.courant_max = 0.5 * mx * cs.dt;
         st.courant_mean = 0.5 * (sum / (graded ? total_volume : V * Nc)) * cs.dt;
@@ -326,10 +339,10 @@ struct Fv {
 #pragma omp parallel for num_threads(threads) collapse(2)
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            double acc[3] = {0, 0, 0};
+            real acc[3] = {0, 0, 0};
             for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) {
-                const double flux = (s ? 1.0 : -1.0) * phi[d][cface(d, s, i, j, k)];
-                double uf[3];
+                const real flux = (s ? 1.0 : -1.0) * phi[d][cface(d, s, i, j, k)];
+                real uf[3];
                 if (onb(d, s, i, j, k)) Ub(U, c, 2 * d + s, uf);
                 else {
                     const int nb = c + (s ? stride[d] : -stride[d]);
@@ -345,11 +358,11 @@ struct Fv {
 #pragma omp parallel for num_threads(threads) collapse(2)
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            double acc[3] = {0, 0, 0};
+            real acc[3] = {0, 0, 0};
             for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) {
-                const double af = alphaf[d][cface(d, s, i, j, k)];
+                const real af = alphaf[d][cface(d, s, i, j, k)];
                 if (onb(d, s, i, j, k)) {
-                    double b[3]; Ub(U, c, 2 * d + s, b);
+                    real b[3]; Ub(U, c, 2 * d + s, b);
                     for (int q = 0; q < 3; ++q) acc[q] += graded ? af * sfd(d, s, i, j, k) * (b[q] - U[3 * (size_t)c + q]) : af * Af * (b[q] - U[3 * (size_t)c + q]) / (0.5 * dx);
                 } else {
                     const int nb = c + (s ? stride[d] : -stride[d]);
@@ -365,55 +378,55 @@ struct Fv {
     // pimple: fvm::ddt(a,Uc) + fvm::div(aPhi,Uc) - fvm::Sp(fvc::ddt(a)+fvc::div(aPhi),Uc) + divDevRhoReff(Uc) == fvm::Sp(uSourceDrag,Uc)
     //                                                                                              (UcEqn.H:3-10), then relax() (UcEqn.H:12)
     // an[2*d+s] = coefficient of the neighbour across face (d,s); src excludes any pressure term.
-    double u_relax_now = 1.0;      // the factor fvMatrix::relax() finds for this outer iteration (Uc / UcFinal)
+    real u_relax_now = 1.0;      // the factor fvMatrix::relax() finds for this outer iteration (Uc / UcFinal)
     vec pPrev;                     // p.prevIter(): stored by pimple.loop() at the start of every outer iteration when p has a relaxation factor
     // boundary value of nut on `patch` next to cell c: 0 zeroGradient, 1 fixedValue, 2 nutkWallFunction [OF-6 nutkWallFunctionFvPatchScalarField::nut():
     // yPlus = Cmu^0.25 y sqrt(k_P)/nu_w; nut_w = nu_w (yPlus kappa/log(E yPlus) - 1) if yPlus > yPlusLam else 0; yPlusLam by ten fixed-point sweeps of
     // ypl = log(max(E ypl, 1))/kappa from 11].  OpenFOAM keeps the values of the last correctNut(); before the first correct() the file's value stands
     bool nut_wall_live = false;
-    double nut_boundary(int patch, int c) const {
+    real nut_boundary(int patch, int c) const {
         const int t = cs.nut_bc[patch];
         if (t == 1 || ((t == 2 || t == 3) && !nut_wall_live)) return cs.nut_value[patch];
         if (t == 3) {       // calculated: nut_ = <model expression> assigns the boundary too [OF-6 GeometricField::operator=]: Ck sqrt(k_b) delta | Cmu k_b^2/eps_b
-            const double kb = cs.k_bc[patch] == 1 ? cs.k_value[patch] : kturb[c];
+            const real kb = cs.k_bc[patch] == 1 ? cs.k_value[patch] : kturb[c];
             if (cs.turbulence_model == 2) return cs.les_ck * std::sqrt(kb) * les_delta(c);
-            const double eb = cs.eps_bc[patch] == 1 ? cs.eps_value[patch] : epsturb[c];
+            const real eb = cs.eps_bc[patch] == 1 ? cs.eps_value[patch] : epsturb[c];
             return cs.ras_cmu * (kb * kb) / eb;
         }
         if (t == 2) {
-            double ypl = 11.0;
-            for (int it = 0; it < 10; ++it) ypl = std::log(std::max(cs.wf_E * ypl, 1.0)) / cs.wf_kappa;
-            const double y = ywall_of(patch / 2, c);
-            const double yPlus = std::pow(cs.ras_cmu, 0.25) * y * std::sqrt(kturb[c]) / cs.nu;
+            real ypl = 11.0;
+            for (int it = 0; it < 10; ++it) ypl = std::log(rmax(cs.wf_E * ypl, 1.0)) / cs.wf_kappa;
+            const real y = ywall_of(patch / 2, c);
+            const real yPlus = std::pow(cs.ras_cmu, 0.25) * y * std::sqrt(kturb[c]) / cs.nu;
             return yPlus > ypl ? cs.nu * (yPlus * cs.wf_kappa / std::log(cs.wf_E * yPlus) - 1.0) : 0.0;
         }
         return nut[c];
     }
     void assemble_momentum() {
-        const double nu = cs.nu, dt = cs.dt;
+        const real nu = cs.nu, dt = cs.dt;
         if (cs.convection_scheme >= 3) limiter_gradient(U);          // the limiter sees the CURRENT U (the scheme is built when UEqn is assembled)
         if (pimple) {
             // explicit part of divDevRhoReff: + fvc::div(alpha nu dev2(T(grad U))) on the RHS (laminar Stokes model)
             grad_U(U, vGrad);
             vec G(9 * (size_t)Nc);
             for (int c = 0; c < Nc; ++c) {
-                const double* T = &vGrad[9 * (size_t)c];
-                const double tr = T[0] + T[4] + T[8];
+                const real* T = &vGrad[9 * (size_t)c];
+                const real tr = T[0] + T[4] + T[8];
                 for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b)
                     G[9 * (size_t)c + 3 * a + b] = (nut.empty() ? alpha[c] * nu : alpha[c] * (nu + nut[c])) * (T[3 * b + a] - (a == b ? (2.0 / 3.0) * tr : 0.0));   // alpha nuEff dev2(T(grad U)) [OF-6 linearViscousStress::divDevRhoReff]
             }
 #pragma omp parallel for num_threads(threads) collapse(2)
             for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
                 const int c = cid(i, j, k);
-                double acc[3] = {0, 0, 0};
+                real acc[3] = {0, 0, 0};
                 for (int d = 0; d < 3; ++d) {
-                    double fv[2][3];
+                    real fv[2][3];
                     for (int s = 0; s < 2; ++s) {
                         if (onb(d, s, i, j, k)) for (int q = 0; q < 3; ++q) fv[s][q] = G[9 * (size_t)c + 3 * d + q];
                         else {
                             const int nb = c + (s ? stride[d] : -stride[d]);
                             for (int q = 0; q < 3; ++q) {
-                                const double gc = G[9 * (size_t)c + 3 * d + q], gn = G[9 * (size_t)nb + 3 * d + q];
+                                const real gc = G[9 * (size_t)c + 3 * d + q], gn = G[9 * (size_t)nb + 3 * d + q];
                                 fv[s][q] = !graded ? 0.5 * (gc + gn) : (s ? lerp(d, fq(d, 1, i, j, k), gc, gn) : lerp(d, fq(d, 0, i, j, k), gn, gc));
                             }
                         }
@@ -426,25 +439,25 @@ struct Fv {
 #pragma omp parallel for num_threads(threads) collapse(2)
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            const double aP = pimple ? alpha[c] : 1.0, aP0 = pimple ? alphaOld[c] : 1.0;
-            const double Vc = vol(i, j, k);
-            double dg = aP * Vc / dt;                                        // fvm::ddt
+            const real aP = pimple ? alpha[c] : 1.0, aP0 = pimple ? alphaOld[c] : 1.0;
+            const real Vc = vol(i, j, k);
+            real dg = aP * Vc / dt;                                        // fvm::ddt
             if (!bdiag.empty()) for (int q = 0; q < 3; ++q) bdiag[3 * (size_t)c + q] = 0.0;
-            double s3[3];
+            real s3[3];
             for (int q = 0; q < 3; ++q) s3[q] = aP0 * Vc * Uold[3 * (size_t)c + q] / dt;
-            double divAPhi = 0.0;
+            real divAPhi = 0.0;
             for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) {
                 const int f = cface(d, s, i, j, k);
-                const double af = pimple ? alphaf[d][f] : 1.0;
-                const double phio = (s ? 1.0 : -1.0) * af * phi[d][f];       // outward (alpha-weighted) flux
+                const real af = pimple ? alphaf[d][f] : 1.0;
+                const real phio = (s ? 1.0 : -1.0) * af * phi[d][f];       // outward (alpha-weighted) flux
                 divAPhi += phio;
-                const double geo = sfd(d, s, i, j, k);                       // |Sf| / |d| (uniform block: dx, the boundary's factor 2 is bfac())
-                double gam = nu * af * geo;                                  // (alpha nu)_f |Sf| / |d|
+                const real geo = sfd(d, s, i, j, k);                       // |Sf| / |d| (uniform block: dx, the boundary's factor 2 is bfac())
+                real gam = nu * af * geo;                                  // (alpha nu)_f |Sf| / |d|
                 if (!nut.empty()) {
                     // - fvm::laplacian(alpha nuEff, U) [OF-6 linearViscousStress::divDevRhoReff]: the cell field alpha (nu + nut) is interpolated
                     // linearly to the faces (gaussLaplacianScheme::fvmLaplacian(vol gamma)); boundary value alpha_b (nu + nut_b) with nut_b by 0/nut
                     if (onb(d, s, i, j, k)) {
-                        const double nb = nut_boundary(2 * d + s, c);
+                        const real nb = nut_boundary(2 * d + s, c);
                         gam = (af * (nu + nb)) * geo;
                     } else {
                         const int nbc = c + (s ? stride[d] : -stride[d]);
@@ -455,7 +468,7 @@ struct Fv {
                     an[2 * d + s][c] = 0.0;
                     const int patch = 2 * d + s;
                     if (cs.u_bc[patch] == 0) {                               // fixedValue
-                        const double gb = bfac() * gam;
+                        const real gb = bfac() * gam;
                         dg += gb;
                         for (int q = 0; q < 3; ++q) s3[q] += (-phio + gb) * cs.u_value[patch][q];
                     } else if (cs.u_bc[patch] == 2) {
@@ -472,12 +485,12 @@ struct Fv {
                 } else {
                     const bool up = cs.convection_scheme == 1 || cs.convection_scheme == 2;      // 1 upwind, 2 linearUpwind (implicit part = upwind)
                     // Gauss linear: the face value is w_P U_P + (1 - w_P) U_N with the linear weights of the (graded) block
-                    const double wP = !graded ? 0.5 : (s ? wlow(d, fq(d, 1, i, j, k)) : 1.0 - wlow(d, fq(d, 0, i, j, k)));
-                    double cP = up ? std::max(phio, 0.0) : wP * phio;
-                    double cN = up ? std::min(phio, 0.0) : (!graded ? 0.5 * phio : (1.0 - wP) * phio);
+                    const real wP = !graded ? 0.5 : (s ? wlow(d, fq(d, 1, i, j, k)) : 1.0 - wlow(d, fq(d, 0, i, j, k)));
+                    real cP = up ? rmax(phio, 0.0) : wP * phio;
+                    real cN = up ? rmin(phio, 0.0) : (!graded ? 0.5 * phio : (1.0 - wP) * phio);
                     if (cs.convection_scheme >= 3) {
                         const int nb = c + (s ? stride[d] : -stride[d]);
-                        const double w = limited_weight(d, fq(d, s, i, j, k), s ? c : nb, s ? nb : c, af * phi[d][f]);
+                        const real w = limited_weight(d, fq(d, s, i, j, k), s ? c : nb, s ? nb : c, af * phi[d][f]);
                         cP = s ? phio * w : phio * (1.0 - w);
                         cN = s ? phio * (1.0 - w) : phio * w;
                     }
@@ -488,13 +501,13 @@ struct Fv {
                         // the second term explicit (deferred correction) with the Gauss-linear gradient of the current U
                         const int nb = c + (s ? stride[d] : -stride[d]);
                         const int uw = phio > 0.0 ? c : nb;
-                        const double half = (phio > 0.0 ? (s ? 0.5 : -0.5) : (s ? -0.5 : 0.5)) * hcell(d, uw);      // half the UPWIND cell's extent, towards the face
+                        const real half = (phio > 0.0 ? (s ? 0.5 : -0.5) : (s ? -0.5 : 0.5)) * hcell(d, uw);      // half the UPWIND cell's extent, towards the face
                         for (int q = 0; q < 3; ++q) s3[q] -= phio * (half * vGrad[9 * (size_t)uw + 3 * d + q]);
                     }
                 }
             }
             if (pimple) {
-                const double S = (alpha[c] - alphaOld[c]) / dt + divAPhi / Vc;  // fvc::ddt(alphac) + fvc::div(alphaPhic)
+                const real S = (alpha[c] - alphaOld[c]) / dt + divAPhi / Vc;  // fvc::ddt(alphac) + fvc::div(alphaPhic)
                 Sc[c] = S;
                 dg -= Vc * S;                                                // - fvm::Sp(S, Uc)
                 dg -= Vc * uSourceDrag[c];                                   // == fvm::Sp(uSourceDrag, Uc)
@@ -506,19 +519,19 @@ struct Fv {
                 // fvMatrix::relax(alpha) [OF-6 fvMatrix.C]: the boundary coefficients join the diagonal for the dominance test (they are
                 // part of dg here all along), D = max(|D|, sum|offdiag|) / alpha, source += (D_new - D_old) psi.  No relaxationFactors
                 // entry for the equation (alpha <= 0): relax() does nothing at all, not even the dominance step.
-                double so = 0.0; for (int q = 0; q < 6; ++q) so += std::fabs(an[q][c]);
+                real so = 0.0; for (int q = 0; q < 6; ++q) so += std::fabs(an[q][c]);
                 // a slip patch's coefficient differs by component: relax() adds cmptMax(cmptMag(internalCoeffs)) before the test and
                 // takes cmptMin(internalCoeffs) (= 0 there) off afterwards, so the whole of it takes part in the dominance test and the
                 // scalar diagonal keeps what the test gave
-                const double bsum = bdiag.empty() ? 0.0 : bdiag[3 * (size_t)c] + bdiag[3 * (size_t)c + 1] + bdiag[3 * (size_t)c + 2];
-                const double dn = std::max(std::fabs(dg + bsum), so) / u_relax_now;
+                const real bsum = bdiag.empty() ? 0.0 : bdiag[3 * (size_t)c] + bdiag[3 * (size_t)c + 1] + bdiag[3 * (size_t)c + 2];
+                const real dn = rmax(std::fabs(dg + bsum), so) / u_relax_now;
                 for (int q = 0; q < 3; ++q) s3[q] += (dn - dg) * U[3 * (size_t)c + q];
                 dg = dn;
             }
             diag[c] = dg;
             for (int q = 0; q < 3; ++q) src[3 * (size_t)c + q] = s3[q];
             // 1/UEqn.A(): fvMatrix::A() adds the COMPONENT AVERAGE of the boundary diagonal (addCmptAvBoundaryDiag)
-            const double bav = bdiag.empty() ? 0.0 : (bdiag[3 * (size_t)c] + bdiag[3 * (size_t)c + 1] + bdiag[3 * (size_t)c + 2]) / 3.0;
+            const real bav = bdiag.empty() ? 0.0 : (bdiag[3 * (size_t)c] + bdiag[3 * (size_t)c + 1] + bdiag[3 * (size_t)c + 2]) / 3.0;
             rAU[c] = 1.0 / ((dg + bav) / Vc);
         }
     }
@@ -527,7 +540,7 @@ struct Fv {
     // Jacobi solve of diag*x + sum an*x_nb = b for the 3 components (stand-in for smoothSolver symGaussSeidel)
     // diagonal of component q: the scalar one + that component's boundary diagonal (slip patches)
     bool bdiag_on = false;       // (solve_vec3 also solves the k / epsilon equations, which have none)
-    inline double dgc(int c, int q) const { return bdiag_on ? diag[c] + bdiag[3 * (size_t)c + q] : diag[c]; }
+    inline real dgc(int c, int q) const { return bdiag_on ? diag[c] + bdiag[3 * (size_t)c + q] : diag[c]; }
     int solve_momentum(const vec& b) {
         bdiag_on = !bdiag.empty();
         const int it = solve_vec3(U, b, cs.u_tol, cs.u_rel_tol, cs.u_max_iter);
@@ -535,24 +548,24 @@ struct Fv {
         return it;
     }
     // Jacobi sweeps on (diag, an) for a 3-component field X (updated in place), lduMatrix-style L1 residual control per component
-    int solve_vec3(vec& X, const vec& b, double tol, double rel_tol, int max_iter) {
+    int solve_vec3(vec& X, const vec& b, real tol, real rel_tol, int max_iter) {
         vec x = X, xn(3 * (size_t)Nc), Ax(3 * (size_t)Nc);
         auto apply = [&](const vec& v, vec& out) {
 #pragma omp parallel for num_threads(threads) collapse(2)
             for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
                 const int c = cid(i, j, k);
-                double acc[3];
+                real acc[3];
                 for (int q = 0; q < 3; ++q) acc[q] = dgc(c, q) * v[3 * (size_t)c + q];      // (fvMatrix::solveSegregated: addBoundaryDiag per component)
                 for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) if (!onb(d, s, i, j, k)) {
-                    const int nb = c + (s ? stride[d] : -stride[d]); const double a = an[2 * d + s][c];
+                    const int nb = c + (s ? stride[d] : -stride[d]); const real a = an[2 * d + s][c];
                     for (int q = 0; q < 3; ++q) acc[q] += a * v[3 * (size_t)nb + q];
                 }
                 for (int q = 0; q < 3; ++q) out[3 * (size_t)c + q] = acc[q];
             }
         };
-        double norm[3], res0[3] = {0, 0, 0};
+        real norm[3], res0[3] = {0, 0, 0};
         {
-            double xbar[3] = {0, 0, 0};
+            real xbar[3] = {0, 0, 0};
             for (int c = 0; c < Nc; ++c) for (int q = 0; q < 3; ++q) xbar[q] += x[3 * (size_t)c + q];
             for (int q = 0; q < 3; ++q) xbar[q] /= Nc;
             apply(x, Ax);
@@ -566,19 +579,19 @@ struct Fv {
             }
             for (int q = 0; q < 3; ++q) { norm[q] += 1e-20; res0[q] /= norm[q]; }
         }
-        auto conv = [&](const double* r) {
+        auto conv = [&](const real* r) {
             for (int q = 0; q < 3; ++q) if (!(r[q] < tol || (rel_tol > 0 && r[q] < rel_tol * res0[q]))) return false;
             return true;
         };
         int it = 0;
-        double res[3] = {res0[0], res0[1], res0[2]};
+        real res[3] = {res0[0], res0[1], res0[2]};
         while (!conv(res) && it < max_iter) {
 #pragma omp parallel for num_threads(threads) collapse(2)
             for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
                 const int c = cid(i, j, k);
-                double acc[3] = {b[3 * (size_t)c], b[3 * (size_t)c + 1], b[3 * (size_t)c + 2]};
+                real acc[3] = {b[3 * (size_t)c], b[3 * (size_t)c + 1], b[3 * (size_t)c + 2]};
                 for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) if (!onb(d, s, i, j, k)) {
-                    const int nb = c + (s ? stride[d] : -stride[d]); const double a = an[2 * d + s][c];
+                    const int nb = c + (s ? stride[d] : -stride[d]); const real a = an[2 * d + s][c];
                     for (int q = 0; q < 3; ++q) acc[q] -= a * x[3 * (size_t)nb + q];
                 }
                 for (int q = 0; q < 3; ++q) xn[3 * (size_t)c + q] = acc[q] / dgc(c, q);
@@ -599,15 +612,15 @@ struct Fv {
 #pragma omp parallel for num_threads(threads) collapse(2)
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            double acc[3] = {src[3 * (size_t)c], src[3 * (size_t)c + 1], src[3 * (size_t)c + 2]};
+            real acc[3] = {src[3 * (size_t)c], src[3 * (size_t)c + 1], src[3 * (size_t)c + 2]};
             for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) if (!onb(d, s, i, j, k)) {
-                const int nb = c + (s ? stride[d] : -stride[d]); const double a = an[2 * d + s][c];
+                const int nb = c + (s ? stride[d] : -stride[d]); const real a = an[2 * d + s][c];
                 for (int q = 0; q < 3; ++q) acc[q] -= a * U[3 * (size_t)nb + q];
             }
             if (!bdiag.empty()) {
                 // fvMatrix::H(): per component (component-averaged boundary diagonal - that component's boundary diagonal) * psi -- what
                 // A() holds too much or too little of for this component goes to H
-                const double bav = (bdiag[3 * (size_t)c] + bdiag[3 * (size_t)c + 1] + bdiag[3 * (size_t)c + 2]) / 3.0;
+                const real bav = (bdiag[3 * (size_t)c] + bdiag[3 * (size_t)c + 1] + bdiag[3 * (size_t)c + 2]) / 3.0;
                 for (int q = 0; q < 3; ++q) acc[q] += (bav - bdiag[3 * (size_t)c + q]) * U[3 * (size_t)c + q];
             }
             for (int q = 0; q < 3; ++q) HbyA[3 * (size_t)c + q] = rAU[c] * (acc[q] / vol(i, j, k));
@@ -632,8 +645,8 @@ struct Fv {
             for (int k = 0; k < nz + (d == 2); ++k) for (int j = 0; j < ny + (d == 1); ++j) for (int i = 0; i < nx + (d == 0); ++i) {
                 const int q = d == 0 ? i : d == 1 ? j : k;
                 const int f = fid(d, i, j, k);
-                double fl = 0.0;
-                const double Afc = area(d, i, j, k);
+                real fl = 0.0;
+                const real Afc = area(d, i, j, k);
                 if (q != 0 && q != n[d]) { const int c = cid(i, j, k), cm = c - stride[d]; fl = lerp(d, q, rAU[cm] * uSource[3 * (size_t)cm + d], rAU[c] * uSource[3 * (size_t)c + d]) * Afc; }
                 phiForces[d][f] = fl + rAUf[d][f] * (cs.g[d] * Afc);
             }
@@ -643,21 +656,21 @@ struct Fv {
     bool adjust_phi_failed = false;
     void compute_phiHbyA() {
         flux_of(HbyA, phiHbyA);
-        const double rDt = 1.0 / cs.dt;
+        const real rDt = 1.0 / cs.dt;
         for (int d = 0; d < 3; ++d)
             for (int k = 0; k < nz + (d == 2); ++k) for (int j = 0; j < ny + (d == 1); ++j) for (int i = 0; i < nx + (d == 0); ++i) {
                 const int q = d == 0 ? i : d == 1 ? j : k;
                 const int f = fid(d, i, j, k);
-                double uf;   // (Sf & U.oldTime()_f)
+                real uf;   // (Sf & U.oldTime()_f)
                 bool fixes = false;
-                const double Afc = area(d, i, j, k);
-                if (q == 0) { const int patch = 2 * d; fixes = cs.u_bc[patch] == 0; double b[3]; Ub(Uold, cid(i, j, k), patch, b); uf = b[d] * Afc; }
-                else if (q == n[d]) { const int patch = 2 * d + 1; fixes = cs.u_bc[patch] == 0; double b[3]; Ub(Uold, cid(i - (d == 0), j - (d == 1), k - (d == 2)), patch, b); uf = b[d] * Afc; }
+                const real Afc = area(d, i, j, k);
+                if (q == 0) { const int patch = 2 * d; fixes = cs.u_bc[patch] == 0; real b[3]; Ub(Uold, cid(i, j, k), patch, b); uf = b[d] * Afc; }
+                else if (q == n[d]) { const int patch = 2 * d + 1; fixes = cs.u_bc[patch] == 0; real b[3]; Ub(Uold, cid(i - (d == 0), j - (d == 1), k - (d == 2)), patch, b); uf = b[d] * Afc; }
                 else { const int c = cid(i, j, k); uf = lerp(d, q, Uold[3 * (size_t)(c - stride[d]) + d], Uold[3 * (size_t)c + d]) * Afc; }
-                const double phiCorr = phiOld[d][f] - uf;
+                const real phiCorr = phiOld[d][f] - uf;
                 // EulerDdtScheme::fvcDdtPhiCoeff: 1 - min(|phiCorr| / (|phi| + small), 1); 0 where U fixes the value
-                double coef = fixes ? 0.0 : 1.0 - std::min(std::fabs(phiCorr) / (std::fabs(phiOld[d][f]) + SMALL), 1.0);
-                double add = rAUf[d][f] * (coef * rDt * phiCorr);
+                real coef = fixes ? 0.0 : 1.0 - rmin(std::fabs(phiCorr) / (std::fabs(phiOld[d][f]) + SMALL), 1.0);
+                real add = rAUf[d][f] * (coef * rDt * phiCorr);
                 if (pimple) add *= alphaf[d][f];
                 phiHbyA[d][f] += add;
                 if (pimple) phiHbyA[d][f] += phiForces[d][f];
@@ -667,21 +680,21 @@ struct Fv {
         bool need_ref = true;
         for (int q = 0; q < 6; ++q) if (cs.p_bc[q] == 1) need_ref = false;
         if (need_ref) {
-            double massIn = 0, fixedOut = 0, adjOut = 0, total = VSMALL;
+            real massIn = 0, fixedOut = 0, adjOut = 0, total = VSMALL;
             for (int d = 0; d < 3; ++d)
                 for (int k = 0; k < nz + (d == 2); ++k) for (int j = 0; j < ny + (d == 1); ++j) for (int i = 0; i < nx + (d == 0); ++i) {
                     const int q = d == 0 ? i : d == 1 ? j : k;
                     const int f = fid(d, i, j, k);
-                    const double fl = phiHbyA[d][f] - (pimple ? phiForces[d][f] : 0.0);
+                    const real fl = phiHbyA[d][f] - (pimple ? phiForces[d][f] : 0.0);
                     if (q == 0 || q == n[d]) {
                         const int s = q == 0 ? 0 : 1;
-                        const double outw = s ? fl : -fl;
+                        const real outw = s ? fl : -fl;
                         if (outw < 0.0) massIn -= outw;
                         else if (cs.u_bc[2 * d + s] == 0) fixedOut += outw;
                         else adjOut += outw;
                     } else total += std::fabs(fl);
                 }
-            double massCorr = 1.0;
+            real massCorr = 1.0;
             if (std::fabs(adjOut) > VSMALL && std::fabs(adjOut) / total > SMALL) massCorr = (massIn - fixedOut) / adjOut;
             else if (std::fabs(fixedOut - massIn) / total > 1e-8) adjust_phi_failed = true;
             if (massCorr != 1.0)
@@ -693,8 +706,8 @@ struct Fv {
                         int i, j, k;
                         if (d == 0) { i = q; j = b1; k = b2; } else if (d == 1) { i = b1; j = q; k = b2; } else { i = b1; j = b2; k = q; }
                         const int f = fid(d, i, j, k);
-                        const double pf = pimple ? phiForces[d][f] : 0.0;
-                        const double fl = phiHbyA[d][f] - pf;
+                        const real pf = pimple ? phiForces[d][f] : 0.0;
+                        const real fl = phiHbyA[d][f] - pf;
                         if ((s ? fl : -fl) > 0.0) phiHbyA[d][f] = fl * massCorr + pf;
                     }
                 }
@@ -711,9 +724,9 @@ struct Fv {
                 if (d == 0) { i = q; j = b1; k = b2; } else if (d == 1) { i = b1; j = q; k = b2; } else { i = b1; j = b2; k = q; }
                 const int f = fid(d, i, j, k);
                 const int c = cid(i - (d == 0 && s), j - (d == 1 && s), k - (d == 2 && s));
-                double ub[3]; Ub(U, c, patch, ub);
-                const double Afc = area(d, i, j, k);
-                const double target = ub[d] * Afc;
+                real ub[3]; Ub(U, c, patch, ub);
+                const real Afc = area(d, i, j, k);
+                const real target = ub[d] * Afc;
                 psn[d][f] = (phiHbyA[d][f] - target) / (rAUf[d][f] * Afc);    // d p / d axis at the face
             }
         }
@@ -724,20 +737,20 @@ struct Fv {
 #pragma omp parallel for num_threads(threads) collapse(2)
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            double dg = 0.0, rhs = 0.0;
+            real dg = 0.0, rhs = 0.0;
             for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) {
                 const int f = cface(d, s, i, j, k);
-                const double af = pimple ? alphaf[d][f] : 1.0;
-                double ph = (s ? 1.0 : -1.0) * af * phiHbyA[d][f];
+                const real af = pimple ? alphaf[d][f] : 1.0;
+                real ph = (s ? 1.0 : -1.0) * af * phiHbyA[d][f];
                 if (onb(d, s, i, j, k) && cs.p_bc[2 * d + s] == 2)           // fixed-gradient source of the laplacian
                     ph = (s ? 1.0 : -1.0) * af * (phiHbyA[d][f] - rAUf[d][f] * area(d, i, j, k) * psn[d][f]);
                 rhs -= ph;
                 if (onb(d, s, i, j, k)) {
                     const int patch = 2 * d + s;
-                    if (cs.p_bc[patch] == 1) { const double gb = bfac() * af * rAUf[d][f] * sfd(d, s, i, j, k); dg += gb; rhs += gb * cs.p_value[patch]; }
+                    if (cs.p_bc[patch] == 1) { const real gb = bfac() * af * rAUf[d][f] * sfd(d, s, i, j, k); dg += gb; rhs += gb * cs.p_value[patch]; }
                     if (s) (d == 0 ? L.ux : d == 1 ? L.uy : L.uz)[c] = 0.0;
                 } else {
-                    const double g = af * rAUf[d][f] * sfd(d, s, i, j, k);
+                    const real g = af * rAUf[d][f] * sfd(d, s, i, j, k);
                     dg += g;
                     if (s) (d == 0 ? L.ux : d == 1 ? L.uy : L.uz)[c] = g;
                 }
@@ -757,7 +770,7 @@ struct Fv {
 #pragma omp parallel for num_threads(threads) collapse(2)
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = i + nx * (j + ny * k);
-            double a = L.diag[c] * x[c];
+            real a = L.diag[c] * x[c];
             if (i > 0) a -= L.ux[c - sx] * x[c - sx];
             if (i < nx - 1) a -= L.ux[c] * x[c + sx];
             if (j > 0) a -= L.uy[c - sy] * x[c - sy];
@@ -821,7 +834,7 @@ struct Fv {
         M.assign((size_t)N * N, 0.0);
         for (int k = 0; k < L.nz; ++k) for (int j = 0; j < L.ny; ++j) for (int i = 0; i < L.nx; ++i) {      // the rows of apply()
             const int c = i + L.nx * (j + L.ny * k);
-            double* row = &M[(size_t)c * N];
+            real* row = &M[(size_t)c * N];
             row[c] = L.diag[c];
             if (i > 0) row[c - 1] = -L.ux[c - 1];
             if (i < L.nx - 1) row[c + 1] = -L.ux[c];
@@ -832,12 +845,12 @@ struct Fv {
         }
         vec colp(N), rowp(N);
         for (int p = 0; p < N; ++p) {
-            const double piv = M[(size_t)p * N + p];
+            const real piv = M[(size_t)p * N + p];
             if (!(piv > 0.0) || !(piv < 1e300)) return;
-            const double ip = 1.0 / piv;
+            const real ip = 1.0 / piv;
             for (int q = 0; q < N; ++q) { colp[q] = M[(size_t)q * N + p]; rowp[q] = M[(size_t)p * N + q]; }
             for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) {
-                double v;
+                real v;
                 if (i == p) v = (j == p) ? ip : rowp[j] * ip;
                 else if (j == p) v = -colp[i] * ip;
                 else v = M[(size_t)i * N + j] - colp[i] * (rowp[j] * ip);
@@ -852,10 +865,10 @@ struct Fv {
     // 1 / (7/6 -+ (5/6) cos(pi/4)): the pair damps that band by 0.34 where two sweeps at the fixed weight 0.8 reach 0.54, for the same
     // work.  Pre-smoothing applies (kMgWa, kMgWb), post-smoothing the reverse order (the adjoint; the V-cycle stays a symmetric
     // positive definite preconditioner).  The kMgCoarseSweeps (120) sweeps of the coarsest level keep the fixed weight.  Same constants as the product.
-    static constexpr double kMgWa = 1.7318685872766142, kMgWb = 0.5695012757370842;
+    static constexpr real kMgWa = 1.7318685872766142, kMgWb = 0.5695012757370842;
     static void jacobi(const MgLevel& L, vec& x, const vec& b, vec& tmp, int sweeps, bool zero_guess, int threads) {
         for (int s = 0; s < sweeps; ++s) {
-            double w = 0.8;
+            real w = 0.8;
             if (sweeps == 2) w = zero_guess ? (s == 0 ? kMgWa : kMgWb) : (s == 0 ? kMgWb : kMgWa);
             if (s == 0 && zero_guess) { for (int c = 0; c < L.N; ++c) x[c] = w * b[c] / L.diag[c]; continue; }
             apply(L, x, tmp, threads);
@@ -868,7 +881,7 @@ struct Fv {
         if (l + 1 == mg.size()) {
             if (coarse_inv_ok) {
                 for (int r = 0; r < L.N; ++r) {
-                    double acc = 0.0;
+                    real acc = 0.0;
                     for (int c = 0; c < L.N; ++c) acc += coarse_inv[(size_t)r * L.N + c] * L.b[c];
                     L.x[r] = acc;
                 }
@@ -900,28 +913,28 @@ struct Fv {
     // OpenFOAM PCG.C, with lduMatrix::solver normFactor; returns iterations
     int solve_pressure(bool final_iter) {
         MgLevel& L = mg[0];
-        const double tol = final_iter ? cs.p_final_tol : cs.p_tol, rel = final_iter ? cs.p_final_rel_tol : cs.p_rel_tol;
+        const real tol = final_iter ? cs.p_final_tol : cs.p_tol, rel = final_iter ? cs.p_final_rel_tol : cs.p_rel_tol;
         vec& wA = pw; vec& rA = pr; vec& pA = pp; vec& zA = pz;
         apply(L, p, wA, threads);
-        double xbar = 0; for (int c = 0; c < Nc; ++c) xbar += p[c]; xbar /= Nc;
+        real xbar = 0; for (int c = 0; c < Nc; ++c) xbar += p[c]; xbar /= Nc;
         { vec ones(Nc, xbar); apply(L, ones, pA, threads); }
-        double norm = 0, res = 0;
+        real norm = 0, res = 0;
         for (int c = 0; c < Nc; ++c) { norm += std::fabs(wA[c] - pA[c]) + std::fabs(pb[c] - pA[c]); rA[c] = pb[c] - wA[c]; res += std::fabs(rA[c]); }
         norm += 1e-20; res /= norm;
-        const double res0 = res;
+        const real res0 = res;
         st.p_initial_residual = res0;
         int it = 0;
-        double wArAold = 1.0;
-        auto converged = [&](double r) { return r < tol || (rel > 0 && r < rel * res0); };
+        real wArAold = 1.0;
+        auto converged = [&](real r) { return r < tol || (rel > 0 && r < rel * res0); };
         if (!converged(res)) {
             do {
                 precondition(rA, zA);
-                double wArA = 0; for (int c = 0; c < Nc; ++c) wArA += zA[c] * rA[c];
+                real wArA = 0; for (int c = 0; c < Nc; ++c) wArA += zA[c] * rA[c];
                 if (it == 0) for (int c = 0; c < Nc; ++c) pA[c] = zA[c];
-                else { const double beta = wArA / wArAold; for (int c = 0; c < Nc; ++c) pA[c] = zA[c] + beta * pA[c]; }
+                else { const real beta = wArA / wArAold; for (int c = 0; c < Nc; ++c) pA[c] = zA[c] + beta * pA[c]; }
                 apply(L, pA, wA, threads);
-                double wApA = 0; for (int c = 0; c < Nc; ++c) wApA += wA[c] * pA[c];
-                const double al = wArA / wApA;
+                real wApA = 0; for (int c = 0; c < Nc; ++c) wApA += wA[c] * pA[c];
+                const real al = wArA / wApA;
                 res = 0;
                 for (int c = 0; c < Nc; ++c) { p[c] += al * pA[c]; rA[c] -= al * wA[c]; res += std::fabs(rA[c]); }
                 res /= norm;
@@ -939,17 +952,17 @@ struct Fv {
             for (int k = 0; k < nz + (d == 2); ++k) for (int j = 0; j < ny + (d == 1); ++j) for (int i = 0; i < nx + (d == 0); ++i) {
                 const int q = d == 0 ? i : d == 1 ? j : k;
                 const int f = fid(d, i, j, k);
-                const double af = pimple ? alphaf[d][f] : 1.0;
-                double fl = 0.0;
+                const real af = pimple ? alphaf[d][f] : 1.0;
+                real fl = 0.0;
                 if (q == 0 || q == n[d]) {
                     const int s = q == 0 ? 0 : 1, patch = 2 * d + s;
                     const int c = cid(i - (d == 0 && s), j - (d == 1 && s), k - (d == 2 && s));
-                    const double geo = graded ? area(d, i, j, k) / delta(d, q) : dx;
-                    if (cs.p_bc[patch] == 1) { const double gb = bfac() * af * rAUf[d][f] * geo; fl = s ? gb * (cs.p_value[patch] - p[c]) : gb * (p[c] - cs.p_value[patch]); }
+                    const real geo = graded ? area(d, i, j, k) / delta(d, q) : dx;
+                    if (cs.p_bc[patch] == 1) { const real gb = bfac() * af * rAUf[d][f] * geo; fl = s ? gb * (cs.p_value[patch] - p[c]) : gb * (p[c] - cs.p_value[patch]); }
                     else if (cs.p_bc[patch] == 2) fl = af * rAUf[d][f] * area(d, i, j, k) * psn[d][f];
                 } else {
                     const int c = cid(i, j, k);
-                    const double geo = graded ? area(d, i, j, k) / delta(d, q) : dx;
+                    const real geo = graded ? area(d, i, j, k) / delta(d, q) : dx;
                     fl = af * rAUf[d][f] * geo * (p[c] - p[c - stride[d]]);
                 }
                 pflux[d][f] = fl;
@@ -957,24 +970,24 @@ struct Fv {
     }
 
     void continuity_errors() {
-        double sl = 0, gl = 0;
+        real sl = 0, gl = 0;
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            double dv = 0;
+            real dv = 0;
             for (int d = 0; d < 3; ++d) for (int s = 0; s < 2; ++s) { const int f = cface(d, s, i, j, k); dv += (s ? 1.0 : -1.0) * (pimple ? alphaf[d][f] : 1.0) * phi[d][f]; }
-            const double Vc = vol(i, j, k);
-            double ce = dv / Vc;
+            const real Vc = vol(i, j, k);
+            real ce = dv / Vc;
             if (pimple) ce += (alpha[c] - alphaOld[c]) / cs.dt;
             sl += std::fabs(ce) * Vc; gl += ce * Vc;
         }
-        const double tv = graded ? total_volume : V * Nc;
+        const real tv = graded ? total_volume : V * Nc;
         st.cont_sum_local = cs.dt * sl / tv; st.cont_global = cs.dt * gl / tv;
         cumulativeContErr += st.cont_global; st.cont_cumulative = cumulativeContErr;
     }
 
     // fvc::reconstruct(s_f) on the uniform block: per axis (s_{f+} + s_{f-}) / (2 |Sf|)
     // ---- one PISO/PIMPLE corrector (icoFoamYade.C:97-140 / pEqn.H) -------------------------------------------
-    double p_relax_now = 0.0;
+    real p_relax_now = 0.0;
     void corrector(bool final_inner) {
         compute_HbyA();
         if (!pimple) interp_rAU();
@@ -1002,7 +1015,7 @@ struct Fv {
             for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
                 const int c = cid(i, j, k);
                 for (int d = 0; d < 3; ++d) {
-                    double sm = 0;
+                    real sm = 0;
                     for (int s = 0; s < 2; ++s) { const int f = cface(d, s, i, j, k); sm += (phiForces[d][f] - pflux[d][f] / alphaf[d][f]) / rAUf[d][f]; }
                     U[3 * (size_t)c + d] = HbyA[3 * (size_t)c + d] + rAU[c] * (sm / (2.0 * area(d, i, j, k)));
                 }
@@ -1015,9 +1028,9 @@ struct Fv {
         st = orc_fv_stats{}; st.cont_cumulative = cumulativeContErr;
         courant();                                                           // icoFoamYade.C:68, pimpleFoamYade.C:63
         if (cs.adjust_time_step) {                                           // setDeltaT.H [OF-6], pimpleFoamYade.C:64
-            const double maxDeltaTFact = cs.max_co / (st.courant_max + SMALL);
-            const double deltaTFact = std::min(std::min(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
-            cs.dt = std::min(deltaTFact * cs.dt, cs.max_delta_t);
+            const real maxDeltaTFact = cs.max_co / (st.courant_max + SMALL);
+            const real deltaTFact = rmin(rmin(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
+            cs.dt = rmin(deltaTFact * cs.dt, cs.max_delta_t);
         }
         st.delta_t = cs.dt;
         // runTime++ : old-time fields (U.oldTime(), phi.oldTime(), alphac.oldTime())
@@ -1050,12 +1063,12 @@ struct Fv {
                     for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
                         const int c = cid(i, j, k);
                         for (int d = 0; d < 3; ++d) {
-                            double sm = 0;
+                            real sm = 0;
                             for (int s = 0; s < 2; ++s) {
                                 const int f = cface(d, s, i, j, k);
-                                double sng;   // snGrad(p) along +axis
-                                const double dl = delta(d, fq(d, s, i, j, k));
-                                if (onb(d, s, i, j, k)) { const double pbd = pbv(c, d, s, f); sng = s ? (pbd - p[c]) / dl : (p[c] - pbd) / dl; }
+                                real sng;   // snGrad(p) along +axis
+                                const real dl = delta(d, fq(d, s, i, j, k));
+                                if (onb(d, s, i, j, k)) { const real pbd = pbv(c, d, s, f); sng = s ? (pbd - p[c]) / dl : (p[c] - pbd) / dl; }
                                 else sng = s ? (p[c + stride[d]] - p[c]) / dl : (p[c] - p[c - stride[d]]) / dl;
                                 sm += phiForces[d][f] / rAUf[d][f] - sng * area(d, i, j, k);
                             }
@@ -1080,94 +1093,94 @@ struct Fv {
     // [OF-6 fvm::SuSp: diag += V max(susp, 0), source -= V min(susp, 0) psi; fvMatrix == volField: source += V field;
     //  bound.C: X = max(max(X, fvc::average(max(X, XMin)) pos0(-X)), XMin)].  alpha.oldTime() == alpha (quirk F-Q1).
     void turb_eqn(int mode) {
-        const double nu = cs.nu, dt = cs.dt, xMin = 1e-15;
-        const double sigma = mode == 0 ? 1.0 : mode == 1 ? cs.ras_sigmaeps : cs.ras_sigmak;
+        const real nu = cs.nu, dt = cs.dt, xMin = 1e-15;
+        const real sigma = mode == 0 ? 1.0 : mode == 1 ? cs.ras_sigmaeps : cs.ras_sigmak;
         int bcv[6];
         for (int q = 0; q < 6; ++q) bcv[q] = mode == 1 ? (cs.eps_bc[q] == 2 ? 0 : cs.eps_bc[q]) : cs.k_bc[q];      // an epsilonWallFunction patch is never asked for a face value: the wall cells are imposed
         const int* bc = bcv;
         auto wallp = [&](int patch) { return mode != 0 && cs.eps_bc[patch] == 2; };
         auto wall_count = [&](int i, int j, int k) { int w = 0; for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) if (wallp(2 * d + sd) && onb(d, sd, i, j, k)) ++w; return w; };
-        const double cmu75 = std::pow(cs.ras_cmu, 0.75), cmu25 = std::pow(cs.ras_cmu, 0.25);
+        const real cmu75 = std::pow(cs.ras_cmu, 0.75), cmu25 = std::pow(cs.ras_cmu, 0.25);
         // the value epsilonWallFunction imposes on a cell with wall faces: the average over them of Cmu^3/4 k^3/2 / (kappa y_w)
         auto wall_eps = [&](int c, int i, int j, int k) {
             if (!graded) return cmu75 * std::pow(kturb[c], 1.5) / (cs.wf_kappa * ywall_of(0, c));
-            double sum = 0.0; int W = 0;
+            real sum = 0.0; int W = 0;
             for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) if (wallp(2 * d + sd) && onb(d, sd, i, j, k)) { sum += cmu75 * std::pow(kturb[c], 1.5) / (cs.wf_kappa * ywall_of(d, c)); ++W; }
-            return sum / (double)W;
+            return sum / (real)W;
         };
         const double* bval = mode == 1 ? cs.eps_value : cs.k_value;
         const int scheme = mode == 1 ? cs.eps_convection_scheme : cs.k_convection_scheme;
-        const double relax = mode == 1 ? cs.eps_relax : cs.k_relax;
+        const real relax = mode == 1 ? cs.eps_relax : cs.k_relax;
         vec& Xf = mode == 1 ? epsturb : kturb;
         vec b3(3 * (size_t)Nc, 0.0), x3(3 * (size_t)Nc, 0.0);
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            const double aP = alpha[c], xc = Xf[c], nutc = nut[c];
-            const double V = vol(i, j, k), delta = les_delta(c);
-            double dg = aP * V / dt, s = aP * V * xc / dt, sumPhi = 0.0;
+            const real aP = alpha[c], xc = Xf[c], nutc = nut[c];
+            const real V = vol(i, j, k), delta = les_delta(c);
+            real dg = aP * V / dt, s = aP * V * xc / dt, sumPhi = 0.0;
             for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) {
                 const int f = cface(d, sd, i, j, k);
-                const double af = alphaf[d][f];
-                const double pv = (sd ? 1.0 : -1.0) * phi[d][f];
-                const double phio = af * pv;
+                const real af = alphaf[d][f];
+                const real pv = (sd ? 1.0 : -1.0) * phi[d][f];
+                const real phio = af * pv;
                 sumPhi += pv;
                 if (onb(d, sd, i, j, k)) {
                     an[2 * d + sd][c] = 0.0;
                     const int patch = 2 * d + sd;
-                    const double nb = nut_boundary(patch, c);
-                    const double gam = (af * (nu + nb / sigma)) * sfd(d, sd, i, j, k);
-                    if (bc[patch] == 1) { const double gb = bfac() * gam; dg += gb; s += (-phio + gb) * bval[patch]; }
+                    const real nb = nut_boundary(patch, c);
+                    const real gam = (af * (nu + nb / sigma)) * sfd(d, sd, i, j, k);
+                    if (bc[patch] == 1) { const real gb = bfac() * gam; dg += gb; s += (-phio + gb) * bval[patch]; }
                     else dg += phio;
                 } else {
                     const int nbc = c + (sd ? stride[d] : -stride[d]);
                     const int qc = d == 0 ? i : d == 1 ? j : k;
-                    const double gam = lerp_side(d, sd, qc, aP * (nu + nutc / sigma), alpha[nbc] * (nu + nut[nbc] / sigma)) * sfd(d, sd, i, j, k);
+                    const real gam = lerp_side(d, sd, qc, aP * (nu + nutc / sigma), alpha[nbc] * (nu + nut[nbc] / sigma)) * sfd(d, sd, i, j, k);
                     const bool up = scheme != 0;
-                    const double wP = !graded ? 0.5 : (sd ? wlow(d, qc + 1) : 1.0 - wlow(d, qc));
-                    const double cP = up ? std::max(phio, 0.0) : wP * phio, cN = up ? std::min(phio, 0.0) : (!graded ? 0.5 * phio : (1.0 - wP) * phio);
+                    const real wP = !graded ? 0.5 : (sd ? wlow(d, qc + 1) : 1.0 - wlow(d, qc));
+                    const real cP = up ? rmax(phio, 0.0) : wP * phio, cN = up ? rmin(phio, 0.0) : (!graded ? 0.5 * phio : (1.0 - wP) * phio);
                     dg += cP + gam;
                     an[2 * d + sd][c] = cN - gam;
                 }
             }
-            const double* T = &vGrad[9 * (size_t)c];
-            const double tr2 = 2.0 * (T[0] + T[4] + T[8]);
-            double GG = 0.0;
+            const real* T = &vGrad[9 * (size_t)c];
+            const real tr2 = 2.0 * (T[0] + T[4] + T[8]);
+            real GG = 0.0;
             for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) GG += T[3 * a + b] * ((T[3 * a + b] + T[3 * b + a]) - (a == b ? (1.0 / 3.0) * tr2 : 0.0));
-            double G = nutc * GG;
+            real G = nutc * GG;
             // epsilonWallFunction [OF-6 epsilonWallFunctionFvPatchScalarField::calculate / updateCoeffs]: in the wall cells
             //   G = sum_f w (nut_w + nu_w) |snGrad U_w| Cmu^0.25 sqrt(k)/(kappa y),  eps = sum_f w Cmu^0.75 k^1.5/(kappa y),  w = 1/(wall faces of the cell)
             const int Wc = wall_count(i, j, k);
             if (Wc) {
-                double Gw = 0.0;
+                real Gw = 0.0;
                 for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) if (wallp(2 * d + sd) && onb(d, sd, i, j, k)) {
                     const int patch = 2 * d + sd;
-                    double ub[3]; Ub(U, c, patch, ub);
-                    const double ywall = ywall_of(d, c);
-                    const double d0 = (ub[0] - U[3 * (size_t)c]) / ywall, d1 = (ub[1] - U[3 * (size_t)c + 1]) / ywall, d2 = (ub[2] - U[3 * (size_t)c + 2]) / ywall;
+                    real ub[3]; Ub(U, c, patch, ub);
+                    const real ywall = ywall_of(d, c);
+                    const real d0 = (ub[0] - U[3 * (size_t)c]) / ywall, d1 = (ub[1] - U[3 * (size_t)c + 1]) / ywall, d2 = (ub[2] - U[3 * (size_t)c + 2]) / ywall;
                     Gw += (nut_boundary(patch, c) + nu) * std::sqrt(d0 * d0 + d1 * d1 + d2 * d2) * cmu25 * std::sqrt(kturb[c]) / (cs.wf_kappa * ywall);
                 }
-                G = Gw / (double)Wc;
+                G = Gw / (real)Wc;
             }
-            const double divU = sumPhi / V;
-            double Su, c1, c2;
+            const real divU = sumPhi / V;
+            real Su, c1, c2;
             if (mode == 0) { Su = aP * G; c1 = (2.0 / 3.0) * aP * divU; c2 = cs.les_ce * aP * std::sqrt(xc) / delta; }
-            else if (mode == 1) { const double kc = kturb[c]; Su = cs.ras_c1 * aP * G * xc / kc; c1 = ((2.0 / 3.0) * cs.ras_c1 - cs.ras_c3) * aP * divU; c2 = cs.ras_c2 * aP * xc / kc; }
+            else if (mode == 1) { const real kc = kturb[c]; Su = cs.ras_c1 * aP * G * xc / kc; c1 = ((2.0 / 3.0) * cs.ras_c1 - cs.ras_c3) * aP * divU; c2 = cs.ras_c2 * aP * xc / kc; }
             else { Su = aP * G; c1 = (2.0 / 3.0) * aP * divU; c2 = aP * epsturb[c] / xc; }
-            dg += V * (std::max(c1, 0.0) + c2);
-            s += V * Su - V * std::min(c1, 0.0) * xc;
+            dg += V * (rmax(c1, 0.0) + c2);
+            s += V * Su - V * rmin(c1, 0.0) * xc;
             if (relax > 0) {
-                double so = 0.0;
+                real so = 0.0;
                 for (int q = 0; q < 6; ++q) so += std::fabs(an[q][c]);
-                const double dn = std::max(std::fabs(dg), so) / relax;
+                const real dn = rmax(std::fabs(dg), so) / relax;
                 s += (dn - dg) * xc;
                 dg = dn;
             }
-            double x0 = xc;
+            real x0 = xc;
             if (mode == 1) {
                 // epsEqn.boundaryManipulate -> fvMatrix::setValues(faceCells, value) [OF-6 fvMatrix.C setValuesFromList]: the wall cell's row becomes
                 // diag x = diag value, its neighbours' coefficients towards it move to their sources
                 if (Wc) {
-                    const double v = wall_eps(c, i, j, k);
+                    const real v = wall_eps(c, i, j, k);
                     for (int q = 0; q < 6; ++q) an[q][c] = 0.0;
                     s = dg * v; x0 = v;
                 } else {
@@ -1189,20 +1202,20 @@ struct Fv {
         vec xn(Nc);
         for (int k = 0; k < nz; ++k) for (int j = 0; j < ny; ++j) for (int i = 0; i < nx; ++i) {
             const int c = cid(i, j, k);
-            const double xc = x3[3 * (size_t)c];
-            double xb = xc;
+            const real xc = x3[3 * (size_t)c];
+            real xb = xc;
             if (!(xc > 0.0)) {
-                const double mP = std::max(xc, xMin);
-                double av = 0.0, asum = 0.0;                      // fvc::average: sum |Sf| x_f / sum |Sf| (six equal faces on the uniform block)
+                const real mP = rmax(xc, xMin);
+                real av = 0.0, asum = 0.0;                      // fvc::average: sum |Sf| x_f / sum |Sf| (six equal faces on the uniform block)
                 for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) {
-                    double xf;
-                    if (onb(d, sd, i, j, k)) { const int patch = 2 * d + sd; xf = std::max(bc[patch] == 1 ? bval[patch] : xc, xMin); }
-                    else { const int nbc = c + (sd ? stride[d] : -stride[d]); xf = lerp_side(d, sd, d == 0 ? i : d == 1 ? j : k, mP, std::max(x3[3 * (size_t)nbc], xMin)); }
+                    real xf;
+                    if (onb(d, sd, i, j, k)) { const int patch = 2 * d + sd; xf = rmax(bc[patch] == 1 ? bval[patch] : xc, xMin); }
+                    else { const int nbc = c + (sd ? stride[d] : -stride[d]); xf = lerp_side(d, sd, d == 0 ? i : d == 1 ? j : k, mP, rmax(x3[3 * (size_t)nbc], xMin)); }
                     if (graded) { av += area(d, i, j, k) * xf; asum += area(d, i, j, k); } else av += xf;
                 }
-                xb = std::max(xc, graded ? av / asum : av / 6.0);
+                xb = rmax(xc, graded ? av / asum : av / 6.0);
             }
-            xn[c] = std::max(xb, xMin);
+            xn[c] = rmax(xb, xMin);
         }
         Xf = xn;
         if (mode == 0) for (int c = 0; c < Nc; ++c) nut[c] = cs.les_ck * std::sqrt(kturb[c]) * les_delta(c);
@@ -1216,19 +1229,19 @@ struct Fv {
         grad_U(U, vGrad);
         if (cs.turbulence_model == 2) { turb_eqn(0); return; }
         if (cs.turbulence_model == 3) { turb_eqn(1); turb_eqn(2); return; }      // kEpsilon::correct(): epsilon first, then k with the new epsilon
-        const double Ck = cs.les_ck, Ce = cs.les_ce;
+        const real Ck = cs.les_ck, Ce = cs.les_ce;
         for (int c = 0; c < Nc; ++c) {
-            const double delta = les_delta(c);
-            const double* T = &vGrad[9 * (size_t)c];
-            double D[3][3];
+            const real delta = les_delta(c);
+            const real* T = &vGrad[9 * (size_t)c];
+            real D[3][3];
             for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) D[a][b] = 0.5 * (T[3 * a + b] + T[3 * b + a]);
-            const double trD = D[0][0] + D[1][1] + D[2][2];
-            const double a = Ce / delta, b = (2.0 / 3.0) * trD;
-            const double third = (1.0 / 3.0) * trD;
-            const double dd = (D[0][0] - third) * D[0][0] + (D[1][1] - third) * D[1][1] + (D[2][2] - third) * D[2][2]
+            const real trD = D[0][0] + D[1][1] + D[2][2];
+            const real a = Ce / delta, b = (2.0 / 3.0) * trD;
+            const real third = (1.0 / 3.0) * trD;
+            const real dd = (D[0][0] - third) * D[0][0] + (D[1][1] - third) * D[1][1] + (D[2][2] - third) * D[2][2]
                             + 2.0 * (D[0][1] * D[0][1]) + 2.0 * (D[0][2] * D[0][2]) + 2.0 * (D[1][2] * D[1][2]);
-            const double cc = 2.0 * Ck * delta * dd;
-            const double r = (-b + std::sqrt(b * b + 4.0 * a * cc)) / (2.0 * a);
+            const real cc = 2.0 * Ck * delta * dd;
+            const real r = (-b + std::sqrt(b * b + 4.0 * a * cc)) / (2.0 * a);
             nut[c] = Ck * delta * std::sqrt(r * r);
         }
     }
@@ -1239,7 +1252,9 @@ struct Fv {
 extern "C" {
 
 // the limiter function of an NVD / TVD scheme at gradient ratio r (tests: Sweby's region)
-double orc_fv_limiter(int scheme, double k, double r) { return Fv::limiter_fn(scheme, 2.0 / std::max(k, SMALL), r); }
+double orc_fv_limiter(int scheme, double k, double r) { return (double)Fv::limiter_fn(scheme, 2.0 / rmax(k, SMALL), r); }
+// mantissa bits of the arithmetic type: 53 in liboracle.so; 64 (x87 long double) is what the front-end demands of liboracle_ld.so
+int orc_fv_real_mant_dig() { return std::numeric_limits<real>::digits; }
 void* orc_fv_create(const orc_fv_case* c) {
     // a graded block carries the laminar operators with Gauss linear / upwind convection only (the closures' delta, wall distance and the
     // linearUpwind correction assume uniform cubes)
@@ -1277,42 +1292,53 @@ static vec* fv_field(Fv* f, const char* name) {
         {"p_uz", &f->mg[0].uz},
         {"mom_diag", &f->diag},
         {"mom_src", &f->src},
+        {"divG", &f->divG},
+        {"mom_an0", &f->an[0]}, {"mom_an1", &f->an[1]}, {"mom_an2", &f->an[2]}, {"mom_an3", &f->an[3]}, {"mom_an4", &f->an[4]}, {"mom_an5", &f->an[5]},
+        {"phiHbyA_x", &f->phiHbyA[0]}, {"phiHbyA_y", &f->phiHbyA[1]}, {"phiHbyA_z", &f->phiHbyA[2]},
     };
     for (const auto& e : tab) if (s == e.nm) return e.v;
     return nullptr;
 }
 int orc_fv_field_size(void* h, const char* name) { vec* v = fv_field((Fv*)h, name); return v ? (int)v->size() : -1; }
-int orc_fv_get(void* h, const char* name, double* out) { vec* v = fv_field((Fv*)h, name); if (!v) return 1; std::memcpy(out, v->data(), v->size() * sizeof(double)); return 0; }
+// (arrays cross the interface as doubles: converting loops, the identity in the double build)
+static void to_double(const vec& v, double* out) { for (size_t q = 0; q < v.size(); ++q) out[q] = (double)v[q]; }
+static void from_double(const double* in, vec& v) { for (size_t q = 0; q < v.size(); ++q) v[q] = in[q]; }
+int orc_fv_get(void* h, const char* name, double* out) { vec* v = fv_field((Fv*)h, name); if (!v) return 1; to_double(*v, out); return 0; }
 int orc_fv_set(void* h, const char* name, const double* in) {
     Fv* f = (Fv*)h; vec* v = fv_field(f, name); if (!v) return 1;
-    std::memcpy(v->data(), in, v->size() * sizeof(double));
+    from_double(in, *v);
     if (std::string(name) == "U") f->flux_of(f->U, f->phi);   // createPhi
     return 0;
 }
-double* orc_fv_ptr(void* h, const char* name) { vec* v = fv_field((Fv*)h, name); return v ? v->data() : nullptr; }
+// the oracle's own storage, for the particle oracle to work on in place: the double build only (null where the storage is not double)
+double* orc_fv_ptr(void* h, const char* name) {
+    vec* v = fv_field((Fv*)h, name);
+    if (!std::is_same<real, double>::value || !v) return nullptr;
+    return reinterpret_cast<double*>(v->data());
+}
 void orc_fv_step_begin(void* h) { ((Fv*)h)->step_begin(); }
 void orc_fv_step_end(void* h) { ((Fv*)h)->step_end(); }
 void orc_fv_get_stats(void* h, orc_fv_stats* out) { *out = ((Fv*)h)->st; }
 // A x = rhs with the oracle's pressure solver (pFinal tolerances) and the matrix of the last step; returns the iteration count
 int orc_fv_solve_p(void* h, const double* rhs, double* x) {
     Fv* f = (Fv*)h;
-    std::memcpy(f->pb.data(), rhs, (size_t)f->Nc * sizeof(double));
-    std::memcpy(f->p.data(), x, (size_t)f->Nc * sizeof(double));
+    from_double(rhs, f->pb);
+    from_double(x, f->p);
     const int it = f->solve_pressure(true);
-    std::memcpy(x, f->p.data(), (size_t)f->Nc * sizeof(double));
+    to_double(f->p, x);
     return it;
 }
 // z = M^-1 r with the preconditioner of the case's p_solver (one V-cycle, or r / diag) and the operators of the last step
 void orc_fv_precondition(void* h, const double* r, double* z) {
     Fv* f = (Fv*)h; vec rv(r, r + f->Nc), zv(f->Nc);
     f->precondition(rv, zv);
-    std::memcpy(z, zv.data(), zv.size() * sizeof(double));
+    to_double(zv, z);
 }
 // y = A x with the current pressure matrix (level 0)
 void orc_fv_apply_p(void* h, const double* x, double* y) {
     Fv* f = (Fv*)h; vec xv(x, x + f->Nc), yv(f->Nc);
     Fv::apply(f->mg[0], xv, yv, f->threads);
-    std::memcpy(y, yv.data(), yv.size() * sizeof(double));
+    to_double(yv, y);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
+LIB_PATH_LD = os.path.join(HERE, "liboracle_ld.so")      # fv_oracle.cpp alone, computing in long double (the reference of tests/test_fv_sweeps_*.py)
 MAXK = 16
 
 _dp = C.POINTER(C.c_double)
@@ -18,7 +19,7 @@ _ip = C.POINTER(C.c_int)
 
 
 def build(force=False):
-    """compile liboracle.so.  The reference driver (oracle/_ref/ref_driver: the reference's FoamYade.C / meshTree.C compiled against the stand-in OpenFOAM
+    """compile liboracle.so and liboracle_ld.so (the FV oracle in long double).  The reference driver (oracle/_ref/ref_driver: the reference's FoamYade.C / meshTree.C compiled against the stand-in OpenFOAM
     header oracle/shim/fvCFD.H) is NOT built here any more (round 6): this tier's rules do not admit a reference build against stand-in headers, so it is
     neither a pin nor a baseline.  The recipe stays (`make -C oracle ref`, FOAMYADE_BUILD_REF=1 here) as the provenance of the fixtures under tests/golden,
     which tests/golden/gen_golden.py produced with it in round 1 and which are regression data, not a pin (parity unpinned)."""
@@ -26,6 +27,9 @@ def build(force=False):
             os.path.getmtime(os.path.join(HERE, f)) > os.path.getmtime(LIB_PATH)
             for f in os.listdir(HERE) if f.endswith(".cpp") and f != "ref_driver.cpp"):
         subprocess.run(["make", "-C", HERE, "liboracle.so"], check=True, stdout=subprocess.DEVNULL)
+    src = os.path.join(HERE, "fv_oracle.cpp")
+    if force or not os.path.exists(LIB_PATH_LD) or os.path.getmtime(src) > os.path.getmtime(LIB_PATH_LD):
+        subprocess.run(["make", "-C", HERE, "liboracle_ld.so"], check=True, stdout=subprocess.DEVNULL)
     if os.environ.get("FOAMYADE_BUILD_REF") == "1" and os.path.isdir("/root/reference/FoamYade") and os.path.exists("/opt/conda/lib/libmpi.so"):
         subprocess.run(["make", "-C", HERE, "ref"], check=True, stdout=subprocess.DEVNULL)
 
@@ -323,30 +327,50 @@ def fv_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 0,
 
 
 _fv_ready = False
+_fv_wide = None
 
 
-def _fv_lib():
-    global _fv_ready
+def _fv_bind(L):
+    L.orc_fv_create.argtypes = [C.POINTER(FvCase)]
+    L.orc_fv_create.restype = C.c_void_p
+    L.orc_fv_destroy.argtypes = [C.c_void_p]
+    L.orc_fv_set_threads.argtypes = [C.c_void_p, C.c_int]
+    L.orc_fv_turbulence_correct.argtypes = [C.c_void_p]
+    L.orc_fv_field_size.argtypes = [C.c_void_p, C.c_char_p]
+    L.orc_fv_get.argtypes = [C.c_void_p, C.c_char_p, _dp]
+    L.orc_fv_set.argtypes = [C.c_void_p, C.c_char_p, _dp]
+    L.orc_fv_ptr.argtypes = [C.c_void_p, C.c_char_p]
+    L.orc_fv_ptr.restype = _dp
+    L.orc_fv_step_begin.argtypes = [C.c_void_p]
+    L.orc_fv_step_end.argtypes = [C.c_void_p]
+    L.orc_fv_get_stats.argtypes = [C.c_void_p, C.POINTER(FvStats)]
+    L.orc_fv_apply_p.argtypes = [C.c_void_p, _dp, _dp]
+    L.orc_fv_precondition.argtypes = [C.c_void_p, _dp, _dp]
+    L.orc_fv_precondition.restype = None
+    L.orc_fv_solve_p.argtypes = [C.c_void_p, _dp, _dp]
+    L.orc_fv_solve_p.restype = C.c_int
+    L.orc_fv_real_mant_dig.argtypes = []
+    L.orc_fv_real_mant_dig.restype = C.c_int
+    return L
+
+
+def _fv_lib(wide=False):
+    """the FV entry points of liboracle.so, or (wide) of liboracle_ld.so: the same source computing in long double behind the same double interface"""
+    global _fv_ready, _fv_wide
+    if wide:
+        if _fv_wide is None:
+            if not os.path.exists(LIB_PATH_LD):
+                build()
+            L = _fv_bind(C.CDLL(LIB_PATH_LD))
+            digits = L.orc_fv_real_mant_dig()
+            if digits != 64:
+                raise RuntimeError(f"oracle: liboracle_ld.so computes with a {digits}-bit mantissa; the reference needs the 64 bits of x87 long double")
+            _fv_wide = L
+        return _fv_wide
     L = lib()
     if not _fv_ready:
-        L.orc_fv_create.argtypes = [C.POINTER(FvCase)]
-        L.orc_fv_create.restype = C.c_void_p
-        L.orc_fv_destroy.argtypes = [C.c_void_p]
-        L.orc_fv_set_threads.argtypes = [C.c_void_p, C.c_int]
-        L.orc_fv_turbulence_correct.argtypes = [C.c_void_p]
-        L.orc_fv_field_size.argtypes = [C.c_void_p, C.c_char_p]
-        L.orc_fv_get.argtypes = [C.c_void_p, C.c_char_p, _dp]
-        L.orc_fv_set.argtypes = [C.c_void_p, C.c_char_p, _dp]
-        L.orc_fv_ptr.argtypes = [C.c_void_p, C.c_char_p]
-        L.orc_fv_ptr.restype = _dp
-        L.orc_fv_step_begin.argtypes = [C.c_void_p]
-        L.orc_fv_step_end.argtypes = [C.c_void_p]
-        L.orc_fv_get_stats.argtypes = [C.c_void_p, C.POINTER(FvStats)]
-        L.orc_fv_apply_p.argtypes = [C.c_void_p, _dp, _dp]
-        L.orc_fv_precondition.argtypes = [C.c_void_p, _dp, _dp]
-        L.orc_fv_precondition.restype = None
-        L.orc_fv_solve_p.argtypes = [C.c_void_p, _dp, _dp]
-        L.orc_fv_solve_p.restype = C.c_int
+        _fv_bind(L)
+        assert L.orc_fv_real_mant_dig() == 53
         _fv_ready = True
     return L
 
@@ -354,9 +378,11 @@ def _fv_lib():
 class FvSolver:
     """icoFoamYade / pimpleFoamYade time loop on the CPU (oracle).  step(records) = one pass of the loop body."""
 
-    def __init__(self, case: FvCase, threads=1):
+    def __init__(self, case: FvCase, threads=1, wide=False):
+        """wide: the long-double build (fields cross the interface as doubles; view() and step(records) are not available there)"""
         self.case = case
-        self.L = _fv_lib()
+        self.wide = bool(wide)
+        self.L = _fv_lib(self.wide)
         self.h = self.L.orc_fv_create(C.byref(case))
         if not self.h:
             raise ValueError("oracle: this case is outside what the restatement carries (graded block with a turbulence model or linearUpwind)")
@@ -372,6 +398,8 @@ class FvSolver:
 
     def view(self, name):
         """numpy view of the oracle's own storage (no copy)"""
+        if self.wide:
+            raise RuntimeError("oracle: the long-double build stores no doubles to view; use get / set")
         n = self.L.orc_fv_field_size(self.h, name.encode())
         assert n >= 0, name
         if n == 0:
@@ -379,11 +407,30 @@ class FvSolver:
         return np.ctypeslib.as_array(self.L.orc_fv_ptr(self.h, name.encode()), shape=(n,))
 
     def get(self, name):
-        return self.view(name).copy()
+        if not self.wide:
+            return self.view(name).copy()
+        n = self.L.orc_fv_field_size(self.h, name.encode())
+        assert n >= 0, name
+        out = np.zeros(n)
+        if n:
+            assert self.L.orc_fv_get(self.h, name.encode(), _d(out)) == 0
+        return out
 
     def set(self, name, arr):
         arr = np.ascontiguousarray(arr, dtype=np.float64).ravel()
+        assert arr.size == self.L.orc_fv_field_size(self.h, name.encode()), name
         assert self.L.orc_fv_set(self.h, name.encode(), _d(arr)) == 0
+
+    def step_fields(self, coupling):
+        """one pass of the loop body with alpha / uSource / uSourceDrag of `coupling` written in where setParticleAction stands, in place of the particle
+        oracle; setSourceZero afterwards through set (either build)"""
+        self.L.orc_fv_step_begin(self.h)
+        for k in ("alpha", "uSource", "uSourceDrag"):
+            self.set(k, coupling[k])
+        self.L.orc_fv_step_end(self.h)
+        self.set("alpha", np.ones(self.Nc))
+        for k, comp in (("uSource", 3), ("uSourceDrag", 1), ("uParticle", 3)):
+            self.set(k, np.zeros(comp * self.Nc))
 
     def stats(self):
         s = FvStats()
@@ -393,6 +440,8 @@ class FvSolver:
     def step(self, records=None, capture=None):
         """records: (n,10) particle records or None (no particles).  Returns the per-particle force array or None.  capture: a dict that receives copies of
         alpha / uSourceDrag / uSource as setParticleAction left them (they are reset at the end of the step)"""
+        if self.wide:
+            raise RuntimeError("oracle: the particle oracle works on double views; step the long-double build with step_fields")
         self.L.orc_fv_step_begin(self.h)
         out = None
         if records is not None:

@@ -1317,7 +1317,7 @@ class VirtualSlabs:
     def get(self, name):
         """global field assembled from the slabs' owned parts (cell fields and phi_z; x/y face fields concatenate likewise)"""
         parts = [s.get(name) for s in self.solvers]
-        if name == "phi_z":      # interface planes are held by both neighbours: keep the lower slab's copy
+        if name in ("phi_z", "phiHbyA_z"):      # interface planes are held by both neighbours: keep the lower slab's copy
             pl = self.case.nx * self.case.ny
             return np.concatenate([p[:-pl] for p in parts[:-1]] + [parts[-1]])
         return np.concatenate(parts)
@@ -1325,7 +1325,7 @@ class VirtualSlabs:
     def set(self, name, arr):
         arr = np.ascontiguousarray(arr, dtype=np.float64).ravel()
         sizes = [s._size(name) for s in self.solvers]
-        assert name != "phi_z" and sum(sizes) == arr.size
+        assert name not in ("phi_z", "phiHbyA_z") and sum(sizes) == arr.size
         offs = np.concatenate([[0], np.cumsum(sizes)])
         self._each(lambda r: self.solvers[r].set(name, arr[offs[r]:offs[r + 1]]))
 

@@ -880,7 +880,10 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
     const E tab[] = {{"U", U.p, 3 * n, 3}, {"p", p.p, n, 1}, {"phi_x", phi[0].p, phi[0].n, 0}, {"phi_y", phi[1].p, phi[1].n, 0}, {"phi_z", phi[2].p, phi[2].n, 0},
                      {"rAU", rAU.p, n, 1}, {"HbyA", HbyA.p, 3 * n, 3}, {"p_rhs", prhs.p, n, 1}, {"mom_diag", mdiag.p, n, 1}, {"mom_src", src.p, 3 * n, 3},
                      {"alpha", alpha.p, n, 1}, {"uSource", uSource.p, 3 * n, 3}, {"uSourceDrag", uSourceDrag.p, n, 1}, {"uParticle", uParticle.p, 3 * n, 3},
-                     {"gradP", gradP.p, 3 * n, 3}, {"divT", divT.p, 3 * n, 3}, {"vGrad", vGrad.p, 9 * n, 9}, {"divG", divG.p, 3 * n, 3}, {"ddtU", ddtU.p, 3 * n, 3}, {"nut", nut.p, n, 1}, {"k", kturb.p, n, 1}, {"epsilon", epsturb.p, n, 1}};
+                     {"gradP", gradP.p, 3 * n, 3}, {"divT", divT.p, 3 * n, 3}, {"vGrad", vGrad.p, 9 * n, 9}, {"divG", divG.p, 3 * n, 3}, {"ddtU", ddtU.p, 3 * n, 3}, {"nut", nut.p, n, 1}, {"k", kturb.p, n, 1}, {"epsilon", epsturb.p, n, 1},
+                     // diagnostics (read-only: fv_solver_api.cpp): the momentum matrix's neighbour coefficients, side 2 d + s, and the flux the pressure equation is assembled from
+                     {"mom_an0", man[0].p, n, 1}, {"mom_an1", man[1].p, n, 1}, {"mom_an2", man[2].p, n, 1}, {"mom_an3", man[3].p, n, 1}, {"mom_an4", man[4].p, n, 1}, {"mom_an5", man[5].p, n, 1},
+                     {"phiHbyA_x", phiHbyA[0].p, phiHbyA[0].n, 0}, {"phiHbyA_y", phiHbyA[1].p, phiHbyA[1].n, 0}, {"phiHbyA_z", phiHbyA[2].p, phiHbyA[2].n, 0}};
     if (s == "T" || s == "heatSp" || s == "heatSu") {
         if (!th.on) return fail(FY_ERR_INVALID, "solver field '%s' does not exist in this case (fy_case_desc.thermal is off)", s.c_str());
         *ptr = (s == "T" ? th.T.p : s == "heatSp" ? th.Sp.p : th.Su.p) + g.c0;
@@ -904,9 +907,10 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
         // kEqn / kEpsilon assemble and solve their transport equations in the momentum matrix's storage after the last corrector
         // (turbulence_correct): these three diagnostics would then return transport-equation data beside a momentum rAU
         const bool transport = cs.turbulence_model == FY_TURBULENCE_KEQN || cs.turbulence_model == FY_TURBULENCE_KEPSILON;
-        if (th.on && (s == "HbyA" || s == "mom_diag"))
+        const bool is_an = s.compare(0, 6, "mom_an") == 0;
+        if (th.on && (s == "HbyA" || s == "mom_diag" || is_an))
             return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is overwritten by the temperature solve in this case (the T equation reuses the momentum matrix's storage)", s.c_str());
-        if (transport && (s == "HbyA" || s == "mom_diag" || s == "mom_src"))
+        if (transport && (s == "HbyA" || s == "mom_diag" || s == "mom_src" || is_an))
             return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is overwritten by the turbulence transport solve in this case (kEqn / kEpsilon reuse the momentum matrix's storage)", s.c_str());
         *ptr = e.p + (size_t)e.comp * g.c0;          // skip the ghost planes below the owned range (comp = 0: face array)
         *count = e.c;

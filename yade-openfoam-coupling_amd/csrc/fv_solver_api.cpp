@@ -134,6 +134,8 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
     if (name && std::strncmp(name, "mg", 2) == 0) return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (rebuilt from the pressure matrix at every assembly)", name);
     if (name && std::strlen(name) > 9 && std::strcmp(name + std::strlen(name) - 9, "_boundary") == 0)
         return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (the boundary values follow from the patch conditions and the cell fields)", name);
+    if (name && (std::strncmp(name, "mom_an", 6) == 0 || std::strncmp(name, "phiHbyA_", 8) == 0))
+        return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (a diagnostic: rebuilt at every momentum assembly / corrector)", name);
     if (name && fy::SolidStats::is_name(name))
         return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (formed from the particles of the last coupling call)", name);
     FY_HIP(hipSetDevice(s->s.device));
