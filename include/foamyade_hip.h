@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 23
+#define FY_ABI_VERSION 24
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -716,6 +716,21 @@ typedef struct fy_poly_mesh {
                                         face of the solver, numbered after the mesh's own (fy_ldu_solver_read_field_host "orig_face" maps the solver's faces to the
                                         caller's); the patches themselves are left without faces, their entries in the per-patch arrays unused */
 } fy_poly_mesh;
+/* Flow-rate control for periodic domains: the role of OpenFOAM's meanVelocityForce fvOption (the arithmetic is OpenFOAM-6's meanVelocityForce.C as recalled, unpinned:
+ * DESIGN.md section 3 "Flow-rate control").  A uniform pressure gradient G along flowDir = ubar / |ubar| is adjusted so that the bulk velocity stays |ubar|.  Device state:
+ * gradP0 (starts at gradient0) and dGradP (starts at 0).  Per momentum assembly: gradP0 += dGradP, dGradP = 0, and flowDir * gradP0 joins the external momentum source
+ * (what "uSource" holds, which still reads back as written).  After every corrector's velocity update, with w_i = 1 (superficial: alpha_i) and V the mesh volume:
+ *     ubar = (S (flowDir . U_i) w_i V_i) / V     rAUave = (S rAU_i w_i V_i) / V     dGradP = relaxation (|ubar| - ubar) / rAUave     U_i += flowDir (rAU_i dGradP)
+ * dGradP is assigned, not accumulated (OpenFOAM's behaviour, kept); phi is left alone.  The sums are block partials folded in a fixed order: FP64, no atomics, the same
+ * bits from run to run.  At most three launches per corrector and one per assembly on the solver's stream, no host synchronisation; their time is the "flow_control"
+ * clock of fy_ldu_solver_get_kernel_timing. */
+typedef struct fy_flow_control_desc {
+    int32_t on;
+    double ubar[3];                  /* the bulk velocity to hold; |ubar| > 0 */
+    double relaxation;               /* in [0, 1]; OpenFOAM's default is 1 */
+    double gradient0;                /* the pressure gradient to start from (a restart: <time>/uniform/meanVelocityForceProperties) */
+    int32_t superficial;             /* pimpleFoamYade only: weigh both sums with the void fraction (0: OpenFOAM's definition) */
+} fy_flow_control_desc;
 typedef struct fy_ldu_case {
     double dt, nu, rho_fluid, rho_particle;
     int32_t n_correctors, n_non_orth_correctors, momentum_predictor, p_ref_cell;
@@ -779,6 +794,7 @@ typedef struct fy_ldu_case {
     const double* T_value;           /* [n_patches] */
     fy_monitor_desc monitors;        /* controlDict functions: the volFieldValue / surfaceFieldValue objects as in fy_case_desc (all zero: none); `patch` is a patch index */
     int32_t solid_stats;             /* the solid-phase statistics as in fy_case_desc, applied with fy_ldu_solver_set_solid_statistics (0: off) */
+    fy_flow_control_desc flow_control;      /* flow-rate control (all zero: off -- nothing allocated, nothing launched), applied at fy_ldu_solver_create */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */
@@ -797,11 +813,17 @@ int fy_ldu_solver_set_monitors(fy_ldu_solver*, const fy_monitor_desc*);
 int fy_ldu_solver_monitor_layout(fy_ldu_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_ldu_solver_get_monitor_rows(fy_ldu_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
 /* Solid-phase statistics as on fy_solver (fy_solver_set_solid_statistics): the same sums, fields and names; a general mesh has no tiles, so the Gaussian scatter goes
- * out as FP64 global atomics.  The pass's launches are the "solid_stats" clock (the only one here) of fy_ldu_solver_get_kernel_timing, switched on and reset by
+ * out as FP64 global atomics.  The pass's launches are the "solid_stats" clock (beside "flow_control", below) of fy_ldu_solver_get_kernel_timing, switched on and reset by
  * fy_ldu_solver_enable_kernel_timing. */
 int fy_ldu_solver_set_solid_statistics(fy_ldu_solver*, int on);
 int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver*, int on);
 int fy_ldu_solver_get_kernel_timing(fy_ldu_solver*, const char* kernel, double* total_ms, int64_t* launches);
+/* Flow-rate control (fy_flow_control_desc above).  set: NULL or on == 0 switches it off and frees its memory; every call with on != 0 restarts the state from gradient0.
+ * FY_ERR_INVALID naming the entry for |ubar| = 0 or not finite, a relaxation outside [0, 1] or not finite, superficial with icoFoamYade.  get: the numbers of the last
+ * correction -- gradient = gradP0 + dGradP, the uncorrected bulk velocity, the mean rAU, dGradP, the corrections so far; any pointer may be NULL; FY_ERR_INVALID while
+ * the option is off.  Only this call waits for the device.  While the option is on, "flow_control" is a second clock of fy_ldu_solver_get_kernel_timing. */
+int fy_ldu_solver_set_flow_control(fy_ldu_solver*, const fy_flow_control_desc*);
+int fy_ldu_solver_get_flow_control(fy_ldu_solver*, double* gradient, double* ubar_uncorrected, double* rAU_ave, double* dGradP, int64_t* corrections);
 /* Heat exchange (fy_ldu_case.thermal.on; FY_ERR_INVALID on a solver without it): the entry points of fy_solver one for one, with the same semantics.  While thermal is
  * on, "T" [nc] (also writable: a non-uniform start), "heatSp" [nc] (W/K), "heatSu" [nc] (W) and, with thermal.beta != 0 and g != 0, "buoyancy" [nc][3] are field names
  * of fy_ldu_solver_read_field_host, and "T" one that fieldAverage accepts. */
@@ -839,7 +861,7 @@ int fy_foam_case_open_general(const char* case_dir, int solver /* FY_SOLVER_ICO 
 int fy_foam_case_poly_mesh(const fy_foam_case*, fy_poly_mesh* out);              /* pointers into the case object: valid until fy_foam_case_close */
 int fy_foam_case_ldu_desc(const fy_foam_case*, fy_ldu_case* out);                 /* ready for fy_ldu_solver_create (patch arrays point into the case object) */
 int fy_foam_case_patch_name(const fy_foam_case*, int patch, char* out, int cap); /* the boundary file's order = fy_poly_mesh's patch numbers */
-int fy_foam_case_write_time_ldu(const fy_foam_case*, fy_ldu_solver*, const char* time_name);     /* runTime.write() (icoFoamYade.C:142): <time>/U, p */
+int fy_foam_case_write_time_ldu(const fy_foam_case*, fy_ldu_solver*, const char* time_name);     /* runTime.write() (icoFoamYade.C:142): <time>/U, p; with flow control on also <time>/uniform/meanVelocityForceProperties */
 int fy_foam_case_write_monitors_ldu(const fy_foam_case*, fy_ldu_solver*);                           /* fy_foam_case_write_monitors for a general case */
 int fy_foam_case_restore_averages_ldu(const fy_foam_case*, fy_ldu_solver*, int* restored);         /* fy_foam_case_restore_averages for a general case */
 

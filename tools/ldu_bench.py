@@ -2,12 +2,14 @@
 """fy_ldu_solver (icoFoamYade on a general polyhedral mesh, LDU addressing) at scale: a lid-driven cavity on n^3 hexahedra written as a polyhedral mesh,
 plain and wavy (non-orthogonal + skewed, one non-orthogonal corrector), against the structured fy_solver on the same lattice.
 usage: ldu_bench.py [n=128] [steps=10] [kind=wavy|lattice|prisms] [particles=0] [p_solver=mg|diag] [nu=1e-4] [solver=ico|pimple] [turb=laminar|kEpsilon|kEpsilonWF]
-             [--thermal] [--particle-cp=C] [--beta=B]                                                                                -> one JSON line
+             [--thermal] [--particle-cp=C] [--beta=B] [--flow-control]                                                               -> one JSON line
 pimple: a closed box under gravity (fixedFluxPressure walls), the cloud at rest in its lower 60 %, Gaussian 4-way coupling; turb (pimple only): RAS kEpsilon with
 zero-gradient k / epsilon / nut patches, or kEpsilonWF: with nutkWallFunction / epsilonWallFunction on every side of the box.
 --thermal: the fluid temperature equation and the particle-fluid heat exchange (fy_ldu_case.thermal) with water's cp and kappa, the fluid at 300 K and the particles
 at 350 K, zeroGradient T patches (tools/thermal_loop_bench.py's case); --particle-cp: the library integrates the particle temperatures; --beta: Boussinesq buoyancy
-about 300 K (it needs gravity: solver=pimple).  The output then carries the T solve's Jacobi passes of the last step and the heat the particles received in the last step"""
+about 300 K (it needs gravity: solver=pimple).  The output then carries the T solve's Jacobi passes of the last step and the heat the particles received in the last step.
+--flow-control: flow-rate control (fy_ldu_case.flow_control) holding Ubar = (0.1 0 0) with relaxation 1, its kernels timed one by one: the output carries the
+"flow_control" clock per step and per launch, and the last correction's numbers"""
 import json
 import os
 import sys
@@ -22,8 +24,9 @@ import poly_meshes as pm  # noqa: E402
 
 flags = {a.split("=")[0]: (a.split("=") + [""])[1] for a in sys.argv[1:] if a.startswith("--")}
 sys.argv = [a for a in sys.argv if not a.startswith("--")]
-if set(flags) - {"--thermal", "--particle-cp", "--beta"}:
-    sys.exit("flags: --thermal [--particle-cp=C] [--beta=B]")
+if set(flags) - {"--thermal", "--particle-cp", "--beta", "--flow-control"}:
+    sys.exit("flags: --thermal [--particle-cp=C] [--beta=B] [--flow-control]")
+flow_on = "--flow-control" in flags
 thermal_on = "--thermal" in flags
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -54,6 +57,8 @@ if thermal_on:
     if flags.get("--beta"):
         loop.update(beta=float(flags["--beta"]), T_ref=300.0)
     kw["thermal"] = prod.thermal_desc(4180.0, 0.6, T_initial=300.0, particle_temperature=350.0, T_tol=1e-8, T_max_iter=50, **loop)
+if flow_on:
+    kw["flow_control"] = prod.flow_control_desc((0.1, 0.0, 0.0))
 t0 = time.time()
 if pimple:
     dt = 1e-4
@@ -75,6 +80,8 @@ if npart:
     s.set_particles(rec)
 for _ in range(3):
     s.step()
+if flow_on:
+    s.enable_kernel_timing(True)
 its = uits = 0
 ms = mp = 0.0
 t0 = time.time()
@@ -89,6 +96,9 @@ out = dict(tool="ldu_bench", kind=kind, turb=turb, cells=int(mesh["n_cells"]), f
 if thermal_on:
     out.update(thermal=True, particle_cp=float(flags.get("--particle-cp") or 0), beta=float(flags.get("--beta") or 0), T_passes_last_step=s.thermal_stats()[0],
                heat_to_particles_W=s.thermal_stats()[2] if npart else 0.0)
+if flow_on:
+    fms, fl = s.kernel_timing("flow_control")
+    out.update(flow_control=s.flow_control(), flow_control_ms_per_step=fms / steps, flow_control_launches_per_step=fl / steps, flow_control_us_per_launch=1e3 * fms / max(fl, 1))
 s.close()
 if kind == "lattice" and n % 8 == 0:
     # the structured solver on the same block with the same controls (PCG + diagonal preconditioner)

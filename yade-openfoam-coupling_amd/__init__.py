@@ -302,6 +302,21 @@ class ThermalDesc(C.Structure):
                 ("particle_cp", C.c_double), ("beta", C.c_double), ("T_ref", C.c_double)]
 
 
+class FlowControlDesc(C.Structure):
+    """fy_flow_control_desc: flow-rate control of a general-mesh solver, the role of OpenFOAM's meanVelocityForce (all zero: off)"""
+    _fields_ = [("on", C.c_int32), ("ubar", C.c_double * 3), ("relaxation", C.c_double), ("gradient0", C.c_double), ("superficial", C.c_int32)]
+
+
+def flow_control_desc(ubar, relaxation=1.0, gradient0=0.0, superficial=False):
+    """a switched-on fy_flow_control_desc: hold the bulk velocity |ubar| along ubar (LduSolver(..., flow_control=...), LduSolver.set_flow_control).  superficial
+    (pimpleFoamYade): both sums are weighted with the void fraction"""
+    d = FlowControlDesc()
+    d.on, d.relaxation, d.gradient0, d.superficial = 1, float(relaxation), float(gradient0), 1 if superficial else 0
+    for q in range(3):
+        d.ubar[q] = float(ubar[q])
+    return d
+
+
 class LduCase(C.Structure):
     _fields_ = [("dt", C.c_double), ("nu", C.c_double), ("rho_fluid", C.c_double), ("rho_particle", C.c_double), ("n_correctors", C.c_int32),
                 ("n_non_orth_correctors", C.c_int32), ("momentum_predictor", C.c_int32), ("p_ref_cell", C.c_int32), ("p_ref_value", C.c_double),
@@ -316,7 +331,7 @@ class LduCase(C.Structure):
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
                 ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp), ("monitors", MonitorDesc),
-                ("solid_stats", C.c_int32)]
+                ("solid_stats", C.c_int32), ("flow_control", FlowControlDesc)]
 
 
 NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
@@ -1440,8 +1455,9 @@ class LduSolver(_Averages, _Monitors, _ParticleHeat):
         L.fy_ldu_solver_write_field_host.argtypes = [C.c_void_p, C.c_char_p, _dp]
 
     def __init__(self, mesh, dt, nu, u_bc, u_val, p_bc, p_val=None, device=0, transport=None, nut_bc=None, nut_val=None, k_bc=None, k_val=None, eps_bc=None, eps_val=None, thermal=None,
-                 T_bc=None, T_val=None, **controls):
-        """thermal: a thermal_desc(...) (its six-sided T_bc / T_value are not read here); T_bc / T_val: FY_BC_T_* and the fixed values per patch (None: zeroGradient)"""
+                 T_bc=None, T_val=None, flow_control=None, **controls):
+        """thermal: a thermal_desc(...) (its six-sided T_bc / T_value are not read here); T_bc / T_val: FY_BC_T_* and the fixed values per patch (None: zeroGradient);
+        flow_control: a flow_control_desc(...)"""
         L = lib()
         self._bind()
         npatch = len(mesh["patch_start"])
@@ -1481,6 +1497,8 @@ class LduSolver(_Averages, _Monitors, _ParticleHeat):
         if T_bc is not None:
             k["tb"], k["tv"] = i32(T_bc), np.ascontiguousarray(T_val if T_val is not None else np.zeros(npatch), np.float64)
             self.case.T_bc, self.case.T_value = _i(k["tb"]), _d(k["tv"])
+        if flow_control is not None:
+            self.case.flow_control = flow_control
         self._create(device, transport)
 
     def _create(self, device, transport):
@@ -1533,12 +1551,27 @@ class LduSolver(_Averages, _Monitors, _ParticleHeat):
         _check(L.fy_ldu_solver_enable_kernel_timing(self._h, int(on)))
 
     def kernel_timing(self, name):
-        """(total_ms, launches) of one instrumented kernel since enable_kernel_timing(True); the one clock here is "solid_stats" """
+        """(total_ms, launches) of one instrumented kernel since enable_kernel_timing(True); the clocks here are "solid_stats" and, with flow control on,
+        "flow_control" (every one of its launches is timed and counted) """
         L = lib()
         L.fy_ldu_solver_get_kernel_timing.argtypes = [C.c_void_p, C.c_char_p, _dp, C.POINTER(C.c_int64)]
         ms = C.c_double(0); n = C.c_int64(0)
         _check(L.fy_ldu_solver_get_kernel_timing(self._h, name.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def set_flow_control(self, desc=None):
+        """fy_ldu_solver_set_flow_control: a flow_control_desc(...) switches the control on and restarts its state from gradient0; None switches it off"""
+        L = lib()
+        L.fy_ldu_solver_set_flow_control.argtypes = [C.c_void_p, C.POINTER(FlowControlDesc)]
+        _check(L.fy_ldu_solver_set_flow_control(self._h, C.byref(desc) if desc is not None else None))
+
+    def flow_control(self):
+        """the last correction's numbers (fy_ldu_solver_get_flow_control): gradient = gradP0 + dGradP, ubar (uncorrected), rAU_ave, dGradP, corrections"""
+        L = lib()
+        L.fy_ldu_solver_get_flow_control.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]
+        g = C.c_double(0); u = C.c_double(0); r = C.c_double(0); d = C.c_double(0); n = C.c_int64(0)
+        _check(L.fy_ldu_solver_get_flow_control(self._h, C.byref(g), C.byref(u), C.byref(r), C.byref(d), C.byref(n)))
+        return dict(gradient=g.value, ubar=u.value, rAU_ave=r.value, dGradP=d.value, corrections=n.value)
 
     def hold_sources(self, on=True):
         L = lib()

@@ -75,6 +75,7 @@ struct fy_foam_case {
     std::vector<std::string> g_patch_name;
     std::vector<int32_t> g_patch_neighbour;      // per patch: its cyclic partner, or -1
     std::vector<std::string> g_patch_class;      // the boundary file's `type` per patch (wall | patch | symmetryPlane | symmetry | cyclic)
+    fy_flow_control_desc flow{};                 // constant/couplingProperties meanVelocityForce (general cases only; fy_ldu_case.flow_control)
     // controlDict functions: the fieldAverage object (desc.average carries its items in this order) and the names of the objects of other types
     struct AvgField { std::string file; int F; std::string solver_name; int ncomp; bool prime2; };      // F: F_U .. F_ALPHA, or -1 (uParticle, uSource: no start-time file)
     std::string avg_name;
@@ -845,6 +846,7 @@ int read_coupling_properties(fy_foam_case* c) {
     c->desc.drag_law = FY_DRAG_REFERENCE; c->desc.force_models = 0;
     c->desc.thermal = fy_thermal_desc{};
     c->desc.solid_stats = 0;
+    c->flow = fy_flow_control_desc{};
     const std::string path = join(c->dir, "constant/couplingProperties");
     if (!file_exists(path)) return FY_OK;
     FoamDict d;
@@ -919,6 +921,52 @@ int read_coupling_properties(fy_foam_case* c) {
             if (t.beta != 0.0 && !h->has("TRef"))
                 return fail(FY_ERR_UNSUPPORTED, "%s: heatTransfer.beta %g needs heatTransfer.TRef, the temperature at which the buoyancy vanishes", path.c_str(), t.beta);
             t.T_convection_scheme = FY_CONVECTION_LINEAR;
+        }
+    }
+    // meanVelocityForce { Ubar; relaxation; superficial; selectionMode all; fields (U); active; }: flow-rate control of a general-mesh case (fy_flow_control_desc), the
+    // role of the fvOption of that name -- constant/fvOptions itself is not read, as the reference's solvers do not read it.  gradient0 is the start time's
+    // uniform/meanVelocityForceProperties `gradient`, when that file is there [OF-6 meanVelocityForce::meanVelocityForce, as recalled]
+    if (d.has("meanVelocityForce")) {
+        const char* accepted = "Ubar, relaxation, superficial, selectionMode, fields, active";
+        const FoamDict* m = d.subdict("meanVelocityForce");
+        if (!m) return fail(FY_ERR_INVALID, "%s: meanVelocityForce must be a dictionary { %s }", path.c_str(), accepted);
+        for (const std::string& k : m->order)
+            if (k != "Ubar" && k != "relaxation" && k != "superficial" && k != "selectionMode" && k != "fields" && k != "active")
+                return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.%s is not an entry this reader knows (%s)", path.c_str(), k.c_str(), accepted);
+        bool active = true;
+        if (m->has("active") && !m->boolean("active", &active)) { m->word("active", &w); return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.active %s; accepts on | off", path.c_str(), w.c_str()); }
+        if (active) {
+            fy_flow_control_desc& f = c->flow;
+            if (!c->general) return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.active on: flow-rate control needs a general mesh: the block has no periodic sides; accepts off", path.c_str());
+            if (m->word("selectionMode", &w) && w != "all") return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.selectionMode %s; accepts all", path.c_str(), w.c_str());
+            if (const std::vector<std::string>* t = m->tokens("fields")) {
+                if (t->size() != 3 || (*t)[0] != "(" || (*t)[2] != ")" || (*t)[1] != c->u_name) {
+                    std::string got;
+                    for (const std::string& x : *t) got += (got.empty() ? "" : " ") + x;
+                    return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.fields %s; accepts (%s)", path.c_str(), got.c_str(), c->u_name.c_str());
+                }
+            }
+            if (!m->vector3("Ubar", f.ubar)) return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.Ubar is missing or not a vector; accepts (Ux Uy Uz), the bulk velocity to hold", path.c_str());
+            const double m2 = f.ubar[0] * f.ubar[0] + f.ubar[1] * f.ubar[1] + f.ubar[2] * f.ubar[2];
+            if (!std::isfinite(m2) || !(m2 > 0)) return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.Ubar must be finite and not zero", path.c_str());
+            f.relaxation = 1.0;
+            if (m->has("relaxation") && (!m->scalar("relaxation", &f.relaxation) || !(f.relaxation >= 0 && f.relaxation <= 1)))
+                return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.relaxation must be a number in [0, 1]", path.c_str());
+            bool sup = false;
+            if (m->has("superficial")) {
+                m->word("superficial", &w);
+                if (!m->boolean("superficial", &sup) || (sup && !gaussian))
+                    return fail(FY_ERR_UNSUPPORTED, "%s: meanVelocityForce.superficial %s; %s accepts %s", path.c_str(), w.c_str(), solver, gaussian ? "on | off" : "off");
+            }
+            f.superficial = sup ? 1 : 0;
+            f.gradient0 = 0.0;
+            const std::string rpath = join(join(c->fdir, c->start_name), "uniform/meanVelocityForceProperties");
+            if (file_exists(rpath)) {
+                FoamDict r;
+                FY_TRY(need_file(rpath, &r));
+                if (!r.scalar("gradient", &f.gradient0) || !std::isfinite(f.gradient0)) return fail(FY_ERR_INVALID, "%s: needs `gradient <number>;`", rpath.c_str());
+            }
+            f.on = 1;
         }
     }
     return FY_OK;
@@ -1944,6 +1992,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->drag_law = d.drag_law; out->force_models = d.force_models; out->solid_stats = d.solid_stats;
     out->average = d.average;
     out->monitors = d.monitors;
+    out->flow_control = c->flow;
     out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
     return FY_OK;
 }
@@ -1967,9 +2016,25 @@ int fy_foam_case_write_time_ldu(const fy_foam_case* c, fy_ldu_solver* s, const c
     FY_TRY(write_solid_stats(c, time_name, [s](const char* nm, int64_t* n) { return fy_ldu_solver_field_count(s, nm, n); }, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); }));
     fy_step_stats st;
     FY_TRY(fy_ldu_solver_get_stats(s, &st));
-    return write_averages(c, time_name, st.delta_t > 0 ? st.delta_t : c->desc.dt, [s](const char* nm, int64_t* n) { return fy_ldu_solver_field_count(s, nm, n); },
+    FY_TRY(write_averages(c, time_name, st.delta_t > 0 ? st.delta_t : c->desc.dt, [s](const char* nm, int64_t* n) { return fy_ldu_solver_field_count(s, nm, n); },
                           [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); },
-                          [s](int i, int64_t* N, double* T) { return fy_ldu_solver_get_average_state(s, i, N, T); });
+                          [s](int i, int64_t* N, double* T) { return fy_ldu_solver_get_average_state(s, i, N, T); }));
+    // meanVelocityForce's restart file [OF-6 meanVelocityForce::writeProps, as recalled]: the gradient the next assembly would use, 17 digits (a restart continues exactly)
+    double gradient = 0.0;
+    if (c->flow.on && fy_ldu_solver_get_flow_control(s, &gradient, nullptr, nullptr, nullptr, nullptr) == FY_OK) {      // (a solver with the control switched off: no file)
+        const std::string udir = join(join(c->fdir, time_name), "uniform");
+        if (mkdir(udir.c_str(), 0777) != 0) {
+            struct stat sb;
+            if (stat(udir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode)) return fail(FY_ERR_INVALID, "cannot create %s", udir.c_str());
+        }
+        const std::string ppath = join(udir, "meanVelocityForceProperties");
+        FILE* f = std::fopen(ppath.c_str(), "wb");
+        if (!f) return fail(FY_ERR_INVALID, "cannot write %s", ppath.c_str());
+        std::fprintf(f, "FoamFile\n{\n    version     2.0;\n    format      ascii;\n    class       dictionary;\n    location    \"%s/uniform\";\n    object      meanVelocityForceProperties;\n}\n\n"
+                        "gradient        %.17g;\n", time_name, gradient);
+        std::fclose(f);
+    }
+    return FY_OK;
 }
 
 int fy_foam_case_restore_averages_ldu(const fy_foam_case* c, fy_ldu_solver* s, int* restored) {

@@ -81,6 +81,9 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     std::printf("             %d points, %d faces (%d internal), %d cells, %d patches\n", pm.n_points, pm.n_faces, pm.n_internal_faces, pm.n_cells, pm.n_patches);
     print_coupling(lc.drag_law, lc.force_models, lc.solid_stats);
     print_functions(fc, lc.average, lc.monitors);
+    if (lc.flow_control.on)
+        std::printf("meanVelocityForce: Ubar (%g %g %g), relaxation %g, superficial %s, initial pressure gradient = %.17g\n", lc.flow_control.ubar[0], lc.flow_control.ubar[1], lc.flow_control.ubar[2],
+                    lc.flow_control.relaxation, lc.flow_control.superficial ? "on" : "off", lc.flow_control.gradient0);
     fy_ldu_solver* s = nullptr;
     if (fy_ldu_solver_create(&pm, &lc, trp, device, &s) != FY_OK) return die("fy_ldu_solver_create");
     fy_ldu_solver_hold_sources(s, 1);                   // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147, pimpleFoamYade.C:107-109)
@@ -112,6 +115,11 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
         std::printf("Time = %s\n\nCourant Number mean: %g max: %g\n", tname, st.courant_mean, st.courant_max);
         std::printf("pressure: %d solves, %d iterations, initial residual %g, final residual %g\n", st.p_solves, st.p_iters_total, st.p_initial_residual, st.p_final_residual);
         std::printf("time step continuity errors : sum local = %g, global = %g, cumulative = %g\n\n", st.cont_err_sum_local, st.cont_err_global, st.cont_err_cumulative);
+        if (lc.flow_control.on) {                               // meanVelocityForce's line [OF-6, as recalled], from the state after the step's last correction
+            double grad = 0, ub = 0;
+            if (fy_ldu_solver_get_flow_control(s, &grad, &ub, nullptr, nullptr, nullptr) != FY_OK) return die("fy_ldu_solver_get_flow_control");
+            std::printf("Pressure gradient source: uncorrected Ubar = %.12g, pressure gradient = %.17g\n\n", ub, grad);
+        }
         if (info.write_interval_steps > 0 && k % info.write_interval_steps == 0)
             if (fy_foam_case_write_time_ldu(fc, s, tname) != FY_OK || fy_foam_case_write_monitors_ldu(fc, s) != FY_OK) return die("writing the time directory");
     }

@@ -2,6 +2,7 @@
 // polyhedral mesh in OpenFOAM's addressing (constant/polyMesh, what createMesh.H hands the solver: icoFoamYade.C:42).  See include/foamyade_hip.h.
 //   ldu_mesh.cpp     host: OpenFOAM's geometry from points / faces / owner / neighbour [OF-6 primitiveMesh*, surfaceInterpolation], cell -> face lists
 //   ldu_kernels.hip  the operators as HIP kernels: one lane per cell GATHERING over the cell's faces, or one lane per face (no scatter, no atomics)
+//   ldu_flow_control.hip  flow-rate control (fy_flow_control_desc): the two sums, the correction, the assembly-time source
 //   ldu_solver.cpp   sequencing + the C entry points
 #pragma once
 #include <hip/hip_runtime.h>
@@ -184,5 +185,14 @@ int launch_ldu_sum(hipStream_t s, const double* x, int n, int ncomp, double* par
 // furthest outside of until it lies inside every face of a cell; cell_out[i] = that cell or -1 (outside the mesh)
 int launch_ldu_find_cell(hipStream_t s, LduGeo g, const double* rec, int rec_len, int64_t n, const int32_t* hint, int32_t* cell_out);
 int launch_ldu_positions(hipStream_t s, const double* rec, int rec_len, int64_t n, double* pos3);      // pos3[i] = rec[i][0..2]
+// ---- flow-rate control (ldu_flow_control.hip; fy_flow_control_desc).  The state record, four doubles; two of them trade places at each momentum assembly
+enum { FLOW_GRADP0 = 0, FLOW_DGRADP, FLOW_UBAR, FLOW_RAUAVE, FLOW_RECORD };
+// the assembly-time update st_out = {st_in.gradP0 + st_in.dGradP, 0, ...} and out[3 c + q] = ext[3 c + q] (null: 0) + dir[q] gradP0; increment: out[3 c + q] += dir[q] st_in.dGradP
+int launch_ldu_flow_source(hipStream_t s, int n_cells, const double* st_in, double* st_out, const double* ext, const double* dir, bool increment, double* out);
+// partials: slot 0 = sum (dir . U) w V, slot 1 = sum rAU w V (w = alpha, or 1 with alpha null), in launch_reduce_finalize's layout for n_cells
+int launch_ldu_flow_sums(hipStream_t s, int n_cells, const double* U, const double* rAU, const double* V, const double* alpha, const double* dir, double* partials);
+// dGradP = relax (mag_ubar - sums[0] / total_volume) / (sums[1] / total_volume), U += dir (rAU dGradP); st's dGradP, ubar, rAUave and *count follow
+int launch_ldu_flow_apply(hipStream_t s, int n_cells, const double* sums, double* st, unsigned long long* count, double mag_ubar, double relax, double total_volume,
+                          const double* dir, const double* rAU, double* U);
 
 }  // namespace fy

@@ -120,7 +120,92 @@ struct LduSolver {
                              });
     }
 
+    // flow-rate control (fy_flow_control_desc; ldu_flow_control.hip; DESIGN.md section 3 "Flow-rate control").  Off: nothing allocated, nothing launched.  The host
+    // keeps no value of the state: `cur` says which of the two records the step reads now, and flips at each momentum assembly
+    struct Flow {
+        bool on = false;
+        fy_flow_control_desc d{};
+        double dir[3] = {0, 0, 0}, mag = 0.0;
+        DevBuf<double> st, sums, usrc;         // [2][FLOW_RECORD], the two folded sums, the effective external source [3 nc]
+        DevBuf<unsigned long long> count;
+        int cur = 0;
+        KernelClock clock;
+        double* rec(int which) { return st.p + (size_t)which * FLOW_RECORD; }
+    } fc;
+    int set_flow_control(const fy_flow_control_desc* d, const char* who) {
+        if (d && d->on) {
+            const double m2 = d->ubar[0] * d->ubar[0] + d->ubar[1] * d->ubar[1] + d->ubar[2] * d->ubar[2];
+            if (!std::isfinite(m2) || !(m2 > 0)) return fail(FY_ERR_INVALID, "%s: flow_control.ubar must be finite with |ubar| > 0", who);
+            if (!std::isfinite(d->relaxation) || d->relaxation < 0 || d->relaxation > 1) return fail(FY_ERR_INVALID, "%s: flow_control.relaxation %g must lie in [0, 1]", who, d->relaxation);
+            if (!std::isfinite(d->gradient0)) return fail(FY_ERR_INVALID, "%s: flow_control.gradient0 must be finite", who);
+            if (d->superficial && !pimple) return fail(FY_ERR_INVALID, "%s: flow_control.superficial needs pimpleFoamYade (icoFoamYade has no void fraction)", who);
+        }
+        FY_HIP(hipSetDevice(device));
+        FY_HIP(hipStreamSynchronize(stream));
+        if (!d || !d->on) {
+            fc.on = false; fc.d = fy_flow_control_desc{};
+            fc.st.release(); fc.sums.release(); fc.usrc.release(); fc.count.release();
+            fc.clock.reset();
+            return FY_OK;
+        }
+        fc.d = *d;
+        fc.mag = std::sqrt(d->ubar[0] * d->ubar[0] + d->ubar[1] * d->ubar[1] + d->ubar[2] * d->ubar[2]);
+        for (int a = 0; a < 3; ++a) fc.dir[a] = d->ubar[a] / fc.mag;
+        if (!fc.st.p) {
+            FY_TRY(fc.st.alloc_exact(2 * FLOW_RECORD)); FY_TRY(fc.sums.alloc_exact(2)); FY_TRY(fc.usrc.alloc_exact(3 * (size_t)nc)); FY_TRY(fc.count.alloc_exact(1));
+        }
+        const double h[2 * FLOW_RECORD] = {d->gradient0, 0, 0, 0, d->gradient0, 0, 0, 0};
+        FY_HIP(hipMemcpyAsync(fc.st.p, h, sizeof(h), hipMemcpyHostToDevice, stream));
+        FY_HIP(hipMemsetAsync(fc.sums.p, 0, 2 * sizeof(double), stream));
+        FY_HIP(hipMemsetAsync(fc.count.p, 0, sizeof(unsigned long long), stream));
+        FY_HIP(hipStreamSynchronize(stream));                  // (set-up only: h dies with this scope)
+        fc.cur = 0;
+        fc.clock.per_collect = (size_t)1 << 20;                // every launch is timed and counted while timing is on: the count is the launch budget's check
+        fc.clock.on = ss.clock.on;
+        fc.on = true;
+        return FY_OK;
+    }
+    // constrain + addSup at a momentum assembly: the state's update and the effective external source, what the equations then read where they read uSourceExt
+    // (increment_into: a later PIMPLE outer iteration, whose uSource already holds the source of the assembly before -- it gains flowDir times the last dGradP)
+    int flow_source(double* increment_into = nullptr) {
+        fc.clock.begin(stream);
+        FY_TRY(launch_ldu_flow_source(stream, nc, fc.rec(fc.cur), fc.rec(1 - fc.cur), ext_source ? uSourceExt.p : nullptr, fc.dir, increment_into != nullptr,
+                                      increment_into ? increment_into : fc.usrc.p));
+        fc.clock.end(stream);
+        fc.cur = 1 - fc.cur;
+        return FY_OK;
+    }
+    // correct(U) after a corrector's velocity update: two sums, their fold, the correction
+    int flow_correct() {
+        fc.clock.begin(stream);
+        FY_TRY(launch_ldu_flow_sums(stream, nc, U.p, rAU.p, d_V.p, fc.d.superficial ? alpha.p : nullptr, fc.dir, partials.p));
+        fc.clock.end(stream);
+        fc.clock.begin(stream);
+        FY_TRY(launch_reduce_finalize(stream, partials.p, nc, 2, nullptr, fc.sums.p, nullptr, 0));
+        fc.clock.end(stream);
+        fc.clock.begin(stream);
+        FY_TRY(launch_ldu_flow_apply(stream, nc, fc.sums.p, fc.rec(fc.cur), fc.count.p, fc.mag, fc.d.relaxation, total_volume, fc.dir, rAU.p, U.p));
+        fc.clock.end(stream);
+        return FY_OK;
+    }
+    int get_flow_control(double* gradient, double* ubar_unc, double* rau_ave, double* dgradp, int64_t* corrections) {
+        if (!fc.on) return fail(FY_ERR_INVALID, "fy_ldu_solver_get_flow_control: flow control is off (fy_ldu_case.flow_control, fy_ldu_solver_set_flow_control)");
+        FY_HIP(hipSetDevice(device));
+        double h[FLOW_RECORD];
+        unsigned long long n = 0;
+        FY_HIP(hipMemcpyAsync(h, fc.rec(fc.cur), sizeof(h), hipMemcpyDeviceToHost, stream));
+        FY_HIP(hipMemcpyAsync(&n, fc.count.p, sizeof(n), hipMemcpyDeviceToHost, stream));
+        FY_HIP(hipStreamSynchronize(stream));
+        if (gradient) *gradient = h[FLOW_GRADP0] + h[FLOW_DGRADP];
+        if (ubar_unc) *ubar_unc = h[FLOW_UBAR];
+        if (rau_ave) *rau_ave = h[FLOW_RAUAVE];
+        if (dgradp) *dgradp = h[FLOW_DGRADP];
+        if (corrections) *corrections = (int64_t)n;
+        return FY_OK;
+    }
+
     ~LduSolver() {
+        fc.clock.destroy();
         if (cpl) fy_destroy(cpl);
         for (auto& t : tim) t.destroy();
         if (side) (void)hipStreamDestroy(side);
@@ -308,6 +393,8 @@ struct LduSolver {
         if (c->solid_stats) FY_TRY(set_solid_statistics(1));                  // couplingProperties solidStatistics (before fieldAverage and the monitors, which may ask for its fields)
         if (c->average.n_items) FY_TRY(set_field_average(&c->average));       // controlDict functions: fieldAverage
         if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));        // volFieldValue / surfaceFieldValue
+        cs.flow_control = fy_flow_control_desc{};
+        if (c->flow_control.on) FY_TRY(set_flow_control(&c->flow_control, "fy_ldu_solver_create"));      // couplingProperties meanVelocityForce
         return FY_OK;
     }
 
@@ -465,6 +552,7 @@ struct LduSolver {
         FY_TRY(reduce_read(nc, 2, nullptr, h));
         st.cont_err_sum_local = cs.dt * h[0] / total_volume; st.cont_err_global = cs.dt * h[1] / total_volume;
         cumulative += st.cont_err_global; st.cont_err_cumulative = cumulative;
+        if (fc.on) FY_TRY(flow_correct());                                                                        // fvOptions.correct(U), after the continuity sums have left the partials
         return FY_OK;
     }
 
@@ -488,6 +576,7 @@ struct LduSolver {
             }
         }
         FY_TRY(launch_ldu_reconstruct(stream, g, ssf.p, HbyA.p, rAU.p, U.p));                                     // :43-46
+        if (fc.on) FY_TRY(flow_correct());                                                                        // fvOptions.correct(Uc) (the continuity sums below read the flux, not U)
         FY_TRY(launch_ldu_pim_continuity(stream, g, pt.p, alpha.p, alpha.p, partials.p));             // :50
         double h[2];
         FY_TRY(reduce_read(nc, 2, nullptr, h));
@@ -517,7 +606,8 @@ struct LduSolver {
         if (beside) FY_HIP(hipStreamWaitEvent(stream, ev_fields, 0));                                             // (whatever the coupling did: the sweeps below read alphaf)
         FY_TRY(launch_ldu_alphaf(stream, g, alpha.p, alphaf.p));                                                  // :83-85
         if (th.on) FY_TRY(heat_coefficients());                                                                   // (the stencils, the cell records and U are still what the force pass saw)
-        if (ext_source) FY_TRY(launch_add_f64(stream, uSource.p, uSourceExt.p, 3 * (size_t)nc));
+        if (fc.on) FY_TRY(flow_source());                                                                         // (the first outer iteration's assembly: gradP0 += dGradP, ext + flowDir gradP0)
+        if (ext_source || fc.on) FY_TRY(launch_add_f64(stream, uSource.p, fc.on ? fc.usrc.p : uSourceExt.p, 3 * (size_t)nc));
         if (th.buoyant) FY_TRY(launch_buoyancy(stream, (size_t)nc, th.T.p, th.d.beta, th.d.T_ref, cs.g, uSource.p, th.buoy.p, th.usrc_sum.p));      // P().uSource: the sum
         const int nOuter = std::max(cs.n_outer_correctors, 1);
         for (int outer = 0; outer < nOuter; ++outer) {                                                             // :90
@@ -526,6 +616,10 @@ struct LduSolver {
             const double p_relax_now = (final_outer && cs.p_relax_final > 0) ? cs.p_relax_final : cs.p_relax;
             if (p_relax_now > 0 && p_relax_now < 1) FY_TRY(launch_copy_f64(stream, pPrev.p, p.p, (size_t)nc));  // storePrevIterFields()
             if (outer > 0) FY_TRY(launch_ldu_grad_vec(stream, g, U.p, vGrad.p));
+            if (outer > 0 && fc.on) {                                                                             // this assembly's gradP0 = the last one's + the last corrector's dGradP
+                FY_TRY(flow_source(uSource.p));
+                if (th.buoyant) FY_TRY(launch_buoyancy(stream, (size_t)nc, th.T.p, th.d.beta, th.d.T_ref, cs.g, uSource.p, th.buoy.p, th.usrc_sum.p));
+            }
             if (g.gradL) FY_TRY(launch_ldu_grad_magsqr(stream, g, U.p, gradL.p));
             FY_TRY(launch_ldu_assemble_momentum_pimple(stream, g, P(), phi.p, Uold.p, U.p, vGrad.p, M(), pt.p, fstress.p, u_relax_now, rAU.p));      // UcEqn.H:3-13
             FY_TRY(launch_ldu_forces(stream, g, P(), rAU.p, rAUf.p, phiForces.p));                               // UcEqn.H:15-20
@@ -600,7 +694,8 @@ struct LduSolver {
             if (th.on) FY_TRY(heat_coefficients());
             // the momentum source: what the coupling left (+ an external one, fy_ldu_solver_write_field_host("uSource", ...)) (+ the buoyancy of the T the step found)
             const double* src = uSource.p;
-            if (ext_source) { FY_TRY(launch_copy_f64(stream, uSourceSum.p, uSource.p, 3 * (size_t)nc)); FY_TRY(launch_add_f64(stream, uSourceSum.p, uSourceExt.p, 3 * (size_t)nc)); src = uSourceSum.p; }
+            if (fc.on) FY_TRY(flow_source());                                                                         // gradP0 += dGradP, ext + flowDir gradP0
+            if (ext_source || fc.on) { FY_TRY(launch_copy_f64(stream, uSourceSum.p, uSource.p, 3 * (size_t)nc)); FY_TRY(launch_add_f64(stream, uSourceSum.p, fc.on ? fc.usrc.p : uSourceExt.p, 3 * (size_t)nc)); src = uSourceSum.p; }
             if (th.buoyant) { FY_TRY(launch_buoyancy(stream, (size_t)nc, th.T.p, th.d.beta, th.d.T_ref, cs.g, src, th.buoy.p, th.usrc_sum.p)); src = th.usrc_sum.p; }
             if (g.gradL) FY_TRY(launch_ldu_grad_magsqr(stream, g, Uold.p, gradL.p));
             FY_TRY(launch_ldu_assemble_momentum(stream, g, phi.p, Uold.p, src, vGrad.p, M(), fcorr.p));                // :79-85 (grad U of the iterate it is assembled from = vGrad)
@@ -630,6 +725,7 @@ struct LduSolver {
         }
         st.ms_particle = tim[0].ms(); st.ms_total = tim[1].ms();
         if (ss.on) ss.clock.collect();
+        if (fc.on) fc.clock.collect();
         return FY_OK;
     }
 
@@ -793,13 +889,25 @@ int fy_ldu_solver_set_field_average(fy_ldu_solver* s, const fy_average_desc* d) 
 int fy_ldu_solver_get_average_state(fy_ldu_solver* s, int item, int64_t* samples, double* time_averaged) { FY_LS(s); return s->s.avg.get_state(item, samples, time_averaged); }
 int fy_ldu_solver_set_average_state(fy_ldu_solver* s, int item, int64_t samples, double time_averaged) { FY_LS(s); return s->s.avg.set_state(item, samples, time_averaged); }
 int fy_ldu_solver_set_solid_statistics(fy_ldu_solver* s, int on) { FY_LS(s); return s->s.set_solid_statistics(on); }
-int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver* s, int on) { FY_LS(s); s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0; return FY_OK; }
+int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver* s, int on) {
+    FY_LS(s);
+    s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0;
+    s->s.fc.clock.reset(); s->s.fc.clock.on = on != 0;
+    return FY_OK;
+}
 int fy_ldu_solver_get_kernel_timing(fy_ldu_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
     FY_LS(s);
     const std::string k = kernel ? kernel : "";
-    if (k != "solid_stats" || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats)", k.c_str());
-    *total_ms = s->s.ss.clock.total_ms; *launches = s->s.ss.clock.launches;
+    const bool flow = k == "flow_control" && s->s.fc.on;
+    if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "");
+    const fy::KernelClock& c = flow ? s->s.fc.clock : s->s.ss.clock;
+    *total_ms = c.total_ms; *launches = c.launches;
     return FY_OK;
+}
+int fy_ldu_solver_set_flow_control(fy_ldu_solver* s, const fy_flow_control_desc* d) { FY_LS(s); return s->s.set_flow_control(d, "fy_ldu_solver_set_flow_control"); }
+int fy_ldu_solver_get_flow_control(fy_ldu_solver* s, double* gradient, double* ubar_uncorrected, double* rAU_ave, double* dGradP, int64_t* corrections) {
+    FY_LS(s);
+    return s->s.get_flow_control(gradient, ubar_uncorrected, rAU_ave, dGradP, corrections);
 }
 int fy_ldu_solver_set_monitors(fy_ldu_solver* s, const fy_monitor_desc* d) { FY_LS(s); return s->s.set_monitors(d); }
 int fy_ldu_solver_monitor_layout(fy_ldu_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_LS(s); return s->s.mon.layout(object, n_values, labels, cap); }
