@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 24
+#define FY_ABI_VERSION 25
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -321,6 +321,42 @@ typedef struct fy_monitor_desc {
     double start_time;              /* the time of the solver's creation (a case's startTime) */
 } fy_monitor_desc;
 
+/* Wall loads: OpenFOAM's forces / wallShearStress / yPlus function objects on the device ([OF-6 forces.C, wallShearStress.C, yPlus.C] as recalled: unpinned, DESIGN.md
+   sections 3 "Wall loads" and 5).  Sampled where the monitors are.  For a boundary face f of a selected patch, outward Sf, n = Sf / |Sf|, owner cell P:
+       G_P[i][j] = d_i U_j      the Gauss-linear gradient of U in P (internal faces linearly interpolated, boundary faces their value as the equations see it)
+       s = (U_b - U_P) delta    delta: the momentum equation's wall coefficient (1 / (n . (Cf - C_P)); half a cell on the block); 0 on a zeroGradient patch
+       G_b = G_P + n (x) (s - n . G_P)          R_b = -nuEff_b dev(twoSymm(G_b)), nuEff_b = nu + nut_b (the void fraction does not enter)
+       wallShearStress = -n . R_b               yPlus = Cmu^1/4 y sqrt(k_P) / nu on a nutkWallFunction patch, y sqrt(nuEff_b |s|) / nu elsewhere (y: nearWallDist)
+       forces:  fP = rho Sf (p_b - p_ref)   fV = rho (Sf . R_b)   mP = (Cf - cofr) x fP   mV = (Cf - cofr) x fV, each summed over the object's faces
+   Every bracket is one IEEE operation; the sums are per-256-block partials folded in a fixed order (no atomics, the same bits from run to run).  A forces row has 12
+   values Fp_x Fp_y Fp_z Fv_x .. Mp_x .. Mv_z; a wallShearStress row per patch of its set min_x min_y min_z max_x max_y max_z; a yPlus row per patch min max average.
+   Rows go to rings on the device as the monitors' do.  A patch set: fy_solver reads `sides` (a mask, bit 2 d + s), fy_ldu_solver patches[0 .. n_patches). */
+#define FY_WALL_LOADS_MAX_FORCES 4
+#define FY_WALL_LOADS_MAX_PATCHES 8
+typedef struct fy_wall_patch_set {
+    int32_t sides;                  /* fy_solver: mask of sides x- x+ y- y+ z- z+ */
+    int32_t n_patches;              /* fy_ldu_solver: patch indices (no cyclic patch) */
+    int32_t patches[FY_WALL_LOADS_MAX_PATCHES];
+} fy_wall_patch_set;
+typedef struct fy_forces_object {
+    char name[32];
+    fy_wall_patch_set set;
+    double rho, p_ref, cofr[3];     /* rhoInf (> 0), pRef, CofR */
+    int32_t interval;               /* one sample every `interval` steps, >= 1 (0 is read as 1) */
+} fy_forces_object;
+typedef struct fy_wall_field_object {
+    int32_t on;
+    fy_wall_patch_set set;
+    int32_t interval;
+} fy_wall_field_object;
+typedef struct fy_wall_loads_desc {
+    int32_t n_forces;               /* all zero (n_forces 0, both `on` 0): off -- no kernel, no memory */
+    fy_forces_object forces[FY_WALL_LOADS_MAX_FORCES];
+    fy_wall_field_object wall_shear_stress, y_plus;      /* objects "wallShearStress", "yPlus": per-face fields "wallShearStress_boundary" [nb][3], "yPlus_boundary" [nb] */
+    int32_t ring_rows;              /* rows of the device ring per object (0: 256) */
+    double start_time;
+} fy_wall_loads_desc;
+
 /* Fluid temperature with particle-fluid heat exchange (a capability the reference does not have; DESIGN.md section 3 "heat exchange", DESIGN_FV.md "T equation").
    Fluid: cp [J/kg/K], kappa [W/m/K], D = kappa / (rho_f cp), Pr = nu rho_f cp / kappa, Deff = D + nut / prt (nut = 0 when laminar).  A particle of diameter d and
    temperature Tp, with the force pass's stencil (cells c, normalised weights w; point-force mode: the containing cell, w = 1, eps = 1):
@@ -434,6 +470,8 @@ typedef struct fy_case_desc {
     fy_monitor_desc monitors;
     /* constant/couplingProperties solidStatistics: the solid-phase statistics, applied at fy_solver_create with fy_solver_set_solid_statistics (0: off) */
     int32_t solid_stats;
+    /* controlDict functions: the forces / wallShearStress / yPlus objects (all zero: none), applied at fy_solver_create with fy_solver_set_wall_loads */
+    fy_wall_loads_desc wall_loads;
 } fy_case_desc;
 
 typedef struct fy_solver fy_solver;
@@ -492,6 +530,19 @@ int fy_solver_set_average_state(fy_solver*, int item, int64_t samples, double ti
 int fy_solver_set_monitors(fy_solver*, const fy_monitor_desc*);
 int fy_solver_monitor_layout(fy_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_solver_get_monitor_rows(fy_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
+
+/* Wall loads on this solver (fy_wall_loads_desc above).  NULL or an all-zero descriptor: off, the buffers freed, nothing launched; a new call starts every history from
+ * empty.  Objects are numbered forces[0 .. n_forces), then "wallShearStress", then "yPlus" (those that are on).  FY_ERR_INVALID, naming the object and the word: an empty
+ * patch set (sides / patches), a side mask past 6 bits, more than FY_WALL_LOADS_MAX_FORCES objects or FY_WALL_LOADS_MAX_PATCHES patches, rho <= 0, a negative interval,
+ * yPlus in a case with neither a turbulence model nor nu > 0; a slab solver: FY_ERR_UNSUPPORTED.  Two launches per sampled step (the face kernel, the fold) on the
+ * solver's stream, no host synchronisation; their time is the "wall_loads" clock of fy_solver_get_kernel_timing (unknown while wall loads are off).
+ * _layout / _get_wall_load_rows: as fy_solver_monitor_layout / fy_solver_get_monitor_rows; only _get_wall_load_rows waits for the device.  Patches are labelled x- x+ y-
+ * y+ z- z+: "min(x-)_x" ... "max(x-)_z" (wallShearStress), "min(x-)" "max(x-)" "average(x-)" (yPlus).
+ * Read-only field names while the object is on: "wallShearStress_boundary" [nb][3], "yPlus_boundary" [nb] in the order of "p_boundary", as the last sample left them
+ * (zeros on faces outside the set).  Always: "nut_boundary" [nb] (nut on the boundary as the equations see it; zeros when laminar), "nearWallDist" [nb]. */
+int fy_solver_set_wall_loads(fy_solver*, const fy_wall_loads_desc*);
+int fy_solver_wall_loads_layout(fy_solver*, int object, int32_t* n_values, char* labels, int cap);
+int fy_solver_get_wall_load_rows(fy_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
 
 /* Solid-phase statistics on this solver (not in the reference; DESIGN.md section 3 "Solid-phase statistics").  on != 0: once per step, after the T equation and before
  * fieldAverage and the monitors sample, one more scatter over the stencils of every located particle of EVERY batch forms eight sums per cell c (w: the stencil
@@ -596,6 +647,18 @@ int fy_foam_case_ignored_function(const fy_foam_case*, int i, char* out, int cap
  * restarted run writes into the directory of its own start time */
 int fy_foam_case_monitor_count(const fy_foam_case*);
 int fy_foam_case_write_monitors(const fy_foam_case*, fy_solver*);
+/* controlDict `functions`, objects of `type forces | wallShearStress | yPlus` (not `enabled false`) become fy_case_desc.wall_loads / fy_ldu_case.wall_loads ([OF-6 forces,
+ * wallShearStress, yPlus] as recalled, unpinned).  forces: patches ( <name> ... ), rho rhoInf with rhoInf <value>, pRef (default 0), CofR (x y z); accepted and unused: p, U,
+ * log, libs, enabled, writeControl | executeControl timeStep with writeInterval | executeInterval N (one sample every N steps).  wallShearStress, yPlus: an optional patches
+ * list, default every patch of type wall; one object of each.  Refused by name with the accepted words (FY_ERR_UNSUPPORTED): every other keyword (porosity, binData,
+ * coordinateSystem, directForceDensity, ...), a rho other than rhoInf, other controls, an unknown or cyclic patch, more than FY_WALL_LOADS_MAX_FORCES forces objects or
+ * FY_WALL_LOADS_MAX_PATCHES patches, a decomposed case.  The solver numbers the objects forces first (in the dictionary's order), then wallShearStress, then yPlus.
+ * fy_foam_case_write_wall_loads (_ldu for a general case) appends the rows the solver has gathered since the last call to <case>/postProcessing/<object>/<start time
+ * name>/forces.dat (time, then Fp Fv Mp Mv as (x y z)) | wallShearStress.dat (per patch a line: time, patch, min vector, max vector) | yPlus.dat (per patch: time, patch,
+ * min, max, average): '#' header lines first, writePrecision digits; a block's patch that covers several sides has one line per side, named <patch>:<side> (x- .. z+).  The
+ * first call of a run creates the file: a restarted run writes into the directory of its own start time */
+int fy_foam_case_wall_loads_count(const fy_foam_case*);
+int fy_foam_case_write_wall_loads(const fy_foam_case*, fy_solver*);
 int fy_foam_case_restore_averages(const fy_foam_case*, fy_solver*, int* restored);
 int fy_foam_case_close(fy_foam_case*);
 
@@ -795,6 +858,7 @@ typedef struct fy_ldu_case {
     fy_monitor_desc monitors;        /* controlDict functions: the volFieldValue / surfaceFieldValue objects as in fy_case_desc (all zero: none); `patch` is a patch index */
     int32_t solid_stats;             /* the solid-phase statistics as in fy_case_desc, applied with fy_ldu_solver_set_solid_statistics (0: off) */
     fy_flow_control_desc flow_control;      /* flow-rate control (all zero: off -- nothing allocated, nothing launched), applied at fy_ldu_solver_create */
+    fy_wall_loads_desc wall_loads;          /* the forces / wallShearStress / yPlus objects as in fy_case_desc (all zero: none); a patch set is patches[0 .. n_patches) */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
 void fy_ldu_case_defaults(fy_ldu_case*);        /* the icoFoam cavity tutorial's controls (as fy_case_defaults); the patch arrays stay NULL */
@@ -812,6 +876,13 @@ int fy_ldu_solver_set_average_state(fy_ldu_solver*, int item, int64_t samples, d
 int fy_ldu_solver_set_monitors(fy_ldu_solver*, const fy_monitor_desc*);
 int fy_ldu_solver_monitor_layout(fy_ldu_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_ldu_solver_get_monitor_rows(fy_ldu_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
+/* Wall loads as on fy_solver (fy_solver_set_wall_loads): a patch set is a list of patch indices, labelled "patch<index>"; a cyclic patch (folded into internal faces) or
+ * a patch that does not exist is refused by name (FY_ERR_INVALID).  delta = deltaCoeffs of the boundary face ("dcNO"), y = nearWallDist, which is then formed for the
+ * selected patches as well as for the wall-function patches.  "wallShearStress_boundary" [nb][3], "yPlus_boundary" [nb] in the solver's boundary-face order; the clock
+ * is "wall_loads" of fy_ldu_solver_get_kernel_timing. */
+int fy_ldu_solver_set_wall_loads(fy_ldu_solver*, const fy_wall_loads_desc*);
+int fy_ldu_solver_wall_loads_layout(fy_ldu_solver*, int object, int32_t* n_values, char* labels, int cap);
+int fy_ldu_solver_get_wall_load_rows(fy_ldu_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
 /* Solid-phase statistics as on fy_solver (fy_solver_set_solid_statistics): the same sums, fields and names; a general mesh has no tiles, so the Gaussian scatter goes
  * out as FP64 global atomics.  The pass's launches are the "solid_stats" clock (beside "flow_control", below) of fy_ldu_solver_get_kernel_timing, switched on and reset by
  * fy_ldu_solver_enable_kernel_timing. */
@@ -862,6 +933,7 @@ int fy_foam_case_poly_mesh(const fy_foam_case*, fy_poly_mesh* out);             
 int fy_foam_case_ldu_desc(const fy_foam_case*, fy_ldu_case* out);                 /* ready for fy_ldu_solver_create (patch arrays point into the case object) */
 int fy_foam_case_patch_name(const fy_foam_case*, int patch, char* out, int cap); /* the boundary file's order = fy_poly_mesh's patch numbers */
 int fy_foam_case_write_time_ldu(const fy_foam_case*, fy_ldu_solver*, const char* time_name);     /* runTime.write() (icoFoamYade.C:142): <time>/U, p; with flow control on also <time>/uniform/meanVelocityForceProperties */
+int fy_foam_case_write_wall_loads_ldu(const fy_foam_case*, fy_ldu_solver*);                         /* fy_foam_case_write_wall_loads for a general case */
 int fy_foam_case_write_monitors_ldu(const fy_foam_case*, fy_ldu_solver*);                           /* fy_foam_case_write_monitors for a general case */
 int fy_foam_case_restore_averages_ldu(const fy_foam_case*, fy_ldu_solver*, int* restored);         /* fy_foam_case_restore_averages for a general case */
 

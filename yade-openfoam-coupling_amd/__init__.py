@@ -214,6 +214,100 @@ class _Monitors:
         return t, v
 
 
+WALL_LOADS_MAX_FORCES, WALL_LOADS_MAX_PATCHES = 4, 8
+
+
+class WallPatchSet(C.Structure):
+    _fields_ = [("sides", C.c_int32), ("n_patches", C.c_int32), ("patches", C.c_int32 * WALL_LOADS_MAX_PATCHES)]
+
+
+class ForcesObject(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("set", WallPatchSet), ("rho", C.c_double), ("p_ref", C.c_double), ("cofr", C.c_double * 3), ("interval", C.c_int32)]
+
+
+class WallFieldObject(C.Structure):
+    _fields_ = [("on", C.c_int32), ("set", WallPatchSet), ("interval", C.c_int32)]
+
+
+class WallLoadsDesc(C.Structure):
+    """fy_wall_loads_desc: the forces / wallShearStress / yPlus objects of a solver (all zero: none)"""
+    _fields_ = [("n_forces", C.c_int32), ("forces", ForcesObject * WALL_LOADS_MAX_FORCES), ("wall_shear_stress", WallFieldObject), ("y_plus", WallFieldObject),
+                ("ring_rows", C.c_int32), ("start_time", C.c_double)]
+
+
+def _wall_patch_set(ps, patches):
+    """patches: a mask of sides bit 2 d + s (a block) or a list of patch indices (a general mesh); counts past the limit are passed on for the library to refuse"""
+    if isinstance(patches, (int, np.integer)):
+        ps.sides = int(patches)
+    else:
+        patches = list(patches)
+        ps.n_patches = len(patches)
+        for q, pa in enumerate(patches[:WALL_LOADS_MAX_PATCHES]):
+            ps.patches[q] = int(pa)
+
+
+def wall_loads_desc(forces=None, wall_shear_stress=None, y_plus=None, ring_rows=0, start_time=0.0):
+    """forces: dicts with name, patches, rho and optionally p_ref, cofr, interval; wall_shear_stress / y_plus: None (off), or a dict with patches and optionally
+    interval (or just the patches) -> WallLoadsDesc.  patches: a mask of sides on a block, a list of patch indices on a general mesh"""
+    d = WallLoadsDesc()
+    forces = list(forces or [])
+    d.n_forces = len(forces)
+    for q, o in enumerate(forces[:WALL_LOADS_MAX_FORCES]):
+        f = d.forces[q]
+        f.name = str(o["name"]).encode()
+        _wall_patch_set(f.set, o["patches"])
+        f.rho, f.p_ref, f.interval = float(o.get("rho", 1.0)), float(o.get("p_ref", 0.0)), int(o.get("interval", 1))
+        for a, x in enumerate(o.get("cofr", (0.0, 0.0, 0.0))):
+            f.cofr[a] = float(x)
+    for obj, o in ((d.wall_shear_stress, wall_shear_stress), (d.y_plus, y_plus)):
+        if o is None:
+            continue
+        o = o if isinstance(o, dict) else dict(patches=o)
+        obj.on, obj.interval = 1, int(o.get("interval", 1))
+        _wall_patch_set(obj.set, o["patches"])
+    d.ring_rows, d.start_time = int(ring_rows), float(start_time)
+    return d
+
+
+class _WallLoads:
+    """wall loads on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*): forces, wallShearStress and yPlus on the device.  Objects are numbered
+    forces first, then wallShearStress, then yPlus; get("wallShearStress_boundary") / get("yPlus_boundary") read the per-face fields of the last sample"""
+
+    def _wl_fn(self, what):
+        f = getattr(lib(), f"{self._AVG_PREFIX}_{what}")
+        f.argtypes = {"set_wall_loads": [C.c_void_p, C.POINTER(WallLoadsDesc)], "wall_loads_layout": [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_int],
+                      "get_wall_load_rows": [C.c_void_p, C.c_int, C.c_int64, C.c_int64, _dp, _dp, C.POINTER(C.c_int64)]}[what]
+        return f
+
+    def set_wall_loads(self, forces=None, wall_shear_stress=None, y_plus=None, ring_rows=0, start_time=0.0):
+        """as wall_loads_desc takes them (or a WallLoadsDesc as the first argument); nothing given: off"""
+        if isinstance(forces, WallLoadsDesc):
+            _check(self._wl_fn("set_wall_loads")(self._h, C.byref(forces)))
+        elif not forces and wall_shear_stress is None and y_plus is None:
+            _check(self._wl_fn("set_wall_loads")(self._h, None))
+        else:
+            d = wall_loads_desc(forces, wall_shear_stress, y_plus, ring_rows, start_time)
+            _check(self._wl_fn("set_wall_loads")(self._h, C.byref(d)))
+
+    def wall_loads_layout(self, obj):
+        """the labels of the values in a row of object `obj`: "Fp_x" ... "Mv_z"; "min(x-)_x" ...; "min(x-)", "max(x-)", "average(x-)" """
+        n = C.c_int32(0); buf = C.create_string_buffer(8192)
+        _check(self._wl_fn("wall_loads_layout")(self._h, int(obj), C.byref(n), buf, 8192))
+        labels = buf.value.decode().split("\n") if n.value else []
+        assert len(labels) == n.value
+        return labels
+
+    def wall_load_rows(self, obj, first_row=0):
+        """(times [rows], values [rows, n_values]) of object `obj` from row `first_row` on; this call waits for the device, sampling never does"""
+        n = C.c_int64(0)
+        _check(self._wl_fn("get_wall_load_rows")(self._h, int(obj), int(first_row), 0, None, None, C.byref(n)))
+        nv = len(self.wall_loads_layout(obj))
+        t = np.zeros(n.value); v = np.zeros((n.value, nv))
+        if n.value:
+            _check(self._wl_fn("get_wall_load_rows")(self._h, int(obj), int(first_row), n.value, _d(t), _d(v), C.byref(n)))
+        return t, v
+
+
 class _ParticleHeat:
     """particle batches and the heat exchange's particle side on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*); the object has _h, _cpl, _batch_n"""
     _AVG_PREFIX = "fy_solver"
@@ -331,7 +425,7 @@ class LduCase(C.Structure):
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
                 ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp), ("monitors", MonitorDesc),
-                ("solid_stats", C.c_int32), ("flow_control", FlowControlDesc)]
+                ("solid_stats", C.c_int32), ("flow_control", FlowControlDesc), ("wall_loads", WallLoadsDesc)]
 
 
 NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
@@ -375,7 +469,7 @@ class CaseDesc(C.Structure):
                 ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double),
                 ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("monitors", MonitorDesc),
-                ("solid_stats", C.c_int32)]
+                ("solid_stats", C.c_int32), ("wall_loads", WallLoadsDesc)]
 
 
 BC_WALL_FUNCTION, BC_NUT_CALCULATED = 2, 3
@@ -840,7 +934,7 @@ def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 
     return c
 
 
-class Solver(_Averages, _Monitors, _ParticleHeat):
+class Solver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
     """the icoFoamYade / pimpleFoamYade executables' time loop (icoFoamYade.C:65-149, pimpleFoamYade.C:60-114): step() is one
     pass of the loop body, including yadeCoupling.setParticleAction and setSourceZero."""
 
@@ -1227,6 +1321,14 @@ class FoamCase:
         f.argtypes = [C.c_void_p, C.c_void_p]
         _check(f(self._h, solver._h))
 
+    _WRITE_WALL_LOADS = "fy_foam_case_write_wall_loads"
+
+    def write_wall_loads(self, solver):
+        """append the rows the solver's wall loads have gathered since the last call to postProcessing/<object>/<start time name>/forces.dat | wallShearStress.dat | yPlus.dat"""
+        f = getattr(lib(), self._WRITE_WALL_LOADS)
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        _check(f(self._h, solver._h))
+
     _RESTORE = "fy_foam_case_restore_averages"
 
     def restore_averages(self, solver):
@@ -1288,6 +1390,7 @@ class GeneralFoamCase(FoamCase):
 
     _RESTORE = "fy_foam_case_restore_averages_ldu"
     _WRITE_MONITORS = "fy_foam_case_write_monitors_ldu"
+    _WRITE_WALL_LOADS = "fy_foam_case_write_wall_loads_ldu"
 
     def write(self, solver, time_name):
         _check(lib().fy_foam_case_write_time_ldu(self._h, solver._h, str(time_name).encode()))
@@ -1434,7 +1537,7 @@ class VirtualSlabs:
         self.solvers, self.comms = [], []
 
 
-class LduSolver(_Averages, _Monitors, _ParticleHeat):
+class LduSolver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
     """icoFoamYade's loop body on a general polyhedral mesh in OpenFOAM's addressing (fy_ldu_solver, include/foamyade_hip.h).  mesh: dict with points (n,3),
     face_offsets, face_points, owner, neighbour, n_cells, patch_start, patch_size (tests/poly_meshes.py builds them); u_bc / p_bc / values per patch; the
     controls are fy_ldu_case's (defaults: the icoFoam cavity tutorial's)"""
@@ -1536,7 +1639,7 @@ class LduSolver(_Averages, _Monitors, _ParticleHeat):
     def get(self, name):
         out = np.zeros(self._size(name))
         _check(lib().fy_ldu_solver_read_field_host(self._h, name.encode(), _d(out)))
-        return out.reshape(-1, 3) if name in ("C", "Cf", "Sf", "kvec", "sep", "U_boundary") else out
+        return out.reshape(-1, 3) if name in ("C", "Cf", "Sf", "kvec", "sep", "U_boundary", "wallShearStress_boundary") else out
 
     geometry = get
 

@@ -86,6 +86,16 @@ struct fy_foam_case {
     // names, and how many rows of the solver's history fy_foam_case_write_monitors has put into the object's .dat file
     struct MonMeta { std::string name, region; bool vol = true; std::vector<std::string> files; std::vector<int> ncomp; mutable int64_t rows_written = 0; };
     std::vector<MonMeta> monitors;
+    // ... and the forces / wallShearStress / yPlus objects (desc.wall_loads carries them; the solver numbers them forces first, then wallShearStress, then yPlus):
+    // kind 0 forces | 1 wallShearStress | 2 yPlus, the patch names in the order of the object's row, the rows fy_foam_case_write_wall_loads has written
+    struct WlMeta { std::string name; int kind = 0; std::vector<std::string> patches; mutable int64_t rows_written = 0; };
+    std::vector<WlMeta> wl_forces, wl_wss, wl_yplus;
+    std::vector<const WlMeta*> wall_loads() const {
+        std::vector<const WlMeta*> v;
+        for (const auto* l : {&wl_forces, &wl_wss, &wl_yplus}) for (const WlMeta& m : *l) v.push_back(&m);
+        return v;
+    }
+    std::string class_of_side[6];               // a block's patch type per side (wall | patch | symmetryPlane ...): the default patch set of wallShearStress / yPlus
 };
 
 namespace {
@@ -316,6 +326,7 @@ int read_block_mesh(fy_foam_case* c) {
             if (!c->patch_of_side[side].empty() && c->patch_of_side[side] != pd.first)
                 return fail(FY_ERR_UNSUPPORTED, "%s: side %d of the box is shared by the patches '%s' and '%s' (one boundary condition per side)", path.c_str(), side, c->patch_of_side[side].c_str(), pd.first.c_str());
             c->patch_of_side[side] = pd.first;
+            c->class_of_side[side] = ty.empty() ? "patch" : ty;
             const int a = side / 2, t1 = (a + 1) % 3, t2 = (a + 2) % 3;
             covered[side] += (fhi[t1] - flo[t1]) * (fhi[t2] - flo[t2]);
         }
@@ -445,6 +456,7 @@ int read_poly_mesh(fy_foam_case* c) {
             if (!c->patch_of_side[side].empty() && c->patch_of_side[side] != pd.first)
                 return fail(FY_ERR_UNSUPPORTED, "%s/boundary: side %d of the box is shared by the patches '%s' and '%s' (one boundary condition per side)", base.c_str(), side, c->patch_of_side[side].c_str(), pd.first.c_str());
             c->patch_of_side[side] = pd.first;
+            c->class_of_side[side] = ty;
             ++side_faces[(size_t)side];
         }
         if (nf > 0) c->patch_order.push_back(pd.first);
@@ -1093,6 +1105,101 @@ int read_monitor(fy_foam_case* c, const std::string& name, const std::string& ty
     return FY_OK;
 }
 
+// One forces / wallShearStress / yPlus object of controlDict `functions` [OF-6 forces, wallShearStress, yPlus as recalled] -> desc.wall_loads and c->wl_*.
+// forces: patches (...), rho rhoInf with rhoInf <v>, pRef (default 0), CofR; p, U, log, libs, enabled, writeControl | executeControl timeStep with writeInterval |
+// executeInterval are accepted and unused beyond the interval.  wallShearStress / yPlus: an optional patches (...), default every patch of type wall.  Everything else
+// is refused by name
+int read_wall_load(fy_foam_case* c, const std::string& name, const std::string& ty, const FoamDict* o, const std::string& where) {
+    const char* w = where.c_str();
+    const int kind = ty == "forces" ? 0 : ty == "wallShearStress" ? 1 : 2;
+    static const char* const common[] = {"type", "libs", "log", "enabled", "patches", "writeControl", "executeControl", "writeInterval", "executeInterval"};
+    static const char* const only_forces[] = {"rho", "rhoInf", "pRef", "CofR", "p", "U"};
+    const char* accepted = kind == 0 ? "type, libs, log, enabled, patches, rho rhoInf, rhoInf, pRef, CofR, p, U, writeControl | executeControl timeStep, writeInterval | executeInterval"
+                                     : "type, libs, log, enabled, patches, writeControl | executeControl timeStep, writeInterval | executeInterval";
+    for (const std::string& k : o->order) {
+        bool known = false;
+        for (const char* a : common) known = known || k == a;
+        if (kind == 0) for (const char* a : only_forces) known = known || k == a;
+        if (!known) return fail(FY_ERR_UNSUPPORTED, "%s: %s is not supported; accepted: %s", w, k.c_str(), accepted);
+    }
+    if (c->proc_count > 1)
+        return fail(FY_ERR_UNSUPPORTED, "%s: type %s is not available in a decomposed (-parallel) run; accepted: an undecomposed case on one domain, or 'enabled false'", w, ty.c_str());
+    fy_wall_loads_desc& wd = c->desc.wall_loads;
+    if (kind == 0 && wd.n_forces >= FY_WALL_LOADS_MAX_FORCES)
+        return fail(FY_ERR_UNSUPPORTED, "%s: more than %d forces objects; accepted: at most %d", w, FY_WALL_LOADS_MAX_FORCES, FY_WALL_LOADS_MAX_FORCES);
+    if (kind != 0 && (kind == 1 ? wd.wall_shear_stress.on : wd.y_plus.on))
+        return fail(FY_ERR_UNSUPPORTED, "%s: a second object of type %s (the first is '%s'); accepted: one enabled object of this type, with all patches in its list", w, ty.c_str(),
+                    (kind == 1 ? c->wl_wss : c->wl_yplus)[0].name.c_str());
+    if (name.size() >= sizeof(wd.forces[0].name)) return fail(FY_ERR_UNSUPPORTED, "%s: the object's name is longer than %zu characters; accepted: a shorter name", w, sizeof(wd.forces[0].name) - 1);
+    std::string word;
+    for (const char* key : {"writeControl", "executeControl"})
+        if (o->word(key, &word) && word != "timeStep") return fail(FY_ERR_UNSUPPORTED, "%s: %s %s is not supported; accepted: timeStep (with writeInterval N)", w, key, word.c_str());
+    double iv = 1, iv2 = 0;
+    const bool h1 = o->scalar("writeInterval", &iv), h2 = o->scalar("executeInterval", &iv2);
+    if (!h1 && h2) iv = iv2;
+    if ((h1 && h2 && iv != iv2) || !(iv >= 1) || iv != std::floor(iv) || iv > 1e9)
+        return fail(FY_ERR_UNSUPPORTED, "%s: writeInterval %g / executeInterval %g is not supported; accepted: one whole number of steps >= 1 for both", w, iv, h2 ? iv2 : iv);
+    // the patch set: the names listed, or (wallShearStress, yPlus) every patch of type wall
+    const std::vector<std::string> patches = field_patches(c);
+    std::string all;
+    for (const std::string& pn : patches) if (all.find(pn) == std::string::npos) all += (all.empty() ? "" : ", ") + pn;
+    std::vector<std::string> want;
+    if (const auto* pt = o->tokens("patches")) {
+        for (const std::string& t : *pt) if (t != "(" && t != ")") want.push_back(t);
+        if (want.empty()) return fail(FY_ERR_INVALID, "%s: the 'patches' list is empty; accepted: %s", w, all.c_str());
+    } else if (kind == 0) {
+        return fail(FY_ERR_INVALID, "%s: no 'patches ( <name> ... )' list; accepted: %s", w, all.c_str());
+    } else {
+        for (size_t q = 0; q < patches.size(); ++q) {
+            const std::string cls = c->general ? c->g_patch_class[q] : c->class_of_side[q];
+            if (cls == "wall" && std::find(want.begin(), want.end(), patches[q]) == want.end()) want.push_back(patches[q]);
+        }
+        if (want.empty()) return fail(FY_ERR_UNSUPPORTED, "%s: the mesh has no patch of type wall; accepted: patches ( <name> ... ) among %s", w, all.c_str());
+    }
+    fy_wall_patch_set set{};
+    fy_foam_case::WlMeta meta;
+    meta.name = name; meta.kind = kind;
+    for (const std::string& pn : want) {
+        if (std::find(meta.patches.begin(), meta.patches.end(), pn) != meta.patches.end()) return fail(FY_ERR_INVALID, "%s: patches: '%s' is listed twice", w, pn.c_str());
+        int found = -1;
+        for (size_t q = 0; q < patches.size(); ++q) if (patches[q] == pn) { if (found < 0) found = (int)q; set.sides |= 1 << q; }
+        if (found < 0) return fail(FY_ERR_UNSUPPORTED, "%s: patches: the mesh has no patch '%s'; accepted: %s", w, pn.c_str(), all.c_str());
+        if (c->general) {
+            if (c->g_patch_neighbour.size() > (size_t)found && c->g_patch_neighbour[(size_t)found] >= 0)
+                return fail(FY_ERR_UNSUPPORTED, "%s: patches: '%s' is a cyclic patch, whose faces are internal faces of the solver's mesh; accepted: patches of boundary faces", w, pn.c_str());
+            if (set.n_patches >= FY_WALL_LOADS_MAX_PATCHES) return fail(FY_ERR_UNSUPPORTED, "%s: more than %d patches; accepted: at most %d", w, FY_WALL_LOADS_MAX_PATCHES, FY_WALL_LOADS_MAX_PATCHES);
+            set.patches[set.n_patches++] = found;
+        }
+        meta.patches.push_back(pn);
+    }
+    if (c->general) set.sides = 0;
+    else {                                       // a block's rows run over the SIDES of the set, in the order x- x+ y- y+ z- z+: one row entry per side, named by its patch
+        meta.patches.clear();
+        static const char* const side_word[] = {"x-", "x+", "y-", "y+", "z-", "z+"};
+        for (int q = 0; q < 6; ++q)
+            if ((set.sides >> q) & 1) meta.patches.push_back(std::count(patches.begin(), patches.end(), patches[(size_t)q]) > 1 ? patches[(size_t)q] + ":" + side_word[q] : patches[(size_t)q]);
+    }
+    wd.start_time = c->start_time;
+    if (kind == 0) {
+        word.clear();
+        if (!o->word("rho", &word) || word != "rhoInf")
+            return fail(FY_ERR_UNSUPPORTED, "%s: rho %s is not supported; accepted: rho rhoInf (with rhoInf <value>: the solvers are incompressible)", w, word.empty() ? "(absent)" : word.c_str());
+        fy_forces_object fo{};
+        std::snprintf(fo.name, sizeof(fo.name), "%s", name.c_str());
+        fo.set = set; fo.interval = (int32_t)iv;
+        if (!o->scalar("rhoInf", &fo.rho) || !(fo.rho > 0)) return fail(FY_ERR_INVALID, "%s: rho rhoInf needs 'rhoInf <value>;' with a positive value", w);
+        if (o->has("pRef") && !o->scalar("pRef", &fo.p_ref)) return fail(FY_ERR_INVALID, "%s: pRef needs a number", w);
+        if (!o->vector3("CofR", fo.cofr)) return fail(FY_ERR_INVALID, "%s: no 'CofR (x y z);'", w);
+        wd.forces[wd.n_forces++] = fo;
+        c->wl_forces.push_back(meta);
+    } else {
+        fy_wall_field_object& fo = kind == 1 ? wd.wall_shear_stress : wd.y_plus;
+        fo.on = 1; fo.set = set; fo.interval = (int32_t)iv;
+        (kind == 1 ? c->wl_wss : c->wl_yplus).push_back(meta);
+    }
+    return FY_OK;
+}
+
 // controlDict `functions` [OF-6 functionObjectList; fieldAverage / fieldAverageItem as recalled]: one fieldAverage object -> desc.average (solver field names)
 // and c->avg_fields (file names); objects of other types are accepted and not run, their names kept.  Everything fieldAverage offers beyond the plain running
 // mean / prime2Mean is refused by name.  Called last in read_controls: which fields the case has depends on the solver and the turbulence model.
@@ -1100,6 +1207,7 @@ int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) 
     c->desc.average = fy_average_desc{};
     c->avg_name.clear(); c->avg_fields.clear(); c->ignored_functions.clear(); c->avg_restart_on_restart = false;
     c->desc.monitors = fy_monitor_desc{}; c->monitors.clear();
+    c->desc.wall_loads = fy_wall_loads_desc{}; c->wl_forces.clear(); c->wl_wss.clear(); c->wl_yplus.clear();
     const FoamDict* fn = d.subdict("functions");
     if (!fn) return FY_OK;
     for (const std::string& name : fn->order) {
@@ -1108,11 +1216,13 @@ int read_functions(fy_foam_case* c, const FoamDict& d, const std::string& path) 
         std::string ty;
         o->word("type", &ty);
         const bool monitor = ty == "volFieldValue" || ty == "surfaceFieldValue";
-        if (ty != "fieldAverage" && !monitor) { c->ignored_functions.push_back(name + " (type " + (ty.empty() ? "?" : ty) + ")"); continue; }
+        const bool wall_load = ty == "forces" || ty == "wallShearStress" || ty == "yPlus";
+        if (ty != "fieldAverage" && !monitor && !wall_load) { c->ignored_functions.push_back(name + " (type " + (ty.empty() ? "?" : ty) + ")"); continue; }
         bool enabled = true;
         if (o->boolean("enabled", &enabled) && !enabled) continue;
         const std::string where = path + ": functions." + name;
         if (monitor) { FY_TRY(read_monitor(c, name, ty, o, where)); continue; }
+        if (wall_load) { FY_TRY(read_wall_load(c, name, ty, o, where)); continue; }
         const char* w = where.c_str();
         if (!c->avg_name.empty())
             return fail(FY_ERR_UNSUPPORTED, "%s: a second object of type fieldAverage (the first is '%s'); accepted: one enabled fieldAverage object, with all fields in its list", w, c->avg_name.c_str());
@@ -1731,6 +1841,64 @@ int write_monitors(const fy_foam_case* c, Layout layout, Rows rows, Measure meas
     }
     return FY_OK;
 }
+
+// The rows the solver's wall loads have gathered since the last call -> postProcessing/<object>/<start time name>/forces.dat | wallShearStress.dat | yPlus.dat (the
+// layout of OpenFOAM-6's files as recalled, unpinned: '#' header lines, then per sample -- forces: time and the four vectors Fp Fv Mp Mv as (x y z); wallShearStress:
+// one line per patch, time, patch, min vector, max vector; yPlus: one line per patch, time, patch, min, max, average)
+template <class Layout, class Rows>
+int write_wall_loads(const fy_foam_case* c, Layout layout, Rows rows) {
+    const std::vector<const fy_foam_case::WlMeta*> metas = c->wall_loads();
+    for (size_t q = 0; q < metas.size(); ++q) {
+        const fy_foam_case::WlMeta& m = *metas[q];
+        int32_t nv = 0;
+        FY_TRY(layout((int)q, &nv));
+        const int per = m.kind == 0 ? 12 : m.kind == 1 ? 6 : 3;
+        if (nv != (m.kind == 0 ? 12 : per * (int)m.patches.size())) return fail(FY_ERR_INVALID, "fy_foam_case_write_wall_loads: object '%s' has %d values in the solver (was it created from this case?)", m.name.c_str(), nv);
+        int64_t have = 0;
+        FY_TRY(rows((int)q, m.rows_written, 0, nullptr, nullptr, &have));
+        std::string dir = join(c->dir, "postProcessing");
+        for (const std::string& part : {std::string(), m.name, c->start_name}) {
+            if (!part.empty()) dir = join(dir, part);
+            if (mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) return fail(FY_ERR_INVALID, "cannot create %s", dir.c_str());
+        }
+        const std::string path = join(dir, m.kind == 0 ? "forces.dat" : m.kind == 1 ? "wallShearStress.dat" : "yPlus.dat");
+        FILE* f = std::fopen(path.c_str(), m.rows_written == 0 ? "w" : "a");
+        if (!f) return fail(FY_ERR_INVALID, "cannot write %s", path.c_str());
+        const int pr = c->write_precision;
+        if (m.rows_written == 0) {
+            if (m.kind == 0) {
+                const fy_forces_object& fo = c->desc.wall_loads.forces[q];
+                std::fprintf(f, "# Forces\n# CofR       : (%.*g %.*g %.*g)\n# rhoInf     : %.*g\n# pRef       : %.*g\n# patches    :", pr, fo.cofr[0], pr, fo.cofr[1], pr, fo.cofr[2], pr, fo.rho, pr, fo.p_ref);
+                for (const std::string& pn : m.patches) std::fprintf(f, " %s", pn.c_str());
+                std::fprintf(f, "\n# Time\tforces(pressure viscous)\tmoment(pressure viscous)\n");
+            } else if (m.kind == 1) std::fprintf(f, "# Wall shear stress\n# Time\tpatch\tmin\tmax\n");
+            else std::fprintf(f, "# y+ ()\n# Time\tpatch\tmin\tmax\taverage\n");
+        }
+        if (have > 0) {
+            std::vector<double> t((size_t)have), v((size_t)have * (size_t)nv);
+            int64_t got = 0;
+            const int rc = rows((int)q, m.rows_written, have, t.data(), v.data(), &got);
+            if (rc != FY_OK) { std::fclose(f); return rc; }
+            for (int64_t r = 0; r < got; ++r) {
+                const double* x = v.data() + (size_t)r * nv;
+                if (m.kind == 0) {
+                    std::fprintf(f, "%.*g", pr, t[(size_t)r]);
+                    for (int g = 0; g < 4; ++g) std::fprintf(f, "\t(%.*g %.*g %.*g)", pr, x[3 * g], pr, x[3 * g + 1], pr, x[3 * g + 2]);
+                    std::fprintf(f, "\n");
+                    continue;
+                }
+                for (size_t p = 0; p < m.patches.size(); ++p, x += per) {
+                    std::fprintf(f, "%.*g\t%s", pr, t[(size_t)r], m.patches[p].c_str());
+                    if (m.kind == 1) std::fprintf(f, "\t(%.*g %.*g %.*g)\t(%.*g %.*g %.*g)\n", pr, x[0], pr, x[1], pr, x[2], pr, x[3], pr, x[4], pr, x[5]);
+                    else std::fprintf(f, "\t%.*g\t%.*g\t%.*g\n", pr, x[0], pr, x[1], pr, x[2]);
+                }
+            }
+            m.rows_written += got;
+        }
+        if (std::fclose(f) != 0) return fail(FY_ERR_INVALID, "cannot write %s", path.c_str());
+    }
+    return FY_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1992,6 +2160,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->drag_law = d.drag_law; out->force_models = d.force_models; out->solid_stats = d.solid_stats;
     out->average = d.average;
     out->monitors = d.monitors;
+    out->wall_loads = d.wall_loads;
     out->flow_control = c->flow;
     out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
     return FY_OK;
@@ -2093,6 +2262,22 @@ int fy_foam_case_write_monitors_ldu(const fy_foam_case* c, fy_ldu_solver* s) {
                               }
                               return FY_OK;
                           });
+}
+
+int fy_foam_case_wall_loads_count(const fy_foam_case* c) { return c ? (int)c->wall_loads().size() : 0; }
+
+int fy_foam_case_write_wall_loads(const fy_foam_case* c, fy_solver* s) {
+    if (!c || !s) return fail(FY_ERR_INVALID, "fy_foam_case_write_wall_loads: null argument");
+    if (c->general) return fail(FY_ERR_INVALID, "fy_foam_case_write_wall_loads: the case holds a general mesh (fy_foam_case_write_wall_loads_ldu)");
+    return write_wall_loads(c, [s](int q, int32_t* nv) { return fy_solver_wall_loads_layout(s, q, nv, nullptr, 0); },
+                            [s](int q, int64_t first, int64_t mx, double* t, double* v, int64_t* n) { return fy_solver_get_wall_load_rows(s, q, first, mx, t, v, n); });
+}
+
+int fy_foam_case_write_wall_loads_ldu(const fy_foam_case* c, fy_ldu_solver* s) {
+    if (!c || !s) return fail(FY_ERR_INVALID, "fy_foam_case_write_wall_loads_ldu: null argument");
+    if (!c->general) return fail(FY_ERR_INVALID, "fy_foam_case_write_wall_loads_ldu: the case was opened as a block (fy_foam_case_write_wall_loads)");
+    return write_wall_loads(c, [s](int q, int32_t* nv) { return fy_ldu_solver_wall_loads_layout(s, q, nv, nullptr, 0); },
+                            [s](int q, int64_t first, int64_t mx, double* t, double* v, int64_t* n) { return fy_ldu_solver_get_wall_load_rows(s, q, first, mx, t, v, n); });
 }
 
 int fy_foam_case_close(fy_foam_case* c) {

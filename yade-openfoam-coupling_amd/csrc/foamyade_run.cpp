@@ -52,12 +52,12 @@ static void print_coupling(int drag_law, unsigned force_models, int solid_stats)
 }
 
 // controlDict functions: what is averaged (the solver's create applies it), and one line per function object of another type -- opened, never run
-static void print_functions(const fy_foam_case* fc, const fy_average_desc& av, const fy_monitor_desc& mon) {
+static void print_functions(const fy_foam_case* fc, const fy_average_desc& av, const fy_monitor_desc& mon, const fy_wall_loads_desc& wl) {
     fy_foam_case_info info;
     if (fy_foam_case_info_get(fc, &info) != FY_OK) return;
     for (int i = 0; i < info.n_ignored_functions; ++i) {
         char name[256];
-        if (fy_foam_case_ignored_function(fc, i, name, (int)sizeof(name)) == FY_OK) std::printf("functions: %s is not run (only fieldAverage, volFieldValue and surfaceFieldValue are implemented)\n", name);
+        if (fy_foam_case_ignored_function(fc, i, name, (int)sizeof(name)) == FY_OK) std::printf("functions: %s is not run (only fieldAverage, volFieldValue, surfaceFieldValue, forces, wallShearStress and yPlus are implemented)\n", name);
     }
     if (av.n_items > 0) {
         std::printf("fieldAverage:");
@@ -70,6 +70,11 @@ static void print_functions(const fy_foam_case* fc, const fy_average_desc& av, c
                                                             mon.objects[i].n_fields, mon.objects[i].n_fields == 1 ? "" : "s");
         std::printf("\n");
     }
+    if (wl.n_forces > 0 || wl.wall_shear_stress.on || wl.y_plus.on) {
+        std::printf("Wall loads:");
+        for (int i = 0; i < wl.n_forces; ++i) std::printf(" %.32s (forces)", wl.forces[i].name);
+        std::printf("%s%s\n", wl.wall_shear_stress.on ? " wallShearStress" : "", wl.y_plus.on ? " yPlus" : "");
+    }
 }
 
 // icoFoamYade on a general mesh: the same loop around fy_ldu_solver (one domain)
@@ -80,7 +85,7 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     if (fy_foam_case_poly_mesh(fc, &pm) != FY_OK || fy_foam_case_ldu_desc(fc, &lc) != FY_OK || fy_foam_case_info_get(fc, &info) != FY_OK) return die("reading the case");
     std::printf("             %d points, %d faces (%d internal), %d cells, %d patches\n", pm.n_points, pm.n_faces, pm.n_internal_faces, pm.n_cells, pm.n_patches);
     print_coupling(lc.drag_law, lc.force_models, lc.solid_stats);
-    print_functions(fc, lc.average, lc.monitors);
+    print_functions(fc, lc.average, lc.monitors, lc.wall_loads);
     if (lc.flow_control.on)
         std::printf("meanVelocityForce: Ubar (%g %g %g), relaxation %g, superficial %s, initial pressure gradient = %.17g\n", lc.flow_control.ubar[0], lc.flow_control.ubar[1], lc.flow_control.ubar[2],
                     lc.flow_control.relaxation, lc.flow_control.superficial ? "on" : "off", lc.flow_control.gradient0);
@@ -121,9 +126,9 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
             std::printf("Pressure gradient source: uncorrected Ubar = %.12g, pressure gradient = %.17g\n\n", ub, grad);
         }
         if (info.write_interval_steps > 0 && k % info.write_interval_steps == 0)
-            if (fy_foam_case_write_time_ldu(fc, s, tname) != FY_OK || fy_foam_case_write_monitors_ldu(fc, s) != FY_OK) return die("writing the time directory");
+            if (fy_foam_case_write_time_ldu(fc, s, tname) != FY_OK || fy_foam_case_write_monitors_ldu(fc, s) != FY_OK || fy_foam_case_write_wall_loads_ldu(fc, s) != FY_OK) return die("writing the time directory");
     }
-    if (fy_foam_case_write_monitors_ldu(fc, s) != FY_OK) return die("writing the monitors");
+    if (fy_foam_case_write_monitors_ldu(fc, s) != FY_OK || fy_foam_case_write_wall_loads_ldu(fc, s) != FY_OK) return die("writing the monitors");
     std::printf("End\n");
     fy_ldu_solver_destroy(s);
     fy_foam_case_close(fc);
@@ -242,12 +247,13 @@ int main(int argc, char** argv) {
     if (master)
         std::printf("Create mesh: %d x %d x %d cells of %g m, %s on the six sides x- x+ y- y+ z- z+: %s %s %s %s %s %s\n", cd.nx, cd.ny, cd.nz, cd.dx,
                     "patches", info.patch_of_side[0], info.patch_of_side[1], info.patch_of_side[2], info.patch_of_side[3], info.patch_of_side[4], info.patch_of_side[5]);
-    if (master) { print_coupling(cd.drag_law, cd.force_models, cd.solid_stats); print_functions(fc, cd.average, cd.monitors); }
+    if (master) { print_coupling(cd.drag_law, cd.force_models, cd.solid_stats); print_functions(fc, cd.average, cd.monitors, cd.wall_loads); }
     if (master && cd.thermal.on)
         std::printf("Heat transfer: nusseltModel %s, Cp %g, kappa %g, Prt %g, particleTemperature %g, particleCp %g, beta %g, TRef %g, div(T) %s\n",
                     cd.thermal.nusselt_law == FY_NUSSELT_GUNN ? "Gunn" : "RanzMarshall", cd.thermal.cp, cd.thermal.kappa, cd.thermal.prt, cd.thermal.particle_temperature,
                     cd.thermal.particle_cp, cd.thermal.beta, cd.thermal.T_ref, cd.thermal.T_convection_scheme == FY_CONVECTION_UPWIND ? "upwind" : "linear");
     fy_solver* s = nullptr;
+    const bool wall_loads = fy_foam_case_wall_loads_count(fc) > 0;          // (one domain: a slab's create refuses them)
     if ((comm ? fy_solver_create_slab(&cd, trp, device, comm, &s) : fy_solver_create(&cd, trp, device, &s)) != FY_OK) return die("fy_solver_create");
     // a slab owns the z-planes [srank nz / ssize, (srank + 1) nz / ssize): a contiguous run of the block's cells, `first` cells in
     // (the field files hold the whole block, or -- processor directories -- exactly this rank's cells)
@@ -329,8 +335,9 @@ int main(int argc, char** argv) {
             tp_resets = now;
         }
         if (info.write_interval_steps > 0 && k % info.write_interval_steps == 0)
-            if (write_time(tname) != FY_OK || (cd.monitors.n_objects > 0 && fy_foam_case_write_monitors(fc, s) != FY_OK)) return die("writing the time directory");
+            if (write_time(tname) != FY_OK || (cd.monitors.n_objects > 0 && fy_foam_case_write_monitors(fc, s) != FY_OK) || (wall_loads && fy_foam_case_write_wall_loads(fc, s) != FY_OK)) return die("writing the time directory");
     }
+    if (wall_loads && fy_foam_case_write_wall_loads(fc, s) != FY_OK) return die("writing the wall loads");
     if (cd.monitors.n_objects > 0 && fy_foam_case_write_monitors(fc, s) != FY_OK) return die("writing the monitors");      // (one domain: a slab's create has refused them)
     if (master) std::printf("End\n");
     fy_solver_destroy(s);

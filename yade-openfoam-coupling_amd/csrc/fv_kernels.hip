@@ -1895,6 +1895,102 @@ __global__ __launch_bounds__(256) void k_monitor_faces(FvGeo g, MonFaceTable t, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ wall loads (wall_loads.hpp): forces, wallShearStress, yPlus
+// coordinate of node q / of the middle of cell q along axis d
+__device__ __forceinline__ double wl_node(const FvGeo& g, const WlBlockGeo& w, int d, int q) {
+#if FY_FVK_GRADED
+    return w.xn[d][q];
+#else
+    return w.org[d] + q * g.dx;
+#endif
+}
+__device__ __forceinline__ double wl_mid(const FvGeo& g, const WlBlockGeo& w, int d, int q) {
+#if FY_FVK_GRADED
+    return 0.5 * (w.xn[d][q] + w.xn[d][q + 1]);
+#else
+    return w.org[d] + (q + 0.5) * g.dx;
+#endif
+}
+// face r of side (D, S) as wl_face_emit wants it: the owner's Gauss-linear gradient of U gathered through the structured neighbours as the stress term forms it
+// (u_face_value, grad_row), s = (U_b - U_P) delta with the momentum equation's wall coefficient (geo_rhalf), p_b (pbv), nut_b (nut_boundary), y (geo_ywall), k_P
+template <int D, int S>
+__device__ __forceinline__ void wl_block_face(const FvGeo& g, const WlBlockGeo& wg, int r, const double* __restrict__ p, const CFace3& psn, const double* __restrict__ U, WlFace& f) {
+    int i, j, k;
+    if (D == 0) { j = r % g.ny; k = r / g.ny; i = S ? g.nx - 1 : 0; }
+    else if (D == 1) { i = r % g.nx; k = r / g.nx; j = S ? g.ny - 1 : 0; }
+    else { i = r % g.nx; j = r / g.nx; k = S ? g.nz - 1 : 0; }
+    const int ijk[3] = {i, j, k};
+    const int c = cidx(g, i, j, k), patch = 2 * D + S;
+    f.patch = patch;
+    f.A = geo_Af(g, D, i, j, k);
+    f.Sf[0] = f.Sf[1] = f.Sf[2] = 0.0;
+    f.Sf[D] = S ? f.A : -f.A;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) f.Cf[a] = a == D ? wl_node(g, wg, a, S ? ndim(g, a) : 0) : wl_mid(g, wg, a, ijk[a]);
+    const double uc[3] = {U[3 * (size_t)c], U[3 * (size_t)c + 1], U[3 * (size_t)c + 2]};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        double fv[2][3];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const bool ob = onb(g, d, s, i, j, k);
+            const double* un = ob ? nullptr : U + 3 * (size_t)(c + (s ? stride_of(g, d) : -stride_of(g, d)));
+            u_face_value(g, d, s, ob, ijk[d], uc, un, fv[s]);
+        }
+        grad_row(g, d, ijk[d], fv, f.G);
+    }
+    double ub[3];
+    Ub(g, U, c, patch, ub);
+    const double delta = geo_rhalf(g, D, ijk[D]);
+    for (int q = 0; q < 3; ++q) f.s[q] = (ub[q] - uc[q]) * delta;
+    f.pb = p ? pbv(g, p, psn, c, D, S, cface(g, D, S, i, j, k)) : 0.0;
+    f.nut_b = g.nut ? nut_boundary(g, patch, c) : 0.0;
+    f.nu = g.nu;
+    f.y = geo_ywall(g, D, c);
+    f.wall_fn = g.nut && g.kturb && g.nut_bc[patch] == 2;
+    f.kP = f.wall_fn ? g.kturb[c] : 0.0;
+    f.cmu25 = g.wf_cmu25;
+}
+__device__ __forceinline__ void wl_block_face_of(const FvGeo& g, const WlBlockGeo& wg, int side, int r, const double* __restrict__ p, const CFace3& psn, const double* __restrict__ U, WlFace& f) {
+    switch (side) {
+        case 0: wl_block_face<0, 0>(g, wg, r, p, psn, U, f); break;
+        case 1: wl_block_face<0, 1>(g, wg, r, p, psn, U, f); break;
+        case 2: wl_block_face<1, 0>(g, wg, r, p, psn, U, f); break;
+        case 3: wl_block_face<1, 1>(g, wg, r, p, psn, U, f); break;
+        case 4: wl_block_face<2, 0>(g, wg, r, p, psn, U, f); break;
+        default: wl_block_face<2, 1>(g, wg, r, p, psn, U, f); break;
+    }
+}
+// fy::WallLoads' face kernel: one lane per boundary face (the read-outs' order), blockIdx.y = the object; an object that is not due this step leaves at once
+__global__ __launch_bounds__(256) void k_wall_loads(FvGeo g, WlTable t, WlBlockGeo wg, const double* __restrict__ p, CFace3 psn, const double* __restrict__ U,
+                                                    double* __restrict__ wss, double* __restrict__ yplus, double* __restrict__ partials) {
+    if (!((t.due >> blockIdx.y) & 1u)) return;
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    int side = 0, r = 0;
+    const bool have = bface_side(g, b, side, r);
+    const WlObj& o = t.o[blockIdx.y];
+    WlFace f{};
+    f.patch = have ? side : -1;
+    bool member = false;
+    for (int q = 0; q < o.np; ++q) member = member || o.patch[q] == f.patch;
+    if (have && member) wl_block_face_of(g, wg, side, r, p, psn, U, f);      // (a face outside the object's set is not gathered: wl_face_emit stores its zeros)
+    wl_face_emit(o, have, f, b, wss, yplus, partials, (int)blockIdx.y * kWlComps * kMonKinds);
+}
+// "nut_boundary" and "nearWallDist" per boundary face
+__global__ __launch_bounds__(256) void k_wall_readouts(FvGeo g, double* __restrict__ nutb, double* __restrict__ yw) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    int side, r;
+    if (!bface_side(g, b, side, r)) return;
+    const int D = side >> 1, S = side & 1;
+    int i, j, k;
+    if (D == 0) { j = r % g.ny; k = r / g.ny; i = S ? g.nx - 1 : 0; }
+    else if (D == 1) { i = r % g.nx; k = r / g.nx; j = S ? g.ny - 1 : 0; }
+    else { i = r % g.nx; j = r / g.nx; k = S ? g.nz - 1 : 0; }
+    const int c = cidx(g, i, j, k);
+    if (nutb) nutb[b] = g.nut ? nut_boundary(g, side, c) : 0.0;
+    if (yw) yw[b] = geo_ywall(g, D, c);
+}
+
 // launch grids of the cell sweeps: the whole owned range, or the block window the geometry names (FvGeo::win_nblk: a range of z-planes, for the
 // sweeps that run beside a halo exchange)
 inline int fv_grid(const FvGeo& g) { return g.win_nblk > 0 ? g.win_nblk : div_up(g.Nc, 256); }
@@ -2132,6 +2228,18 @@ int launch_boundary_values(hipStream_t s, FvGeo g, const double* p, CFace3 psn, 
 int launch_monitor_faces(hipStream_t s, FvGeo g, MonFaceTable t, const double* p, CFace3 psn, const double* U, const double* T, TPatch te, CFace3 phi, double* partials, int nblk) {
     if (t.n <= 0) return FY_OK;
     hipLaunchKernelGGL(k_monitor_faces, dim3(nblk, t.n), dim3(256), 0, s, g, t, p, psn, U, T, te, phi, partials);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_wall_loads(hipStream_t s, FvGeo g, WlTable t, WlBlockGeo wg, const double* p, CFace3 psn, const double* U, double* wss, double* yplus, double* partials, int nblk) {
+    if (t.n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_wall_loads, dim3(nblk, t.n), dim3(256), 0, s, g, t, wg, p, psn, U, wss, yplus, partials);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_wall_readouts(hipStream_t s, FvGeo g, double* nutb, double* yw) {
+    const int nb = 2 * (g.ny * g.nz + g.nx * g.nz + g.nx * g.ny);
+    hipLaunchKernelGGL(k_wall_readouts, dim3(div_up(nb, 256)), dim3(256), 0, s, g, nutb, yw);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "fv_linalg_kernels.hpp"
 #include "monitors.hpp"
+#include "wall_loads.hpp"
 
 namespace fy {
 
@@ -82,6 +83,9 @@ struct ScalarEqn { int upwind; int bc[6]; double val[6]; double D, rPrt, rRhoCp;
 // T's six patch conditions as device arrays (bc[6]: 0 zeroGradient | 1 fixedValue, val[6]), for the kernels that take a boundary face's side from the lane
 struct TPatch { const int* bc; const double* val; };
 struct TurbEqn { int mode; double ck, ce, delta, c1, c2, c3, sigma, xmin, relax; int upwind; int bc[6]; double val[6]; int wall[6]; double cmu75, cmu25, kappa; };
+
+// where the block lies, for the face centres of the wall loads' moments: the origin (uniform block) or the node coordinates per axis (graded block: device arrays of n + 1)
+struct WlBlockGeo { double org[3]; const double* xn[3]; };
 
 // The launchers that take an FvGeo exist twice: fy::launch_* for the uniform block (dx, Af, V constants in every kernel) and fy::gr::launch_* for a
 // graded block (per-axis cell sizes, linear-interpolation weights, |Sf| / |d| per face) -- ONE source, fv_kernels.hip, compiled once per geometry

@@ -100,3 +100,7 @@ int launch_p_ghost_uz(hipStream_t s, FvGeo g, CFace3 rAUf, CFace3 alphaf, PMat A
 int launch_boundary_values(hipStream_t s, FvGeo g, const double* p, CFace3 psn, const double* U, const double* T, TPatch te, double* pb, double* ub, double* tb);
 // fy::Monitors' face kernel (monitors.hpp): the five partials of every wanted component of every surface object, nblk blocks per object
 int launch_monitor_faces(hipStream_t s, FvGeo g, MonFaceTable t, const double* p, CFace3 psn, const double* U, const double* T, TPatch te, CFace3 phi, double* partials, int nblk);
+// fy::WallLoads' face kernel (wall_loads.hpp): every due object's per-face outputs and the partials of its components, nblk blocks per object
+int launch_wall_loads(hipStream_t s, FvGeo g, WlTable t, WlBlockGeo wg, const double* p, CFace3 psn, const double* U, double* wss, double* yplus, double* partials, int nblk);
+// "nut_boundary" / "nearWallDist" per boundary face in the order of launch_boundary_values; a null output is skipped
+int launch_wall_readouts(hipStream_t s, FvGeo g, double* nutb, double* yw);

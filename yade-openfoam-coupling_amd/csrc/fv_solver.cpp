@@ -325,6 +325,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     if (c->solid_stats) FY_TRY(set_solid_statistics(1));                      // couplingProperties solidStatistics (before fieldAverage and the monitors, which may ask for its fields)
     if (c->average.n_items) FY_TRY(set_field_average(&c->average));           // controlDict functions: fieldAverage
     if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));            // volFieldValue / surfaceFieldValue
+    if (!WallLoads::empty(&c->wall_loads)) FY_TRY(set_wall_loads(&c->wall_loads));      // forces / wallShearStress / yPlus
     return FY_OK;
 }
 
@@ -390,6 +391,34 @@ int Solver::set_monitors(const fy_monitor_desc* d) {
                              if (mask <= 0 || mask > 63) { *why = mask == 0 ? "the side mask is empty (bit 2 d + s for the sides x- x+ y- y+ z- z+)" : "side mask " + std::to_string(mask) + " (6 bits: x- x+ y- y+ z- z+)"; return 0; }
                              return 1;
                          });
+}
+
+int Solver::set_wall_loads(const fy_wall_loads_desc* d) {
+    FY_HIP(hipSetDevice(device));
+    if (!WallLoads::empty(d) && comm->size > 1) {
+        wl.off();
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_set_wall_loads: wall loads are not available on z-slabs (fy_solver_create_slab over %d ranks, foamYadeHip_mpi -parallel): "
+                                        "run the case on one domain", comm->size);
+    }
+    if (!WallLoads::empty(d) && g.graded && !d_xn[0].p) {                       // node coordinates: the origin plus the running sum of the cell sizes
+        for (int a = 0; a < 3; ++a) {
+            std::vector<double> x(h_host[a].size() + 1);
+            x[0] = cs.origin[a];
+            for (size_t q = 0; q < h_host[a].size(); ++q) x[q + 1] = x[q] + h_host[a][q];
+            FY_TRY(d_xn[a].alloc_exact(x.size()));
+            FY_HIP(hipMemcpy(d_xn[a].p, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+    }
+    const size_t nb = 2 * ((size_t)g.ny * g.nz + (size_t)g.nx * g.nz + (size_t)g.nx * g.ny);
+    return wl.configure(d, nb, cs.nu > 0 || g.nut != nullptr, stream, "fy_solver_set_wall_loads",
+                        [](const fy_wall_patch_set& set, const char* on, int* patches, int* np, std::vector<std::string>* names) {
+                            static const char* const side[] = {"x-", "x+", "y-", "y+", "z-", "z+"};
+                            if (set.sides == 0) return fail(FY_ERR_INVALID, "fy_solver_set_wall_loads: object '%s': the patch set is empty (sides: bit 2 d + s for x- x+ y- y+ z- z+)", on);
+                            if (set.sides < 0 || set.sides > 63) return fail(FY_ERR_INVALID, "fy_solver_set_wall_loads: object '%s': sides %d (6 bits: x- x+ y- y+ z- z+)", on, set.sides);
+                            *np = 0;
+                            for (int q = 0; q < 6; ++q) if ((set.sides >> q) & 1) { patches[(*np)++] = q; names->push_back(side[q]); }
+                            return (int)FY_OK;
+                        });
 }
 
 // fold the block partials, all-reduce over the slabs, read back
@@ -842,6 +871,8 @@ int Solver::step() {
     mon.elapsed += cs.dt;
     if (mon.on()) FY_TRY(mon.sample(stream, Vcell.p, g.V, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); },
                                     [this](const MonFaceTable& t, double* pf, int nblk) { return FVK(launch_monitor_faces, stream, g, t, p.p, C3(psn), U.p, th.T.p, TPatch{d_Tbc.p, d_Tval.p}, phi_now(), pf, nblk); }));
+    if (wl.on()) FY_TRY(wl.sample(stream, wl.start_time + mon.elapsed, [this](const WlTable& t, double* pf, int nblk, double* wss, double* yplus) {
+        return FVK(launch_wall_loads, stream, g, t, wl_geo(), p.p, C3(psn), U.p, wss, yplus, pf, nblk); }));
     if (hold_sources) sources_pending = true;                                              // reset deferred to the next step (fy_solver_hold_sources)
     else FY_TRY(cpl->c.set_source_zero());                                                // icoFoamYade.C:147, pimpleFoamYade.C:109
     if (timing) tim[3].stop(stream);
@@ -862,7 +893,7 @@ int Solver::step() {
         st.ms_total = tim[3].ms();
         st.ms_other = st.ms_total - st.ms_particle - st.ms_momentum - st.ms_pressure;
         for (auto& k : kc) k.collect();
-        avg.clock.collect(); mon.clock.collect();
+        avg.clock.collect(); mon.clock.collect(); wl.m.clock.collect();
         if (th.on) { th.clk_coeff.collect(); th.clk_flux.collect(); th.clk_asm.collect(); th.clk_buoy.collect(); }
         if (ss.on) ss.clock.collect();
     }
@@ -948,6 +979,18 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
         TPatch tp;
         FY_TRY(t_patch(&tp));
         FY_TRY(FVK(launch_boundary_values, stream, g, p.p, C3(psn), U.p, th.T.p, tp, s == "p_boundary" ? b.p : nullptr, s == "U_boundary" ? b.p : nullptr, s == "T_boundary" ? b.p : nullptr));
+        *ptr = b.p;
+        return FY_OK;
+    }
+    if (wl.lookup(s, ptr, count)) return FY_OK;                  // wallShearStress_boundary, yPlus_boundary as the last sample left them
+    if (s == "nut_boundary" || s == "nearWallDist") {            // formed on request: nut_boundary() / geo_ywall per boundary face (zeros when laminar)
+        if (comm->size > 1) return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is not available on z-slabs (fy_solver_create_slab over %d ranks)", s.c_str(), comm->size);
+        const size_t nb = 2 * ((size_t)g.ny * g.nz + (size_t)g.nx * g.nz + (size_t)g.nx * g.ny);
+        DevBuf<double>& b = s == "nut_boundary" ? bndNut : bndY;
+        *count = nb;
+        FY_HIP(hipSetDevice(device));
+        if (!b.p) FY_TRY(b.alloc_exact(nb));
+        FY_TRY(FVK(launch_wall_readouts, stream, g, s == "nut_boundary" ? b.p : nullptr, s == "nearWallDist" ? b.p : nullptr));
         *ptr = b.p;
         return FY_OK;
     }

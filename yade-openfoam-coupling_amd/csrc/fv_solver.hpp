@@ -307,6 +307,12 @@ struct Solver {
     DevBuf<int> d_Tbc;
     int t_patch(TPatch* out);      // T's patch conditions on the device (uploaded once; null arrays without thermal)
     int set_monitors(const fy_monitor_desc* d);
+    // wall loads (wall_loads.hpp), sampled where the monitors are; d_xn: the node coordinates of a graded block (the face centres of the moments); bndNut / bndY: the
+    // read-outs "nut_boundary" / "nearWallDist", formed on request
+    WallLoads wl;
+    DevBuf<double> d_xn[3], bndNut, bndY;
+    WlBlockGeo wl_geo() const { return WlBlockGeo{{cs.origin[0], cs.origin[1], cs.origin[2]}, {d_xn[0].p, d_xn[1].p, d_xn[2].p}}; }
+    int set_wall_loads(const fy_wall_loads_desc* d);
     Thermal th;
     int thermal_create(const fy_case_desc* c);          // validation + allocation, from create()
     int heat_coefficients();

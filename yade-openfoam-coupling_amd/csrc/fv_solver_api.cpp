@@ -138,6 +138,8 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
         return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (a diagnostic: rebuilt at every momentum assembly / corrector)", name);
     if (name && fy::SolidStats::is_name(name))
         return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (formed from the particles of the last coupling call)", name);
+    // ("nut_boundary", "wallShearStress_boundary", "yPlus_boundary": the _boundary rule above)
+    if (name && std::strcmp(name, "nearWallDist") == 0) return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: 'nearWallDist' is read-only (it follows from the mesh)");
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
     {
@@ -180,6 +182,14 @@ int fy_solver_get_monitor_rows(fy_solver* s, int object, int64_t first_row, int6
     FY_S(s);
     FY_HIP(hipSetDevice(s->s.device));
     return s->s.mon.get_rows(s->s.stream, object, first_row, max_rows, times, values, n_rows);
+}
+
+int fy_solver_set_wall_loads(fy_solver* s, const fy_wall_loads_desc* d) { FY_S(s); return s->s.set_wall_loads(d); }
+int fy_solver_wall_loads_layout(fy_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_S(s); return s->s.wl.m.layout(object, n_values, labels, cap); }
+int fy_solver_get_wall_load_rows(fy_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
+    FY_S(s);
+    FY_HIP(hipSetDevice(s->s.device));
+    return s->s.wl.m.get_rows(s->s.stream, object, first_row, max_rows, times, values, n_rows);
 }
 
 int fy_solver_set_particle_temperatures_host(fy_solver* s, int batch, const double* Tp) { FY_S(s); return s->s.set_particle_temperatures(batch, Tp, false); }
@@ -260,6 +270,7 @@ int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     for (auto& k : s->s.kc) { k.reset(); k.on = on != 0; }
     s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
     s->s.mon.clock.reset(); s->s.mon.clock.on = on != 0;
+    s->s.wl.m.clock.reset(); s->s.wl.m.clock.on = on != 0;
     for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm, &s->s.th.clk_buoy}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
     s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0;
     return FY_OK;
@@ -283,6 +294,7 @@ int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_
     FY_S(s);
     const std::string k = kernel ? kernel : "";
     if (k == "monitors" && total_ms && launches) { *total_ms = s->s.mon.clock.total_ms; *launches = s->s.mon.clock.launches; return FY_OK; }
+    if (k == "wall_loads" && total_ms && launches && s->s.wl.on()) { *total_ms = s->s.wl.m.clock.total_ms; *launches = s->s.wl.m.clock.launches; return FY_OK; }
     if (k == "solid_stats" && total_ms && launches) { *total_ms = s->s.ss.clock.total_ms; *launches = s->s.ss.clock.launches; return FY_OK; }
     if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }
     if ((k == "heat_coeff" || k == "heat_flux" || k == "T_assemble" || k == "buoyancy") && total_ms && launches) {

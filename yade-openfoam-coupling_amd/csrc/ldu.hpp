@@ -13,6 +13,7 @@
 #include "../../include/foamyade_hip.h"
 #include "common.hpp"
 #include "monitors.hpp"
+#include "wall_loads.hpp"
 
 namespace fy {
 
@@ -171,6 +172,8 @@ int launch_ldu_nut_boundary(hipStream_t s, LduGeo g, LduPim P, double* out);    
 int launch_ldu_boundary_values(hipStream_t s, LduGeo g, const double* p, const double* U, LduTEqn E, double* pb, double* ub, double* tb);
 // fy::Monitors' face kernel (monitors.hpp): the five partials of every wanted component of every surface object, nblk blocks per object
 int launch_ldu_monitor_faces(hipStream_t s, LduGeo g, MonFaceTable t, const double* p, const double* U, LduTEqn E, const double* phi, double* partials, int nblk);
+// fy::WallLoads' face kernel (wall_loads.hpp): every due object's per-face outputs and the partials of its components, nblk blocks per object; ywall: nearWallDist per boundary face
+int launch_ldu_wall_loads(hipStream_t s, LduGeo g, LduPim P, WlTable t, const double* p, const double* U, const double* ywall, double* wss, double* yplus, double* partials, int nblk);
 int launch_ldu_forces(hipStream_t s, LduGeo g, LduPim P, const double* rAU, double* rAUf, double* phiForces);
 int launch_ldu_ssf_predictor(hipStream_t s, LduGeo g, const double* phiForces, const double* rAUf, const double* p, const double* gradp, double* ssf);
 int launch_ldu_reconstruct(hipStream_t s, LduGeo g, const double* ssf, const double* base, const double* scale, double* out);

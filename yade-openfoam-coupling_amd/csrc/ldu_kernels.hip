@@ -871,6 +871,56 @@ __global__ __launch_bounds__(256) void k_ldu_monitor_faces(LduGeo g, MonFaceTabl
         mon_block_reduce_store(v, partials, slot0 + q * kMonKinds, (int)gridDim.x, (int)blockIdx.x);
     }
 }
+// fy::WallLoads' face kernel (wall_loads.hpp): one lane per boundary face, blockIdx.y = the object; an object that is not due this step leaves at once.  The lane of a
+// face on one of the object's patches gathers the Gauss-linear gradient of U in the face's owner cell through the slot coefficients (as k_ldu_grad_vec forms it: the
+// owner only, no field pass), s = (U_b - U_P) deltaCoeffs, p_b, nut_b, y and k_P; wl_face_emit does the rest
+__global__ __launch_bounds__(256) void k_ldu_wall_loads(LduGeo g, LduPim P, WlTable t, const double* __restrict__ p, const double* __restrict__ U, const double* __restrict__ ywall,
+                                                        double* __restrict__ wss, double* __restrict__ yplus, double* __restrict__ partials) {
+    if (!((t.due >> blockIdx.y) & 1u)) return;
+    const WlObj& o = t.o[blockIdx.y];
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    const bool have = b < g.nFaces - g.nInt;
+    WlFace f{};
+    f.patch = have ? g.patch_of[b] : -1;
+    bool member = false;
+    for (int q = 0; q < o.np; ++q) member = member || o.patch[q] == f.patch;
+    if (have && member) {
+        const int fc = g.nInt + b, c = g.own[fc];
+        const D3 S = ld3(g.Sf, fc), X = ld3(g.Cf, fc);
+        f.Sf[0] = S.x; f.Sf[1] = S.y; f.Sf[2] = S.z;
+        f.Cf[0] = X.x; f.Cf[1] = X.y; f.Cf[2] = X.z;
+        f.A = g.magSf[fc];
+        const size_t n = (size_t)g.nCells, wn = (size_t)g.Wall * n;
+        const D3 uc = ld3(U, c);
+        const double g0[3] = {g.gG0[c], g.gG0[n + c], g.gG0[2 * n + c]}, u0[3] = {uc.x, uc.y, uc.z};
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) f.G[3 * i + j] = g0[i] * u0[j];
+        for (int k = 0; k < g.Wall; ++k) {
+            const size_t e = (size_t)k * n + c;
+            const int nb = g.en[e];
+            if (nb == -2) break;
+            const D3 uf = nb >= 0 ? ld3(U, nb) : Ub(g, U, g.ef[e]);
+            const double s[3] = {g.gB[e], g.gB[wn + e], g.gB[2 * wn + e]}, u[3] = {uf.x, uf.y, uf.z};
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) f.G[3 * i + j] += s[i] * u[j];
+        }
+        const D3 ub = Ub(g, U, fc);
+        const double dc = g.dcNO[fc];
+        f.s[0] = (ub.x - uc.x) * dc; f.s[1] = (ub.y - uc.y) * dc; f.s[2] = (ub.z - uc.z) * dc;
+        f.pb = pbv(g, p, fc);
+        f.nut_b = ldu_nut_b(g, P, fc);
+        f.nu = g.nu;
+        f.y = ywall ? ywall[b] : 0.0;
+        f.wall_fn = P.nut && P.k && P.nut_bc[f.patch] == FY_BC_WALL_FUNCTION;
+        f.kP = f.wall_fn ? P.k[c] : 0.0;
+        f.cmu25 = P.wf_cmu25;
+    }
+    wl_face_emit(o, have, f, b, wss, yplus, partials, (int)blockIdx.y * kWlComps * kMonKinds);
+}
 // bound(k, kMin) (fv_closures.hpp: bound_value; fvc::average = sum |Sf| k_f / sum |Sf|, formed only where pos0(-k) = 1), then correctNut()
 __global__ __launch_bounds__(256) void k_ldu_k_bound_nut(LduGeo g, LduPim P, LduKEqn K, const double* __restrict__ x3, double* __restrict__ X, double* __restrict__ nut) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -1220,6 +1270,12 @@ int launch_ldu_nut_boundary(hipStream_t s, LduGeo g, LduPim P, double* out) {
 int launch_ldu_boundary_values(hipStream_t s, LduGeo g, const double* p, const double* U, LduTEqn E, double* pb, double* ub, double* tb) {
     if (g.nFaces == g.nInt) return FY_OK;
     hipLaunchKernelGGL(k_ldu_boundary_values, dim3(div_up(g.nFaces - g.nInt, 256)), dim3(256), 0, s, g, p, U, E, pb, ub, tb);
+    FY_LAUNCH_CHECK();
+    return FY_OK;
+}
+int launch_ldu_wall_loads(hipStream_t s, LduGeo g, LduPim P, WlTable t, const double* p, const double* U, const double* ywall, double* wss, double* yplus, double* partials, int nblk) {
+    if (t.n <= 0) return FY_OK;
+    hipLaunchKernelGGL(k_ldu_wall_loads, dim3(nblk, t.n), dim3(256), 0, s, g, P, t, p, U, ywall, wss, yplus, partials);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

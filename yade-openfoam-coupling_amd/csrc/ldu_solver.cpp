@@ -120,6 +120,43 @@ struct LduSolver {
                              });
     }
 
+    // wall loads (wall_loads.hpp), sampled where the monitors are.  A patch set is a list of patch indices; nearWallDist (ywall) is then formed for the selected patches
+    // as well as for the wall-function patches (wf_on: what setup_wall_functions switched on)
+    WallLoads wl;
+    std::vector<char> wf_on;
+    int set_wall_loads(const fy_wall_loads_desc* d) {
+        FY_HIP(hipSetDevice(device));
+        std::vector<char> sel = wf_on;
+        sel.resize((size_t)hm.nPatches, 0);
+        FY_TRY(wl.configure(d, (size_t)(nf - ni), cs.nu > 0 || les, stream, "fy_ldu_solver_set_wall_loads",
+                            [this](const fy_wall_patch_set& set, const char* on, int* patches, int* np, std::vector<std::string>* names) {
+                                const char* who = "fy_ldu_solver_set_wall_loads";
+                                if (set.n_patches == 0) return fail(FY_ERR_INVALID, "%s: object '%s': the patch set is empty (patches)", who, on);
+                                if (set.n_patches < 0 || set.n_patches > FY_WALL_LOADS_MAX_PATCHES)
+                                    return fail(FY_ERR_INVALID, "%s: object '%s': %d patches (1 to FY_WALL_LOADS_MAX_PATCHES = %d)", who, on, set.n_patches, FY_WALL_LOADS_MAX_PATCHES);
+                                for (int q = 0; q < set.n_patches; ++q) {
+                                    const int pa = set.patches[q];
+                                    if (pa < 0 || pa >= hm.nPatches) return fail(FY_ERR_INVALID, "%s: object '%s': patch %d does not exist (the mesh has %d)", who, on, pa, hm.nPatches);
+                                    if (hm.psize[(size_t)pa] == 0) return fail(FY_ERR_INVALID, "%s: object '%s': patch %d is a cyclic patch or has no faces (a cyclic patch is folded into internal faces)", who, on, pa);
+                                    for (int r = 0; r < q; ++r) if (set.patches[r] == pa) return fail(FY_ERR_INVALID, "%s: object '%s': patch %d is listed twice", who, on, pa);
+                                    patches[q] = pa; names->push_back("patch" + std::to_string(pa));
+                                }
+                                *np = set.n_patches;
+                                return (int)FY_OK;
+                            }));
+        for (int q = 0; q < wl.tab.n; ++q)                                    // yPlus reads y on its patches
+            if (wl.tab.o[q].kind == WL_YPLUS) for (int r = 0; r < wl.tab.o[q].np; ++r) sel[(size_t)wl.tab.o[q].patch[r]] = 1;
+        // nearWallDist follows from the CURRENT configuration alone: the wall-function patches plus the yPlus object's, whatever was configured before
+        std::vector<char> now_on((size_t)hm.nPatches, 0);
+        for (size_t b = 0; b < ywall.size(); ++b) if (ywall[b] != 0.0) now_on[(size_t)hm.patch_of[b]] = 1;
+        if (sel != now_on) {                                        // (the wall-function patches' distances come out as they were: the same statement on the same data)
+            FY_HIP(hipStreamSynchronize(stream));
+            hm.near_wall_dist(sel, &ywall);
+            FY_TRY(up(d_ywall, ywall));
+        }
+        return FY_OK;
+    }
+
     // flow-rate control (fy_flow_control_desc; ldu_flow_control.hip; DESIGN.md section 3 "Flow-rate control").  Off: nothing allocated, nothing launched.  The host
     // keeps no value of the state: `cur` says which of the two records the step reads now, and flips at each momentum assembly
     struct Flow {
@@ -395,6 +432,7 @@ struct LduSolver {
         if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));        // volFieldValue / surfaceFieldValue
         cs.flow_control = fy_flow_control_desc{};
         if (c->flow_control.on) FY_TRY(set_flow_control(&c->flow_control, "fy_ldu_solver_create"));      // couplingProperties meanVelocityForce
+        if (!WallLoads::empty(&c->wall_loads)) FY_TRY(set_wall_loads(&c->wall_loads));                   // forces / wallShearStress / yPlus
         return FY_OK;
     }
 
@@ -448,6 +486,7 @@ struct LduSolver {
         if (!(c->wf_kappa > 0 && c->wf_E > 0)) return fail(FY_ERR_INVALID, "fy_ldu_solver: wall-function constants kappa, E must be positive");
         wf_yplam = wall_yplus_lam(c->wf_kappa, c->wf_E);
         hm.near_wall_dist(on, &ywall);
+        wf_on = on;
         FY_TRY(up(d_ywall, ywall));
         std::vector<int32_t> cnt((size_t)nc, 0), wall_of((size_t)nc, -1), cell, off(1, 0), face;
         for (int b = 0; b < nb; ++b) if (wf_eps[(size_t)hm.patch_of[(size_t)b]]) ++cnt[(size_t)hm.own[(size_t)(ni + b)]];
@@ -714,6 +753,8 @@ struct LduSolver {
         mon.elapsed += cs.dt;
         if (mon.on()) FY_TRY(mon.sample(stream, g.V, 0.0, [this](const std::string& nm, int* comp) { return avg_source(nm, comp); },
                                         [this](const MonFaceTable& t, double* pf, int nblk) { return launch_ldu_monitor_faces(stream, g, t, p.p, U.p, th.eq, phi.p, pf, nblk); }));
+        if (wl.on()) FY_TRY(wl.sample(stream, wl.start_time + mon.elapsed, [this](const WlTable& t, double* pf, int nblk, double* wss, double* yplus) {
+            return launch_ldu_wall_loads(stream, g, pimple ? P() : LduPim{}, t, p.p, U.p, d_ywall.p, wss, yplus, pf, nblk); }));
         if (hold_sources) sources_pending = true;                                                                 // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147)
         else FY_TRY(cpl->c.set_source_zero());                                                                    // :147
         tim[1].stop(stream);
@@ -726,6 +767,7 @@ struct LduSolver {
         st.ms_particle = tim[0].ms(); st.ms_total = tim[1].ms();
         if (ss.on) ss.clock.collect();
         if (fc.on) fc.clock.collect();
+        if (wl.on()) wl.m.clock.collect();
         return FY_OK;
     }
 
@@ -767,6 +809,7 @@ struct LduSolver {
             *ptr = b.p;
             return FY_OK;
         }
+        if (wl.lookup(s, ptr, count)) return FY_OK;                                // wallShearStress_boundary, yPlus_boundary as the last sample left them
         if (s == "nut_boundary") {                                                 // formed on request: nut_b as ldu_nut_b gives it now
             *count = les ? (size_t)(nf - ni) : 0;
             if (*count) {
@@ -893,13 +936,15 @@ int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver* s, int on) {
     FY_LS(s);
     s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0;
     s->s.fc.clock.reset(); s->s.fc.clock.on = on != 0;
+    s->s.wl.m.clock.reset(); s->s.wl.m.clock.on = on != 0;
     return FY_OK;
 }
 int fy_ldu_solver_get_kernel_timing(fy_ldu_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
     FY_LS(s);
     const std::string k = kernel ? kernel : "";
+    if (k == "wall_loads" && s->s.wl.on() && total_ms && launches) { *total_ms = s->s.wl.m.clock.total_ms; *launches = s->s.wl.m.clock.launches; return FY_OK; }
     const bool flow = k == "flow_control" && s->s.fc.on;
-    if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "");
+    if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats%s%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "", s->s.wl.on() ? ", wall_loads" : "");
     const fy::KernelClock& c = flow ? s->s.fc.clock : s->s.ss.clock;
     *total_ms = c.total_ms; *launches = c.launches;
     return FY_OK;
@@ -915,6 +960,13 @@ int fy_ldu_solver_get_monitor_rows(fy_ldu_solver* s, int object, int64_t first_r
     FY_LS(s);
     FY_HIP(hipSetDevice(s->s.device));
     return s->s.mon.get_rows(s->s.stream, object, first_row, max_rows, times, values, n_rows);
+}
+int fy_ldu_solver_set_wall_loads(fy_ldu_solver* s, const fy_wall_loads_desc* d) { FY_LS(s); return s->s.set_wall_loads(d); }
+int fy_ldu_solver_wall_loads_layout(fy_ldu_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_LS(s); return s->s.wl.m.layout(object, n_values, labels, cap); }
+int fy_ldu_solver_get_wall_load_rows(fy_ldu_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
+    FY_LS(s);
+    FY_HIP(hipSetDevice(s->s.device));
+    return s->s.wl.m.get_rows(s->s.stream, object, first_row, max_rows, times, values, n_rows);
 }
 int fy_ldu_solver_set_particle_temperatures_host(fy_ldu_solver* s, int batch, const double* Tp) { FY_LS(s); return s->s.th.part.set_temperatures(s->s.cpl->c, s->s.device, s->s.stream, batch, Tp, false); }
 int fy_ldu_solver_set_particle_temperatures_device(fy_ldu_solver* s, int batch, const double* d_Tp) { FY_LS(s); return s->s.th.part.set_temperatures(s->s.cpl->c, s->s.device, s->s.stream, batch, d_Tp, true); }
