@@ -74,7 +74,7 @@ struct orc_fv_stats {
 
 namespace {
 
-// The arithmetic type.  liboracle.so computes in double; liboracle_ld.so is this file alone with -DORC_REAL='long double', the reference the FV sweeps are held
+// The arithmetic type.  liboracle.so computes in double; liboracle_ld.so is this file (and ldu_oracle.cpp) with -DORC_REAL='long double', the reference the FV sweeps are held
 // to (tests/test_fv_sweeps_*.py).  The C interface (orc_fv_case, orc_fv_stats, every array that crosses it) is double in both.  Literals such as 2.0 / 3.0 stay
 // double-rounded in the wide build too: they are the constants the kernels use.
 #ifdef ORC_REAL

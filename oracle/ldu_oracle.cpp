@@ -15,20 +15,33 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
-typedef std::vector<double> vec;
-const double SMALL = 1e-15, VSMALL = 1e-300;
+// The arithmetic type.  liboracle.so computes in double; liboracle_ld.so compiles this file (and fv_oracle.cpp) with -DORC_REAL='long double': the reference the
+// general-mesh FV sweeps are held to (tests/test_ldu_sweeps_*.py).  vec, V3, geometry, matrices, solvers and reductions are `real`; the C interface (orc_ldu_case,
+// orc_ldu_stats, every array that crosses it) is double in both builds, and so are the tolerances and SMALL / VSMALL.  Constants that no binary fraction
+// holds (1 / 3, 2 / 3, 1 / 10 ...) are formed in `real`: in the double build that is the literal's value, bit for bit
+#ifdef ORC_REAL
+typedef ORC_REAL real;
+#else
+typedef double real;
+#endif
+inline real rmax(real a, real b) { return (a < b) ? b : a; }      // (std::max / std::min, whose two arguments must agree in type)
+inline real rmin(real a, real b) { return (b < a) ? b : a; }
+typedef std::vector<real> vec;
+const real SMALL = 1e-15, VSMALL = 1e-300;
 
-struct V3 { double x, y, z; };
+struct V3 { real x, y, z; };
 inline V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 inline V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-inline double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+inline V3 operator*(real s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
+inline real dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 inline V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-inline double mag(V3 a) { return std::sqrt(dot(a, a)); }
+inline real mag(V3 a) { return std::sqrt(dot(a, a)); }
 
 extern "C" struct orc_ldu_case {
     int solver;                 // 0 icoFoamYade, 1 pimpleFoamYade
@@ -78,18 +91,18 @@ struct Ldu {
     V3 face_centre_of(int f) const {
         const int n = foff[f + 1] - foff[f];
         const int* q = &fpts[foff[f]];
-        if (n == 3) return (1.0 / 3.0) * (pts[q[0]] + pts[q[1]] + pts[q[2]]);
+        if (n == 3) return (real(1) / 3) * (pts[q[0]] + pts[q[1]] + pts[q[2]]);
         V3 fc{0, 0, 0};
         for (int a = 0; a < n; ++a) fc = fc + pts[q[a]];
-        fc = (1.0 / n) * fc;
+        fc = (real(1) / n) * fc;
         V3 sumAc{0, 0, 0};
-        double sumA = 0.0;
+        real sumA = 0.0;
         for (int a = 0; a < n; ++a) {
             const V3 p0 = pts[q[a]], p1 = pts[q[(a + 1) % n]];
-            const double aa = mag(cross(p1 - p0, fc - p0));
+            const real aa = mag(cross(p1 - p0, fc - p0));
             sumA += aa; sumAc = sumAc + aa * (p0 + p1 + fc);
         }
-        return sumA < VSMALL ? fc : (1.0 / 3.0) * ((1.0 / sumA) * sumAc);
+        return sumA < VSMALL ? fc : (real(1) / 3) * ((1.0 / sumA) * sumAc);
     }
     // [OF-6 cyclicPolyPatch / cyclicFvPatch], translational, faces matched one to one in order: the pair (face i of A, face i of B) is ONE face between the two cells behind
     // it; owner = the lower-numbered cell, the face's points those of that cell's half; delta = patchD - nbrPatchD puts the neighbour at C_N + (Cf_own half - Cf_other half).
@@ -144,22 +157,22 @@ struct Ldu {
     std::vector<int> nut_bc; vec nut_val;
     vec kturb; std::vector<int> k_bc; vec k_val;      // LES kEqn, RAS kEpsilon
     vec epsturb; std::vector<int> eps_bc; vec eps_val; // RAS kEpsilon
-    double eb_of(int pa, int c) const { return eps_bc[pa] == 1 ? eps_val[pa] : epsturb[c]; }
+    real eb_of(int pa, int c) const { return eps_bc[pa] == 1 ? eps_val[pa] : epsturb[c]; }
     bool nut_live = false;                             // correctNut() has run: a `calculated` nut patch carries the model's expression, before that the file's value
     int k_iters = 0;
-    double kb_of(int pa, int c) const { return k_bc[pa] == 1 ? k_val[pa] : kturb[c]; }
-    double les_delta(int c) const { return cs.les_delta_coeff * std::cbrt(V[c]); }
+    real kb_of(int pa, int c) const { return k_bc[pa] == 1 ? k_val[pa] : kturb[c]; }
+    real les_delta(int c) const { return cs.les_delta_coeff * std::cbrt(V[c]); }
     // nut on boundary face f (patch pa, cell c): zeroGradient, fixedValue, or calculated [OF-6 GeometricField::operator=: nut_ = Ck sqrt(k_) delta assigns the patches too]
-    double nut_bnd(int pa, int c) const {
+    real nut_bnd(int pa, int c) const {
         if (nut.empty()) return 0.0;
         if (nut_bc[pa] == 1 || (nut_bc[pa] == 3 && !nut_live)) return nut_val[pa];
-        if (nut_bc[pa] == 3 && cs.turbulence_model == 3) { const double kb = kb_of(pa, c); return cs.ras_cmu * (kb * kb) / eb_of(pa, c); }
+        if (nut_bc[pa] == 3 && cs.turbulence_model == 3) { const real kb = kb_of(pa, c); return cs.ras_cmu * (kb * kb) / eb_of(pa, c); }
         if (nut_bc[pa] == 3) return cs.les_ck * std::sqrt(kb_of(pa, c)) * les_delta(c);
         return nut[c];
     }
     bool pimple = false;
     orc_ldu_stats st{};
-    double cumulative = 0.0;
+    real cumulative = 0.0;
     bool adjust_phi_failed = false;
 
     // ------------------------------------------------------------------------------------------------ geometry [OF-6 primitiveMesh*.C]
@@ -169,22 +182,22 @@ struct Ldu {
             const int n = foff[f + 1] - foff[f];
             const int* q = &fpts[foff[f]];
             if (n == 3) {
-                Cf[f] = (1.0 / 3.0) * (pts[q[0]] + pts[q[1]] + pts[q[2]]);
+                Cf[f] = (real(1) / 3) * (pts[q[0]] + pts[q[1]] + pts[q[2]]);
                 Sf[f] = 0.5 * cross(pts[q[1]] - pts[q[0]], pts[q[2]] - pts[q[0]]);
             } else {
                 V3 fc{0, 0, 0};
                 for (int a = 0; a < n; ++a) fc = fc + pts[q[a]];
-                fc = (1.0 / n) * fc;
+                fc = (real(1) / n) * fc;
                 V3 sumN{0, 0, 0}, sumAc{0, 0, 0};
-                double sumA = 0.0;
+                real sumA = 0.0;
                 for (int a = 0; a < n; ++a) {
                     const V3 p0 = pts[q[a]], p1 = pts[q[(a + 1) % n]];
                     const V3 c = p0 + p1 + fc;
                     const V3 nn = cross(p1 - p0, fc - p0);
-                    const double aa = mag(nn);
+                    const real aa = mag(nn);
                     sumN = sumN + nn; sumA += aa; sumAc = sumAc + aa * c;
                 }
-                Cf[f] = sumA < VSMALL ? fc : (1.0 / 3.0) * ((1.0 / sumA) * sumAc);
+                Cf[f] = sumA < VSMALL ? fc : (real(1) / 3) * ((1.0 / sumA) * sumAc);
                 Sf[f] = 0.5 * sumN;
             }
             magSf[f] = mag(Sf[f]);
@@ -193,33 +206,33 @@ struct Ldu {
         for (int f = 0; f < nFaces; ++f) { cfaces[own[f]].push_back(f); if (f < nInt) cfaces[nei[f]].push_back(f); }
         std::vector<V3> cEst(nCells, V3{0, 0, 0});
         // (a folded cyclic face seen from its neighbour cell lies at that cell's own half: Cf - sep)
-        for (int c = 0; c < nCells; ++c) { for (int f : cfaces[c]) cEst[c] = cEst[c] + (f < nInt && nei[f] == c ? Cf[f] - sepf(f) : Cf[f]); cEst[c] = (1.0 / cfaces[c].size()) * cEst[c]; }
+        for (int c = 0; c < nCells; ++c) { for (int f : cfaces[c]) cEst[c] = cEst[c] + (f < nInt && nei[f] == c ? Cf[f] - sepf(f) : Cf[f]); cEst[c] = (real(1) / cfaces[c].size()) * cEst[c]; }
         C.assign(nCells, V3{0, 0, 0}); V.assign(nCells, 0.0);
         for (int f = 0; f < nFaces; ++f) {
             {
                 const int c = own[f];
-                const double pyr3 = std::max(dot(Sf[f], Cf[f] - cEst[c]), VSMALL);
+                const real pyr3 = rmax(dot(Sf[f], Cf[f] - cEst[c]), VSMALL);
                 const V3 pc = 0.75 * Cf[f] + 0.25 * cEst[c];
                 C[c] = C[c] + pyr3 * pc; V[c] += pyr3;
             }
             if (f < nInt) {
                 const int c = nei[f];
                 const V3 cfn = Cf[f] - sepf(f);
-                const double pyr3 = std::max(dot(Sf[f], cEst[c] - cfn), VSMALL);
+                const real pyr3 = rmax(dot(Sf[f], cEst[c] - cfn), VSMALL);
                 const V3 pc = 0.75 * cfn + 0.25 * cEst[c];
                 C[c] = C[c] + pyr3 * pc; V[c] += pyr3;
             }
         }
-        for (int c = 0; c < nCells; ++c) { C[c] = (1.0 / V[c]) * C[c]; V[c] *= (1.0 / 3.0); }
+        for (int c = 0; c < nCells; ++c) { C[c] = (1.0 / V[c]) * C[c]; V[c] *= (real(1) / 3); }
         // surfaceInterpolation [OF-6]: weights, nonOrthDeltaCoeffs, nonOrthCorrectionVectors
         w.assign(nInt, 0.5); dcNO.assign(nFaces, 0.0); kvec.assign(nInt, V3{0, 0, 0});
         for (int f = 0; f < nInt; ++f) {
             const V3 cn = C[nei[f]] + sepf(f);
-            const double sOwn = std::fabs(dot(Sf[f], Cf[f] - C[own[f]])), sNei = std::fabs(dot(Sf[f], cn - Cf[f]));
+            const real sOwn = std::fabs(dot(Sf[f], Cf[f] - C[own[f]])), sNei = std::fabs(dot(Sf[f], cn - Cf[f]));
             w[f] = sNei / (sOwn + sNei);
             const V3 d = cn - C[own[f]];
             const V3 n = (1.0 / magSf[f]) * Sf[f];
-            dcNO[f] = 1.0 / std::max(dot(n, d), 0.05 * mag(d));
+            dcNO[f] = 1.0 / rmax(dot(n, d), (real(5) / 100) * mag(d));
             kvec[f] = n - dcNO[f] * d;
         }
         for (int f = nInt; f < nFaces; ++f) {                  // fvPatch::deltaCoeffs on a non-coupled patch: 1 / (nf & (Cf - Cn)); no correction vector
@@ -240,7 +253,7 @@ struct Ldu {
         }
         return uc;
     }
-    double pb_val(int f) const {
+    real pb_val(int f) const {
         const int pa = patch_of[f - nInt];
         if (p_bc[pa] == 1) return p_val[pa];
         if (p_bc[pa] == 2 && pimple) return p[own[f]] + psn[f - nInt] / dcNO[f];      // fixedFluxPressure: a fixed-gradient patch, p_b = p_P + snGrad / deltaCoeffs
@@ -252,7 +265,7 @@ struct Ldu {
     template <class B> void grad_scalar(const vec& s, B bval, std::vector<V3>& g) const {
         g.assign(nCells, V3{0, 0, 0});
         for (int f = 0; f < nInt; ++f) {
-            const double sf = w[f] * s[own[f]] + (1.0 - w[f]) * s[nei[f]];
+            const real sf = w[f] * s[own[f]] + (1.0 - w[f]) * s[nei[f]];
             g[own[f]] = g[own[f]] + sf * Sf[f]; g[nei[f]] = g[nei[f]] - sf * Sf[f];
         }
         for (int f = nInt; f < nFaces; ++f) g[own[f]] = g[own[f]] + bval(f) * Sf[f];
@@ -261,8 +274,8 @@ struct Ldu {
     // fvc::grad(U): T[c][3 i + j] = d_i U_j
     void grad_vector(const vec& F, vec& T) const {
         T.assign(9 * (size_t)nCells, 0.0);
-        auto add = [&](int c, V3 S, V3 u, double sgn) {
-            const double s[3] = {S.x, S.y, S.z}, uu[3] = {u.x, u.y, u.z};
+        auto add = [&](int c, V3 S, V3 u, real sgn) {
+            const real s[3] = {S.x, S.y, S.z}, uu[3] = {u.x, u.y, u.z};
             for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T[9 * (size_t)c + 3 * i + j] += sgn * s[i] * uu[j];
         };
         for (int f = 0; f < nInt; ++f) {
@@ -305,7 +318,7 @@ struct Ldu {
             // fvc::reconstruct's tensor per cell: inv(sum_f Sf Sf / |Sf|) [OF-6 fvcReconstruct.C]
             vec T(9 * nc, 0.0);
             for (int f = 0; f < nFaces; ++f) {
-                const double sv[3] = {Sf[f].x, Sf[f].y, Sf[f].z};
+                const real sv[3] = {Sf[f].x, Sf[f].y, Sf[f].z};
                 for (int side = 0; side < (f < nInt ? 2 : 1); ++side) {
                     const int c = side ? nei[f] : own[f];
                     for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) T[9 * (size_t)c + 3 * a + b] += sv[a] * sv[b] / magSf[f];
@@ -313,8 +326,8 @@ struct Ldu {
             }
             recon.assign(9 * nc, 0.0);
             for (size_t c = 0; c < nc; ++c) {
-                const double* t = &T[9 * c]; double* q = &recon[9 * c];
-                const double det = t[0] * (t[4] * t[8] - t[5] * t[7]) - t[1] * (t[3] * t[8] - t[5] * t[6]) + t[2] * (t[3] * t[7] - t[4] * t[6]);
+                const real* t = &T[9 * c]; real* q = &recon[9 * c];
+                const real det = t[0] * (t[4] * t[8] - t[5] * t[7]) - t[1] * (t[3] * t[8] - t[5] * t[6]) + t[2] * (t[3] * t[7] - t[4] * t[6]);
                 q[0] = (t[4] * t[8] - t[5] * t[7]) / det; q[1] = (t[2] * t[7] - t[1] * t[8]) / det; q[2] = (t[1] * t[5] - t[2] * t[4]) / det;
                 q[3] = (t[5] * t[6] - t[3] * t[8]) / det; q[4] = (t[0] * t[8] - t[2] * t[6]) / det; q[5] = (t[2] * t[3] - t[0] * t[5]) / det;
                 q[6] = (t[3] * t[7] - t[4] * t[6]) / det; q[7] = (t[1] * t[6] - t[0] * t[7]) / det; q[8] = (t[0] * t[4] - t[1] * t[3]) / det;
@@ -334,13 +347,13 @@ struct Ldu {
         vec sumPhi(nCells, 0.0);
         for (int f = 0; f < nInt; ++f) { sumPhi[own[f]] += std::fabs(phi[f]); sumPhi[nei[f]] += std::fabs(phi[f]); }
         for (int f = nInt; f < nFaces; ++f) sumPhi[own[f]] += std::fabs(phi[f]);
-        double mx = 0, sm = 0, tv = 0;
-        for (int c = 0; c < nCells; ++c) { mx = std::max(mx, sumPhi[c] / V[c]); sm += sumPhi[c]; tv += V[c]; }
+        real mx = 0, sm = 0, tv = 0;
+        for (int c = 0; c < nCells; ++c) { mx = rmax(mx, sumPhi[c] / V[c]); sm += sumPhi[c]; tv += V[c]; }
         st.courant_max = 0.5 * mx * cs.dt; st.courant_mean = 0.5 * (sm / tv) * cs.dt;
         if (pimple && cs.adjust_time_step) {                     // setDeltaT.H [OF-6]
-            const double maxDeltaTFact = cs.max_co / (st.courant_max + SMALL);
-            const double deltaTFact = std::min(std::min(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
-            cs.dt = std::min(deltaTFact * cs.dt, cs.max_delta_t);
+            const real maxDeltaTFact = cs.max_co / (st.courant_max + SMALL);
+            const real deltaTFact = rmin(rmin(maxDeltaTFact, 1 + (real(1) / 10) * maxDeltaTFact), real(12) / 10);
+            cs.dt = rmin(deltaTFact * cs.dt, cs.max_delta_t);
         }
         st.delta_t = cs.dt;
         Uold = U; phiOld = phi;                                  // runTime++ : old-time fields
@@ -360,19 +373,19 @@ struct Ldu {
             if (f < nInt) {
                 const int n = nei[f];
                 const V3 uf = w[f] * at(U, o) + (1.0 - w[f]) * at(U, n);
-                const double kk[3] = {kvec[f].x, kvec[f].y, kvec[f].z};
+                const real kk[3] = {kvec[f].x, kvec[f].y, kvec[f].z};
                 const V3 du = at(U, n) - at(U, o);
-                const double d3[3] = {du.x, du.y, du.z}, u3[3] = {uf.x, uf.y, uf.z};
+                const real d3[3] = {du.x, du.y, du.z}, u3[3] = {uf.x, uf.y, uf.z};
                 for (int j = 0; j < 3; ++j) {
-                    double cj = 0.0;
+                    real cj = 0.0;
                     for (int i = 0; i < 3; ++i) cj += kk[i] * (w[f] * vGrad[9 * (size_t)o + 3 * i + j] + (1.0 - w[f]) * vGrad[9 * (size_t)n + 3 * i + j]);
-                    const double lap = alphaf[f] * magSf[f] * (dcNO[f] * d3[j] + cj);
+                    const real lap = alphaf[f] * magSf[f] * (dcNO[f] * d3[j] + cj);
                     ddtU[3 * (size_t)o + j] += phi[f] * u3[j]; ddtU[3 * (size_t)n + j] -= phi[f] * u3[j];
                     divT[3 * (size_t)o + j] += lap; divT[3 * (size_t)n + j] -= lap;
                 }
             } else {
                 const V3 ub = Ub(U, f), d = ub - at(U, o);
-                const double u3[3] = {ub.x, ub.y, ub.z}, d3[3] = {d.x, d.y, d.z};
+                const real u3[3] = {ub.x, ub.y, ub.z}, d3[3] = {d.x, d.y, d.z};
                 for (int j = 0; j < 3; ++j) { ddtU[3 * (size_t)o + j] += phi[f] * u3[j]; divT[3 * (size_t)o + j] += alphaf[f] * magSf[f] * dcNO[f] * d3[j]; }
             }
         }
@@ -383,7 +396,7 @@ struct Ldu {
     }
     // UcEqn.H:3-13: fvm::ddt(alphac, Uc) + fvm::div(alphaPhic, Uc) - fvm::Sp(fvc::ddt(alphac) + fvc::div(alphaPhic), Uc) + divDevRhoReff(Uc) == fvm::Sp(uSourceDrag, Uc); relax()
     // [OF-6 linearViscousStress::divDevRhoReff = - fvm::laplacian(alpha nu, U) - fvc::div(alpha nu dev2(T(grad U)))].  alphac.oldTime() == alphac (fv_oracle.cpp, quirk F-Q1)
-    void assemble_momentum_pimple(double u_relax_now) {
+    void assemble_momentum_pimple(real u_relax_now) {
         const size_t nc = nCells;
         if (cs.convection_scheme >= 3) limiter_gradient(U);
         std::fill(diag.begin(), diag.end(), 0.0); std::fill(src.begin(), src.end(), 0.0);
@@ -393,45 +406,45 @@ struct Ldu {
         for (size_t c = 0; c < nc; ++c) {
             diag[c] += alpha[c] * V[c] / cs.dt;
             for (int q = 0; q < 3; ++q) src[3 * c + q] += alpha[c] * V[c] / cs.dt * Uold[3 * c + q];
-            const double* T = &vGradNow[9 * c];
-            const double tr = T[0] + T[4] + T[8];
-            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) G[9 * c + 3 * a + b] = alpha[c] * (cs.nu + (nut.empty() ? 0.0 : nut[c])) * (T[3 * b + a] - (a == b ? (2.0 / 3.0) * tr : 0.0));
+            const real* T = &vGradNow[9 * c];
+            const real tr = T[0] + T[4] + T[8];
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) G[9 * c + 3 * a + b] = alpha[c] * (cs.nu + (nut.empty() ? 0.0 : nut[c])) * (T[3 * b + a] - (a == b ? (real(2) / 3) * tr : 0.0));
         }
-        auto stress = [&](int f, double* t) {                   // Sf . (alpha nu dev2(T(grad U)))_f, the cell tensor interpolated linearly (a boundary face: its cell's)
-            const double sv[3] = {Sf[f].x, Sf[f].y, Sf[f].z};
+        auto stress = [&](int f, real* t) {                   // Sf . (alpha nu dev2(T(grad U)))_f, the cell tensor interpolated linearly (a boundary face: its cell's)
+            const real sv[3] = {Sf[f].x, Sf[f].y, Sf[f].z};
             for (int b = 0; b < 3; ++b) {
                 t[b] = 0.0;
                 for (int a = 0; a < 3; ++a) {
-                    const double go = G[9 * (size_t)own[f] + 3 * a + b];
+                    const real go = G[9 * (size_t)own[f] + 3 * a + b];
                     t[b] += sv[a] * (f < nInt ? w[f] * go + (1.0 - w[f]) * G[9 * (size_t)nei[f] + 3 * a + b] : go);
                 }
             }
         };
         for (int f = 0; f < nInt; ++f) {
-            const double fl = alphaf[f] * phi[f];
+            const real fl = alphaf[f] * phi[f];
             // - fvm::laplacian(alpha nuEff, U): the cell field alpha (nu + nut) interpolated linearly [OF-6 gaussLaplacianScheme::fvmLaplacian(vol gamma)]
-            const double g = (nut.empty() ? cs.nu * alphaf[f] : w[f] * alpha[own[f]] * (cs.nu + nut[own[f]]) + (1.0 - w[f]) * alpha[nei[f]] * (cs.nu + nut[nei[f]])) * magSf[f];
-            double lo = -conv_weight(f, fl) * fl, up = lo + fl;
+            const real g = (nut.empty() ? cs.nu * alphaf[f] : w[f] * alpha[own[f]] * (cs.nu + nut[own[f]]) + (1.0 - w[f]) * alpha[nei[f]] * (cs.nu + nut[nei[f]])) * magSf[f];
+            real lo = -conv_weight(f, fl) * fl, up = lo + fl;
             lo -= g * dcNO[f]; up -= g * dcNO[f];
             lower[f] = lo; upper[f] = up;
             diag[own[f]] -= lo; diag[nei[f]] -= up;
             offsum[own[f]] += std::fabs(up); offsum[nei[f]] += std::fabs(lo);
             divAPhi[own[f]] += fl; divAPhi[nei[f]] -= fl;
-            const double kk[3] = {kvec[f].x, kvec[f].y, kvec[f].z};
-            double t[3];
+            const real kk[3] = {kvec[f].x, kvec[f].y, kvec[f].z};
+            real t[3];
             stress(f, t);
             for (int j = 0; j < 3; ++j) {
-                double corr = 0.0;
+                real corr = 0.0;
                 for (int i = 0; i < 3; ++i) corr += kk[i] * (w[f] * vGradNow[9 * (size_t)own[f] + 3 * i + j] + (1.0 - w[f]) * vGradNow[9 * (size_t)nei[f] + 3 * i + j]);
                 src[3 * (size_t)own[f] + j] += g * corr + t[j]; src[3 * (size_t)nei[f] + j] -= g * corr + t[j];
             }
         }
         for (int f = nInt; f < nFaces; ++f) {
             const int b = f - nInt, pa = patch_of[b], c = own[f];
-            const double nutb = nut_bnd(pa, c);
-            const double g = (cs.nu + nutb) * magSf[f] * dcNO[f];        // (alphac's boundary value is 1)
+            const real nutb = nut_bnd(pa, c);
+            const real g = (cs.nu + nutb) * magSf[f] * dcNO[f];        // (alphac's boundary value is 1)
             divAPhi[c] += phi[f];
-            double t[3];
+            real t[3];
             stress(f, t);
             for (int q = 0; q < 3; ++q) src[3 * (size_t)c + q] += t[q];
             if (u_bc[pa] == 0) { bint[b] += g; for (int q = 0; q < 3; ++q) bsrc[3 * (size_t)b + q] += (-phi[f] + g) * u_val[3 * pa + q]; }
@@ -440,7 +453,7 @@ struct Ldu {
         }
         if (cs.convection_scheme == 2) { vec aphi(nFaces); for (int f = 0; f < nFaces; ++f) aphi[f] = alphaf[f] * phi[f]; linear_upwind_source(aphi); }
         for (size_t c = 0; c < nc; ++c) {
-            const double S = divAPhi[c] / V[c];                          // + fvc::ddt(alphac) = 0
+            const real S = divAPhi[c] / V[c];                          // + fvc::ddt(alphac) = 0
             diag[c] -= V[c] * S;
             diag[c] -= V[c] * uSourceDrag[c];
         }
@@ -448,7 +461,7 @@ struct Ldu {
             for (size_t c = 0; c < nc; ++c) {
                 // (a symmetry face's coefficient differs by component: relax() adds cmptMax(cmptMag(internalCoeffs)) before the dominance test and takes
                 // cmptMin(internalCoeffs) off afterwards)
-                const double dg = dgc((int)c), dn = std::max(std::fabs(dg + (has_slip ? bmaxs[c] : 0.0)), offsum[c]) / u_relax_now - (has_slip ? bmins[c] : 0.0);
+                const real dg = dgc((int)c), dn = rmax(std::fabs(dg + (has_slip ? bmaxs[c] : 0.0)), offsum[c]) / u_relax_now - (has_slip ? bmins[c] : 0.0);
                 for (int q = 0; q < 3; ++q) src[3 * c + q] += (dn - dg) * U[3 * c + q];
                 diag[c] += dn - dg;
             }
@@ -458,7 +471,7 @@ struct Ldu {
     void interp_rAU_and_forces() {                               // rAUcf, phicForces = fvc::flux(rAUc uSource) + rAUcf (g & Sf) (UcEqn.H:15-20); uSource's boundary value is 0
         const V3 gv{cs.g[0], cs.g[1], cs.g[2]};
         for (int f = 0; f < nFaces; ++f) {
-            double fl = 0.0;
+            real fl = 0.0;
             if (f < nInt) {
                 const int o = own[f], n = nei[f];
                 rAUf[f] = w[f] * rAU[o] + (1.0 - w[f]) * rAU[n];
@@ -476,17 +489,17 @@ struct Ldu {
             if (f < nInt) out[nei[f]] = out[nei[f]] + t;
         }
         for (int c = 0; c < nCells; ++c) {
-            const double* R = &recon[9 * (size_t)c];
+            const real* R = &recon[9 * (size_t)c];
             const V3 a = out[c];
             out[c] = V3{R[0] * a.x + R[1] * a.y + R[2] * a.z, R[3] * a.x + R[4] * a.y + R[5] * a.z, R[6] * a.x + R[7] * a.y + R[8] * a.z};
         }
     }
-    double sngrad_p(int f, const std::vector<V3>& gp) const {    // corrected snGrad(p) on face f (boundary faces carry no correction)
+    real sngrad_p(int f, const std::vector<V3>& gp) const {    // corrected snGrad(p) on face f (boundary faces carry no correction)
         if (f < nInt) return dcNO[f] * (p[nei[f]] - p[own[f]]) + dot(kvec[f], w[f] * gp[own[f]] + (1.0 - w[f]) * gp[nei[f]]);
         return dcNO[f] * (pb_val(f) - p[own[f]]);
     }
     // pEqn.H
-    void corrector_pimple(bool final_corr, double p_relax_now) {
+    void corrector_pimple(bool final_corr, real p_relax_now) {
         compute_HbyA();                                          // :2
         {
             // :4-11 phiHbyA = fvc::flux(HbyA) + alphacf rAUcf fvc::ddtCorr(Uc, phic); compute_phiHbyA() forms the ico expression and adjusts it (:13-16)
@@ -505,17 +518,17 @@ struct Ldu {
             grad_scalar(p, [&](int f) { return pb_val(f); }, gp);
             std::fill(pdiag.begin(), pdiag.end(), 0.0); std::fill(pb.begin(), pb.end(), 0.0);
             for (int f = 0; f < nInt; ++f) {
-                const double gm = alphaf[f] * rAUf[f] * magSf[f];
+                const real gm = alphaf[f] * rAUf[f] * magSf[f];
                 pcoef[f] = gm * dcNO[f];
                 pcorr[f] = gm * dot(kvec[f], w[f] * gp[own[f]] + (1.0 - w[f]) * gp[nei[f]]);
                 pdiag[own[f]] += pcoef[f]; pdiag[nei[f]] += pcoef[f];
-                const double t = -alphaf[f] * phiHbyA[f] + pcorr[f];
+                const real t = -alphaf[f] * phiHbyA[f] + pcorr[f];
                 pb[own[f]] += t; pb[nei[f]] -= t;
             }
             for (int f = nInt; f < nFaces; ++f) {
                 const int pa = patch_of[f - nInt], c = own[f];
                 pcoef[f] = alphaf[f] * rAUf[f] * magSf[f] * dcNO[f];
-                double ph = alphaf[f] * phiHbyA[f];
+                real ph = alphaf[f] * phiHbyA[f];
                 if (p_bc[pa] == 2) ph = alphaf[f] * (phiHbyA[f] - rAUf[f] * magSf[f] * psn[f - nInt]);       // the fixed-gradient source of the laplacian
                 pb[c] -= ph;
                 if (p_bc[pa] == 1) { pdiag[c] += pcoef[f]; pb[c] += pcoef[f] * p_val[pa]; }
@@ -524,7 +537,7 @@ struct Ldu {
             solve_pressure(final_corr && no == cs.n_non_orth_correctors);
             if (no == cs.n_non_orth_correctors) {
                 for (int f = 0; f < nFaces; ++f) {
-                    double pf;
+                    real pf;
                     if (f < nInt) pf = pcoef[f] * (p[nei[f]] - p[own[f]]) + pcorr[f];
                     else {
                         const int pa = patch_of[f - nInt];
@@ -544,7 +557,7 @@ struct Ldu {
         vec div(nCells, 0.0);                                                                           // :50 continuityErrs.H: fvc::ddt(alphac) + fvc::div(alphacf phic)
         for (int f = 0; f < nInt; ++f) { div[own[f]] += alphaf[f] * phi[f]; div[nei[f]] -= alphaf[f] * phi[f]; }
         for (int f = nInt; f < nFaces; ++f) div[own[f]] += alphaf[f] * phi[f];
-        double sl = 0, gl = 0, tv = 0;
+        real sl = 0, gl = 0, tv = 0;
         for (int c = 0; c < nCells; ++c) { sl += std::fabs(div[c]); gl += div[c]; tv += V[c]; }
         st.cont_sum_local = cs.dt * sl / tv; st.cont_global = cs.dt * gl / tv;
         cumulative += st.cont_global; st.cont_cumulative = cumulative;
@@ -554,8 +567,8 @@ struct Ldu {
         const int nOuter = std::max(cs.n_outer, 1);
         for (int outer = 0; outer < nOuter; ++outer) {
             const bool final_outer = outer == nOuter - 1;
-            const double u_relax_now = (final_outer && cs.u_relax_final > 0) ? cs.u_relax_final : cs.u_relax;
-            const double p_relax_now = (final_outer && cs.p_relax_final > 0) ? cs.p_relax_final : cs.p_relax;
+            const real u_relax_now = (final_outer && cs.u_relax_final > 0) ? cs.u_relax_final : cs.u_relax;
+            const real p_relax_now = (final_outer && cs.p_relax_final > 0) ? cs.p_relax_final : cs.p_relax;
             if (p_relax_now > 0 && p_relax_now < 1) pPrev = p;
             grad_vector(U, vGradNow);
             assemble_momentum_pimple(u_relax_now);
@@ -587,13 +600,13 @@ struct Ldu {
     // (no wall functions on a general mesh: they need nearWallDist)
     void turb_eqn(int mode) {
         const size_t nc = nCells;
-        const double kMin = 1e-15;
-        const double sigma = mode == 0 ? 1.0 : mode == 1 ? cs.ras_sigmaeps : cs.ras_sigmak;
+        const real kMin = 1e-15;
+        const real sigma = mode == 0 ? 1.0 : mode == 1 ? cs.ras_sigmaeps : cs.ras_sigmak;
         vec& Xf = mode == 1 ? epsturb : kturb;
         const std::vector<int>& xbc = mode == 1 ? eps_bc : k_bc;
         const vec& xval = mode == 1 ? eps_val : k_val;
         const int scheme = mode == 1 ? cs.eps_convection_scheme : cs.k_convection_scheme;
-        const double relax = mode == 1 ? cs.eps_relax : cs.k_relax;
+        const real relax = mode == 1 ? cs.eps_relax : cs.k_relax;
         auto xb_of = [&](int pa, int c) { return xbc[pa] == 1 ? xval[pa] : Xf[c]; };
         std::vector<V3> gk;
         grad_scalar(Xf, [&](int f) { return xb_of(patch_of[f - nInt], own[f]); }, gk);
@@ -604,41 +617,41 @@ struct Ldu {
         for (size_t c = 0; c < nc; ++c) { diag[c] += alpha[c] * V[c] / cs.dt; src[3 * c] += alpha[c] * V[c] / cs.dt * Xf[c]; }
         for (int f = 0; f < nInt; ++f) {
             const int o = own[f], n = nei[f];
-            const double fl = alphaf[f] * phi[f];
-            const double gam = (w[f] * alpha[o] * (cs.nu + nut[o] / sigma) + (1.0 - w[f]) * alpha[n] * (cs.nu + nut[n] / sigma)) * magSf[f];
-            const double wc = scheme ? (fl >= 0.0 ? 1.0 : 0.0) : w[f];
-            double lo = -wc * fl, up = lo + fl;
+            const real fl = alphaf[f] * phi[f];
+            const real gam = (w[f] * alpha[o] * (cs.nu + nut[o] / sigma) + (1.0 - w[f]) * alpha[n] * (cs.nu + nut[n] / sigma)) * magSf[f];
+            const real wc = scheme ? (fl >= 0.0 ? 1.0 : 0.0) : w[f];
+            real lo = -wc * fl, up = lo + fl;
             lo -= gam * dcNO[f]; up -= gam * dcNO[f];
             lower[f] = lo; upper[f] = up;
             diag[o] -= lo; diag[n] -= up;
             offsum[o] += std::fabs(up); offsum[n] += std::fabs(lo);
             sumPhi[o] += phi[f]; sumPhi[n] -= phi[f];
-            const double corr = gam * dot(kvec[f], w[f] * gk[o] + (1.0 - w[f]) * gk[n]);
+            const real corr = gam * dot(kvec[f], w[f] * gk[o] + (1.0 - w[f]) * gk[n]);
             src[3 * (size_t)o] += corr; src[3 * (size_t)n] -= corr;
         }
         for (int f = nInt; f < nFaces; ++f) {
             const int b = f - nInt, pa = patch_of[b], c = own[f];
             sumPhi[c] += phi[f];
-            const double fl = alphaf[f] * phi[f];
-            if (xbc[pa] == 1) { const double gb = (cs.nu + nut_bnd(pa, c) / sigma) * magSf[f] * dcNO[f]; bint[b] += gb; bsrc[3 * (size_t)b] += (-fl + gb) * xval[pa]; }
+            const real fl = alphaf[f] * phi[f];
+            if (xbc[pa] == 1) { const real gb = (cs.nu + nut_bnd(pa, c) / sigma) * magSf[f] * dcNO[f]; bint[b] += gb; bsrc[3 * (size_t)b] += (-fl + gb) * xval[pa]; }
             else bint[b] += fl;
         }
         for (size_t c = 0; c < nc; ++c) {
-            const double* T = &vGrad[9 * c];
-            const double tr2 = 2.0 * (T[0] + T[4] + T[8]);
-            double GG = 0.0;
-            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) GG += T[3 * a + b] * ((T[3 * a + b] + T[3 * b + a]) - (a == b ? (1.0 / 3.0) * tr2 : 0.0));
-            const double G = nut[c] * GG, divU = sumPhi[c] / V[c], xc = Xf[c], aP = alpha[c];
-            double Su, c1, c2;
-            if (mode == 0) { Su = aP * G; c1 = (2.0 / 3.0) * aP * divU; c2 = cs.les_ce * aP * std::sqrt(xc) / les_delta((int)c); }
-            else if (mode == 1) { const double kc = kturb[c]; Su = cs.ras_c1 * aP * G * xc / kc; c1 = ((2.0 / 3.0) * cs.ras_c1 - cs.ras_c3) * aP * divU; c2 = cs.ras_c2 * aP * xc / kc; }
-            else { Su = aP * G; c1 = (2.0 / 3.0) * aP * divU; c2 = aP * epsturb[c] / xc; }
-            diag[c] += V[c] * (std::max(c1, 0.0) + c2);
-            src[3 * c] += V[c] * Su - V[c] * std::min(c1, 0.0) * xc;
+            const real* T = &vGrad[9 * c];
+            const real tr2 = 2.0 * (T[0] + T[4] + T[8]);
+            real GG = 0.0;
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) GG += T[3 * a + b] * ((T[3 * a + b] + T[3 * b + a]) - (a == b ? (real(1) / 3) * tr2 : 0.0));
+            const real G = nut[c] * GG, divU = sumPhi[c] / V[c], xc = Xf[c], aP = alpha[c];
+            real Su, c1, c2;
+            if (mode == 0) { Su = aP * G; c1 = (real(2) / 3) * aP * divU; c2 = cs.les_ce * aP * std::sqrt(xc) / les_delta((int)c); }
+            else if (mode == 1) { const real kc = kturb[c]; Su = cs.ras_c1 * aP * G * xc / kc; c1 = ((real(2) / 3) * cs.ras_c1 - cs.ras_c3) * aP * divU; c2 = cs.ras_c2 * aP * xc / kc; }
+            else { Su = aP * G; c1 = (real(2) / 3) * aP * divU; c2 = aP * epsturb[c] / xc; }
+            diag[c] += V[c] * (rmax(c1, 0.0) + c2);
+            src[3 * c] += V[c] * Su - V[c] * rmin(c1, 0.0) * xc;
         }
         if (relax > 0) {
             for (size_t c = 0; c < nc; ++c) {
-                const double dg = dgc((int)c), dn = std::max(std::fabs(dg), offsum[c]) / relax;
+                const real dg = dgc((int)c), dn = rmax(std::fabs(dg), offsum[c]) / relax;
                 src[3 * c] += (dn - dg) * Xf[c];
                 diag[c] += dn - dg;
             }
@@ -646,7 +659,7 @@ struct Ldu {
         // the scalar equation through the three-component Jacobi solve (components 1 and 2 are 0 = 0: converged from the start)
         vec keepU = U;
         const bool slip = has_slip; has_slip = false;
-        const double ut = cs.u_tol, ur = cs.u_rel_tol; const int um = cs.u_max_iter;
+        const real ut = cs.u_tol, ur = cs.u_rel_tol; const int um = cs.u_max_iter;
         if (mode == 1) { cs.u_tol = cs.eps_tol; cs.u_rel_tol = cs.eps_rel_tol; cs.u_max_iter = cs.eps_max_iter; } else { cs.u_tol = cs.k_tol; cs.u_rel_tol = cs.k_rel_tol; cs.u_max_iter = cs.k_max_iter; }
         for (size_t c = 0; c < nc; ++c) { U[3 * c] = Xf[c]; U[3 * c + 1] = 0.0; U[3 * c + 2] = 0.0; }
         k_iters += solve_momentum(vec(3 * nc, 0.0));
@@ -655,20 +668,20 @@ struct Ldu {
         U = keepU; has_slip = slip; cs.u_tol = ut; cs.u_rel_tol = ur; cs.u_max_iter = um;
         // bound()
         vec xm(nc);
-        for (size_t c = 0; c < nc; ++c) xm[c] = std::max(x[c], kMin);
+        for (size_t c = 0; c < nc; ++c) xm[c] = rmax(x[c], kMin);
         for (int c = 0; c < nCells; ++c) {
-            double xb = x[c];
+            real xb = x[c];
             if (!(x[c] > 0.0)) {
-                double av = 0.0, asum = 0.0;                         // fvc::average: sum |Sf| x_f / sum |Sf|
+                real av = 0.0, asum = 0.0;                         // fvc::average: sum |Sf| x_f / sum |Sf|
                 for (int f : cfaces[c]) {
-                    double xf;
+                    real xf;
                     if (f < nInt) xf = w[f] * xm[own[f]] + (1.0 - w[f]) * xm[nei[f]];
-                    else { const int pa = patch_of[f - nInt]; xf = std::max(xbc[pa] == 1 ? xval[pa] : x[c], kMin); }
+                    else { const int pa = patch_of[f - nInt]; xf = rmax(xbc[pa] == 1 ? xval[pa] : x[c], kMin); }
                     av += magSf[f] * xf; asum += magSf[f];
                 }
-                xb = std::max(x[c], av / asum);
+                xb = rmax(x[c], av / asum);
             }
-            Xf[c] = std::max(xb, kMin);
+            Xf[c] = rmax(xb, kMin);
         }
         if (mode == 0) for (int c = 0; c < nCells; ++c) nut[c] = cs.les_ck * std::sqrt(kturb[c]) * les_delta(c);
         else if (mode == 2) for (int c = 0; c < nCells; ++c) nut[c] = cs.ras_cmu * (kturb[c] * kturb[c]) / epsturb[c];
@@ -679,15 +692,15 @@ struct Ldu {
         if (cs.turbulence_model == 2) { turb_eqn(0); return; }
         if (cs.turbulence_model == 3) { turb_eqn(1); turb_eqn(2); return; }      // kEpsilon::correct(): epsilon first, then k with the new epsilon
         for (int c = 0; c < nCells; ++c) {
-            const double delta = cs.les_delta_coeff * std::cbrt(V[c]);
-            const double* T = &vGrad[9 * (size_t)c];
-            double D[3][3];
+            const real delta = cs.les_delta_coeff * std::cbrt(V[c]);
+            const real* T = &vGrad[9 * (size_t)c];
+            real D[3][3];
             for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) D[a][b] = 0.5 * (T[3 * a + b] + T[3 * b + a]);
-            const double trD = D[0][0] + D[1][1] + D[2][2], a = cs.les_ce / delta, b = (2.0 / 3.0) * trD, third = (1.0 / 3.0) * trD;
-            const double dd = (D[0][0] - third) * D[0][0] + (D[1][1] - third) * D[1][1] + (D[2][2] - third) * D[2][2]
+            const real trD = D[0][0] + D[1][1] + D[2][2], a = cs.les_ce / delta, b = (real(2) / 3) * trD, third = (real(1) / 3) * trD;
+            const real dd = (D[0][0] - third) * D[0][0] + (D[1][1] - third) * D[1][1] + (D[2][2] - third) * D[2][2]
                             + 2.0 * (D[0][1] * D[0][1]) + 2.0 * (D[0][2] * D[0][2]) + 2.0 * (D[1][2] * D[1][2]);
-            const double cc = 2.0 * cs.les_ck * delta * dd;
-            const double r = (-b + std::sqrt(b * b + 4.0 * a * cc)) / (2.0 * a);
+            const real cc = 2.0 * cs.les_ck * delta * dd;
+            const real r = (-b + std::sqrt(b * b + 4.0 * a * cc)) / (2.0 * a);
             nut[c] = cs.les_ck * delta * std::sqrt(r * r);
         }
     }
@@ -706,16 +719,16 @@ struct Ldu {
         for (int f = 0; f < nInt; ++f) {
             // gaussConvectionScheme<linear>::fvmDiv: lower = -w phi, upper = lower + phi, negSumDiag
             // ... or upwind [OF-6 upwind::weights]: the owner's weight is pos0(flux)
-            double lo = -conv_weight(f, phi[f]) * phi[f], up = lo + phi[f];
+            real lo = -conv_weight(f, phi[f]) * phi[f], up = lo + phi[f];
             // - gaussLaplacianScheme::fvmLaplacianUncorrected: upper = lower = gamma |Sf| nonOrthDeltaCoeffs, negSumDiag
-            const double g = cs.nu * magSf[f] * dcNO[f];
+            const real g = cs.nu * magSf[f] * dcNO[f];
             lo -= g; up -= g;
             lower[f] = lo; upper[f] = up;
             diag[own[f]] -= lo; diag[nei[f]] -= up;
         }
         for (int f = nInt; f < nFaces; ++f) {
             const int b = f - nInt, pa = patch_of[b], c = own[f];
-            const double g = cs.nu * magSf[f] * dcNO[f];
+            const real g = cs.nu * magSf[f] * dcNO[f];
             if (u_bc[pa] == 0) {                                 // fixedValue: valueInternalCoeffs 0, valueBoundaryCoeffs U_b; gradient coefficients -/+ deltaCoeffs
                 bint[b] += g;
                 for (int q = 0; q < 3; ++q) bsrc[3 * (size_t)b + q] += -phi[f] * u_val[3 * pa + q] + g * u_val[3 * pa + q];
@@ -728,10 +741,10 @@ struct Ldu {
         }
         // the explicit non-orthogonal part of -laplacian(nu, U): gamma |Sf| (k & interpolate(grad(U))) per face, its divergence on the right-hand side
         for (int f = 0; f < nInt; ++f) {
-            const double g = cs.nu * magSf[f];
-            const double kk[3] = {kvec[f].x, kvec[f].y, kvec[f].z};
+            const real g = cs.nu * magSf[f];
+            const real kk[3] = {kvec[f].x, kvec[f].y, kvec[f].z};
             for (int j = 0; j < 3; ++j) {
-                double corr = 0.0;
+                real corr = 0.0;
                 for (int i = 0; i < 3; ++i)
                     corr += kk[i] * (w[f] * vGradNow[9 * (size_t)own[f] + 3 * i + j] + (1.0 - w[f]) * vGradNow[9 * (size_t)nei[f] + 3 * i + j]);
                 src[3 * (size_t)own[f] + j] += g * corr; src[3 * (size_t)nei[f] + j] -= g * corr;
@@ -747,26 +760,26 @@ struct Ldu {
         for (int c = 0; c < nCells; ++c) lphi[c] = (F[3 * (size_t)c] * F[3 * (size_t)c] + F[3 * (size_t)c + 1] * F[3 * (size_t)c + 1]) + F[3 * (size_t)c + 2] * F[3 * (size_t)c + 2];
         grad_scalar(lphi, [&](int f) { const V3 b = Ub(F, f); return (b.x * b.x + b.y * b.y) + b.z * b.z; }, gradL);
     }
-    static double limiter_fn(int scheme, double twoByk, double r) {
+    static real limiter_fn(int scheme, real twoByk, real r) {
         switch (scheme) {
-            case 3: return std::max(std::min(twoByk * r, 1.0), 0.0);
+            case 3: return rmax(rmin(twoByk * r, 1.0), 0.0);
             case 4: return (r + std::fabs(r)) / (1.0 + std::fabs(r));
-            case 5: return std::max(std::min(std::min(2.0 * r, 0.5 * r + 0.5), 2.0), 0.0);
-            case 6: return std::max(std::min(std::min(r, 1.0), 2.0), 0.0);
-            case 7: return std::max(std::max(std::min(2.0 * r, 1.0), std::min(r, 2.0)), 0.0);
-            default: return std::max(std::min((3.0 + r) / 4.0, 2.0), 0.0);
+            case 5: return rmax(rmin(rmin(2.0 * r, 0.5 * r + 0.5), 2.0), 0.0);
+            case 6: return rmax(rmin(rmin(r, 1.0), 2.0), 0.0);
+            case 7: return rmax(rmax(rmin(2.0 * r, 1.0), rmin(r, 2.0)), 0.0);
+            default: return rmax(rmin((3.0 + r) / 4.0, 2.0), 0.0);
         }
     }
-    double conv_weight(int f, double fl) const {                 // the owner's weight of the convected value on internal face f
+    real conv_weight(int f, real fl) const {                 // the owner's weight of the convected value on internal face f
         if (cs.convection_scheme == 0) return w[f];
-        const double up = fl >= 0.0 ? 1.0 : 0.0;
+        const real up = fl >= 0.0 ? 1.0 : 0.0;
         if (cs.convection_scheme <= 2) return up;
-        const double gradf = lphi[nei[f]] - lphi[own[f]];
-        const double gradcf = dot((C[nei[f]] + sepf(f)) - C[own[f]], gradL[fl > 0.0 ? own[f] : nei[f]]);
-        double r;
+        const real gradf = lphi[nei[f]] - lphi[own[f]];
+        const real gradcf = dot((C[nei[f]] + sepf(f)) - C[own[f]], gradL[fl > 0.0 ? own[f] : nei[f]]);
+        real r;
         if (std::fabs(gradcf) >= 1000.0 * std::fabs(gradf)) r = 2.0 * 1000.0 * (gradcf >= 0 ? 1.0 : -1.0) * (gradf >= 0 ? 1.0 : -1.0) - 1.0;
         else r = 2.0 * (gradcf / gradf) - 1.0;
-        const double lim = limiter_fn(cs.convection_scheme, 2.0 / std::max(cs.convection_limiter_k, SMALL), r);
+        const real lim = limiter_fn(cs.convection_scheme, 2.0 / rmax(cs.convection_limiter_k, SMALL), r);
         return lim * w[f] + (1.0 - lim) * up;
     }
     vec vGradNow;                                                // grad(U) of the iterate the momentum matrix is assembled from
@@ -778,7 +791,7 @@ struct Ldu {
             const int up = flux[f] >= 0.0 ? own[f] : nei[f];
             const V3 d = Cf[f] - (flux[f] >= 0.0 ? C[up] : C[up] + sepf(f));      // (a folded cyclic face: the neighbour's image)
             for (int j = 0; j < 3; ++j) {
-                const double lu = flux[f] * ((d.x * vGradNow[9 * (size_t)up + j] + d.y * vGradNow[9 * (size_t)up + 3 + j]) + d.z * vGradNow[9 * (size_t)up + 6 + j]);
+                const real lu = flux[f] * ((d.x * vGradNow[9 * (size_t)up + j] + d.y * vGradNow[9 * (size_t)up + 3 + j]) + d.z * vGradNow[9 * (size_t)up + 6 + j]);
                 src[3 * (size_t)own[f] + j] -= lu; src[3 * (size_t)nei[f] + j] += lu;
             }
         }
@@ -788,21 +801,21 @@ struct Ldu {
     // gradientInternalCoeffs U_P; basicSymmetryFvPatchField: snGradTransformDiag = (|n_x|, |n_y|, |n_z|), snGrad = -n (n & U_P) deltaCoeffs]: a per-component diagonal, kept
     // apart from the scalar one as fvMatrix keeps internalCoeffs apart from the lduMatrix, and an explicit remainder formed with the U the matrix is assembled around.
     // The flux through the face is U_b & Sf = 0 up to rounding: the convection term sees it like a zeroGradient face
-    void slip_face(int f, double g) {
+    void slip_face(int f, real g) {
         const int b = f - nInt, c = own[f];
         const V3 n = (1.0 / magSf[f]) * Sf[f], uc = at(U, c);
-        const double nn[3] = {n.x, n.y, n.z}, an[3] = {std::fabs(n.x), std::fabs(n.y), std::fabs(n.z)}, u3[3] = {uc.x, uc.y, uc.z}, un = dot(n, uc);
+        const real nn[3] = {n.x, n.y, n.z}, an[3] = {std::fabs(n.x), std::fabs(n.y), std::fabs(n.z)}, u3[3] = {uc.x, uc.y, uc.z}, un = dot(n, uc);
         for (int q = 0; q < 3; ++q) {
             bdg[3 * (size_t)c + q] += g * an[q];
             bsrc[3 * (size_t)b + q] += g * (an[q] * u3[q] - nn[q] * un);
         }
-        bmaxs[c] += g * std::max(an[0], std::max(an[1], an[2]));
-        bmins[c] += g * std::min(an[0], std::min(an[1], an[2]));
+        bmaxs[c] += g * rmax(an[0], rmax(an[1], an[2]));
+        bmins[c] += g * rmin(an[0], rmin(an[1], an[2]));
         bint[b] += phi[f];
     }
-    double dgq(int c, int q) const { return has_slip ? dgc(c) + bdg[3 * (size_t)c + q] : dgc(c); }                                  // fvMatrix::solveSegregated: addBoundaryDiag per component
-    double dgA(int c) const { return has_slip ? dgc(c) + (bdg[3 * (size_t)c] + bdg[3 * (size_t)c + 1] + bdg[3 * (size_t)c + 2]) / 3.0 : dgc(c); }      // fvMatrix::A(): addCmptAvBoundaryDiag
-    double dgc(int c) const { double d = diag[c]; for (int f : cfaces[c]) if (f >= nInt) d += bint[f - nInt]; return d; }
+    real dgq(int c, int q) const { return has_slip ? dgc(c) + bdg[3 * (size_t)c + q] : dgc(c); }                                  // fvMatrix::solveSegregated: addBoundaryDiag per component
+    real dgA(int c) const { return has_slip ? dgc(c) + (bdg[3 * (size_t)c] + bdg[3 * (size_t)c + 1] + bdg[3 * (size_t)c + 2]) / 3.0 : dgc(c); }      // fvMatrix::A(): addCmptAvBoundaryDiag
+    real dgc(int c) const { real d = diag[c]; for (int f : cfaces[c]) if (f >= nInt) d += bint[f - nInt]; return d; }
     void total_source(vec& b) const {
         b = src;
         for (int f = nInt; f < nFaces; ++f) for (int q = 0; q < 3; ++q) b[3 * (size_t)own[f] + q] += bsrc[3 * (size_t)(f - nInt) + q];
@@ -822,7 +835,7 @@ struct Ldu {
         total_source(b);
         for (int c = 0; c < nCells; ++c) for (int q = 0; q < 3; ++q) b[3 * (size_t)c + q] -= V[c] * gp[3 * (size_t)c + q];      // == -fvc::grad(p)
         vec x = U, xn(U.size()), Ax(U.size()), Aref(U.size()), ones(U.size());
-        double xbar[3] = {0, 0, 0}, norm[3], res0[3] = {0, 0, 0};
+        real xbar[3] = {0, 0, 0}, norm[3], res0[3] = {0, 0, 0};
         for (int c = 0; c < nCells; ++c) for (int q = 0; q < 3; ++q) xbar[q] += x[3 * (size_t)c + q];
         for (int q = 0; q < 3; ++q) xbar[q] /= nCells;
         for (int c = 0; c < nCells; ++c) for (int q = 0; q < 3; ++q) ones[3 * (size_t)c + q] = xbar[q];
@@ -834,12 +847,12 @@ struct Ldu {
             res0[q] += std::fabs(b[e] - Ax[e]);
         }
         for (int q = 0; q < 3; ++q) { norm[q] += 1e-20; res0[q] /= norm[q]; }
-        auto conv = [&](const double* r) {
+        auto conv = [&](const real* r) {
             for (int q = 0; q < 3; ++q) if (!(r[q] < cs.u_tol || (cs.u_rel_tol > 0 && r[q] < cs.u_rel_tol * res0[q]))) return false;
             return true;
         };
         int it = 0;
-        double res[3] = {res0[0], res0[1], res0[2]};
+        real res[3] = {res0[0], res0[1], res0[2]};
         while (!conv(res) && it < cs.u_max_iter) {
             xn = b;
             for (int f = 0; f < nInt; ++f) for (int q = 0; q < 3; ++q) {
@@ -869,7 +882,7 @@ struct Ldu {
         for (int c = 0; c < nCells; ++c) {
             rAU[c] = 1.0 / (dgA(c) / V[c]);
             if (has_slip) {                                      // fvMatrix::H(): what a component's boundary diagonal has over the average stays with H
-                const double av = (bdg[3 * (size_t)c] + bdg[3 * (size_t)c + 1] + bdg[3 * (size_t)c + 2]) / 3.0;
+                const real av = (bdg[3 * (size_t)c] + bdg[3 * (size_t)c + 1] + bdg[3 * (size_t)c + 2]) / 3.0;
                 for (int q = 0; q < 3; ++q) b[3 * (size_t)c + q] += (av - bdg[3 * (size_t)c + q]) * U[3 * (size_t)c + q];
             }
             for (int q = 0; q < 3; ++q) HbyA[3 * (size_t)c + q] = rAU[c] * (b[3 * (size_t)c + q] / V[c]);
@@ -884,9 +897,9 @@ struct Ldu {
     // phiHbyA = fvc::flux(HbyA) + fvc::interpolate(rAU) fvc::ddtCorr(U, phi) (icoFoamYade.C:101-106), adjustPhi (:108)
     void compute_phiHbyA() { compute_phiHbyA_with(vec()); }
     void compute_phiHbyA_with(const vec& af) {                  // af: alphacf on the ddtCorr term (pEqn.H:9), empty in icoFoamYade
-        const double rDt = 1.0 / cs.dt;
+        const real rDt = real(1) / cs.dt;
         for (int f = 0; f < nFaces; ++f) {
-            double fl, uf;
+            real fl, uf;
             bool fixes = false;
             if (f < nInt) {
                 rAUf[f] = w[f] * rAU[own[f]] + (1.0 - w[f]) * rAU[nei[f]];
@@ -898,22 +911,22 @@ struct Ldu {
                 uf = dot(Ub(Uold, f), Sf[f]);
                 fixes = u_bc[patch_of[f - nInt]] == 0;
             }
-            const double phiCorr = phiOld[f] - uf;
-            const double coef = fixes ? 0.0 : 1.0 - std::min(std::fabs(phiCorr) / (std::fabs(phiOld[f]) + SMALL), 1.0);     // EulerDdtScheme::fvcDdtPhiCoeff
+            const real phiCorr = phiOld[f] - uf;
+            const real coef = fixes ? 0.0 : 1.0 - rmin(std::fabs(phiCorr) / (std::fabs(phiOld[f]) + SMALL), 1.0);     // EulerDdtScheme::fvcDdtPhiCoeff
             phiHbyA[f] = fl + (af.empty() ? 1.0 : af[f]) * (rAUf[f] * (coef * rDt * phiCorr));
         }
         bool need_ref = true;
         for (int pa = 0; pa < nPatches; ++pa) if (p_bc[pa] == 1) need_ref = false;
         if (need_ref) {                                          // adjustPhi [OF-6 adjustPhi.C]
-            double massIn = 0, fixedOut = 0, adjOut = 0, total = VSMALL;
+            real massIn = 0, fixedOut = 0, adjOut = 0, total = VSMALL;
             for (int f = 0; f < nInt; ++f) total += std::fabs(phiHbyA[f]);
             for (int f = nInt; f < nFaces; ++f) {
-                const double outw = phiHbyA[f];
+                const real outw = phiHbyA[f];
                 if (outw < 0.0) massIn -= outw;
                 else if (u_bc[patch_of[f - nInt]] == 0) fixedOut += outw;
                 else adjOut += outw;
             }
-            double massCorr = 1.0;
+            real massCorr = 1.0;
             if (std::fabs(adjOut) > VSMALL && std::fabs(adjOut) / total > SMALL) massCorr = (massIn - fixedOut) / adjOut;
             else if (std::fabs(fixedOut - massIn) / total > 1e-8) adjust_phi_failed = true;
             if (massCorr != 1.0)
@@ -954,32 +967,32 @@ struct Ldu {
     }
     // OpenFOAM PCG.C with the diagonal preconditioner and lduMatrix::solver::normFactor
     int solve_pressure(bool final_iter) {
-        const double tol = final_iter ? cs.p_final_tol : cs.p_tol, rel = final_iter ? cs.p_final_rel_tol : cs.p_rel_tol;
+        const real tol = final_iter ? cs.p_final_tol : cs.p_tol, rel = final_iter ? cs.p_final_rel_tol : cs.p_rel_tol;
         const int n = nCells;
         vec Ax(n), r(n), z(n), pp(n), wv(n), ref(n);
-        double xbar = 0;
+        real xbar = 0;
         for (int c = 0; c < n; ++c) xbar += p[c];
         xbar /= n;
         apply_p(p, Ax);
         vec xb(n, xbar); apply_p(xb, ref);
-        double norm = 0, res = 0;
+        real norm = 0, res = 0;
         for (int c = 0; c < n; ++c) { r[c] = pb[c] - Ax[c]; norm += std::fabs(Ax[c] - ref[c]) + std::fabs(pb[c] - ref[c]); res += std::fabs(r[c]); }
         norm += 1e-20; res /= norm;
-        const double res0 = res;
+        const real res0 = res;
         st.p_initial_residual = res0;
-        auto conv = [&](double rr) { return rr < tol || (rel > 0 && rr < rel * res0); };
+        auto conv = [&](real rr) { return rr < tol || (rel > 0 && rr < rel * res0); };
         int it = 0;
-        double rho_old = 1.0;
+        real rho_old = 1.0;
         if (!conv(res)) {
             do {
-                double rho = 0;
+                real rho = 0;
                 for (int c = 0; c < n; ++c) { z[c] = r[c] / pdiag[c]; rho += z[c] * r[c]; }
                 if (it == 0) pp = z;
-                else { const double beta = rho / rho_old; for (int c = 0; c < n; ++c) pp[c] = z[c] + beta * pp[c]; }
+                else { const real beta = rho / rho_old; for (int c = 0; c < n; ++c) pp[c] = z[c] + beta * pp[c]; }
                 apply_p(pp, wv);
-                double pAp = 0;
+                real pAp = 0;
                 for (int c = 0; c < n; ++c) pAp += wv[c] * pp[c];
-                const double al = rho / pAp;
+                const real al = rho / pAp;
                 res = 0;
                 for (int c = 0; c < n; ++c) { p[c] += al * pp[c]; r[c] -= al * wv[c]; res += std::fabs(r[c]); }
                 res /= norm;
@@ -1009,7 +1022,7 @@ struct Ldu {
         vec div(nCells, 0.0);
         for (int f = 0; f < nInt; ++f) { div[own[f]] += phi[f]; div[nei[f]] -= phi[f]; }
         for (int f = nInt; f < nFaces; ++f) div[own[f]] += phi[f];
-        double sl = 0, gl = 0, tv = 0;
+        real sl = 0, gl = 0, tv = 0;
         for (int c = 0; c < nCells; ++c) { sl += std::fabs(div[c]); gl += div[c]; tv += V[c]; }
         st.cont_sum_local = cs.dt * sl / tv; st.cont_global = cs.dt * gl / tv;
         cumulative += st.cont_global; st.cont_cumulative = cumulative;
@@ -1042,7 +1055,7 @@ vec* ldu_field(Ldu* s, const std::string& n) {
     const struct { const char* nm; vec* v; } tab[] = {{"U", &s->U}, {"p", &s->p}, {"phi", &s->phi}, {"uSource", &s->uSource}, {"vGrad", &s->vGrad}, {"rAU", &s->rAU},
         {"HbyA", &s->HbyA}, {"p_diag", &s->pdiag}, {"p_coef", &s->pcoef}, {"p_rhs", &s->pb}, {"mom_diag", &s->diag}, {"mom_lower", &s->lower}, {"mom_upper", &s->upper},
         {"mom_src", &s->src}, {"phiHbyA", &s->phiHbyA}, {"alpha", &s->alpha}, {"uSourceDrag", &s->uSourceDrag}, {"gradP", &s->gradP}, {"divT", &s->divT}, {"ddtU", &s->ddtU},
-        {"phiForces", &s->phiForces}, {"rAUf", &s->rAUf}, {"nut", &s->nut}, {"k", &s->kturb}, {"epsilon", &s->epsturb}};
+        {"phiForces", &s->phiForces}, {"rAUf", &s->rAUf}, {"nut", &s->nut}, {"k", &s->kturb}, {"epsilon", &s->epsturb}, {"vGradNow", &s->vGradNow}};
     for (const auto& e : tab) if (n == e.nm) return e.v;
     return nullptr;
 }
@@ -1081,8 +1094,8 @@ void orc_ldu_destroy(void* h) { delete (Ldu*)h; }
 int orc_ldu_geometry(void* h, const char* name, double* out) {
     Ldu* s = (Ldu*)h;
     const std::string n = name;
-    auto put3 = [&](const std::vector<V3>& v) { for (size_t q = 0; q < v.size(); ++q) { out[3 * q] = v[q].x; out[3 * q + 1] = v[q].y; out[3 * q + 2] = v[q].z; } return (int)(3 * v.size()); };
-    auto put1 = [&](const vec& v) { std::memcpy(out, v.data(), v.size() * sizeof(double)); return (int)v.size(); };
+    auto put3 = [&](const std::vector<V3>& v) { for (size_t q = 0; q < v.size(); ++q) { out[3 * q] = (double)v[q].x; out[3 * q + 1] = (double)v[q].y; out[3 * q + 2] = (double)v[q].z; } return (int)(3 * v.size()); };
+    auto put1 = [&](const vec& v) { for (size_t q = 0; q < v.size(); ++q) out[q] = (double)v[q]; return (int)v.size(); };
     if (n == "C") return put3(s->C);
     if (n == "Cf") return put3(s->Cf);
     if (n == "Sf") return put3(s->Sf);
@@ -1096,7 +1109,41 @@ int orc_ldu_geometry(void* h, const char* name, double* out) {
     if (n == "counts") { out[0] = s->nFaces; out[1] = s->nInt; out[2] = s->nIntReal; return 3; }
     return 0;
 }
-double* orc_ldu_ptr(void* h, const char* name, int* n) { vec* v = ldu_field((Ldu*)h, name); if (!v) return nullptr; *n = (int)v->size(); return v->data(); }
+int orc_ldu_real_mant_dig() { return std::numeric_limits<real>::digits; }
+// the oracle's own storage: the double build only (null where the storage is not double, and for the names that are formed on request)
+double* orc_ldu_ptr(void* h, const char* name, int* n) {
+    vec* v = ldu_field((Ldu*)h, name);
+    if (!std::is_same<real, double>::value || !v) return nullptr;
+    *n = (int)v->size();
+    return reinterpret_cast<double*>(v->data());
+}
+// copy-out / copy-in as doubles (converting loops, the identity in the double build).  Two names are formed on request, in the form the HIP solver stores them:
+// mom_dg = the momentum diagonal with the patches' internal coefficients (Ldu::dgc), mom_b = the source with the patches' boundary coefficients (Ldu::total_source)
+int orc_ldu_field_size(void* h, const char* name) {
+    Ldu* s = (Ldu*)h;
+    const std::string n = name;
+    if (n == "mom_dg") return s->nCells;
+    if (n == "mom_b") return 3 * s->nCells;
+    vec* v = ldu_field(s, n);
+    return v ? (int)v->size() : -1;
+}
+int orc_ldu_get(void* h, const char* name, double* out) {
+    Ldu* s = (Ldu*)h;
+    const std::string n = name;
+    if (n == "mom_dg") { for (int c = 0; c < s->nCells; ++c) out[c] = (double)s->dgc(c); return 0; }
+    vec tmp;
+    const vec* v = ldu_field(s, n);
+    if (n == "mom_b") { s->total_source(tmp); v = &tmp; }
+    if (!v) return 1;
+    for (size_t q = 0; q < v->size(); ++q) out[q] = (double)(*v)[q];
+    return 0;
+}
+int orc_ldu_set(void* h, const char* name, const double* in) {
+    vec* v = ldu_field((Ldu*)h, name);
+    if (!v) return 1;
+    for (size_t q = 0; q < v->size(); ++q) (*v)[q] = in[q];
+    return 0;
+}
 void orc_ldu_step_begin(void* h) { ((Ldu*)h)->step_begin(); }
 void orc_ldu_step_end(void* h) { ((Ldu*)h)->step_end(); }
 void orc_ldu_refresh_phi(void* h) { Ldu* s = (Ldu*)h; s->flux_of(s->U, s->phi); }      // createPhi after U was set from outside

@@ -11,7 +11,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
-LIB_PATH_LD = os.path.join(HERE, "liboracle_ld.so")      # fv_oracle.cpp alone, computing in long double (the reference of tests/test_fv_sweeps_*.py)
+LIB_PATH_LD = os.path.join(HERE, "liboracle_ld.so")      # fv_oracle.cpp and ldu_oracle.cpp computing in long double (the reference of tests/test_fv_sweeps_*.py, tests/test_ldu_sweeps_*.py)
 MAXK = 16
 
 _dp = C.POINTER(C.c_double)
@@ -19,7 +19,7 @@ _ip = C.POINTER(C.c_int)
 
 
 def build(force=False):
-    """compile liboracle.so and liboracle_ld.so (the FV oracle in long double).  The reference driver (oracle/_ref/ref_driver: the reference's FoamYade.C / meshTree.C compiled against the stand-in OpenFOAM
+    """compile liboracle.so and liboracle_ld.so (the two FV oracles in long double).  The reference driver (oracle/_ref/ref_driver: the reference's FoamYade.C / meshTree.C compiled against the stand-in OpenFOAM
     header oracle/shim/fvCFD.H) is NOT built here any more (round 6): this tier's rules do not admit a reference build against stand-in headers, so it is
     neither a pin nor a baseline.  The recipe stays (`make -C oracle ref`, FOAMYADE_BUILD_REF=1 here) as the provenance of the fixtures under tests/golden,
     which tests/golden/gen_golden.py produced with it in round 1 and which are regression data, not a pin (parity unpinned)."""
@@ -27,8 +27,7 @@ def build(force=False):
             os.path.getmtime(os.path.join(HERE, f)) > os.path.getmtime(LIB_PATH)
             for f in os.listdir(HERE) if f.endswith(".cpp") and f != "ref_driver.cpp"):
         subprocess.run(["make", "-C", HERE, "liboracle.so"], check=True, stdout=subprocess.DEVNULL)
-    src = os.path.join(HERE, "fv_oracle.cpp")
-    if force or not os.path.exists(LIB_PATH_LD) or os.path.getmtime(src) > os.path.getmtime(LIB_PATH_LD):
+    if force or not os.path.exists(LIB_PATH_LD) or any(os.path.getmtime(os.path.join(HERE, f)) > os.path.getmtime(LIB_PATH_LD) for f in ("fv_oracle.cpp", "ldu_oracle.cpp")):
         subprocess.run(["make", "-C", HERE, "liboracle_ld.so"], check=True, stdout=subprocess.DEVNULL)
     if os.environ.get("FOAMYADE_BUILD_REF") == "1" and os.path.isdir("/root/reference/FoamYade") and os.path.exists("/opt/conda/lib/libmpi.so"):
         subprocess.run(["make", "-C", HERE, "ref"], check=True, stdout=subprocess.DEVNULL)
@@ -524,23 +523,46 @@ class LduStats(C.Structure):
 
 
 _ldu_ready = False
+_ldu_wide = None
 
 
-def _ldu_lib():
-    global _ldu_ready
+def _ldu_bind(L):
+    L.orc_ldu_create.argtypes = [C.c_int, _dp, C.c_int, C.c_int, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(LduCase)]
+    L.orc_ldu_create.restype = C.c_void_p
+    L.orc_ldu_destroy.argtypes = [C.c_void_p]
+    L.orc_ldu_geometry.argtypes = [C.c_void_p, C.c_char_p, _dp]
+    L.orc_ldu_ptr.argtypes = [C.c_void_p, C.c_char_p, _ip]
+    L.orc_ldu_ptr.restype = C.POINTER(C.c_double)
+    for f in ("orc_ldu_step_begin", "orc_ldu_step_end", "orc_ldu_refresh_phi"):
+        getattr(L, f).argtypes = [C.c_void_p]
+    L.orc_ldu_get_stats.argtypes = [C.c_void_p, C.POINTER(LduStats)]
+    L.orc_ldu_adjust_phi_failed.argtypes = [C.c_void_p]
+    L.orc_ldu_sngrad.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _dp]
+    L.orc_ldu_field_size.argtypes = [C.c_void_p, C.c_char_p]
+    L.orc_ldu_get.argtypes = [C.c_void_p, C.c_char_p, _dp]
+    L.orc_ldu_set.argtypes = [C.c_void_p, C.c_char_p, _dp]
+    L.orc_ldu_real_mant_dig.argtypes = []
+    L.orc_ldu_real_mant_dig.restype = C.c_int
+    return L
+
+
+def _ldu_lib(wide=False):
+    """the general-mesh entry points of liboracle.so, or (wide) of liboracle_ld.so: the same source computing in long double behind the same double interface"""
+    global _ldu_ready, _ldu_wide
+    if wide:
+        if _ldu_wide is None:
+            if not os.path.exists(LIB_PATH_LD):
+                build()
+            L = _ldu_bind(C.CDLL(LIB_PATH_LD))
+            digits = L.orc_ldu_real_mant_dig()
+            if digits != 64:
+                raise RuntimeError(f"oracle: liboracle_ld.so computes with a {digits}-bit mantissa; the reference needs the 64 bits of x87 long double")
+            _ldu_wide = L
+        return _ldu_wide
     L = lib()
     if not _ldu_ready:
-        L.orc_ldu_create.argtypes = [C.c_int, _dp, C.c_int, C.c_int, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _ip, _ip, _ip, C.POINTER(LduCase)]
-        L.orc_ldu_create.restype = C.c_void_p
-        L.orc_ldu_destroy.argtypes = [C.c_void_p]
-        L.orc_ldu_geometry.argtypes = [C.c_void_p, C.c_char_p, _dp]
-        L.orc_ldu_ptr.argtypes = [C.c_void_p, C.c_char_p, _ip]
-        L.orc_ldu_ptr.restype = C.POINTER(C.c_double)
-        for f in ("orc_ldu_step_begin", "orc_ldu_step_end", "orc_ldu_refresh_phi"):
-            getattr(L, f).argtypes = [C.c_void_p]
-        L.orc_ldu_get_stats.argtypes = [C.c_void_p, C.POINTER(LduStats)]
-        L.orc_ldu_adjust_phi_failed.argtypes = [C.c_void_p]
-        L.orc_ldu_sngrad.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _dp]
+        _ldu_bind(L)
+        assert L.orc_ldu_real_mant_dig() == 53
         _ldu_ready = True
     return L
 
@@ -555,9 +577,11 @@ class LduSolver:
                  adjust_time_step=0, max_co=1.0, max_delta_t=1e300, turbulence_model=0, les_ck=0.094, les_ce=1.048, les_delta_coeff=1.0, nut_initial=0.0,
                  nut_bc=None, nut_val=None, convection_scheme=0, convection_limiter_k=1.0, k_initial=0.0, k_bc=None, k_val=None, k_convection_scheme=0, k_tol=1e-6,
                  k_rel_tol=0.0, k_max_iter=1000, k_relax=0.0, ras_cmu=0.09, ras_c1=1.44, ras_c2=1.92, ras_c3=0.0, ras_sigmak=1.0, ras_sigmaeps=1.3, eps_initial=0.0,
-                 eps_bc=None, eps_val=None, eps_convection_scheme=0, eps_tol=1e-6, eps_rel_tol=0.0, eps_max_iter=1000, eps_relax=0.0):
-        """solver = 1: pimpleFoamYade -- step(source, alpha, drag) then takes the void fraction and the implicit drag coefficient the coupling would leave"""
-        self.L = _ldu_lib()
+                 eps_bc=None, eps_val=None, eps_convection_scheme=0, eps_tol=1e-6, eps_rel_tol=0.0, eps_max_iter=1000, eps_relax=0.0, wide=False):
+        """solver = 1: pimpleFoamYade -- step(source, alpha, drag) then takes the void fraction and the implicit drag coefficient the coupling would leave.
+        wide: the long-double build (fields cross the interface as doubles through get / set; view() is not available there)"""
+        self.wide = bool(wide)
+        self.L = _ldu_lib(self.wide)
         self.mesh = mesh
         npatch = len(mesh["patch_start"])
         self._keep = dict(points=np.ascontiguousarray(mesh["points"], np.float64), foff=np.ascontiguousarray(mesh["face_offsets"], np.int32),
@@ -605,6 +629,9 @@ class LduSolver:
         return out
 
     def view(self, name):
+        """numpy view of the oracle's own storage (no copy)"""
+        if self.wide:
+            raise RuntimeError("oracle: the long-double build stores no doubles to view; use get / set")
         n = C.c_int(0)
         ptr = self.L.orc_ldu_ptr(self.h, name.encode(), C.byref(n))
         if not ptr:
@@ -612,24 +639,41 @@ class LduSolver:
         return np.ctypeslib.as_array(ptr, shape=(n.value,))
 
     def get(self, name):
-        return self.view(name).copy()
+        """a copy, as doubles (either build); besides the stored fields: mom_dg, mom_b -- the momentum diagonal and source with the patches' coefficients added"""
+        n = self.L.orc_ldu_field_size(self.h, name.encode())
+        if n < 0:
+            raise KeyError(name)
+        out = np.zeros(n)
+        if n:
+            assert self.L.orc_ldu_get(self.h, name.encode(), _d(out)) == 0
+        return out
 
     def set(self, name, arr):
-        self.view(name)[:] = np.ascontiguousarray(arr, np.float64).ravel()
+        arr = np.ascontiguousarray(arr, np.float64).ravel()
+        n = self.L.orc_ldu_field_size(self.h, name.encode())
+        if n < 0:
+            raise KeyError(name)
+        assert arr.size == n, (name, arr.size, n)
+        if n:
+            assert self.L.orc_ldu_set(self.h, name.encode(), _d(arr)) == 0
         if name == "U":
             self.L.orc_ldu_refresh_phi(self.h)
+
+    def _fill(self, name, arr, default):
+        n = self.L.orc_ldu_field_size(self.h, name.encode())
+        self.set(name, np.full(n, default) if arr is None else arr)
 
     def step(self, source=None, alpha=None, drag=None):
         """source: (nc,3) explicit momentum source uSource for this step (what the coupling would leave), or None; pimpleFoamYade: alpha (the void fraction) and
         drag (uSourceDrag, the implicit coefficient) too.  They are placed where setParticleAction sits in the loop: after the pre-coupling fields"""
         self.L.orc_ldu_step_begin(self.h)
-        self.view("uSource")[:] = 0.0 if source is None else np.ascontiguousarray(source, np.float64).ravel()
+        self._fill("uSource", source, 0.0)
         if self.pimple:
-            self.view("alpha")[:] = 1.0 if alpha is None else np.ascontiguousarray(alpha, np.float64).ravel()
-            self.view("uSourceDrag")[:] = 0.0 if drag is None else np.ascontiguousarray(drag, np.float64).ravel()
+            self._fill("alpha", alpha, 1.0)
+            self._fill("uSourceDrag", drag, 0.0)
         self.L.orc_ldu_step_end(self.h)
         if self.pimple:                                   # yadeCoupling.setSourceZero() (pimpleFoamYade.C:109)
-            self.view("alpha")[:] = 1.0; self.view("uSourceDrag")[:] = 0.0; self.view("uSource")[:] = 0.0
+            self._fill("alpha", None, 1.0); self._fill("uSourceDrag", None, 0.0); self._fill("uSource", None, 0.0)
 
     def stats(self):
         s = LduStats()

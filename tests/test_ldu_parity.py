@@ -1,7 +1,11 @@
 """fy_ldu_solver (icoFoamYade's loop body on a general polyhedral mesh, HIP: csrc/ldu_*.{cpp,hip}) against oracle/ldu_oracle.cpp, the CPU restatement, and
 against the structured HIP solver on a lattice.  FV parity is unpinned (OpenFOAM-6 is not here): what the restatement itself is held to is in
 tests/test_ldu_oracle.py.  Tolerances: geometry 1e-13; matrices of the first step 1e-10; fields after a few steps 2e-6 (both sides converge the same
-linear systems to their tolerances with the same algorithms, summed in another order)."""
+linear systems to their tolerances with the same algorithms, summed in another order).
+
+What is held to ROUNDING is in tests/test_ldu_sweeps_parity.py: with every iteration count frozen the kernels of ldu_kernels.hip and the driver are compared field by
+field with this restatement compiled in long double, within 50 x the double restatement's own distance from it (tests/ldu_sweep_cases.py: mesh kinds, convection
+schemes, patches, loop counts, closures).  This file keeps the converged runs: more steps, larger meshes, the multigrid preconditioner, the cloud on each mesh kind."""
 import numpy as np
 import pytest
 
