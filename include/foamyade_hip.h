@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 25
+#define FY_ABI_VERSION 26
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -904,6 +904,12 @@ int fy_ldu_solver_get_particle_heat_host(fy_ldu_solver*, int batch, double* q);
 int fy_ldu_solver_get_thermal_stats(fy_ldu_solver*, int32_t* iterations, double* initial_residual, double* heat_to_particles_W);
 int fy_ldu_solver_get_particle_thermal_state(fy_ldu_solver*, int batch, double* Tp, int64_t* resets);
 int fy_ldu_solver_hold_sources(fy_ldu_solver*, int on);                    /* as fy_solver_hold_sources: setSourceZero deferred to the next step's start (runTime.write() sees alpha / uSource) */
+/* Point-force mode (icoFoamYade): the cell mesh.findCell (FoamYade.C:251) gave each particle of the last fy_set_particles_* at the last step, in the caller's order,
+ * -1 where fy_get_found_host says -1.  Read-only; waits for the device.  mesh.findCell is decided by OpenFOAM's face-fan tetrahedra (polyMesh::CELL_TETS; star-shaped
+ * cells): a point on a shared triangle, edge or vertex gets one of the cells that share it.  In Gaussian mode (pimpleFoamYade) a particle has a stencil of cells, not
+ * one cell: FY_ERR_UNSUPPORTED, fy_last_error() names this call (fy_get_stencils_host on fy_ldu_solver_coupling() gives the stencils).  FY_ERR_INVALID until a step
+ * has located the particles last set (before the first step; between fy_set_particles_* and the next step). */
+int fy_ldu_solver_get_particle_cells_host(fy_ldu_solver*, int32_t* out_cells /* [n] */);
 fy_ctx* fy_ldu_solver_coupling(fy_ldu_solver*);                              /* FoamYade on this mesh (point force); fy_set_particles_* as usual */
 /* fields by name, host copies: "U" [nc][3], "p", "phi" [n_faces], "uSource" [nc][3] (added to what the coupling leaves: an external momentum source),
  * "rAU", "HbyA", "phiHbyA", "p_diag", "p_coef" [n_faces], "p_rhs", "vGrad" [nc][9]; with pimpleFoamYade "alpha" [nc], "alphaf" [n_faces] (the void fraction on the faces, 1 on the boundary), "uSourceDrag", "uParticle"; with heat transfer "T", "heatSp", "heatSu", "buoyancy" (below); geometry: "C" "V" "Cf" "Sf" "magSf" "w" "dcNO" "kvec";

@@ -26,7 +26,10 @@ def test_library_exports_every_declared_symbol(product):
     assert not missing, f"declared in include/foamyade_hip.h but not exported: {missing}"
     import re
     hdr = open(os.path.join(ROOT, "include", "foamyade_hip.h")).read()
-    assert L.fy_abi_version() == int(re.search(r"#define FY_ABI_VERSION (\d+)", hdr).group(1))      # the library was built from this header
+    assert L.fy_abi_version() == int(re.search(r"#define FY_ABI_VERSION (\d+)", hdr).group(1)) >= 26      # the library was built from this header
+    assert "fy_ldu_solver_get_particle_cells_host" in names                 # (ABI 26: the cell mesh.findCell gave each particle, point-force mode)
+    L.fy_ldu_solver_get_particle_cells_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+    assert L.fy_ldu_solver_get_particle_cells_host(None, None) != 0         # a null solver is refused, not dereferenced
 
 
 # the launchers of fv_linalg_kernels.hip (and its two host helpers): none takes an FvGeo

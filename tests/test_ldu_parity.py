@@ -108,10 +108,13 @@ def test_lattice_block_equals_the_structured_hip_solver(product):
     f.close(); g.close()
 
 
-def test_point_force_coupling_on_a_general_mesh(product):
-    """mesh.findCell (FoamYade.C:251) on a non-lattice mesh = nearest centre + a walk across faces: every particle lands in the cell whose face planes
-    contain it (checked by brute force from the solver's own geometry), particles outside the mesh are not found, and the Stokes drag / torque and the
-    momentum source follow FoamYade.C:437-453 from that cell's U and grad U"""
+def test_point_force_coupling_on_a_general_mesh(product, oracle):
+    """mesh.findCell (FoamYade.C:251) on a non-lattice mesh = nearest centre + a walk across faces: every particle lands in a cell one of whose face-fan tetrahedra
+    holds it (OpenFOAM's CELL_TETS decomposition, checked by brute force in long double from the mesh dictionary: tests/find_cell_ref.py -- the half-spaces through
+    Cf along Sf, which this test used before, do not tile a mesh with warped faces: 13 of these 2 243 interior points lie in another cell by them), particles outside
+    the mesh are not found, and the Stokes drag / torque and the momentum source follow FoamYade.C:437-453 from that cell's U and grad U.  The adversarial inputs
+    (vertices, faces, other cell shapes, cyclic halves) are tests/test_ldu_find_cell.py's"""
+    import find_cell_ref as fr
     n = 8
     mesh = pm.hex_block(n, n, n, vertex_map=pm.wavy(0.04), renumber_seed=12)
     nu, rho = 0.01, 1000.0
@@ -127,21 +130,19 @@ def test_point_force_coupling_on_a_general_mesh(product):
     s.set_particles(rec)
     # the step's grad U is that of U0; the source is consumed by the step, so look at the forces
     s.step()
-    F, found = s.forces(), s.found()
-    C_, Cf, Sf, V = s.geometry("C"), s.geometry("Cf"), s.geometry("Sf"), s.geometry("V")
-    own, nei, ni = mesh["owner"], mesh["neighbour"], len(mesh["neighbour"])
+    F, found, cells = s.forces(), s.found(), s.particle_cells()
     inside_box = np.all((rec[:, 0:3] > 1e-9) & (rec[:, 0:3] < 1 - 1e-9), axis=1)
     assert np.all(found[inside_box] == 1) and np.all(found[~inside_box & np.any((rec[:, 0:3] < -1e-9) | (rec[:, 0:3] > 1 + 1e-9), axis=1)] == -1)
-    # brute force: the cell all of whose faces have the point on the inner side
-    cells_of_face = [(own[f], +1.0) for f in range(len(own))] + [(nei[f], -1.0) for f in range(ni)]
-    face_id = list(range(len(own))) + list(range(ni))
-    for i in np.where(inside_box)[0][:400]:
-        x = rec[i, 0:3]
-        s_out = np.einsum("fk,fk->f", x[None, :] - Cf[face_id], Sf[face_id]) * np.array([sg for _, sg in cells_of_face])
-        worst = np.full(mesh["n_cells"], -np.inf)
-        np.maximum.at(worst, np.array([c for c, _ in cells_of_face]), s_out)
-        c = int(np.argmin(worst))
-        assert worst[c] <= 1e-12
+    o = oracle.LduSolver(mesh, 1e-3, nu, [0] * 6, lid(), [0] * 6)
+    ref = fr.FindCellRef(mesh, o.geometry("C"))
+    o.close()
+    # brute force: the cell with a tetrahedron that holds the point (exactly one for each of these points)
+    idx = np.where(inside_box)[0]
+    holds = ref.cells_of(rec[idx, 0:3])
+    assert all(len(h) == 1 for h in holds)
+    for i, h in zip(idx, holds):
+        c = int(cells[i])
+        assert c in h
         dia = 2 * rec[i, 9]
         drag = 3 * np.pi * dia * nu * rho * (U0[c] - rec[i, 3:6])
         np.testing.assert_allclose(F[i, 0:3], drag, rtol=1e-10, atol=1e-16)

@@ -1738,6 +1738,16 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
         _check(lib().fy_get_found_host(self._cpl, 0, _i(out)))
         return out
 
+    def particle_cells(self):
+        """point-force mode: the cell mesh.findCell gave each record of the last set_particles at the last step (int32, the caller's order, -1: not found);
+        refused by name in Gaussian mode (fy_ldu_solver_get_particle_cells_host)"""
+        L = lib()
+        L.fy_ldu_solver_get_particle_cells_host.argtypes = [C.c_void_p, _ip]
+        n = self._batch_n[0] if getattr(self, "_batch_n", None) else 0       # (no set_particles yet: the library refuses the call by name)
+        out = np.full(n, -1, dtype=np.int32)
+        _check(L.fy_ldu_solver_get_particle_cells_host(self._h, _i(out) if out.size else None))
+        return out
+
     def step(self, source=None):
         """source: an external momentum source [nc][3] added to what the coupling leaves (kept until set again)"""
         if source is not None:

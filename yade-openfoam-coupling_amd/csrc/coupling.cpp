@@ -99,7 +99,7 @@ int Coupling::create(const fy_mesh_desc* m, const fy_field_ptrs* f, int gaussian
     gaussian = gaussian_interp != 0;
     structured = m->nx > 0;
     rectilinear = structured && m->xf && m->yf && m->zf;          // graded block: lattice INDEXING, but no lattice of centres
-    if (!gaussian && !structured && !ldu_geo) return fail(FY_ERR_UNSUPPORTED, "point-force mode needs the structured block description, or a general mesh's face addressing (fy_ldu_solver): the findCell stand-ins");
+    if (!gaussian && !structured && !(ldu_geo && ldu_fans)) return fail(FY_ERR_UNSUPPORTED, "point-force mode needs the structured block description, or a general mesh's face addressing (fy_ldu_solver): the findCell stand-ins");
     if (structured && (int64_t)m->nx * m->ny * m->nz != m->n_cells) return fail(FY_ERR_INVALID, "nx*ny*nz != n_cells");
     if (tr) { transport = *tr; has_transport = true; }
 
@@ -456,6 +456,7 @@ void Coupling::set_num_batches(int nb) {
 
 int Coupling::ensure_batch(Batch& b, int64_t n) {
     b.n = n;
+    b.cells_valid = false;
     if (n == 0) return FY_OK;
     const size_t cap = (size_t)n;
     FY_TRY(b.force.reserve(6 * cap));
@@ -636,6 +637,7 @@ int Coupling::ensure_found(Batch& b) {
 
 // the device part of setParticleAction for one Yade proc (FoamYade.C:612-628 loop body)
 int Coupling::run_batch(Batch& b) {
+    if (b.n == 0) b.cells_valid = true;              // (an empty set has been located)
     if (b.n == 0 && !slab.active) return FY_OK;      // (in slab mode the halo exchanges are collective: every rank walks the same path)
     ForceParams fp{rhoF, nu, 1e-09, rhoP, delta_t, force_models, 0, vol_uniform ? v0 : 0.0, drag_law};
     if (gaussian) {
@@ -868,16 +870,17 @@ int Coupling::run_batch(Batch& b) {
         g.cell_of = nullptr;
         if (!structured) {
             // a general mesh (fy_ldu_solver): mesh.findCell (FoamYade.C:251) = the cell whose centre is nearest (the k-d tree), then a walk across
-            // the faces the point lies outside of until it is inside every face of a cell (k_ldu_find_cell)
+            // the faces whose fans the point lies beyond until a face-fan tetrahedron of a cell holds it (k_ldu_find_cell)
             FY_TRY(b.pos3.reserve(3 * (size_t)std::max<int64_t>(b.n, 1))); FY_TRY(b.cell_hint.reserve((size_t)std::max<int64_t>(b.n, 1)));
             FY_TRY(launch_ldu_positions(stream, b.d_rec, 10, b.n, b.pos3.p));
             FY_TRY(launch_nearest_cell(stream, d_tree.p, nullptr, implicit, n_cells, b.pos3.p, b.n, b.cell_hint.p));
-            FY_TRY(launch_ldu_find_cell(stream, *ldu_geo, b.d_rec, 10, b.n, b.cell_hint.p, b.cell_hint.p));
+            FY_TRY(launch_ldu_find_cell(stream, *ldu_geo, *ldu_fans, b.d_rec, 10, b.n, b.cell_hint.p, b.cell_hint.p));
             g.cell_of = b.cell_hint.p;
         }
         if (timing) marks.mark(3, stream);
         const CellWindow cw{slab.active ? slab.base : 0, n_field};
         FY_TRY(launch_point_force(stream, b.d_rec, b.n, g, fp, cw, d_vol.p, dU, dVGrad, dUSource, b.force.p, b.found.p, b.incell.p, own_of(b)));
+        b.cells_valid = true;
         if (timing) marks.mark(4, stream);
     }
     return FY_OK;
@@ -1369,6 +1372,17 @@ int Coupling::get_found_host(int bi, int32_t* out) {
     Batch& b = *batches[bi];
     FY_TRY(ensure_found(b));
     if (b.n) FY_HIP(hipMemcpyAsync(out, b.found.p, (size_t)b.n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    FY_HIP(hipStreamSynchronize(stream));
+    return FY_OK;
+}
+
+int Coupling::get_particle_cells_host(int bi, int32_t* out, const char* who) {
+    if (gaussian) return fail(FY_ERR_UNSUPPORTED, "%s: Gaussian mode gives a particle a stencil of cells, not one cell (fy_get_stencils_host); point-force mode only", who);
+    if (bi < 0 || bi >= n_batches || bi >= (int)batches.size()) return fail(FY_ERR_INVALID, "%s: no particles were set", who);
+    Batch& b = *batches[bi];
+    if (b.n && !out) return fail(FY_ERR_INVALID, "%s: null array", who);
+    if (!b.cells_valid) return fail(FY_ERR_INVALID, "%s: no step was taken since these particles were set", who);
+    if (b.n) FY_HIP(hipMemcpyAsync(out, b.incell.p, (size_t)b.n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     FY_HIP(hipStreamSynchronize(stream));
     return FY_OK;
 }

@@ -25,6 +25,7 @@ struct Batch {
     DevBuf<uint32_t> key, rank;
     const double* torque_zero_buf = nullptr;   // force buffer whose torque slots [0, torque_zero_n) are known to be zero
     int64_t torque_zero_n = 0;
+    bool cells_valid = false;            // point-force mode: incell holds the cells of these particles (set by the step, cleared when particles are set)
     bool found_stale = false;            // Gaussian mode: `found` is formed lazily from the chain lengths (ensure_found)
     int64_t binned_n = -1;               // particle count the current placement (orig) was computed for
     int bin_age = 0;                     // steps since it was computed
@@ -95,6 +96,7 @@ struct Coupling {
     bool mid_hook_done = true;
     int run_mid_hook() { if (mid_hook && !mid_hook_done) { mid_hook_done = true; return mid_hook(mid_hook_user); } return 0; }
     fy_transport transport{};
+    const struct LduFans* ldu_fans = nullptr; // with it: the faces' point lists and the points, what mesh.findCell's tetrahedra are made of
     const struct LduGeo* ldu_geo = nullptr;   // set before create() by fy_ldu_solver: the general mesh's face addressing on the device (point-force locate)
     int comm_sz_diff = 0;                // FoamYade.H:74
     bool serial_yade = true;             // FoamYade.H:91
@@ -231,6 +233,7 @@ struct Coupling {
     int slab_events();                   // create ev_a / ev_b / ev_tail on first use
     int get_forces_host(int bi, double* out);
     int get_found_host(int bi, int32_t* out);
+    int get_particle_cells_host(int bi, int32_t* out, const char* who);      // point-force mode: the cell mesh.findCell gave each record of the last call, -1: none
     int get_stencils_host(int bi, int32_t* k, int32_t* ids, double* w, int32_t* chain);
     int get_tree_preorder(int32_t* out);
     int field_by_name(const char* name, double** p, size_t* count);

@@ -37,6 +37,16 @@ struct LduHostMesh {
     // the points and, per patch, its first face in the solver's numbering; per boundary face (f - nInt) its points: what nearWallDist measures to
     std::vector<double> pts;
     std::vector<int32_t> pstart, psize, bf_off, bf_pts;
+    // mesh.findCell's tetrahedra (k_ldu_find_cell; with pts above they go to the device in point-force mode only): every face's point list in the solver's numbering
+    // [fp_off[f], fp_off[f + 1]) of fp_pts; entry nFaces + (f - n_real_internal): folded cyclic face f as its NEIGHBOUR cell has it (the other half's own list, at its
+    // own place; other_half = the caller's face, filled by fold_cyclics and emptied by build once the lists are copied).  Per cell the square of the radius of the
+    // ball round C that holds the cell (its furthest face point).  A grid of bins over the bounding box, no bin edge shorter than the largest such radius: the cells
+    // by the bin of their centre, [bin_off[b], bin_off[b + 1]) of bin_cell, b = ix + bin_n[0] (iy + bin_n[1] iz), i = clamp(floor((x - bbox_min) bin_inv))
+    std::vector<int32_t> fp_off, fp_pts, other_half;
+    std::vector<double> cell_r2;
+    int bin_n[3] = {1, 1, 1};
+    double bin_inv[3] = {0, 0, 0};
+    std::vector<int32_t> bin_off, bin_cell;
     // nearWallDist [OF-6 nearWallDist::correct, cellDistFuncs]: per boundary face of a patch with on[patch] set, the distance from its owner's centre to the nearest of
     // the faces of the same patch that share a point with it (itself included); 0 on the other patches
     void near_wall_dist(const std::vector<char>& on, std::vector<double>* y) const;
@@ -68,6 +78,25 @@ struct LduGeo {
     const double* sep;                                   // [3 nInt] or null: folded cyclic faces -- the neighbour cell's image is C_N + sep_f (zero on the mesh's own internal faces)
     int nIntReal;                                        // faces [nIntReal, nInt) are folded cyclic pairs
 };
+
+// what mesh.findCell's stand-in reads beside LduGeo (device pointers): the points, the faces' point lists, the cells' balls, the mesh's bounding box
+struct LduFans {
+    const double* pts;
+    const int32_t *fp_off, *fp_pts;
+    const double* cell_r2;
+    double bbmin[3], bbmax[3];
+    int bin_n[3];                                        // the bins of the cells' centres (LduHostMesh)
+    double bin_inv[3];
+    const int32_t *bin_off, *bin_cell;
+};
+// the bin of coordinate x along axis a: the same statement on the host (the cells' centres) and on the device (a particle)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int ldu_bin_of(double x, double lo, double inv, int n) {
+    const double t = (x - lo) * inv;
+    return t >= (double)(n - 1) ? n - 1 : (t > 0.0 ? (int)t : 0);
+}
 
 // momentum matrix in LDU form: diag [nc] (boundary diagonal included), lower / upper per internal face, b [3 nc] (boundary sources included)
 struct LduMom {
@@ -184,9 +213,9 @@ int launch_ldu_pim_flux(hipStream_t s, LduGeo g, const double* p, const double* 
                         const double* phiForces, const double* psn, double* phi, double* ssf, double* aphi /* [nF]: alphacf phic */);
 int launch_ldu_pim_continuity(hipStream_t s, LduGeo g, const double* aphi, const double* alpha, const double* alphaOld, double* partials);
 int launch_ldu_sum(hipStream_t s, const double* x, int n, int ncomp, double* partials);                  // slot q = sum of component q
-// mesh.findCell stand-in for the point-force locate: from the nearest centre (hint[i], or -1: not located) walk across the face the point lies
-// furthest outside of until it lies inside every face of a cell; cell_out[i] = that cell or -1 (outside the mesh)
-int launch_ldu_find_cell(hipStream_t s, LduGeo g, const double* rec, int rec_len, int64_t n, const int32_t* hint, int32_t* cell_out);
+// mesh.findCell for the point-force locate, by OpenFOAM's face-fan tetrahedra (polyMesh::CELL_TETS): from the cell whose centre is nearest (hint[i], or -1: not
+// located) walk across the face whose fan the point lies beyond until a tetrahedron of the cell holds it; cell_out[i] = that cell or -1 (outside the mesh)
+int launch_ldu_find_cell(hipStream_t s, LduGeo g, LduFans fans, const double* rec, int rec_len, int64_t n, const int32_t* hint, int32_t* cell_out);
 int launch_ldu_positions(hipStream_t s, const double* rec, int rec_len, int64_t n, double* pos3);      // pos3[i] = rec[i][0..2]
 // ---- flow-rate control (ldu_flow_control.hip; fy_flow_control_desc).  The state record, four doubles; two of them trade places at each momentum assembly
 enum { FLOW_GRADP0 = 0, FLOW_DGRADP, FLOW_UBAR, FLOW_RAUAVE, FLOW_RECORD };

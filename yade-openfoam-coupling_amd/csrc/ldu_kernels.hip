@@ -1073,39 +1073,80 @@ __global__ __launch_bounds__(256) void k_ldu_sum(const double* __restrict__ x, i
     block_reduce_store<3>(v, mx, partials, blockIdx.x, gridDim.x);
 }
 
-// mesh.findCell (FoamYade.C:251) on a general mesh of convex cells: from the cell whose centre is nearest, step across the face the point lies
-// furthest outside of until no face has it outside (tolerance 1e-10 of the cell's size); a boundary face on the way = outside the mesh
-__global__ __launch_bounds__(256) void k_ldu_find_cell(LduGeo g, const double* __restrict__ rec, int rec_len, int64_t n, const int32_t* __restrict__ hint, int32_t* __restrict__ cell_out) {
+// mesh.findCell (FoamYade.C:251) on a general mesh, decided as OpenFOAM decides it [OF-6 polyMesh::findCell, CELL_TETS]: every face is split into the triangles
+// (p0, p_i, p_i+1) of its point list, which both of its cells share, and a cell is the union of the tetrahedra (C, p0, p_i, p_i+1) -- they tile the mesh without gaps
+// or overlaps whatever the faces' warp, which the half-spaces through Cf along Sf do not.  STAR-SHAPED cells are assumed (the centre sees every face triangle from
+// its inner side), as by the decomposition itself: then the cones the centre spans with the triangles tile the directions round it.
+//
+// The ONE statement of the inside test.  x = C + mu_a (a - C) + mu_b (b - C) + mu_c (c - C): (mu, 1 - sum mu) are the barycentric coordinates of x in the tetrahedron;
+// x is in it with all four >= -FIND_CELL_TOL, in the triangle's cone with the three mu >= -FIND_CELL_TOL.  Returns 1: a tetrahedron of cell c holds x; 0: none does,
+// and *beyond = the face of the cone x lies in, beyond its triangle (the cone that holds x best, should rounding leave x in none), or -1 where that cone's
+// tetrahedron misses x by the tolerance only (the caller then asks every cell).
+constexpr double FIND_CELL_TOL = 1e-10;
+__device__ __forceinline__ D3 sub3(D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ D3 cross3(D3 a, D3 b) { return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ int ldu_cell_holds(const LduGeo& g, const LduFans& F, int c, D3 x, int* beyond) {
+    const D3 o = ld3(g.C, c), r = sub3(x, o);
+    double best = -1e300, best_lc = 0.0;
+    int best_f = -1;
+    FY_CELL_FACES(g, c, f, nb) {
+        const int e = (g.sep && f >= g.nIntReal && f < g.nInt && nb < c) ? g.nFaces + (f - g.nIntReal) : f;      // (the neighbour cell of a folded cyclic pair has its own half's point list)
+        const int q0 = F.fp_off[e], q1 = F.fp_off[e + 1];
+        const D3 A = sub3(ld3(F.pts, F.fp_pts[q0]), o);
+        D3 B = sub3(ld3(F.pts, F.fp_pts[q0 + 1]), o);
+        for (int q = q0 + 2; q < q1; ++q) {
+            const D3 Cc = sub3(ld3(F.pts, F.fp_pts[q]), o);
+            const D3 BxC = cross3(B, Cc);
+            const double D = dot3(A, BxC);
+            if (D != 0.0) {
+                const double ma = dot3(r, BxC) / D, mb = dot3(r, cross3(Cc, A)) / D, mc = dot3(r, cross3(A, B)) / D;
+                const double lc = 1.0 - ((ma + mb) + mc);
+                const double cone = fmin(ma, fmin(mb, mc));
+                if (cone >= -FIND_CELL_TOL && lc >= -FIND_CELL_TOL) return 1;
+                if (cone > best) { best = cone; best_lc = lc; best_f = f; }
+            }
+            B = Cc;
+        }
+    }
+    *beyond = best_lc < -FIND_CELL_TOL ? best_f : -1;
+    return 0;
+}
+
+// from the cell whose centre is nearest, step across the face whose fan the point lies beyond until a tetrahedron of the cell holds it.  A walk that leaves through a
+// boundary face (beyond a cyclic half is outside the mesh, as mesh.findCell has it), that has not arrived after 32 steps (round an edge of warped faces it can turn
+// in circles) or that meets a cone undecided by rounding proves nothing about an interior point: such a point asks every cell whose ball holds it -- polyMesh::findCell
+// asks all cells when the nearest one is not it; here the cells of the 27 bins round the point's (LduFans: no bin edge is shorter than the largest ball's radius, so
+// a cell whose ball holds the point has its centre in one of them) -- so no point that a tetrahedron holds is given up.  Outside the mesh's bounding box: -1 at once.
+__global__ __launch_bounds__(256) void k_ldu_find_cell(LduGeo g, LduFans F, const double* __restrict__ rec, int rec_len, int64_t n, const int32_t* __restrict__ hint, int32_t* __restrict__ cell_out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double* r = rec + (size_t)rec_len * (size_t)i;
     const D3 x{r[0], r[1], r[2]};
     int c = hint[i];
-    if (!(x.x == x.x) || !(x.y == x.y) || !(x.z == x.z)) c = -1;
-    for (int hop = 0; c >= 0 && hop < 64; ++hop) {
-        // step across the INTERNAL face the point is furthest outside of; the point is outside the mesh only when every face it violates is a
-        // boundary (or cyclic) face -- on a curved or concave boundary the extended plane of the hint cell's wall face can be the worst offender
-        // while an internal face still leads to the containing cell
-        double worst = 0.0, worst_b = 0.0;
-        int wf = -1, wn = -1;
-        const double tol = 1e-10 * cbrt(g.V[c]);
-        FY_CELL_FACES(g, c, f, nb) {
-            const D3 S = ld3(g.Sf, f);
-            D3 cf = ld3(g.Cf, f);
-            const double sg = (f >= g.nInt || nb > c) ? 1.0 : -1.0;
-            const bool folded = g.sep && f >= g.nIntReal && f < g.nInt;
-            if (folded && sg < 0) { const D3 sp = ld3(g.sep, f); cf = D3{cf.x - sp.x, cf.y - sp.y, cf.z - sp.z}; }      // (seen from the neighbour, the face lies at that cell's own half)
-            const double s = sg * dot3(D3{x.x - cf.x, x.y - cf.y, x.z - cf.z}, S) / g.magSf[f];
-            const int to = folded ? -1 : nb;                                  // (beyond a cyclic half = outside the mesh, as mesh.findCell has it)
-            if (to >= 0) { if (s > worst) { worst = s; wf = f; wn = to; } }
-            else if (s > worst_b) worst_b = s;
-        }
-        if (wf < 0 || worst <= tol) {               // no internal face violated: inside this cell, or beyond a boundary face of it
-            if (worst_b > tol) c = -1;
-            break;
-        }
-        c = wn;
-        if (hop == 63) c = -1;
+    const double pad = 1e-9 * fmax(F.bbmax[0] - F.bbmin[0], fmax(F.bbmax[1] - F.bbmin[1], F.bbmax[2] - F.bbmin[2]));
+    if (!(x.x >= F.bbmin[0] - pad && x.x <= F.bbmax[0] + pad && x.y >= F.bbmin[1] - pad && x.y <= F.bbmax[1] + pad && x.z >= F.bbmin[2] - pad && x.z <= F.bbmax[2] + pad)) c = -1;      // (NaN too)
+    if (c < 0) { cell_out[i] = -1; return; }
+    bool arrived = false;
+    for (int hop = 0; hop < 32; ++hop) {
+        int f = -1;
+        if (ldu_cell_holds(g, F, c, x, &f)) { arrived = true; break; }
+        if (f < 0 || f >= g.nInt || (g.sep && f >= g.nIntReal)) break;
+        c = g.own[f] == c ? g.nei[f] : g.own[f];
+    }
+    if (!arrived) {
+        c = -1;
+        const int bx = ldu_bin_of(x.x, F.bbmin[0], F.bin_inv[0], F.bin_n[0]), by = ldu_bin_of(x.y, F.bbmin[1], F.bin_inv[1], F.bin_n[1]), bz = ldu_bin_of(x.z, F.bbmin[2], F.bin_inv[2], F.bin_n[2]);
+        for (int iz = max(bz - 1, 0); iz <= min(bz + 1, F.bin_n[2] - 1) && c < 0; ++iz)
+            for (int iy = max(by - 1, 0); iy <= min(by + 1, F.bin_n[1] - 1) && c < 0; ++iy)
+                for (int ix = max(bx - 1, 0); ix <= min(bx + 1, F.bin_n[0] - 1) && c < 0; ++ix) {
+                    const size_t b = (size_t)ix + (size_t)F.bin_n[0] * ((size_t)iy + (size_t)F.bin_n[1] * (size_t)iz);
+                    for (int q = F.bin_off[b]; q < F.bin_off[b + 1]; ++q) {
+                        const int k = F.bin_cell[q];
+                        const D3 d = sub3(x, ld3(g.C, k));
+                        int f;
+                        if (dot3(d, d) <= F.cell_r2[k] * (1.0 + 1e-9) && ldu_cell_holds(g, F, k, x, &f)) { c = k; break; }
+                    }
+                }
     }
     cell_out[i] = c;
 }
@@ -1342,8 +1383,8 @@ int launch_ldu_positions(hipStream_t s, const double* rec, int rec_len, int64_t 
     FY_LAUNCH_CHECK();
     return FY_OK;
 }
-int launch_ldu_find_cell(hipStream_t s, LduGeo g, const double* rec, int rec_len, int64_t n, const int32_t* hint, int32_t* cell_out) {
-    if (n > 0) hipLaunchKernelGGL(k_ldu_find_cell, dim3(div_up(n, 256)), dim3(256), 0, s, g, rec, rec_len, n, hint, cell_out);
+int launch_ldu_find_cell(hipStream_t s, LduGeo g, LduFans fans, const double* rec, int rec_len, int64_t n, const int32_t* hint, int32_t* cell_out) {
+    if (n > 0) hipLaunchKernelGGL(k_ldu_find_cell, dim3(div_up(n, 256)), dim3(256), 0, s, g, fans, rec, rec_len, n, hint, cell_out);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

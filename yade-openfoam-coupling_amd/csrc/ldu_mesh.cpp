@@ -69,7 +69,7 @@ int LduHostMesh::fold_cyclics(fy_poly_mesh* m) {
     for (int a = 0; a < np; ++a)
         for (int q = 0; q < m->patch_size[a]; ++q) { const int f = m->patch_start[a] + q; if (f < nI || f >= nF) return fail(FY_ERR_INVALID, "fy_poly_mesh: patch %d does not hold boundary faces of its own", a); }
     n_real_internal = nI;
-    f_off.clear(); f_pts.clear(); f_own.clear(); f_nei.clear(); sep.clear(); orig_face.clear();
+    f_off.clear(); f_pts.clear(); f_own.clear(); f_nei.clear(); sep.clear(); orig_face.clear(); other_half.clear();
     f_off.push_back(0);
     auto add_face = [&](int f) {
         for (int q = m->face_offsets[f]; q < m->face_offsets[f + 1]; ++q) f_pts.push_back(m->face_points[q]);
@@ -97,6 +97,7 @@ int LduHostMesh::fold_cyclics(fy_poly_mesh* m) {
             const bool baseA = cA < cB;
             const size_t nf = f_own.size();
             add_face(baseA ? fA : fB);
+            other_half.push_back(baseA ? fB : fA);
             f_own.push_back(baseA ? cA : cB); f_nei.push_back(baseA ? cB : cA);
             const V3 sp = baseA ? ca - cb : cb - ca;                 // the neighbour's image = C_N + sep
             sep[3 * nf] = sp.x; sep[3 * nf + 1] = sp.y; sep[3 * nf + 2] = sp.z;
@@ -122,7 +123,7 @@ int LduHostMesh::build(const fy_poly_mesh* m_in) {
     if (!m || m->n_points < 4 || m->n_faces < 4 || m->n_cells < 1 || m->n_internal_faces < 0 || m->n_internal_faces > m->n_faces || !m->points || !m->face_offsets ||
         !m->face_points || !m->owner || (m->n_internal_faces > 0 && !m->neighbour) || m->n_patches < 1 || !m->patch_start || !m->patch_size)
         return fail(FY_ERR_INVALID, "fy_poly_mesh: missing arrays or empty mesh");
-    sep.clear(); orig_face.clear(); n_real_internal = m->n_internal_faces;
+    sep.clear(); orig_face.clear(); other_half.clear(); n_real_internal = m->n_internal_faces;
     bool any_cyclic = false;
     if (m->patch_neighbour) for (int a = 0; a < m->n_patches; ++a) any_cyclic = any_cyclic || m->patch_neighbour[a] >= 0;
     if (any_cyclic) FY_TRY(fold_cyclics(m));
@@ -151,6 +152,18 @@ int LduHostMesh::build(const fy_poly_mesh* m_in) {
         bf_pts.insert(bf_pts.end(), m->face_points + m->face_offsets[f], m->face_points + m->face_offsets[f + 1]);
         bf_off.push_back((int32_t)bf_pts.size());
     }
+    fp_off.assign(1, 0); fp_pts.clear();
+    for (int f = 0; f < nFaces; ++f) {
+        fp_pts.insert(fp_pts.end(), m->face_points + m->face_offsets[f], m->face_points + m->face_offsets[f + 1]);
+        fp_off.push_back((int32_t)fp_pts.size());
+    }
+    // entry nFaces + (f - n_real_internal): folded face f as its neighbour cell has it -- the other half's own point list, at its own place (mesh.findCell's triangles
+    // are the fan of the list as stored).  m_in still has the caller's faces
+    for (int32_t f : other_half) {
+        fp_pts.insert(fp_pts.end(), m_in->face_points + m_in->face_offsets[f], m_in->face_points + m_in->face_offsets[f + 1]);
+        fp_off.push_back((int32_t)fp_pts.size());
+    }
+    std::vector<int32_t>().swap(other_half);
     // ---- faces
     Cf.assign(3 * (size_t)nFaces, 0.0); Sf = Cf; magSf.assign((size_t)nFaces, 0.0);
     for (int f = 0; f < nFaces; ++f) {
@@ -207,6 +220,41 @@ int LduHostMesh::build(const fy_poly_mesh* m_in) {
         if (!(V[(size_t)c] > 0)) return fail(FY_ERR_INVALID, "fy_poly_mesh: cell %d has no volume (are the faces' points ordered outwards of their owners?)", c);
         put(C, c, (1.0 / V[(size_t)c]) * at(C.data(), c));
         V[(size_t)c] *= (1.0 / 3.0);
+    }
+    // ---- mesh.findCell's balls: the furthest face point of each cell from its centre
+    cell_r2.assign((size_t)nCells, 0.0);
+    for (int f = 0; f < nFaces; ++f)
+        for (int side = 0; side < (f < nInt ? 2 : 1); ++side) {
+            const int c = side ? nei[f] : own[f];
+            const size_t e = side && f >= n_real_internal ? (size_t)nFaces + (size_t)(f - n_real_internal) : (size_t)f;
+            for (int32_t q = fp_off[e]; q < fp_off[e + 1]; ++q) {
+                const V3 d = at(pts.data(), fp_pts[(size_t)q]) - at(C.data(), c);
+                cell_r2[(size_t)c] = std::max(cell_r2[(size_t)c], dot(d, d));
+            }
+        }
+    // the bins of the centres: as many per axis as keep every bin edge above the largest radius (a cell that holds x has its centre within that radius of x: in x's bin
+    // or one next to it), at most 128 per axis
+    {
+        double rmax = 0.0;
+        for (double r2 : cell_r2) rmax = std::max(rmax, std::sqrt(r2));
+        size_t nb = 1;
+        for (int a = 0; a < 3; ++a) {
+            const double ext = bbox_max[a] - bbox_min[a];
+            bin_n[a] = (int)std::min(128.0, std::max(1.0, std::floor(ext / (1.001 * rmax))));
+            bin_inv[a] = bin_n[a] / ext;
+            nb *= (size_t)bin_n[a];
+        }
+        auto bin_of = [&](int c) {
+            const V3 cc = at(C.data(), c);
+            return (size_t)ldu_bin_of(cc.x, bbox_min[0], bin_inv[0], bin_n[0]) +
+                   (size_t)bin_n[0] * ((size_t)ldu_bin_of(cc.y, bbox_min[1], bin_inv[1], bin_n[1]) + (size_t)bin_n[1] * (size_t)ldu_bin_of(cc.z, bbox_min[2], bin_inv[2], bin_n[2]));
+        };
+        bin_off.assign(nb + 1, 0);
+        for (int c = 0; c < nCells; ++c) ++bin_off[bin_of(c) + 1];
+        for (size_t q = 0; q < nb; ++q) bin_off[q + 1] += bin_off[q];
+        bin_cell.assign((size_t)nCells, 0);
+        std::vector<int32_t> fill(bin_off.begin(), bin_off.end() - 1);
+        for (int c = 0; c < nCells; ++c) bin_cell[(size_t)fill[bin_of(c)]++] = c;
     }
     // ---- fvc::reconstruct's tensor: inv(sum over the cell's faces of Sf Sf / |Sf|) (symmetric positive definite for any closed cell)
     recon.assign(9 * (size_t)nCells, 0.0);

@@ -32,6 +32,10 @@ struct LduSolver {
     // geometry + addressing on the device
     DevBuf<int32_t> d_own, d_nei, d_patch_of, d_cf_off, d_cf_face, d_ubc, d_pbc, d_ef, d_en;
     DevBuf<double> d_Cf, d_Sf, d_magSf, d_C, d_V, d_w, d_dcNO, d_kvec, d_uval, d_pval, d_recon;
+    // mesh.findCell's tetrahedra (point-force mode only): points, the faces' point lists, the cells' balls
+    DevBuf<int32_t> d_fp_off, d_fp_pts, d_bin_off, d_bin_cell;
+    DevBuf<double> d_pts, d_cell_r2;
+    LduFans fans{};
     // fields
     DevBuf<double> U, Uold, p, phi, phiOld, uSource, uSourceExt, uSourceSum, vGrad, gradp, dummy3, dummy1;
     DevBuf<double> mdiag, mlower, mupper, mb, fcorr, xscr, rAU, HbyA, rAUf, phiHbyA, pcoef, pcorr, pdiag, prhs, pr, pu, pw, pp, ps;
@@ -419,6 +423,14 @@ struct LduSolver {
             if (!cpl) return fail(FY_ERR_INVALID, "out of host memory");
             cpl->c.ext_stream = stream;
             cpl->c.ldu_geo = &g;
+            if (!pimple) {
+                FY_TRY(up(d_pts, hm.pts)); FY_TRY(up(d_fp_off, hm.fp_off)); FY_TRY(up(d_fp_pts, hm.fp_pts)); FY_TRY(up(d_cell_r2, hm.cell_r2));
+                fans.pts = d_pts.p; fans.fp_off = d_fp_off.p; fans.fp_pts = d_fp_pts.p; fans.cell_r2 = d_cell_r2.p;
+                FY_TRY(up(d_bin_off, hm.bin_off)); FY_TRY(up(d_bin_cell, hm.bin_cell));
+                fans.bin_off = d_bin_off.p; fans.bin_cell = d_bin_cell.p;
+                for (int a = 0; a < 3; ++a) { fans.bbmin[a] = hm.bbox_min[a]; fans.bbmax[a] = hm.bbox_max[a]; fans.bin_n[a] = hm.bin_n[a]; fans.bin_inv[a] = hm.bin_inv[a]; }
+                cpl->c.ldu_fans = &fans;
+            }
             FY_TRY(cpl->c.create(&md, &fp, pimple ? 1 : 0, tr, device));        // gaussianInterp: false in icoFoamYade (icoFoamYade.C:53), true in pimpleFoamYade (pimpleFoamYade.C:52)
             cpl->c.rhoP = c->rho_particle; cpl->c.rhoF = c->rho_fluid; cpl->c.nu = c->nu;      // setScalarProperties (icoFoamYade.C:55)
             if (c->drag_law != FY_DRAG_REFERENCE) FY_TRY(cpl->c.set_drag_law(c->drag_law));                  // constant/couplingProperties
@@ -980,6 +992,11 @@ int fy_ldu_solver_get_thermal_stats(fy_ldu_solver* s, int32_t* iterations, doubl
     if (initial_residual) *initial_residual = S.th.res0;
     if (heat_to_particles_W) FY_TRY(S.th.part.total_heat(S.device, S.stream, heat_to_particles_W));
     return FY_OK;
+}
+int fy_ldu_solver_get_particle_cells_host(fy_ldu_solver* s, int32_t* out_cells) {
+    FY_LS(s);
+    FY_HIP(hipSetDevice(s->s.device));
+    return s->s.cpl->c.get_particle_cells_host(0, out_cells, "fy_ldu_solver_get_particle_cells_host");
 }
 int fy_ldu_solver_hold_sources(fy_ldu_solver* s, int on) { FY_LS(s); s->s.hold_sources = on != 0; return FY_OK; }
 int fy_ldu_solver_mg_levels(fy_ldu_solver* s, int cap, int32_t* cells, int32_t* slots, int* n_levels) {

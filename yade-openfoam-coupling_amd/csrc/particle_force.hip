@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void k_point_force(const double* __restrict__ 
     double* F = force_out + 6 * (size_t)i;
     int cglob;
     if (g.cell_of) {
-        // general mesh: mesh.findCell (FoamYade.C:251) was stood in for by the nearest centre + a walk across faces (k_ldu_find_cell)
+        // general mesh: mesh.findCell (FoamYade.C:251) was answered by the nearest centre + a walk to the cell whose face-fan tetrahedra hold the point (k_ldu_find_cell)
         cglob = g.cell_of[i];
         if (cglob < 0) {
             F[0] = F[1] = F[2] = F[3] = F[4] = F[5] = 0.0;
