@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 26
+#define FY_ABI_VERSION 27
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -357,6 +357,59 @@ typedef struct fy_wall_loads_desc {
     double start_time;
 } fy_wall_loads_desc;
 
+/* Inlets: a fixed-value velocity side (fy_solver) or patch (fy_ldu_solver) whose value varies over its faces and in time (DESIGN.md section 3 "Inlets").  Each face f
+   of the side or patch carries
+       U_f(t) = a_0(t) S_0,f + a_1(t) S_1,f + a_2(t) S_2,f                  (n_terms = 1 .. 3, summed left to right, every bracket one IEEE operation)
+   a_m: a scalar function of time (fy_time_function), evaluated on the host in double once per step at the time the step advances to, start_time + the elapsed time of
+   the steps so far + the step's own delta_t, right after that delta_t is fixed and before any kernel of the step reads a boundary value.  S_m: a vector shape --
+   FY_SHAPE_UNIFORM one vector (shape[3]), FY_SHAPE_PER_FACE one per face (shape[n_faces][3], in the order in which "U_boundary" lists the side's or patch's faces), or
+   FY_SHAPE_FLOW_RATE, which the library forms itself: -n_f / sum |S_f| over the side or patch (n_f the outward unit normal), so that a_m is the volumetric flow rate
+   INTO the domain.  The side's or patch's u_value is then read nowhere.  One launch per step on the solver's stream (the "inlets" kernel clock), no host
+   synchronisation, no atomics; the shapes are uploaded once.  phi is not touched: it picks up the new boundary flux where the loop re-forms it (OpenFOAM's fvc::grad(U)
+   before UEqn would still see the previous value; here every consumer of the step sees the new one).
+   Time functions restate OpenFOAM-6's Function1 set as recalled (unpinned):
+       FY_TIME_CONSTANT   value
+       FY_TIME_TABLE      linear interpolation of points[n_points][2] = (t, v), times strictly increasing; outside [t_0, t_last] FY_TIME_CLAMP holds the end value,
+                          FY_TIME_REPEAT maps t to t_0 + (u - span floor(u / span)), u = t - t_0, span = t_last - t_0 (n_points >= 2 then)
+       FY_TIME_SINE       amplitude sin(2 pi frequency (t - t0))
+       FY_TIME_SQUARE     amplitude times +1 while frac(frequency (t - t0)) < mark_space / (1 + mark_space), else -1 (mark_space 0 is read as 1)
+   All zero (n = 0): no inlets -- nothing allocated, nothing launched, and every kernel computes exactly what it did without them. */
+#define FY_TIME_CONSTANT 0
+#define FY_TIME_TABLE 1
+#define FY_TIME_SINE 2
+#define FY_TIME_SQUARE 3
+#define FY_TIME_CLAMP 0
+#define FY_TIME_REPEAT 1
+#define FY_SHAPE_UNIFORM 0
+#define FY_SHAPE_PER_FACE 1
+#define FY_SHAPE_FLOW_RATE 2
+#define FY_INLETS_MAX 16
+typedef struct fy_time_function {
+    int32_t kind;                   /* FY_TIME_* */
+    double value;                   /* constant */
+    double amplitude, frequency, t0, mark_space;      /* sine, square: frequency > 0 */
+    int32_t n_points;               /* table */
+    const double* points;           /* [n_points][2], copied when the inlets are set */
+    int32_t out_of_bounds;          /* FY_TIME_CLAMP | FY_TIME_REPEAT */
+} fy_time_function;
+typedef struct fy_inlet_term {
+    fy_time_function f;
+    int32_t shape_kind;             /* FY_SHAPE_* */
+    const double* shape;            /* [3] | [n_faces][3] | not read; copied when the inlets are set */
+} fy_inlet_term;
+typedef struct fy_inlet_desc {
+    int32_t patch;                  /* fy_solver: the side 0 .. 5 (x- x+ y- y+ z- z+); fy_ldu_solver: the patch index.  It must be FY_BC_U_FIXED_VALUE */
+    int32_t n_terms;                /* 1 .. 3 */
+    fy_inlet_term terms[3];
+} fy_inlet_desc;
+typedef struct fy_inlets_desc {
+    double start_time;
+    int32_t n;                      /* 0 .. FY_INLETS_MAX, at most one inlet per side or patch */
+    const fy_inlet_desc* inlets;
+} fy_inlets_desc;
+/* the value of a time function at t: the host arithmetic of the inlets, exported so that it can be checked without a device.  NaN for a NULL or malformed function */
+double fy_time_function_eval(const fy_time_function* f, double t);
+
 /* Fluid temperature with particle-fluid heat exchange (a capability the reference does not have; DESIGN.md section 3 "heat exchange", DESIGN_FV.md "T equation").
    Fluid: cp [J/kg/K], kappa [W/m/K], D = kappa / (rho_f cp), Pr = nu rho_f cp / kappa, Deff = D + nut / prt (nut = 0 when laminar).  A particle of diameter d and
    temperature Tp, with the force pass's stencil (cells c, normalised weights w; point-force mode: the containing cell, w = 1, eps = 1):
@@ -470,6 +523,8 @@ typedef struct fy_case_desc {
     fy_monitor_desc monitors;
     /* constant/couplingProperties solidStatistics: the solid-phase statistics, applied at fy_solver_create with fy_solver_set_solid_statistics (0: off) */
     int32_t solid_stats;
+    /* inlets on fixed-value velocity sides (all zero: none -- nothing allocated, nothing launched), applied at fy_solver_create with fy_solver_set_inlets */
+    fy_inlets_desc inlets;
     /* controlDict functions: the forces / wallShearStress / yPlus objects (all zero: none), applied at fy_solver_create with fy_solver_set_wall_loads */
     fy_wall_loads_desc wall_loads;
 } fy_case_desc;
@@ -540,6 +595,13 @@ int fy_solver_get_monitor_rows(fy_solver*, int object, int64_t first_row, int64_
  * y+ z- z+: "min(x-)_x" ... "max(x-)_z" (wallShearStress), "min(x-)" "max(x-)" "average(x-)" (yPlus).
  * Read-only field names while the object is on: "wallShearStress_boundary" [nb][3], "yPlus_boundary" [nb] in the order of "p_boundary", as the last sample left them
  * (zeros on faces outside the set).  Always: "nut_boundary" [nb] (nut on the boundary as the equations see it; zeros when laminar), "nearWallDist" [nb]. */
+/* Inlets on this solver (fy_inlets_desc above).  NULL or n == 0: none, the buffers freed.  Allowed until the first step (afterwards FY_ERR_INVALID): the solver is left
+ * as a create with these inlets would have left it -- the faces carry the value at start_time and the initial boundary flux is re-formed from the current U.
+ * FY_ERR_INVALID by name: a term count outside 1 .. 3, an unknown function or shape kind, a table without points or with times that do not increase, frequency <= 0,
+ * a per-face shape on a side without faces or without its array, a side that does not exist, is listed twice or is not FY_BC_U_FIXED_VALUE (fy_ldu_solver: a cyclic
+ * patch has no faces).  FY_ERR_UNSUPPORTED: a slab solver; no patch fixes the pressure, no velocity patch is adjustable and a term's shape carries a net normal flux
+ * (the rule of fy_solver_create's balance check).  "inlets" is a clock of fy_solver_get_kernel_timing while inlets are set. */
+int fy_solver_set_inlets(fy_solver*, const fy_inlets_desc*);
 int fy_solver_set_wall_loads(fy_solver*, const fy_wall_loads_desc*);
 int fy_solver_wall_loads_layout(fy_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_solver_get_wall_load_rows(fy_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
@@ -579,7 +641,7 @@ int fy_solver_get_particle_thermal_state(fy_solver*, int batch, double* Tp, int6
 
 /* ---- OpenFOAM case directories (what the reference's executables get from runTime / mesh / the field constructors, createFields.H
  * of both solvers, and give back with runTime.write()).  Supported subset: ONE axis-aligned blockMesh hex block of uniform cubes whose
- * six sides are covered by `boundary` patches; velocity patches fixedValue (uniform) / noSlip / zeroGradient; pressure patches
+ * six sides are covered by `boundary` patches; velocity patches fixedValue (uniform, or a nonuniform list: an inlet) / uniformFixedValue / flowRateInletVelocity (inlets, above) / noSlip / zeroGradient; pressure patches
  * zeroGradient / fixedValue (uniform) / fixedFluxPressure; internalField uniform or nonuniform; fixed deltaT.  Everything else is
  * refused with FY_ERR_UNSUPPORTED and a message naming file and keyword.
  *   system/blockMeshDict, system/controlDict, system/fvSolution (PISO | PIMPLE, solvers.p / pFinal / U),
@@ -858,6 +920,7 @@ typedef struct fy_ldu_case {
     fy_monitor_desc monitors;        /* controlDict functions: the volFieldValue / surfaceFieldValue objects as in fy_case_desc (all zero: none); `patch` is a patch index */
     int32_t solid_stats;             /* the solid-phase statistics as in fy_case_desc, applied with fy_ldu_solver_set_solid_statistics (0: off) */
     fy_flow_control_desc flow_control;      /* flow-rate control (all zero: off -- nothing allocated, nothing launched), applied at fy_ldu_solver_create */
+    fy_inlets_desc inlets;                  /* inlets on fixed-value velocity patches as in fy_case_desc (all zero: none), applied with fy_ldu_solver_set_inlets */
     fy_wall_loads_desc wall_loads;          /* the forces / wallShearStress / yPlus objects as in fy_case_desc (all zero: none); a patch set is patches[0 .. n_patches) */
 } fy_ldu_case;
 typedef struct fy_ldu_solver fy_ldu_solver;
@@ -880,6 +943,9 @@ int fy_ldu_solver_get_monitor_rows(fy_ldu_solver*, int object, int64_t first_row
  * a patch that does not exist is refused by name (FY_ERR_INVALID).  delta = deltaCoeffs of the boundary face ("dcNO"), y = nearWallDist, which is then formed for the
  * selected patches as well as for the wall-function patches.  "wallShearStress_boundary" [nb][3], "yPlus_boundary" [nb] in the solver's boundary-face order; the clock
  * is "wall_loads" of fy_ldu_solver_get_kernel_timing. */
+/* Inlets as on fy_solver (fy_solver_set_inlets): `patch` is a patch index, a per-face shape follows the patch's faces in the solver's boundary-face order; the clock
+ * is "inlets" of fy_ldu_solver_get_kernel_timing. */
+int fy_ldu_solver_set_inlets(fy_ldu_solver*, const fy_inlets_desc*);
 int fy_ldu_solver_set_wall_loads(fy_ldu_solver*, const fy_wall_loads_desc*);
 int fy_ldu_solver_wall_loads_layout(fy_ldu_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_ldu_solver_get_wall_load_rows(fy_ldu_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);

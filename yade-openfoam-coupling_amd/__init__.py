@@ -308,6 +308,106 @@ class _WallLoads:
         return t, v
 
 
+TIME_CONSTANT, TIME_TABLE, TIME_SINE, TIME_SQUARE = 0, 1, 2, 3
+TIME_CLAMP, TIME_REPEAT = 0, 1
+SHAPE_UNIFORM, SHAPE_PER_FACE, SHAPE_FLOW_RATE = 0, 1, 2
+INLETS_MAX = 16
+
+
+class TimeFunction(C.Structure):
+    """fy_time_function: constant | table | sine | square"""
+    _fields_ = [("kind", C.c_int32), ("value", C.c_double), ("amplitude", C.c_double), ("frequency", C.c_double), ("t0", C.c_double), ("mark_space", C.c_double),
+                ("n_points", C.c_int32), ("points", C.POINTER(C.c_double)), ("out_of_bounds", C.c_int32)]
+
+
+class InletTerm(C.Structure):
+    _fields_ = [("f", TimeFunction), ("shape_kind", C.c_int32), ("shape", C.POINTER(C.c_double))]
+
+
+class InletDesc(C.Structure):
+    _fields_ = [("patch", C.c_int32), ("n_terms", C.c_int32), ("terms", InletTerm * 3)]
+
+
+class InletsDesc(C.Structure):
+    """fy_inlets_desc: the inlets of a solver (all zero: none).  An object built by inlets_desc keeps the arrays its pointers name alive (_keep)"""
+    _fields_ = [("start_time", C.c_double), ("n", C.c_int32), ("inlets", C.POINTER(InletDesc))]
+
+
+def time_function(spec, keep=None):
+    """spec -> TimeFunction: a number (constant), or a dict with kind "constant" (value) | "table" (points [(t, v) ...], out_of_bounds "clamp" | "repeat") |
+    "sine" | "square" (amplitude, frequency, t0, mark_space); a TimeFunction passes through.  keep: a list that takes the arrays the pointers name"""
+    if isinstance(spec, TimeFunction):
+        return spec
+    f = TimeFunction()
+    if isinstance(spec, (int, float, np.floating, np.integer)):
+        f.kind, f.value = TIME_CONSTANT, float(spec)
+        return f
+    kind = spec["kind"]
+    f.kind = {"constant": TIME_CONSTANT, "table": TIME_TABLE, "sine": TIME_SINE, "square": TIME_SQUARE}.get(kind, kind if isinstance(kind, int) else -1)
+    f.value = float(spec.get("value", 0.0))
+    f.amplitude, f.frequency, f.t0 = float(spec.get("amplitude", 1.0)), float(spec.get("frequency", 0.0)), float(spec.get("t0", 0.0))
+    f.mark_space = float(spec.get("mark_space", 1.0))
+    oob = spec.get("out_of_bounds", "clamp")
+    f.out_of_bounds = {"clamp": TIME_CLAMP, "repeat": TIME_REPEAT}.get(oob, oob if isinstance(oob, int) else -1)
+    if "points" in spec:
+        pts = np.ascontiguousarray(spec["points"], np.float64).reshape(-1, 2)
+        f.n_points, f.points = pts.shape[0], _d(pts)
+        f._pts = pts
+        if keep is not None:
+            keep.append(pts)
+    return f
+
+
+def time_function_eval(spec, t):
+    """fy_time_function_eval: the library's host arithmetic for a time function at t (NaN for a malformed one); no device needed"""
+    L = lib()
+    L.fy_time_function_eval.argtypes = [C.POINTER(TimeFunction), C.c_double]
+    L.fy_time_function_eval.restype = C.c_double
+    keep = []
+    f = time_function(spec, keep)
+    return float(L.fy_time_function_eval(C.byref(f), float(t)))
+
+
+def inlets_desc(inlets, start_time=0.0):
+    """inlets: dicts with patch (a side 0 .. 5 of a block, a patch index of a general mesh) and terms, each a dict with f (what time_function takes) and shape:
+    a vector (uniform), an (n_faces, 3) array (per face, in "U_boundary"'s order on that side or patch) or "flow_rate" -> InletsDesc.  Counts past the limits are
+    passed on for the library to refuse"""
+    d = InletsDesc()
+    d._keep = keep = []
+    inlets = list(inlets or [])
+    arr = (InletDesc * max(len(inlets), 1))()
+    keep.append(arr)
+    for q, spec in enumerate(inlets):
+        o = arr[q]
+        terms = list(spec["terms"])
+        o.patch, o.n_terms = int(spec["patch"]), len(terms)
+        for m, t in enumerate(terms[:3]):
+            o.terms[m].f = time_function(t.get("f", 1.0), keep)
+            sh = t.get("shape")
+            if isinstance(sh, str) or sh is None:
+                o.terms[m].shape_kind = SHAPE_FLOW_RATE if sh == "flow_rate" else (SHAPE_UNIFORM if sh is None else -1)
+            else:
+                a = np.ascontiguousarray(sh, np.float64)
+                o.terms[m].shape_kind = SHAPE_UNIFORM if a.size == 3 and a.ndim == 1 else SHAPE_PER_FACE
+                o.terms[m].shape = _d(a)
+                keep.append(a)
+            if "shape_kind" in t:
+                o.terms[m].shape_kind = int(t["shape_kind"])
+    d.start_time, d.n, d.inlets = float(start_time), len(inlets), arr
+    return d
+
+
+class _Inlets:
+    """inlets on a solver object (Solver: fy_solver_set_inlets, LduSolver: fy_ldu_solver_set_inlets)"""
+
+    def set_inlets(self, inlets=None, start_time=0.0):
+        """as inlets_desc takes them (or an InletsDesc); None or empty: no inlets.  Allowed until the first step"""
+        f = getattr(lib(), f"{self._AVG_PREFIX}_set_inlets")
+        f.argtypes = [C.c_void_p, C.POINTER(InletsDesc)]
+        d = inlets if isinstance(inlets, InletsDesc) else (inlets_desc(inlets, start_time) if inlets else None)
+        _check(f(self._h, C.byref(d) if d is not None else None))
+
+
 class _ParticleHeat:
     """particle batches and the heat exchange's particle side on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*); the object has _h, _cpl, _batch_n"""
     _AVG_PREFIX = "fy_solver"
@@ -425,7 +525,7 @@ class LduCase(C.Structure):
                 ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int32), ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double),
                 ("eps_max_iter", C.c_int32), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("T_bc", _ip), ("T_value", _dp), ("monitors", MonitorDesc),
-                ("solid_stats", C.c_int32), ("flow_control", FlowControlDesc), ("wall_loads", WallLoadsDesc)]
+                ("solid_stats", C.c_int32), ("flow_control", FlowControlDesc), ("inlets", InletsDesc), ("wall_loads", WallLoadsDesc)]
 
 
 NUSSELT_RANZ_MARSHALL, NUSSELT_GUNN = 0, 1
@@ -469,7 +569,7 @@ class CaseDesc(C.Structure):
                 ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double),
                 ("hx", C.POINTER(C.c_double)), ("hy", C.POINTER(C.c_double)), ("hz", C.POINTER(C.c_double)), ("convection_limiter_k", C.c_double),
                 ("drag_law", C.c_int32), ("force_models", C.c_uint32), ("average", AverageDesc), ("thermal", ThermalDesc), ("monitors", MonitorDesc),
-                ("solid_stats", C.c_int32), ("wall_loads", WallLoadsDesc)]
+                ("solid_stats", C.c_int32), ("inlets", InletsDesc), ("wall_loads", WallLoadsDesc)]
 
 
 BC_WALL_FUNCTION, BC_NUT_CALCULATED = 2, 3
@@ -903,7 +1003,8 @@ def case_defaults(solver):
 
 def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 0, 0), u_bc=None, u_val=None, p_bc=None,
               p_val=None, origin=(0, 0, 0), grading=None, **kw):
-    """grading = (hx, hy, hz): cell sizes along the axes of a graded block (fy_case_desc.hx / hy / hz); dx is then ignored"""
+    """grading = (hx, hy, hz): cell sizes along the axes of a graded block (fy_case_desc.hx / hy / hz); dx is then ignored.  inlets = an inlets_desc(...) or the
+    list it takes (fy_case_desc.inlets)"""
     c = case_defaults(solver)
     if grading is not None:
         c._grading = [np.ascontiguousarray(a, dtype=np.float64) for a in grading]      # kept alive on the case object
@@ -923,6 +1024,10 @@ def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 
         if u_val is not None:
             for a in range(3):
                 c.u_value[q][a] = u_val[q][a]
+    inlets = kw.pop("inlets", None)
+    if inlets is not None:                  # an inlets_desc(...) or what it takes (start_time 0); kept alive on the case object
+        c._inlets = inlets if isinstance(inlets, InletsDesc) else inlets_desc(inlets)
+        c.inlets = c._inlets
     for k, v in kw.items():
         assert hasattr(c, k), k
         if isinstance(v, (list, tuple)):
@@ -934,7 +1039,7 @@ def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 
     return c
 
 
-class Solver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
+class Solver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
     """the icoFoamYade / pimpleFoamYade executables' time loop (icoFoamYade.C:65-149, pimpleFoamYade.C:60-114): step() is one
     pass of the loop body, including yadeCoupling.setParticleAction and setSourceZero."""
 
@@ -1537,7 +1642,7 @@ class VirtualSlabs:
         self.solvers, self.comms = [], []
 
 
-class LduSolver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
+class LduSolver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
     """icoFoamYade's loop body on a general polyhedral mesh in OpenFOAM's addressing (fy_ldu_solver, include/foamyade_hip.h).  mesh: dict with points (n,3),
     face_offsets, face_points, owner, neighbour, n_cells, patch_start, patch_size (tests/poly_meshes.py builds them); u_bc / p_bc / values per patch; the
     controls are fy_ldu_case's (defaults: the icoFoam cavity tutorial's)"""
@@ -1558,9 +1663,9 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
         L.fy_ldu_solver_write_field_host.argtypes = [C.c_void_p, C.c_char_p, _dp]
 
     def __init__(self, mesh, dt, nu, u_bc, u_val, p_bc, p_val=None, device=0, transport=None, nut_bc=None, nut_val=None, k_bc=None, k_val=None, eps_bc=None, eps_val=None, thermal=None,
-                 T_bc=None, T_val=None, flow_control=None, **controls):
+                 T_bc=None, T_val=None, flow_control=None, inlets=None, **controls):
         """thermal: a thermal_desc(...) (its six-sided T_bc / T_value are not read here); T_bc / T_val: FY_BC_T_* and the fixed values per patch (None: zeroGradient);
-        flow_control: a flow_control_desc(...)"""
+        flow_control: a flow_control_desc(...); inlets: an inlets_desc(...) or what it takes (start_time 0)"""
         L = lib()
         self._bind()
         npatch = len(mesh["patch_start"])
@@ -1602,6 +1707,9 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
             self.case.T_bc, self.case.T_value = _i(k["tb"]), _d(k["tv"])
         if flow_control is not None:
             self.case.flow_control = flow_control
+        if inlets is not None:
+            k["inlets"] = inlets if isinstance(inlets, InletsDesc) else inlets_desc(inlets)      # (the arrays the descriptor names stay alive with the solver)
+            self.case.inlets = k["inlets"]
         self._create(device, transport)
 
     def _create(self, device, transport):
@@ -1655,7 +1763,7 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _ParticleHeat):
 
     def kernel_timing(self, name):
         """(total_ms, launches) of one instrumented kernel since enable_kernel_timing(True); the clocks here are "solid_stats" and, with flow control on,
-        "flow_control" (every one of its launches is timed and counted) """
+        "flow_control" (every one of its launches is timed and counted), with wall loads "wall_loads", with inlets "inlets" """
         L = lib()
         L.fy_ldu_solver_get_kernel_timing.argtypes = [C.c_void_p, C.c_char_p, _dp, C.POINTER(C.c_int64)]
         ms = C.c_double(0); n = C.c_int64(0)

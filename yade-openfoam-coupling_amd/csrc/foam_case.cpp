@@ -96,6 +96,16 @@ struct fy_foam_case {
         return v;
     }
     std::string class_of_side[6];               // a block's patch type per side (wall | patch | symmetryPlane ...): the default patch set of wallShearStress / yPlus
+    // inlets (fy_inlets_desc; DESIGN.md section 3 "Inlets"): the velocity patches whose entry is fixedValue with a nonuniform list, uniformFixedValue or
+    // flowRateInletVelocity.  patch: the side of a block, the patch index of a general mesh; a per-face shape lies in "U_boundary"'s order on that side or patch
+    struct InletTerm { fy_time_function f{}; std::vector<double> pts; int shape_kind = FY_SHAPE_UNIFORM; std::vector<double> shape; };
+    struct Inlet { int patch = 0; std::vector<InletTerm> terms; };
+    std::vector<Inlet> inlets;
+    mutable std::vector<fy_inlet_desc> inlet_descs;      // what fy_foam_case_desc / fy_foam_case_ldu_desc hand out: pointers into `inlets`
+    // a block read from constant/polyMesh: per side, for face r of the side in "U_boundary"'s order, its place in its PATCH's face list (empty: blockMeshDict alone,
+    // where blockMesh's face order cannot be verified)
+    std::vector<int32_t> side_face_src[6];
+    mutable std::vector<double> u_boundary_now;          // fy_foam_case_write_time*: the solver's "U_boundary" while the fields are written (the inlet patches' `value`)
 };
 
 namespace {
@@ -434,6 +444,7 @@ int read_poly_mesh(fy_foam_case* c) {
     std::vector<std::pair<std::string, FoamDict> > patches;
     FY_TRY(named_dicts(tk, base + "/boundary", &patches));
     std::vector<size_t> side_faces(6, 0);
+    for (int sd = 0; sd < 6; ++sd) c->side_face_src[sd].assign((size_t)nn[(sd / 2 + 1) % 3] * (size_t)nn[(sd / 2 + 2) % 3], -1);
     for (auto& pd : patches) {
         int nf = 0, sf = 0;
         std::string ty;
@@ -458,6 +469,13 @@ int read_poly_mesh(fy_foam_case* c) {
             c->patch_of_side[side] = pd.first;
             c->class_of_side[side] = ty;
             ++side_faces[(size_t)side];
+            {   // the face's place on its side in "U_boundary"'s order (the lower remaining axis fastest), from its smallest corner
+                int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
+                for (int m = 0; m < 4; ++m) for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], pidx[3 * (size_t)fpt[4 * f + m] + a]);
+                const int d = side / 2;
+                const size_t r = d == 0 ? (size_t)lo[1] + (size_t)nn[1] * lo[2] : d == 1 ? (size_t)lo[0] + (size_t)nn[0] * lo[2] : (size_t)lo[0] + (size_t)nn[0] * lo[1];
+                if (r < c->side_face_src[side].size()) c->side_face_src[side][r] = q;
+            }
         }
         if (nf > 0) c->patch_order.push_back(pd.first);
     }
@@ -482,15 +500,18 @@ int read_poly_mesh(fy_foam_case* c) {
     return FY_OK;
 }
 
-std::string entry_text(const FoamDict& d) {
+std::string entry_text(const FoamDict& d, const std::string& indent = "        ") {
     std::string t;
     for (const std::string& k : d.order) {
         const auto* tk = d.tokens(k);
-        if (!tk) continue;
+        if (!tk) {                                             // a sub-dictionary (an inlet's function: `uniformValue { type sine; ... }`, `uniformValueCoeffs { ... }`)
+            if (const FoamDict* sub = d.subdict(k)) t += indent + k + "\n" + indent + "{\n" + entry_text(*sub, indent + "    ") + indent + "}\n";
+            continue;
+        }
         bool blob = false;
         for (const std::string& s : *tk) blob = blob || (!s.empty() && s[0] == '\x01');
         if (blob) continue;                                // (a binary list: not text; the types that need a value here take `uniform`)
-        t += "        " + k;
+        t += indent + k;
         for (const std::string& s : *tk) t += " " + s;
         t += ";\n";
     }
@@ -556,6 +577,175 @@ bool uniform_vector(const FoamDict& pd, double* v) {
     return vt && !vt->empty() && (*vt)[0] == "uniform" && pd.vector3("value", v);
 }
 
+// ---- inlets: OpenFOAM-6's Function1 entries [Constant, Table, Sine, Square, as recalled -- unpinned] -> the terms of an inlet (include/foamyade_hip.h "Inlets")
+using InletTerm = fy_foam_case::InletTerm;
+bool tok_num(const std::vector<std::string>& t, size_t i, double* v) { return i < t.size() && fy::foam_tok_is_number(t[i], v); }
+// `(x y z)` at token i
+bool tok_vec(const std::vector<std::string>& t, size_t i, double* v) {
+    return i + 4 < t.size() && t[i] == "(" && tok_num(t, i + 1, v) && tok_num(t, i + 2, v + 1) && tok_num(t, i + 3, v + 2) && t[i + 4] == ")";
+}
+// the rows `(t v)` / `(t (x y z))` of a table from token i on ("(" or a count and "(")
+bool read_table_rows(const std::vector<std::string>& t, size_t i, int ncomp, std::vector<double>* times, std::vector<double>* vals) {
+    double x;
+    if (tok_num(t, i, &x)) ++i;
+    if (i >= t.size() || t[i] != "(") return false;
+    for (++i; i < t.size() && t[i] != ")";) {
+        if (t[i] != "(" || !tok_num(t, i + 1, &x)) return false;
+        times->push_back(x);
+        i += 2;
+        double v[3];
+        if (ncomp == 1) { if (!tok_num(t, i, v)) return false; vals->push_back(v[0]); i += 1; }
+        else { if (!tok_vec(t, i, v)) return false; vals->insert(vals->end(), v, v + 3); i += 5; }
+        if (i >= t.size() || t[i] != ")") return false;
+        ++i;
+    }
+    return !times->empty() && i < t.size();
+}
+// entry `key` of patch dictionary pd as a Function1 of scalars (ncomp 1: a flow rate, every term takes the flow-rate shape) or of vectors (ncomp 3) -> terms.
+// Written `key <number | (x y z)>;`, `key constant <value>;`, `key table ((t v) ...);`, `key sine | square;` with `<key>Coeffs { ... }`, or `key { type ...; ... }`
+int read_function1(const FoamDict& pd, const std::string& key, int ncomp, const std::string& w, std::vector<InletTerm>* out) {
+    const FoamDict* sub = pd.subdict(key);
+    const std::vector<std::string>* tk = sub ? nullptr : pd.tokens(key);
+    if (!sub && (!tk || tk->empty())) return fail(FY_ERR_UNSUPPORTED, "%s: no '%s' entry", w.c_str(), key.c_str());
+    std::string type;
+    const FoamDict* co = nullptr;
+    size_t at = 0;
+    if (sub) {
+        if (!sub->word("type", &type)) return fail(FY_ERR_UNSUPPORTED, "%s: '%s' is a dictionary without a type", w.c_str(), key.c_str());
+        co = sub->subdict(type + "Coeffs") ? sub->subdict(type + "Coeffs") : sub;
+    } else {
+        double v;
+        if ((*tk)[0] == "(" || fy::foam_tok_is_number((*tk)[0], &v)) type = "constant";
+        else { type = (*tk)[0]; at = 1; co = pd.subdict(key + "Coeffs"); }
+    }
+    const char* accepted = "accepted: constant, table (outOfBounds clamp | repeat), sine, square";
+    auto shaped = [&](InletTerm& T, const double* vec) {          // a scalar function's terms carry the flow-rate shape, a vector function's a vector
+        if (ncomp == 1) T.shape_kind = FY_SHAPE_FLOW_RATE;
+        else { T.shape_kind = FY_SHAPE_UNIFORM; T.shape.assign(vec, vec + 3); }
+    };
+    if (type == "constant" || type == "uniform") {
+        const std::vector<std::string>* vt = sub ? co->tokens("value") : tk;
+        InletTerm T;
+        T.f.kind = FY_TIME_CONSTANT; T.f.value = 1.0;
+        double v[3] = {0, 0, 0};
+        if (!vt || (ncomp == 1 ? !tok_num(*vt, sub ? 0 : at, &T.f.value) : !tok_vec(*vt, sub ? 0 : at, v)))
+            return fail(FY_ERR_UNSUPPORTED, "%s: %s constant needs %s", w.c_str(), key.c_str(), ncomp == 1 ? "a number" : "a vector (x y z)");
+        shaped(T, v);
+        out->push_back(T);
+        return FY_OK;
+    }
+    if (type == "table") {
+        const std::vector<std::string>* vt = sub ? co->tokens("values") : tk;
+        std::vector<double> times, vals;
+        if (!vt || !read_table_rows(*vt, sub ? 0 : at, ncomp, &times, &vals))
+            return fail(FY_ERR_UNSUPPORTED, "%s: %s table needs rows %s", w.c_str(), key.c_str(), ncomp == 1 ? "((t v) ...)" : "((t (x y z)) ...)");
+        int oob = FY_TIME_CLAMP;
+        std::string word;
+        if (co && co->word("outOfBounds", &word)) {
+            if (word == "repeat") oob = FY_TIME_REPEAT;
+            else if (word != "clamp") return fail(FY_ERR_UNSUPPORTED, "%s: %s table: outOfBounds '%s' is not supported (clamp, repeat)", w.c_str(), key.c_str(), word.c_str());
+        }
+        if (co && co->word("interpolationScheme", &word) && word != "linear") return fail(FY_ERR_UNSUPPORTED, "%s: %s table: interpolationScheme '%s' is not supported (linear)", w.c_str(), key.c_str(), word.c_str());
+        if (co && co->has("file")) return fail(FY_ERR_UNSUPPORTED, "%s: %s table: a table read from a file (tableFile) is not supported", w.c_str(), key.c_str());
+        for (int a = 0; a < ncomp; ++a) {
+            InletTerm T;
+            T.f.kind = FY_TIME_TABLE; T.f.out_of_bounds = oob; T.f.n_points = (int32_t)times.size();
+            for (size_t q = 0; q < times.size(); ++q) { T.pts.push_back(times[q]); T.pts.push_back(vals[q * (size_t)ncomp + a]); }
+            const double e[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
+            shaped(T, e);
+            out->push_back(T);
+        }
+        return FY_OK;
+    }
+    if (type == "sine" || type == "square") {
+        if (!co) return fail(FY_ERR_UNSUPPORTED, "%s: %s %s needs its coefficients (%sCoeffs { amplitude; frequency; scale; level; }, or a dictionary with `type %s`)", w.c_str(), key.c_str(), type.c_str(), key.c_str(), type.c_str());
+        InletTerm W, L;
+        W.f.kind = type == "sine" ? FY_TIME_SINE : FY_TIME_SQUARE;
+        W.f.amplitude = 1.0; W.f.mark_space = 1.0;
+        const auto* at_ = co->tokens("amplitude");
+        if (at_) for (const std::string& x : *at_) if (x == "(" || x == "table" || x == "sine" || x == "square") return fail(FY_ERR_UNSUPPORTED, "%s: %s %s: amplitude must be a number (`amplitude 2;` or `amplitude constant 2;`)", w.c_str(), key.c_str(), type.c_str());
+        co->scalar("amplitude", &W.f.amplitude);
+        if (!co->scalar("frequency", &W.f.frequency)) return fail(FY_ERR_UNSUPPORTED, "%s: %s %s needs a frequency", w.c_str(), key.c_str(), type.c_str());
+        co->scalar("start", &W.f.t0); co->scalar("t0", &W.f.t0);
+        co->scalar("markSpace", &W.f.mark_space);
+        L.f.kind = FY_TIME_CONSTANT; L.f.value = 1.0;
+        double sc[3] = {0, 0, 0}, lv[3] = {0, 0, 0};
+        if (ncomp == 1) {
+            if (!co->scalar("scale", &sc[0]) || !co->scalar("level", &lv[0])) return fail(FY_ERR_UNSUPPORTED, "%s: %s %s needs scale and level (numbers)", w.c_str(), key.c_str(), type.c_str());
+            W.f.amplitude *= sc[0]; L.f.value = lv[0];
+        } else if (!co->vector3("scale", sc) || !co->vector3("level", lv)) return fail(FY_ERR_UNSUPPORTED, "%s: %s %s needs scale and level (vectors)", w.c_str(), key.c_str(), type.c_str());
+        shaped(W, sc); shaped(L, lv);
+        out->push_back(W); out->push_back(L);
+        return FY_OK;
+    }
+    return fail(FY_ERR_UNSUPPORTED, "%s: %s of type '%s' is not supported (%s; not tableFile, polynomial, coded)", w.c_str(), key.c_str(), type.c_str(), accepted);
+}
+// the sides of a block that patch `name` covers
+int sides_of_patch(const fy_foam_case* c, const std::string& name) { int n = 0; for (int s = 0; s < 6; ++s) n += c->patch_of_side[s] == name; return n; }
+size_t side_size(const fy_foam_case* c, int side) {
+    const int nn[3] = {c->desc.nx, c->desc.ny, c->desc.nz};
+    return (size_t)nn[(side / 2 + 1) % 3] * (size_t)nn[(side / 2 + 2) % 3];
+}
+// a velocity patch whose entry makes it an inlet: ty = fixedValue with a non-empty `value nonuniform List<vector>`, uniformFixedValue, flowRateInletVelocity
+int inlet_condition(fy_foam_case* c, const std::string& path, size_t pa, const std::string& name, const FoamDict& pd, const std::string& ty) {
+    const std::string w = path + ": patch '" + name + "'";
+    if (!c->general && c->proc_count > 0) return fail(FY_ERR_UNSUPPORTED, "%s: %s in a decomposed case is not supported (inlets run on one domain)", w.c_str(), ty.c_str());
+    if (c->general) for (int32_t nb : c->g_patch_neighbour) if (nb >= 0) return fail(FY_ERR_UNSUPPORTED, "%s: %s in a case with cyclic patches is not supported", w.c_str(), ty.c_str());
+    fy_foam_case::Inlet in;
+    in.patch = (int)pa;
+    if (ty == "fixedValue") {
+        std::vector<double> v;
+        if (!fy::foam_read_list(*pd.tokens("value"), 2, 3, &v)) return fail(FY_ERR_INVALID, "%s: malformed 'value nonuniform List<vector>'", w.c_str());
+        InletTerm T;
+        T.f.kind = FY_TIME_CONSTANT; T.f.value = 1.0; T.shape_kind = FY_SHAPE_PER_FACE;
+        if (c->general) {
+            if (v.size() != 3 * (size_t)c->g_patch_size[pa]) return fail(FY_ERR_INVALID, "%s: the nonuniform value holds %zu vectors, the patch has %d faces", w.c_str(), v.size() / 3, (int)c->g_patch_size[pa]);
+            T.shape = v;
+        } else {
+            const std::vector<int32_t>& src = c->side_face_src[pa];
+            if (src.empty())
+                return fail(FY_ERR_UNSUPPORTED, "%s: a nonuniform fixedValue needs constant/polyMesh: with system/blockMeshDict alone the order of blockMesh's boundary faces cannot be "
+                                                "verified here (run blockMesh, or give 'value uniform (x y z)')", w.c_str());
+            size_t total = 0;
+            for (int s = 0; s < 6; ++s) if (c->patch_of_side[s] == name) total += side_size(c, s);
+            if (v.size() != 3 * total) return fail(FY_ERR_INVALID, "%s: the nonuniform value holds %zu vectors, the patch has %zu faces", w.c_str(), v.size() / 3, total);
+            T.shape.resize(3 * src.size());
+            for (size_t r = 0; r < src.size(); ++r) {
+                if (src[r] < 0 || (size_t)src[r] >= total) return fail(FY_ERR_INVALID, "%s: a face of side %zu has no place in the patch's face list", w.c_str(), pa);
+                for (int q = 0; q < 3; ++q) T.shape[3 * r + q] = v[3 * (size_t)src[r] + q];
+            }
+        }
+        in.terms.push_back(T);
+    } else if (ty == "uniformFixedValue") {
+        FY_TRY(read_function1(pd, "uniformValue", 3, w, &in.terms));
+    } else {
+        bool ex = false;
+        if (pd.has("massFlowRate") || pd.has("rho") || pd.has("rhoInlet")) return fail(FY_ERR_UNSUPPORTED, "%s: flowRateInletVelocity with massFlowRate / rho is not supported (volumetricFlowRate)", w.c_str());
+        if (pd.boolean("extrapolateProfile", &ex) && ex) return fail(FY_ERR_UNSUPPORTED, "%s: flowRateInletVelocity with extrapolateProfile is not supported", w.c_str());
+        if (!c->general && sides_of_patch(c, name) > 1) return fail(FY_ERR_UNSUPPORTED, "%s: flowRateInletVelocity on a patch that covers several sides of the block is not supported", w.c_str());
+        FY_TRY(read_function1(pd, "volumetricFlowRate", 1, w, &in.terms));
+    }
+    c->inlets.push_back(in);
+    return FY_OK;
+}
+// the case's inlets as the solvers take them (pointers into the case object)
+void inlets_desc(const fy_foam_case* c, fy_inlets_desc* out) {
+    c->inlet_descs.assign(c->inlets.size(), fy_inlet_desc{});
+    for (size_t q = 0; q < c->inlets.size(); ++q) {
+        const fy_foam_case::Inlet& in = c->inlets[q];
+        fy_inlet_desc& d = c->inlet_descs[q];
+        d.patch = in.patch; d.n_terms = (int32_t)in.terms.size();
+        for (size_t m = 0; m < in.terms.size() && m < 3; ++m) {
+            d.terms[m].f = in.terms[m].f;
+            if (in.terms[m].f.kind == FY_TIME_TABLE) d.terms[m].f.points = in.terms[m].pts.data();
+            d.terms[m].shape_kind = in.terms[m].shape_kind;
+            d.terms[m].shape = in.terms[m].shape.empty() ? nullptr : in.terms[m].shape.data();
+        }
+    }
+    *out = fy_inlets_desc{};
+    out->start_time = c->start_time; out->n = (int32_t)c->inlets.size(); out->inlets = c->inlets.empty() ? nullptr : c->inlet_descs.data();
+}
+
 // whether the case has field F: U and p always, nut with a turbulence model, k with kEqn / kEpsilon, epsilon with kEpsilon, alpha with pimpleFoamYade
 bool has_field(const fy_foam_case* c, int F) {
     const int tm = c->desc.turbulence_model;
@@ -581,7 +771,8 @@ std::vector<std::string> field_patches(const fy_foam_case* c) {
 }
 
 // one patch's entry of field F (type ty): its FY_BC_* code and value, or the refusal.  The two kinds of case take different sets of types:
-//   both      U: fixedValue (uniform), noSlip, zeroGradient, symmetryPlane / symmetry / slip.  p: zeroGradient, symmetryPlane / symmetry, fixedValue (uniform).
+//   both      U: fixedValue (uniform, or one vector per face: an inlet), uniformFixedValue and flowRateInletVelocity (volumetricFlowRate) with a Function1 of the kinds
+//             read_function1 takes (inlets: DESIGN.md section 3), noSlip, zeroGradient, symmetryPlane / symmetry / slip.  p: zeroGradient, symmetryPlane / symmetry, fixedValue (uniform).
 //             nut: zeroGradient, symmetryPlane / symmetry, fixedValue (uniform), calculated and nutkWallFunction with kEqn / kEpsilon.
 //             k: zeroGradient, symmetryPlane / symmetry, kqRWallFunction, fixedValue (uniform).  epsilon: those of k but kqRWallFunction, epsilonWallFunction
 //   a block   also takes `value nonuniform List<...> 0()` for a fixedValue U or p (decomposePar's value of a patch without a face on the processor), and
@@ -612,10 +803,13 @@ int patch_condition(fy_foam_case* c, int F, const std::string& path, size_t pa, 
     }
     switch (F) {
         case F_U:
+            if (ty == "uniformFixedValue" || ty == "flowRateInletVelocity") { *bc = FY_BC_U_FIXED_VALUE; return inlet_condition(c, path, pa, name, pd, ty); }
             if (ty == "fixedValue") {
                 *bc = FY_BC_U_FIXED_VALUE;
+                const auto* vt = pd.tokens("value");
+                if (vt && vt->size() > 2 && (*vt)[0] == "nonuniform" && !empty_patch_value(vt, 3)) return inlet_condition(c, path, pa, name, pd, ty);      // one vector per face
                 if ((g || !empty_patch_value(pd.tokens("value"), 3)) && !uniform_vector(pd, val))
-                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform (x y z)'", path.c_str(), pn);
+                    return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': fixedValue needs 'value uniform (x y z)' or 'value nonuniform List<vector> N(...)'", path.c_str(), pn);
                 return FY_OK;
             }
             if (ty == "noSlip") { *bc = FY_BC_U_FIXED_VALUE; return FY_OK; }
@@ -676,6 +870,7 @@ int patch_condition(fy_foam_case* c, int F, const std::string& path, size_t pa, 
             break;
     }
     static const char* const what[] = {"velocity", "pressure", "nut", "k", "epsilon"};
+    // (the velocity lists name the types of a plain patch; an inlet's -- uniformFixedValue, flowRateInletVelocity -- are in INTEGRATION.md section 6)
     static const char* const block_types[] = {"fixedValue, noSlip, zeroGradient, symmetryPlane, symmetry, slip", "zeroGradient, fixedValue, fixedFluxPressure",
                                               "zeroGradient, fixedValue; calculated / nutkWallFunction with kEqn / kEpsilon", "zeroGradient, kqRWallFunction, fixedValue",
                                               "zeroGradient, fixedValue, epsilonWallFunction"};
@@ -1595,6 +1790,61 @@ int read_controls(fy_foam_case* c) {
     return read_functions(c, control_dict, join(c->dir, "system/controlDict"));
 }
 
+// An inlet patch in a written time directory keeps its entry as read -- type, function dictionary -- with `value` as the faces' current values (u_boundary_now: the
+// solver's "U_boundary"), in the patch's own face order, so that a run restarted from the directory continues the function at its own time.  false: not an inlet patch,
+// or no solver behind the write (fy_foam_case_write_fields: the entry as read)
+bool inlet_entry(const fy_foam_case* c, const std::string& pn, const std::string& as_read, std::string* text) {
+    if (c->u_boundary_now.empty()) return false;
+    const std::vector<double>& ub = c->u_boundary_now;
+    std::vector<double> v;
+    bool inlet = false;
+    if (c->general) {
+        for (const auto& in : c->inlets) if (c->g_patch_name[(size_t)in.patch] == pn) {
+            inlet = true;
+            const size_t b0 = (size_t)(c->g_patch_start[(size_t)in.patch] - c->g_internal), n = (size_t)c->g_patch_size[(size_t)in.patch];
+            if (3 * (b0 + n) > ub.size()) return false;
+            v.assign(ub.begin() + 3 * b0, ub.begin() + 3 * (b0 + n));
+        }
+    } else {
+        for (const auto& in : c->inlets) inlet = inlet || c->patch_of_side[in.patch] == pn;
+        if (!inlet) return false;
+        size_t total = 0, base = 0;
+        for (int s = 0; s < 6; ++s) if (c->patch_of_side[s] == pn) total += side_size(c, s);
+        v.assign(3 * total, 0.0);
+        for (int s = 0; s < 6; ++s) {
+            const size_t n = side_size(c, s);
+            if (c->patch_of_side[s] == pn)
+                for (size_t r = 0; r < n; ++r) {
+                    const size_t at = c->side_face_src[s].empty() ? r : (size_t)c->side_face_src[s][r];      // (blockMeshDict alone: a one-side patch in the side's own order)
+                    if (at < total && 3 * (base + r) + 2 < ub.size()) for (int q = 0; q < 3; ++q) v[3 * at + q] = ub[3 * (base + r) + q];
+                }
+            base += n;
+        }
+    }
+    if (!inlet) return false;
+    text->clear();
+    size_t pos = 0;
+    while (pos < as_read.size()) {                            // the entry as read, line by line, without its value
+        const size_t e = as_read.find(";\n", pos);
+        const size_t end = e == std::string::npos ? as_read.size() : e + 2;
+        if (as_read.compare(pos, 14, "        value ") != 0) text->append(as_read, pos, end - pos);
+        pos = end;
+    }
+    char buf[128];
+    std::snprintf(buf, sizeof(buf), "        value           nonuniform List<vector> %zu", v.size() / 3);
+    *text += buf;
+    if (c->write_binary) {
+        *text += "(";
+        text->append((const char*)v.data(), v.size() * sizeof(double));
+        *text += ");\n";
+    } else {
+        *text += "\n(\n";
+        for (size_t q = 0; q + 2 < v.size(); q += 3) { std::snprintf(buf, sizeof(buf), "(%.*g %.*g %.*g)\n", c->write_precision, v[q], c->write_precision, v[q + 1], c->write_precision, v[q + 2]); *text += buf; }
+        *text += ");\n";
+    }
+    return true;
+}
+
 int write_field(const fy_foam_case* c, const std::string& tdir, const std::string& tname, const std::string& name, const char* cls, const char* dims, int ncomp,
                 const std::vector<double>& v, const PatchField* bcs, const char* default_bc, const std::vector<std::pair<std::string, std::string> >& extras) {
     const std::string path = tdir + "/" + name;
@@ -1630,6 +1880,13 @@ int write_field(const fy_foam_case* c, const std::string& tdir, const std::strin
         size_t pa = names.size();
         for (size_t q = 0; q < names.size(); ++q) if (names[q] == pn) pa = q;
         const bool known = bcs && pa < bcs->text.size() && !bcs->text[pa].empty();
+        std::string inlet_text;
+        if (known && bcs == &c->bcs[F_U] && inlet_entry(c, pn, bcs->text[pa], &inlet_text)) {
+            std::fprintf(f, "    %s\n    {\n", pn.c_str());
+            std::fwrite(inlet_text.data(), 1, inlet_text.size(), f);      // (a binary list: not a C string)
+            std::fprintf(f, "    }\n");
+            continue;
+        }
         std::fprintf(f, "    %s\n    {\n%s    }\n", pn.c_str(), known ? bcs->text[pa].c_str() : default_bc);
     }
     // a decomposed case's processor patches, as the start time's file had them (fields without a start-time file: those of U, type only)
@@ -1958,6 +2215,7 @@ int fy_foam_case_desc(const fy_foam_case* c, fy_case_desc* out) {
     if (!c || !out) return fail(FY_ERR_INVALID, "fy_foam_case_desc: null argument");
     if (c->general) return fail(FY_ERR_UNSUPPORTED, "fy_foam_case_desc: the case holds a general mesh: fy_foam_case_poly_mesh + fy_foam_case_ldu_desc for fy_ldu_solver_create");
     *out = c->desc;
+    inlets_desc(c, &out->inlets);
     return FY_OK;
 }
 
@@ -2072,7 +2330,16 @@ int fy_foam_case_write_time(const fy_foam_case* c, fy_solver* s, const char* tim
     int64_t cnt = 0;
     FY_TRY(fy_solver_field_count(s, "p", &cnt));
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_UNSUPPORTED, "fy_foam_case_write_time: the solver holds %lld cells, the case's field files %zu (a slab of an undecomposed case: gather the slabs and use fy_foam_case_write_fields)", (long long)cnt, c->fcells);
-    FY_TRY(write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_EPS, F_K}, [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); }));
+    c->u_boundary_now.clear();
+    if (!c->inlets.empty()) {                             // the inlet patches' `value`: the faces' current values
+        int64_t nb = 0;
+        FY_TRY(fy_solver_field_count(s, "U_boundary", &nb));
+        c->u_boundary_now.resize((size_t)nb);
+        FY_TRY(fy_solver_read_field_host(s, "U_boundary", c->u_boundary_now.data()));
+    }
+    const int wrc = write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_EPS, F_K}, [s](const char* nm, double* v) { return fy_solver_read_field_host(s, nm, v); });
+    c->u_boundary_now.clear();
+    FY_TRY(wrc);
     if (has_field(c, F_T)) {                              // T | T.<phase> beside them, with the start time's patch entries
         std::vector<double> T(c->fcells);
         FY_TRY(fy_solver_read_field_host(s, "T", T.data()));
@@ -2162,6 +2429,7 @@ int fy_foam_case_ldu_desc(const fy_foam_case* c, fy_ldu_case* out) {
     out->monitors = d.monitors;
     out->wall_loads = d.wall_loads;
     out->flow_control = c->flow;
+    inlets_desc(c, &out->inlets);
     out->u_bc = U.bc.data(); out->u_value = U.val.data(); out->p_bc = p.bc.data(); out->p_value = p.val.data();
     return FY_OK;
 }
@@ -2181,7 +2449,16 @@ int fy_foam_case_write_time_ldu(const fy_foam_case* c, fy_ldu_solver* s, const c
     FY_TRY(fy_ldu_solver_field_count(s, "p", &cnt));
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_INVALID, "fy_foam_case_write_time_ldu: the solver holds %lld cells, the case %zu", (long long)cnt, c->fcells);
     // (alpha: with fy_ldu_solver_hold_sources, before setSourceZero)
-    FY_TRY(write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_K, F_EPS}, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); }));
+    c->u_boundary_now.clear();
+    if (!c->inlets.empty()) {                             // the inlet patches' `value`: the faces' current values
+        int64_t nb = 0;
+        FY_TRY(fy_ldu_solver_field_count(s, "U_boundary", &nb));
+        c->u_boundary_now.resize((size_t)nb);
+        FY_TRY(fy_ldu_solver_read_field_host(s, "U_boundary", c->u_boundary_now.data()));
+    }
+    const int wrc = write_solver_fields(c, time_name, {F_U, F_P, F_ALPHA, F_NUT, F_K, F_EPS}, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); });
+    c->u_boundary_now.clear();
+    FY_TRY(wrc);
     FY_TRY(write_solid_stats(c, time_name, [s](const char* nm, int64_t* n) { return fy_ldu_solver_field_count(s, nm, n); }, [s](const char* nm, double* v) { return fy_ldu_solver_read_field_host(s, nm, v); }));
     fy_step_stats st;
     FY_TRY(fy_ldu_solver_get_stats(s, &st));

@@ -150,8 +150,29 @@ __device__ __forceinline__ bool onb(const FvGeo& g, int d, int s, int i, int j, 
 // face coordinate q along d (0..ndim): physical low / high boundary?
 __device__ __forceinline__ bool face_low_b(const FvGeo& g, int d, int q) { return d == 2 ? (q + g.kglob0 == 0) : (q == 0); }
 __device__ __forceinline__ bool face_high_b(const FvGeo& g, int d, int q) { return d == 2 ? (q + g.kglob0 == g.nzglob) : (q == ndim(g, d)); }
+// Inlets (FvGeo::inl): the index of the boundary face of owned cell c (storage index) on side `patch` in "U_boundary"'s order -- the six sides x- x+ y- y+ z- z+,
+// each side's faces with the lower remaining axis fastest.  Single domain only (an inlet refuses z-slabs): the storage index is the lattice index
+__device__ __forceinline__ int boundary_face_of(const FvGeo& g, int patch, int c) {
+    const int t = c - g.c0, i = t % g.nx, jk = t / g.nx;
+    const int nyz = g.ny * g.nz, nxz = g.nx * g.nz, nxy = g.nx * g.ny, d = patch >> 1, s = patch & 1;
+    return d == 0 ? s * nyz + jk : d == 1 ? 2 * nyz + s * nxz + (i + g.nx * (jk / g.ny)) : 2 * (nyz + nxz) + s * nxy + (i + g.nx * (jk % g.ny));
+}
+// component q of the value a fixedValue side `patch` carries at the boundary face of cell c: the side's one vector, or the face's own where the side is an inlet
+// (null pointer, no inlets: exactly the uniform read, as it always was, behind one scalar test of a kernel argument)
+__device__ __forceinline__ double u_fixed(const FvGeo& g, int patch, int c, int q) {
+    if (g.inl != nullptr) { const InletView v = *g.inl; if ((v.sides >> patch) & 1) return v.u_face[3 * (size_t)boundary_face_of(g, patch, c) + q]; }
+    return g.u_val[patch][q];
+}
+// ... and the whole vector behind one test
+__device__ __forceinline__ void u_fixed3(const FvGeo& g, int patch, int c, double* out) {
+    out[0] = g.u_val[patch][0]; out[1] = g.u_val[patch][1]; out[2] = g.u_val[patch][2];
+    if (g.inl != nullptr) {
+        const InletView v = *g.inl;
+        if ((v.sides >> patch) & 1) { const double* u = v.u_face + 3 * (size_t)boundary_face_of(g, patch, c); out[0] = u[0]; out[1] = u[1]; out[2] = u[2]; }
+    }
+}
 __device__ __forceinline__ void Ub(const FvGeo& g, const double* F, int c, int patch, double* out) {
-    if (g.u_bc[patch] == 0) { out[0] = g.u_val[patch][0]; out[1] = g.u_val[patch][1]; out[2] = g.u_val[patch][2]; }
+    if (g.u_bc[patch] == 0) u_fixed3(g, patch, c, out);
     else { out[0] = F[3 * (size_t)c]; out[1] = F[3 * (size_t)c + 1]; out[2] = F[3 * (size_t)c + 2]; }
     // symmetryPlane / slip on a planar, axis-aligned patch [OF-6 basicSymmetryFvPatchField::evaluate]: the cell value without its normal component
     if (g.u_bc[patch] == 2) out[patch >> 1] = 0.0;
@@ -340,7 +361,7 @@ __device__ __forceinline__ void phiHbyA_face(const FvGeo& g, size_t f, int i, in
     } else {
         double uf;
         bool fixes = false;
-        if (bpatch >= 0) { fixes = g.u_bc[bpatch] == 0; double b[3]; Ub(g, Uold, bc, bpatch, b); uf = b[D] * Afc; }
+        if (bpatch >= 0) { fixes = g.u_bc[bpatch] == 0; double b[3]; if (bpatch == 2 * D) Ub(g, Uold, bc, 2 * D, b); else Ub(g, Uold, bc, 2 * D + 1, b); uf = b[D] * Afc; }      // (the side as a constant: FvGeo's tables are indexed by it)
         else { const int c = cidx(g, i, j, k); uf = geo_lerp(g, D, q, Uold[3 * (size_t)(c - stride_of(g, D)) + D], Uold[3 * (size_t)c + D]) * Afc; }
         const double po = phiOld[f];
         const double phiCorr = po - uf;
@@ -353,7 +374,8 @@ __device__ __forceinline__ void phiHbyA_face(const FvGeo& g, size_t f, int i, in
     if (g.pimple) v += phiForces[f];
     out[f] = v;
     if (bpatch >= 0 && g.p_bc[bpatch] == 2) {
-        double ub[3]; Ub(g, U, bc, bpatch, ub);
+        double ub[3];
+        if (bpatch == 2 * D) Ub(g, U, bc, 2 * D, ub); else Ub(g, U, bc, 2 * D + 1, ub);
         psn[f] = (v - ub[D] * Afc) / (rAUf[f] * Afc);
     }
 }
@@ -498,10 +520,10 @@ __global__ __launch_bounds__(256) void k_courant(FvGeo g, CFace3 phi, double* __
 // ---- the explicit stress term G = alpha nuEff dev2(T(grad U)) and its divergence, piece by piece: stated once for the two sweeps that hand G through memory
 // (k_pre_coupling, k_div_G) and for the sweep that keeps it in LDS (k_stress_div), so that both paths form every value by the same operations in the same order
 // U at face (d, s) of a cell (qc = its index along d) from the cell's value uc and its neighbour's un: on a physical boundary Ub() on the cell's own value
-__device__ __forceinline__ void u_face_value(const FvGeo& g, int d, int s, bool on_boundary, int qc, const double (&uc)[3], const double* un, double (&fv)[3]) {
+__device__ __forceinline__ void u_face_value(const FvGeo& g, int d, int s, bool on_boundary, int qc, int c, const double (&uc)[3], const double* un, double (&fv)[3]) {
     if (on_boundary) {
         const int patch = 2 * d + s;
-        if (g.u_bc[patch] == 0) { fv[0] = g.u_val[patch][0]; fv[1] = g.u_val[patch][1]; fv[2] = g.u_val[patch][2]; }
+        if (g.u_bc[patch] == 0) u_fixed3(g, patch, c, fv);
         else { fv[0] = uc[0]; fv[1] = uc[1]; fv[2] = uc[2]; }
         if (g.u_bc[patch] == 2) fv[d] = 0.0;
     } else {
@@ -593,7 +615,7 @@ __global__ __launch_bounds__(256) void k_pre_coupling(FvGeo g, const double* __r
         double fv[2][3], fp[2] = {0, 0};
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            u_face_value(g, d, s, bnd[d][s], ijk[d], uc, un6[d][s], fv[s]);
+            u_face_value(g, d, s, bnd[d][s], ijk[d], c, uc, un6[d][s], fv[s]);
             if (bnd[d][s]) {
                 if (pf) {
                     fp[s] = pbv(g, p, psn, c, d, s, cface(g, d, s, i, j, k));
@@ -747,7 +769,7 @@ __device__ __forceinline__ void stress_rows_at(const FvGeo& g, const double* __r
     for (int d = 0; d < 3; ++d) {
         double fv[2][3];
 #pragma unroll
-        for (int s = 0; s < 2; ++s) u_face_value(g, d, s, bnd[d][s], ijk[d], uc, un6[d][s], fv[s]);
+        for (int s = 0; s < 2; ++s) u_face_value(g, d, s, bnd[d][s], ijk[d], c, uc, un6[d][s], fv[s]);
         grad_row(g, d, ijk[d], fv, T);
     }
     const double tr = stress_trace(T);
@@ -1188,7 +1210,9 @@ __global__ __launch_bounds__(256) void k_assemble_momentum(FvGeo g, const double
                 if (g.u_bc[patch] == 0) {
                     const double gb = kBfac * gam;
                     dg += gb;
-                    for (int q = 0; q < 3; ++q) s3[q] += (-phio + gb) * g.u_val[patch][q];
+                    double ub[3];
+                    u_fixed3(g, patch, c, ub);
+                    for (int q = 0; q < 3; ++q) s3[q] += (-phio + gb) * ub[q];
                 } else {
                     // symmetryPlane / slip [OF-6 transformFvPatchField::gradientInternalCoeffs with basicSymmetry's snGradTransformDiag]: the
                     // NORMAL component sees a fixed value 0 (implicit coefficient only), the tangential ones a zero gradient
@@ -1593,8 +1617,8 @@ __device__ __forceinline__ double rAUf_at(const FvGeo& g, const FaceSrc& a, size
 // Only what boundary faces alone need (psn, U at a fixedFluxPressure patch) stays behind a branch: interior waves skip it.
 
 // value of a vector field's component d at a boundary face, from the field's own-cell value (Ub, component d: patch >> 1 == d here)
-__device__ __forceinline__ double ub_normal(const FvGeo& g, int patch, int d, double own_d) {
-    return g.u_bc[patch] == 0 ? g.u_val[patch][d] : (g.u_bc[patch] == 2 ? 0.0 : own_d);
+__device__ __forceinline__ double ub_normal(const FvGeo& g, int patch, int d, int c, double own_d) {
+    return g.u_bc[patch] == 0 ? u_fixed(g, patch, c, d) : (g.u_bc[patch] == 2 ? 0.0 : own_d);
 }
 // flux correction + velocity correction [+ continuity errors + the next pass's Courant sums] in one sweep (icoFoamYade.C:127-137, pEqn.H:39-45,
 // continuityErrs.H, CourantNo.H): k_flux_correct_cells and k_U_correct<DIAG> without the face field between them
@@ -1766,7 +1790,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                 }
                 const double af = afv[d][s], rf = rfv[d][s];
                 const double Afc = geo_Af(g, d, fi, fj, fk);
-                double pv = (b ? ub_normal(g, patch, d, hb[d]) : lerp_face(g, d, s, q, hb[d], hn[d][s])) * Afc;      // face_flux_vec(HbyA)
+                double pv = (b ? ub_normal(g, patch, d, c, hb[d]) : lerp_face(g, d, s, q, hb[d], hn[d][s])) * Afc;      // face_flux_vec(HbyA)
                 double add = rf * dc[d][s];
                 if (pim) add *= af;
                 pv += add;
@@ -1777,7 +1801,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                 gg6[d][s] = 0.0;
                 if (b) {
                     if (g.p_bc[patch] == 2) {               // constrainPressure (fixedFluxPressure): snGrad(p) from the flux that must pass
-                        const double ubd = ub_normal(g, patch, d, g.u_bc[patch] == 1 ? U[3 * (size_t)c + d] : 0.0);
+                        const double ubd = ub_normal(g, patch, d, c, g.u_bc[patch] == 1 ? U[3 * (size_t)c + d] : 0.0);
                         const double psn_v = (pv - ubd * Afc) / (rf * Afc);
                         if (own) psn.a[d][fx[d][s]] = psn_v;
                         ph = (s ? 1.0 : -1.0) * af * (pv - rf * geo_Af(g, d, i, j, k) * psn_v);
@@ -1935,7 +1959,7 @@ __device__ __forceinline__ void wl_block_face(const FvGeo& g, const WlBlockGeo& 
         for (int s = 0; s < 2; ++s) {
             const bool ob = onb(g, d, s, i, j, k);
             const double* un = ob ? nullptr : U + 3 * (size_t)(c + (s ? stride_of(g, d) : -stride_of(g, d)));
-            u_face_value(g, d, s, ob, ijk[d], uc, un, fv[s]);
+            u_face_value(g, d, s, ob, ijk[d], c, uc, un, fv[s]);
         }
         grad_row(g, d, ijk[d], fv, f.G);
     }

@@ -12,6 +12,9 @@
 
 namespace fy {
 
+// an inlet's view for the kernels (FvGeo::inl)
+struct InletView { const double* u_face; int sides; };
+
 // geometry + boundary conditions, passed by value to every kernel
 // z-slab decomposition: a rank owns nz consecutive z-planes of a global block of nzglob planes; every CELL array
 // carries gz ghost planes below and above them (storage index c = i + nx*(j + ny*(k + gz)), owned cells are the contiguous range
@@ -25,6 +28,10 @@ struct FvGeo {
     double rdx, rhdx, rV;   // 1/dx, 1/(dx/2), 1/V: the uniform block's deltaCoeffs and reciprocal volume (one FP64 multiply instead of a ~60-cycle divide per use)
     int u_bc[6];            // FY_BC_U_*
     double u_val[6][3];
+    // inlets (inlets.hpp): null, or a record on the device -- u_face [all boundary faces][3] in "U_boundary"'s order, read in u_val's place on the sides of the mask
+    // `sides` (bit 2 d + s).  Null: every side is uniform and every kernel computes exactly what it did without the pointer.  One pointer, and the record behind it
+    // rather than in here: the sweeps are short of scalar registers, and what a kernel argument holds is live from the kernel's first instruction.  Single domain only
+    const InletView* inl;
     int p_bc[6];            // FY_BC_P_*
     double p_val[6];
     int pimple;

@@ -27,11 +27,15 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     if (c->thermal.on && cm && cm->size > 1)        // (before anything collective: every rank leaves here)
         return fail(FY_ERR_UNSUPPORTED, "fy_solver_create_slab: heat transfer (fy_case_desc.thermal.on) is not available on z-slabs (%d ranks; foamYadeHip_mpi -parallel): "
                                         "run the case on one domain", cm->size);
+    if (c->inlets.n && cm && cm->size > 1)
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_create_slab: inlets (fy_case_desc.inlets) are not available on z-slabs (%d ranks; foamYadeHip_mpi -parallel): "
+                                        "run the case on one domain", cm->size);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FY_ERR_NO_DEVICE, "no HIP device visible: libfoamyade_hip has no CPU path");
     if (dev < 0 || dev >= ndev) return fail(FY_ERR_INVALID, "device ordinal out of range");
     cs = *c; device = dev; pimple = c->solver == FY_SOLVER_PIMPLE;
     cs.hx = cs.hy = cs.hz = nullptr;        // (the caller's arrays are copied below, not kept)
+    cs.inlets = fy_inlets_desc{};           // (copied by set_inlets at the end of create)
     comm = cm ? cm : &self_comm;
     FY_HIP(hipSetDevice(device));
     FY_HIP(hipStreamCreate(&stream));
@@ -97,6 +101,7 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     g.lim_twoByk = 2.0 / std::max(c->convection_limiter_k, 1e-15);
     g.rdx = 1.0 / g.dx; g.rhdx = 1.0 / (0.5 * g.dx); g.rV = 1.0 / g.V;
     g.pimple = pimple ? 1 : 0; g.dt = c->dt; g.nu = c->nu;
+    g.inl = nullptr;
     bool need_ref = true;
     for (int q = 0; q < 6; ++q) {
         if (c->u_bc[q] != FY_BC_U_FIXED_VALUE && c->u_bc[q] != FY_BC_U_ZERO_GRADIENT && c->u_bc[q] != FY_BC_U_SLIP) return fail(FY_ERR_INVALID, "fy_solver_create: unknown velocity boundary type %d on side %d", c->u_bc[q], q);
@@ -164,19 +169,10 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
         // adjustPhi (icoFoamYade.C:108, pEqn.H:13-16) acts when no patch fixes the pressure.  It is the identity when every patch fixes U
         // and the prescribed normal velocities balance (closed boxes, cavities): nothing is launched then.  With fixed-value patches
         // that do NOT balance and no patch to adjust, OpenFOAM stops at the first corrector; say so here.
-        double net = 0.0, mag = 0.0;
-        bool adjustable = false;
-        const double area[3] = {(double)c->ny * c->nz, (double)c->nx * c->nz, (double)c->nx * c->ny};
-        for (int q = 0; q < 6; ++q) {
-            if (c->u_bc[q] == FY_BC_U_SLIP) continue;                       // (carries no flux, and none to adjust)
-            if (c->u_bc[q] != FY_BC_U_FIXED_VALUE) { adjustable = true; continue; }
-            const double un = c->u_value[q][q / 2] * ((q & 1) ? 1.0 : -1.0) * area[q / 2];
-            net += un; mag += std::fabs(un);
-        }
-        if (!adjustable && std::fabs(net) > 1e-8 * (mag + 1e-300))
-            return fail(FY_ERR_UNSUPPORTED, "no patch fixes the pressure and the fixed-value velocity patches do not balance (net flux %g of %g): OpenFOAM's adjustPhi "
-                                            "ends such a run with 'Continuity error cannot be removed by adjusting the outflow'", net, mag);
-        adjust_phi = adjustable || mag > 0.0;
+        // (a side with an inlet does not read its u_value: set_inlets, at the end of create, repeats the check with the inlets' own fluxes)
+        int inlet_sides = 0;
+        for (int r = 0; r < c->inlets.n && r < FY_INLETS_MAX && c->inlets.inlets; ++r) if (c->inlets.inlets[r].patch >= 0 && c->inlets.inlets[r].patch < 6) inlet_sides |= 1 << c->inlets.inlets[r].patch;
+        FY_TRY(balance_check(inlet_sides, false, &adjust_phi));
     }
 
     const size_t n = nstore;
@@ -326,6 +322,84 @@ int Solver::create(const fy_case_desc* c, const fy_transport* tr, int dev, Comm*
     if (c->average.n_items) FY_TRY(set_field_average(&c->average));           // controlDict functions: fieldAverage
     if (c->monitors.n_objects) FY_TRY(set_monitors(&c->monitors));            // volFieldValue / surfaceFieldValue
     if (!WallLoads::empty(&c->wall_loads)) FY_TRY(set_wall_loads(&c->wall_loads));      // forces / wallShearStress / yPlus
+    if (c->inlets.n) FY_TRY(set_inlets(&c->inlets, "fy_solver_create"));                 // inlets on fixed-value sides
+    return FY_OK;
+}
+
+// adjustPhi (icoFoamYade.C:108, pEqn.H:13-16) acts when no patch fixes the pressure.  It is the identity when every patch fixes U and the prescribed normal
+// velocities balance (closed boxes, cavities): nothing is launched then.  With fixed-value patches that do NOT balance and no patch to adjust, OpenFOAM stops at the
+// first corrector; say so at once.  inlet_sides: the sides that carry an inlet (their u_value is not read); inlet_flux: an inlet's shape carries a net normal flux,
+// which changes in time -- only an adjustable patch can take it up
+int Solver::balance_check(int inlet_sides, bool inlet_flux, bool* adjust) const {
+    double net = 0.0, mag = 0.0;
+    bool adjustable = false;
+    const double area[3] = {(double)cs.ny * cs.nz, (double)cs.nx * cs.nz, (double)cs.nx * cs.ny};
+    for (int q = 0; q < 6; ++q) {
+        if (cs.u_bc[q] == FY_BC_U_SLIP) continue;                       // (carries no flux, and none to adjust)
+        if (cs.u_bc[q] != FY_BC_U_FIXED_VALUE) { adjustable = true; continue; }
+        if ((inlet_sides >> q) & 1) continue;
+        const double un = cs.u_value[q][q / 2] * ((q & 1) ? 1.0 : -1.0) * area[q / 2];
+        net += un; mag += std::fabs(un);
+    }
+    if (!adjustable && (inlet_flux || std::fabs(net) > 1e-8 * (mag + 1e-300)))
+        return fail(FY_ERR_UNSUPPORTED, "no patch fixes the pressure and the fixed-value velocity patches do not balance (net flux %g of %g%s): OpenFOAM's adjustPhi "
+                                        "ends such a run with 'Continuity error cannot be removed by adjusting the outflow'", net, mag,
+                    inlet_flux ? "; an inlet's shape carries a net normal flux and no velocity patch is adjustable" : "");
+    *adjust = adjustable || mag > 0.0 || inlet_flux;
+    return FY_OK;
+}
+
+int Solver::set_inlets(const fy_inlets_desc* d, const char* who) {
+    FY_HIP(hipSetDevice(device));
+    const bool any = d && d->n != 0;
+    if (any && comm->size > 1)
+        return fail(FY_ERR_UNSUPPORTED, "%s: inlets are not available on z-slabs (fy_solver_create_slab over %d ranks, foamYadeHip_mpi -parallel): run the case on one domain", who, comm->size);
+    if (stepped) return fail(FY_ERR_INVALID, "%s: the solver has stepped already; inlets are set at create or before the first step", who);
+    if (!any && !inl.on()) return FY_OK;                              // nothing to set and nothing was set (a slab solver comes no further)
+    FY_HIP(hipStreamSynchronize(stream));
+    const int nside[3] = {g.ny * g.nz, g.nx * g.nz, g.nx * g.ny};
+    int base[6];
+    for (int q = 0, b = 0; q < 6; ++q) { base[q] = b; b += nside[q / 2]; }
+    Inlets fresh;
+    FY_TRY(fresh.configure(d, stream, who, [&](int q, InletPatch* out) {
+        if (q < 0 || q > 5) return fail(FY_ERR_INVALID, "%s: side %d does not exist (0 .. 5: x- x+ y- y+ z- z+)", who, q);
+        if (cs.u_bc[q] != FY_BC_U_FIXED_VALUE) return fail(FY_ERR_INVALID, "%s: side %d is not a fixedValue velocity side (FY_BC_U_FIXED_VALUE): no inlet there", who, q);
+        const int D = q / 2, n = nside[D];
+        out->n_faces = n; out->base = base[q];
+        out->Sf.assign(3 * (size_t)n, 0.0);
+        for (int r = 0; r < n; ++r) {                                  // the faces in "U_boundary"'s order: the lower remaining axis fastest; A as geo_Af forms it
+            const int a = D == 0 ? r % g.ny : r % g.nx, b = D == 0 ? r / g.ny : r / g.nx;
+            double A = g.Af;
+            if (g.graded) A = D == 0 ? h_host[1][(size_t)a] * h_host[2][(size_t)b] : D == 1 ? h_host[0][(size_t)a] * h_host[2][(size_t)b] : h_host[0][(size_t)a] * h_host[1][(size_t)b];
+            out->Sf[3 * (size_t)r + D] = (q & 1) ? A : -A;
+        }
+        return (int)FY_OK;
+    }));
+    bool adj = false;
+    if (g.need_ref) {
+        int sides = 0;
+        for (const Inlets::One& o : fresh.in) sides |= 1 << o.patch;
+        FY_TRY(balance_check(sides, fresh.on() && !fresh.flux_free(), &adj));
+    }
+    inl.take(fresh);
+    g.inl = nullptr;
+    if (!inl.on()) { uFace.release(); dInletView.release(); }
+    else {
+        if (!uFace.p) { FY_TRY(uFace.alloc_exact(3 * (size_t)(base[5] + nside[2]))); FY_TRY(zero(uFace)); FY_TRY(dInletView.alloc_exact(1)); }
+        InletView v{uFace.p, 0};
+        for (const Inlets::One& o : inl.in) v.sides |= 1 << o.patch;
+        FY_HIP(hipMemcpy(dInletView.p, &v, sizeof(v), hipMemcpyHostToDevice));
+        g.inl = dInletView.p;
+        FY_TRY(inl.update(stream, inl.start_time, uFace.p));          // the start time's value, as the 0/U file would hold it
+    }
+    if (g.need_ref) {
+        adjust_phi = adj;
+        if (adjust_phi && !adj_sums.p) { FY_TRY(adj_sums.alloc_exact(4)); FY_TRY(adj_err.alloc_exact(1)); FY_HIP(hipMemsetAsync(adj_err.p, 0, sizeof(int), stream)); }
+        face_arrays = face_arrays || adjust_phi;
+    }
+    carry_valid = false;                                              // (the carried Courant sums may no longer describe phi)
+    FY_TRY(flux_of_U());
+    FY_HIP(hipStreamSynchronize(stream));
     return FY_OK;
 }
 
@@ -702,6 +776,8 @@ int Solver::step() {
         else { FY_TRY(reduce_read(2, true, h)); note_courant(h); }
     }
     st.delta_t = cs.dt;
+    if (inl.on()) FY_TRY(inl.update(stream, (inl.start_time + mon.elapsed) + cs.dt, uFace.p));      // the inlets' value at the time this step advances to, before any kernel reads it
+    stepped = true;                    // (from here on the fields move: set_inlets refuses)
     // runTime++ : store old-time fields.  phi.oldTime(): the flux arrays trade places instead of being copied -- what was phi is phiOld now, and until
     // the first flux correction of this step rewrites phi (every face of it) the current flux is read from phiOld (phi_now())
     if (cs.n_correctors > 0) {
@@ -893,7 +969,7 @@ int Solver::step() {
         st.ms_total = tim[3].ms();
         st.ms_other = st.ms_total - st.ms_particle - st.ms_momentum - st.ms_pressure;
         for (auto& k : kc) k.collect();
-        avg.clock.collect(); mon.clock.collect(); wl.m.clock.collect();
+        avg.clock.collect(); mon.clock.collect(); wl.m.clock.collect(); inl.clock.collect();
         if (th.on) { th.clk_coeff.collect(); th.clk_flux.collect(); th.clk_asm.collect(); th.clk_buoy.collect(); }
         if (ss.on) ss.clock.collect();
     }

@@ -15,6 +15,7 @@
 #include "field_average.hpp"
 #include "fv_kernels.hpp"
 #include "heat_exchange.hpp"
+#include "inlets.hpp"
 #include "solid_stats.hpp"
 
 // geometry-dependent launchers exist per geometry model (fv_kernels.hpp): the uniform block's in fy, the graded block's in fy::gr
@@ -145,7 +146,7 @@ struct Solver {
         for (auto& t : tim) t.destroy();
         for (auto& k : kc) k.destroy();
         for (auto& k : clk_xwait) k.destroy();
-        clk_mom.destroy(); clk_pres.destroy();
+        clk_mom.destroy(); clk_pres.destroy(); inl.clock.destroy();
         if (ev_ready) (void)hipEventDestroy(ev_ready);
         if (ev_halo) (void)hipEventDestroy(ev_halo);
         if (ev_fields) (void)hipEventDestroy(ev_fields);
@@ -313,6 +314,15 @@ struct Solver {
     DevBuf<double> d_xn[3], bndNut, bndY;
     WlBlockGeo wl_geo() const { return WlBlockGeo{{cs.origin[0], cs.origin[1], cs.origin[2]}, {d_xn[0].p, d_xn[1].p, d_xn[2].p}}; }
     int set_wall_loads(const fy_wall_loads_desc* d);
+    // inlets (inlets.hpp; DESIGN.md section 3 "Inlets"): uFace [all boundary faces][3] in "U_boundary"'s order holds the value of every face of an inlet side (FvGeo::inl
+    // points at the record that names it and the sides; the other sides' entries are never read).  Set at create or before the first step; off: nothing allocated, nothing launched
+    Inlets inl;
+    DevBuf<double> uFace;
+    DevBuf<InletView> dInletView;
+    bool stepped = false;
+    int balance_check(int inlet_sides, bool inlet_flux, bool* adjust) const;
+    int set_inlets(const fy_inlets_desc* d, const char* who);
+    int flux_of_U() { return FVK(launch_flux_of, stream, g, U.p, F3(phi)); }      // createPhi with the boundary values as they are now
     Thermal th;
     int thermal_create(const fy_case_desc* c);          // validation + allocation, from create()
     int heat_coefficients();

@@ -159,7 +159,7 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
         s->s.U_ghosts_fresh = false;
         FY_TRY(s->s.halo_U());
         // (per geometry model, like Solver::create's: on a graded block the uniform launcher would take every face for a dx x dx square midway between its cells)
-        FY_TRY(s->s.g.graded ? fy::gr::launch_flux_of(s->s.stream, s->s.g, s->s.U.p, s->s.F3(s->s.phi)) : fy::launch_flux_of(s->s.stream, s->s.g, s->s.U.p, s->s.F3(s->s.phi)));
+        FY_TRY(s->s.flux_of_U());
     }
     if (std::string(name) == "nut") FY_TRY(s->s.halo_cells(s->s.nut, 1, 1));
     if (std::string(name) == "k") FY_TRY(s->s.halo_cells(s->s.kturb, 1, 1));
@@ -185,6 +185,7 @@ int fy_solver_get_monitor_rows(fy_solver* s, int object, int64_t first_row, int6
 }
 
 int fy_solver_set_wall_loads(fy_solver* s, const fy_wall_loads_desc* d) { FY_S(s); return s->s.set_wall_loads(d); }
+int fy_solver_set_inlets(fy_solver* s, const fy_inlets_desc* d) { FY_S(s); return s->s.set_inlets(d, "fy_solver_set_inlets"); }
 int fy_solver_wall_loads_layout(fy_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_S(s); return s->s.wl.m.layout(object, n_values, labels, cap); }
 int fy_solver_get_wall_load_rows(fy_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
     FY_S(s);
@@ -271,6 +272,7 @@ int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
     s->s.mon.clock.reset(); s->s.mon.clock.on = on != 0;
     s->s.wl.m.clock.reset(); s->s.wl.m.clock.on = on != 0;
+    s->s.inl.clock.reset(); s->s.inl.clock.on = on != 0;
     for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm, &s->s.th.clk_buoy}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
     s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0;
     return FY_OK;
@@ -294,6 +296,7 @@ int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_
     FY_S(s);
     const std::string k = kernel ? kernel : "";
     if (k == "monitors" && total_ms && launches) { *total_ms = s->s.mon.clock.total_ms; *launches = s->s.mon.clock.launches; return FY_OK; }
+    if (k == "inlets" && total_ms && launches && s->s.inl.on()) { *total_ms = s->s.inl.clock.total_ms; *launches = s->s.inl.clock.launches; return FY_OK; }
     if (k == "wall_loads" && total_ms && launches && s->s.wl.on()) { *total_ms = s->s.wl.m.clock.total_ms; *launches = s->s.wl.m.clock.launches; return FY_OK; }
     if (k == "solid_stats" && total_ms && launches) { *total_ms = s->s.ss.clock.total_ms; *launches = s->s.ss.clock.launches; return FY_OK; }
     if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }

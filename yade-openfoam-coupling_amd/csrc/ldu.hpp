@@ -3,6 +3,7 @@
 //   ldu_mesh.cpp     host: OpenFOAM's geometry from points / faces / owner / neighbour [OF-6 primitiveMesh*, surfaceInterpolation], cell -> face lists
 //   ldu_kernels.hip  the operators as HIP kernels: one lane per cell GATHERING over the cell's faces, or one lane per face (no scatter, no atomics)
 //   ldu_flow_control.hip  flow-rate control (fy_flow_control_desc): the two sums, the correction, the assembly-time source
+//   inlets.hpp / .cpp / .hip  inlets (fy_inlets_desc), shared with the block solver: the time functions, the shapes, the step's update kernel
 //   ldu_solver.cpp   sequencing + the C entry points
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,6 +78,10 @@ struct LduGeo {
     const double *gB, *gG0, *rT;
     const double* sep;                                   // [3 nInt] or null: folded cyclic faces -- the neighbour cell's image is C_N + sep_f (zero on the mesh's own internal faces)
     int nIntReal;                                        // faces [nIntReal, nInt) are folded cyclic pairs
+    // inlets (inlets.hpp; null: none -- every fixed-value patch carries its u_val): u_face [nF - nInt][3] the value per boundary face, read on the patches with
+    // u_inlet[patch] != 0 in u_val's place (ldu_u_fixed in ldu_kernels.hip)
+    const double* u_face;
+    const int32_t* u_inlet;
 };
 
 // what mesh.findCell's stand-in reads beside LduGeo (device pointers): the points, the faces' point lists, the cells' balls, the mesh's bounding box

@@ -23,9 +23,15 @@ __device__ __forceinline__ D3 lerp3(double w, D3 a, D3 b) { return D3{w * a.x + 
 
 // boundary value of a velocity-like field on boundary face f: the patch's value (fixedValue), the cell's (zeroGradient), or the cell's without its component along the
 // face's normal (symmetry / symmetryPlane / slip [OF-6 basicSymmetryFvPatchField::evaluate]: (U_P + transform(I - 2 n n, U_P)) / 2)
+// the value of a fixedValue patch at its boundary face f: the patch's one vector, or the face's own where the patch is an inlet (LduGeo::u_face; null: no inlets, the
+// uniform load as it always was)
+__device__ __forceinline__ D3 ldu_u_fixed(const LduGeo& g, int pa, int f) {
+    if (g.u_face && g.u_inlet[pa]) return ld3(g.u_face, f - g.nInt);
+    return ld3(g.u_val, pa);
+}
 __device__ __forceinline__ D3 Ub(const LduGeo& g, const double* F, int f) {
     const int pa = g.patch_of[f - g.nInt];
-    if (g.u_bc[pa] == FY_BC_U_FIXED_VALUE) return ld3(g.u_val, pa);
+    if (g.u_bc[pa] == FY_BC_U_FIXED_VALUE) return ldu_u_fixed(g, pa, f);
     const D3 uc = ld3(F, g.own[f]);
     if (g.u_bc[pa] == FY_BC_U_SLIP) {
         const double rm = 1.0 / g.magSf[f];
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(256) void k_ldu_mom_cells(LduGeo g, const double* _
             const int pa = g.patch_of[f - g.nInt];
             if (g.u_bc[pa] == FY_BC_U_FIXED_VALUE) {
                 const double gm = g.nu * g.magSf[f] * g.dcNO[f];
-                const D3 ub = ld3(g.u_val, pa);
+                const D3 ub = ldu_u_fixed(g, pa, f);
                 dg += gm;
                 b[0] += (-phi[f] + gm) * ub.x; b[1] += (-phi[f] + gm) * ub.y; b[2] += (-phi[f] + gm) * ub.z;
             } else {
@@ -625,7 +631,7 @@ __global__ __launch_bounds__(256) void k_ldu_pmom_cells(LduGeo g, LduPim P, cons
             b[0] += st.x; b[1] += st.y; b[2] += st.z;
             if (g.u_bc[pa] == FY_BC_U_FIXED_VALUE) {
                 const double gm = (g.nu + ldu_nut_b(g, P, f)) * g.magSf[f] * g.dcNO[f];
-                const D3 ub = ld3(g.u_val, pa);
+                const D3 ub = ldu_u_fixed(g, pa, f);
                 dg += gm;
                 b[0] += (-fl + gm) * ub.x; b[1] += (-fl + gm) * ub.y; b[2] += (-fl + gm) * ub.z;
             } else {

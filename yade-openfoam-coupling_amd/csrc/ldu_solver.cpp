@@ -14,6 +14,7 @@
 #include "fv_kernels.hpp"
 #include "fv_linalg_kernels.hpp"
 #include "heat_exchange.hpp"
+#include "inlets.hpp"
 #include "solid_stats.hpp"
 #include "ldu.hpp"
 #include "ldu_amg.hpp"
@@ -245,8 +246,54 @@ struct LduSolver {
         return FY_OK;
     }
 
+    // inlets (inlets.hpp; DESIGN.md section 3 "Inlets").  Off: nothing allocated, nothing launched, g.u_face null.  uFace [nb][3] holds the value of every face of an
+    // inlet patch (the other faces' entries are never read); dInlet flags the inlet patches
+    Inlets inl;
+    DevBuf<double> uFace;
+    DevBuf<int32_t> dInlet;
+    bool stepped = false;
+    std::vector<int32_t> h_ubc;               // the patches' velocity conditions as the solver was created with them
+    int set_inlets(const fy_inlets_desc* d, const char* who) {
+        if (stepped) return fail(FY_ERR_INVALID, "%s: the solver has stepped already; inlets are set at create or before the first step", who);
+        FY_HIP(hipSetDevice(device));
+        if ((!d || d->n == 0) && !inl.on()) return FY_OK;                   // nothing to set and nothing was set
+        FY_HIP(hipStreamSynchronize(stream));
+        Inlets fresh;
+        FY_TRY(fresh.configure(d, stream, who, [this, who](int pa, InletPatch* out) {
+            if (pa < 0 || pa >= hm.nPatches) return fail(FY_ERR_INVALID, "%s: patch %d does not exist (the mesh has %d)", who, pa, hm.nPatches);
+            if (hm.psize[(size_t)pa] == 0) return fail(FY_ERR_INVALID, "%s: patch %d is a cyclic patch or has no faces (a cyclic patch is folded into internal faces): no inlet there", who, pa);
+            if (h_ubc[(size_t)pa] != FY_BC_U_FIXED_VALUE) return fail(FY_ERR_INVALID, "%s: patch %d is not a fixedValue velocity patch (FY_BC_U_FIXED_VALUE): no inlet there", who, pa);
+            out->n_faces = hm.psize[(size_t)pa]; out->base = hm.pstart[(size_t)pa] - ni;
+            out->Sf.assign(hm.Sf.begin() + 3 * (size_t)hm.pstart[(size_t)pa], hm.Sf.begin() + 3 * ((size_t)hm.pstart[(size_t)pa] + (size_t)hm.psize[(size_t)pa]));
+            return (int)FY_OK;
+        }));
+        if (fresh.on() && need_ref && !fresh.flux_free()) {               // adjustPhi's precondition, as fy_solver_create states it for the block
+            bool adjustable = false;
+            for (int pa = 0; pa < hm.nPatches; ++pa) adjustable = adjustable || (hm.psize[(size_t)pa] > 0 && h_ubc[(size_t)pa] == FY_BC_U_ZERO_GRADIENT);
+            if (!adjustable)
+                return fail(FY_ERR_UNSUPPORTED, "%s: no patch fixes the pressure and the fixed-value velocity patches do not balance (an inlet's shape carries a net normal flux and no "
+                                                "velocity patch is adjustable): OpenFOAM's adjustPhi ends such a run with 'Continuity error cannot be removed by adjusting the outflow'", who);
+        }
+        inl.take(fresh);
+        if (!inl.on()) {
+            uFace.release(); dInlet.release();
+            g.u_face = nullptr; g.u_inlet = nullptr;
+        } else {
+            std::vector<int32_t> flag((size_t)hm.nPatches, 0);
+            for (const Inlets::One& o : inl.in) flag[(size_t)o.patch] = 1;
+            FY_TRY(up(dInlet, flag));
+            if (!uFace.p) { FY_TRY(uFace.alloc_exact(3 * std::max<size_t>((size_t)(nf - ni), 1))); FY_TRY(zero(uFace)); }
+            g.u_face = uFace.p; g.u_inlet = dInlet.p;
+            FY_TRY(inl.update(stream, inl.start_time, uFace.p));           // the start time's value, as the 0/U file would hold it
+        }
+        FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                 // createPhi with the boundary values as they are now
+        FY_HIP(hipStreamSynchronize(stream));
+        return FY_OK;
+    }
+
     ~LduSolver() {
         fc.clock.destroy();
+        inl.clock.destroy();
         if (cpl) fy_destroy(cpl);
         for (auto& t : tim) t.destroy();
         if (side) (void)hipStreamDestroy(side);
@@ -295,6 +342,7 @@ struct LduSolver {
         std::vector<int32_t> ubc(c->u_bc, c->u_bc + hm.nPatches), pbc(c->p_bc, c->p_bc + hm.nPatches);
         std::vector<double> uval(c->u_value, c->u_value + 3 * (size_t)hm.nPatches), pval(c->p_value, c->p_value + hm.nPatches);
         need_ref = true;
+        h_ubc = ubc;
         for (int pa = 0; pa < hm.nPatches; ++pa) {
             if (ubc[(size_t)pa] != FY_BC_U_FIXED_VALUE && ubc[(size_t)pa] != FY_BC_U_ZERO_GRADIENT && ubc[(size_t)pa] != FY_BC_U_SLIP)
                 return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: velocity patch type %d (fixedValue, zeroGradient, symmetry / slip)", ubc[(size_t)pa]);
@@ -445,6 +493,8 @@ struct LduSolver {
         cs.flow_control = fy_flow_control_desc{};
         if (c->flow_control.on) FY_TRY(set_flow_control(&c->flow_control, "fy_ldu_solver_create"));      // couplingProperties meanVelocityForce
         if (!WallLoads::empty(&c->wall_loads)) FY_TRY(set_wall_loads(&c->wall_loads));                   // forces / wallShearStress / yPlus
+        cs.inlets = fy_inlets_desc{};
+        if (c->inlets.n) FY_TRY(set_inlets(&c->inlets, "fy_ldu_solver_create"));                          // (the caller's arrays are copied, not kept)
         return FY_OK;
     }
 
@@ -734,6 +784,8 @@ struct LduSolver {
             g.dt = cs.dt;
         }
         st.delta_t = cs.dt;
+        if (inl.on()) FY_TRY(inl.update(stream, (inl.start_time + mon.elapsed) + cs.dt, uFace.p));                  // the inlets' value at the time this step advances to, before any kernel reads it
+        stepped = true;                    // (from here on the fields move: set_inlets refuses)
         FY_HIP(hipMemcpyAsync(Uold.p, U.p, 3 * (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, stream));    // runTime++: old-time fields
         FY_HIP(hipMemcpyAsync(phiOld.p, phi.p, (size_t)nf * sizeof(double), hipMemcpyDeviceToDevice, stream));
         FY_TRY(launch_ldu_grad_vec(stream, g, U.p, vGrad.p));                                                      // :71
@@ -780,6 +832,7 @@ struct LduSolver {
         if (ss.on) ss.clock.collect();
         if (fc.on) fc.clock.collect();
         if (wl.on()) wl.m.clock.collect();
+        if (inl.on()) inl.clock.collect();
         return FY_OK;
     }
 
@@ -949,14 +1002,16 @@ int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver* s, int on) {
     s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0;
     s->s.fc.clock.reset(); s->s.fc.clock.on = on != 0;
     s->s.wl.m.clock.reset(); s->s.wl.m.clock.on = on != 0;
+    s->s.inl.clock.reset(); s->s.inl.clock.on = on != 0;
     return FY_OK;
 }
 int fy_ldu_solver_get_kernel_timing(fy_ldu_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
     FY_LS(s);
     const std::string k = kernel ? kernel : "";
     if (k == "wall_loads" && s->s.wl.on() && total_ms && launches) { *total_ms = s->s.wl.m.clock.total_ms; *launches = s->s.wl.m.clock.launches; return FY_OK; }
+    if (k == "inlets" && s->s.inl.on() && total_ms && launches) { *total_ms = s->s.inl.clock.total_ms; *launches = s->s.inl.clock.launches; return FY_OK; }
     const bool flow = k == "flow_control" && s->s.fc.on;
-    if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats%s%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "", s->s.wl.on() ? ", wall_loads" : "");
+    if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats%s%s%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "", s->s.wl.on() ? ", wall_loads" : "", s->s.inl.on() ? ", inlets" : "");
     const fy::KernelClock& c = flow ? s->s.fc.clock : s->s.ss.clock;
     *total_ms = c.total_ms; *launches = c.launches;
     return FY_OK;
@@ -974,6 +1029,7 @@ int fy_ldu_solver_get_monitor_rows(fy_ldu_solver* s, int object, int64_t first_r
     return s->s.mon.get_rows(s->s.stream, object, first_row, max_rows, times, values, n_rows);
 }
 int fy_ldu_solver_set_wall_loads(fy_ldu_solver* s, const fy_wall_loads_desc* d) { FY_LS(s); return s->s.set_wall_loads(d); }
+int fy_ldu_solver_set_inlets(fy_ldu_solver* s, const fy_inlets_desc* d) { FY_LS(s); return s->s.set_inlets(d, "fy_ldu_solver_set_inlets"); }
 int fy_ldu_solver_wall_loads_layout(fy_ldu_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_LS(s); return s->s.wl.m.layout(object, n_values, labels, cap); }
 int fy_ldu_solver_get_wall_load_rows(fy_ldu_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
     FY_LS(s);
