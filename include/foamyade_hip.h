@@ -241,7 +241,10 @@ enum { FY_SOLVER_ICO = 0, FY_SOLVER_PIMPLE = 1 };
 /* boundary patches of the block, in this order */
 enum { FY_XMIN = 0, FY_XMAX = 1, FY_YMIN = 2, FY_YMAX = 3, FY_ZMIN = 4, FY_ZMAX = 5 };
 enum { FY_BC_U_FIXED_VALUE = 0, FY_BC_U_ZERO_GRADIENT = 1,
-       FY_BC_U_SLIP = 2 /* symmetryPlane / symmetry / slip on the block's (planar) side: normal component 0, tangential components zeroGradient */ };
+       FY_BC_U_SLIP = 2 /* symmetryPlane / symmetry / slip on the block's (planar) side: normal component 0, tangential components zeroGradient */,
+       /* open boundaries, fy_ldu_solver only (fy_solver_create refuses them as unknown); see "Open boundaries" at fy_ldu_solver_get_open_boundary_stats */
+       FY_BC_U_INLET_OUTLET = 3 /* inletOutlet: u_value where the flux enters (phi < 0), zeroGradient where it leaves */,
+       FY_BC_U_PRESSURE_INLET_OUTLET = 4 /* pressureInletOutletVelocity: n (n . U_P) where the flux enters, zeroGradient where it leaves; takes no value */ };
 enum { FY_BC_P_ZERO_GRADIENT = 0, FY_BC_P_FIXED_VALUE = 1, FY_BC_P_FIXED_FLUX = 2 };
 enum { FY_PSOLVER_PCG_JACOBI = 0, FY_PSOLVER_PCG_MG = 1 };
 
@@ -264,6 +267,7 @@ enum { FY_PSOLVER_PCG_JACOBI = 0, FY_PSOLVER_PCG_MG = 1 };
 #define FY_BC_NUT_ZERO_GRADIENT 0
 #define FY_BC_NUT_FIXED_VALUE 1
 #define FY_BC_NUT_CALCULATED 3          /* nut_bc: `calculated` patch = the model's expression on the boundary values of k (and epsilon); kEqn / kEpsilon */
+#define FY_BC_NUT_INLET_OUTLET 4        /* k_bc, eps_bc of fy_ldu_case only (nut_bc refuses it): inletOutlet -- the patch's value where the flux enters, zeroGradient where it leaves */
 #define FY_BC_WALL_FUNCTION 2           /* nut_bc: nutkWallFunction (needs a model with k); eps_bc: epsilonWallFunction; k takes zeroGradient (kqRWallFunction) */
 /* fieldAverage: running means and second central moments of cell fields, updated on the device once per step (OpenFOAM's fieldAverage function object
    [OF-6 fieldAverage, fieldAverageTemplates.C, as recalled: OpenFOAM is not at hand to pin it]).  An item is one field with its mean m and, with
@@ -425,6 +429,7 @@ double fy_time_function_eval(const fy_time_function* f, double t);
 #define FY_NUSSELT_GUNN 1
 #define FY_BC_T_ZERO_GRADIENT 0
 #define FY_BC_T_FIXED_VALUE 1
+#define FY_BC_T_INLET_OUTLET 2          /* fy_ldu_case.T_bc only: inletOutlet -- T_value where the flux enters, zeroGradient where it leaves */
 typedef struct fy_thermal_desc {
     int32_t on;
     double cp, kappa;               /* > 0 */
@@ -864,8 +869,9 @@ typedef struct fy_ldu_case {
     double u_tol, u_rel_tol; int32_t u_max_iter;
     int32_t p_solver;                /* FY_PSOLVER_PCG_JACOBI: PCG.C with the diagonal preconditioner | FY_PSOLVER_PCG_MG: preconditioned by an agglomeration
                                         multigrid V-cycle (fvSolution: solver / preconditioner GAMG) built from the face areas like faceAreaPair */
-    const int32_t* u_bc;             /* per patch: FY_BC_U_FIXED_VALUE | FY_BC_U_ZERO_GRADIENT | FY_BC_U_SLIP (symmetryPlane / symmetry / slip: each face with its own normal) */
-    const double* u_value;           /* [n_patches][3] */
+    const int32_t* u_bc;             /* per patch: FY_BC_U_FIXED_VALUE | FY_BC_U_ZERO_GRADIENT | FY_BC_U_SLIP (symmetryPlane / symmetry / slip: each face with its own normal) |
+                                        FY_BC_U_INLET_OUTLET | FY_BC_U_PRESSURE_INLET_OUTLET (open boundaries, below) */
+    const double* u_value;           /* [n_patches][3]; the inlet value of an FY_BC_U_INLET_OUTLET patch */
     const int32_t* p_bc;             /* per patch: FY_BC_P_ZERO_GRADIENT | FY_BC_P_FIXED_VALUE */
     const double* p_value;           /* [n_patches] */
     /* pimpleFoamYade on the general mesh (solver = FY_SOLVER_PIMPLE; pimpleFoamYade.C:60-114, UcEqn.H, pEqn.H): Gaussian 4-way coupling, the void-fraction-
@@ -889,7 +895,7 @@ typedef struct fy_ldu_case {
      * div(alphaPhic,k) (FY_CONVECTION_LINEAR | _UPWIND), solvers.k, relaxationFactors equations k (<= 0: none); nut patches may then be FY_BC_NUT_CALCULATED
      * (the file's value until the first correctNut(), Ck sqrt(k_b) delta afterwards) */
     double k_initial;
-    const int32_t* k_bc;             /* NULL: zeroGradient everywhere */
+    const int32_t* k_bc;             /* NULL: zeroGradient everywhere; FY_BC_NUT_INLET_OUTLET: k_value where the flux enters */
     const double* k_value;
     int32_t k_convection_scheme;
     double k_tol, k_rel_tol; int32_t k_max_iter;
@@ -900,7 +906,7 @@ typedef struct fy_ldu_case {
      * production replaced by (1/W) sum (nut_w + nu) |snGrad U| Cmu^1/4 sqrt(k) / (kappa y) over its W faces on those patches, y the faces' nearWallDist */
     double ras_cmu, ras_c1, ras_c2, ras_c3, ras_sigmak, ras_sigmaeps;      /* fy_ldu_case_defaults: 0.09, 1.44, 1.92, 0, 1, 1.3 */
     double eps_initial;
-    const int32_t* eps_bc;           /* NULL: zeroGradient everywhere */
+    const int32_t* eps_bc;           /* NULL: zeroGradient everywhere; FY_BC_NUT_INLET_OUTLET: eps_value where the flux enters */
     const double* eps_value;
     int32_t eps_convection_scheme;
     double eps_tol, eps_rel_tol; int32_t eps_max_iter;
@@ -914,7 +920,7 @@ typedef struct fy_ldu_case {
      * diffusion term is Gauss linear corrected like every laplacian here: gam_f = alphaf_f (D + nut / prt)_f |Sf|, implicit part gam_f dcNO_f, explicit part
      * gam_f (kvec_f . (grad T_old)_f) added to the owner and taken from the neighbour; the Gaussian scatter of Sp / Su goes out as FP64 global atomics (no tiles) */
     fy_thermal_desc thermal;
-    const int32_t* T_bc;             /* per patch: FY_BC_T_ZERO_GRADIENT | FY_BC_T_FIXED_VALUE (NULL: zeroGradient everywhere); a symmetry / slip patch takes
+    const int32_t* T_bc;             /* per patch: FY_BC_T_ZERO_GRADIENT | FY_BC_T_FIXED_VALUE | FY_BC_T_INLET_OUTLET (NULL: zeroGradient everywhere); a symmetry / slip patch takes
                                         FY_BC_T_ZERO_GRADIENT, folded cyclic pairs are internal faces and need nothing */
     const double* T_value;           /* [n_patches] */
     fy_monitor_desc monitors;        /* controlDict functions: the volFieldValue / surfaceFieldValue objects as in fy_case_desc (all zero: none); `patch` is a patch index */
@@ -961,6 +967,17 @@ int fy_ldu_solver_get_kernel_timing(fy_ldu_solver*, const char* kernel, double* 
  * the option is off.  Only this call waits for the device.  While the option is on, "flow_control" is a second clock of fy_ldu_solver_get_kernel_timing. */
 int fy_ldu_solver_set_flow_control(fy_ldu_solver*, const fy_flow_control_desc*);
 int fy_ldu_solver_get_flow_control(fy_ldu_solver*, double* gradient, double* ubar_uncorrected, double* rAU_ave, double* dGradP, int64_t* corrections);
+/* Open boundaries (a side where fluid may leave or come back in, face by face): u_bc FY_BC_U_INLET_OUTLET | FY_BC_U_PRESSURE_INLET_OUTLET, k_bc / eps_bc
+ * FY_BC_NUT_INLET_OUTLET, T_bc FY_BC_T_INLET_OUTLET; from a case directory the words inletOutlet (inletValue uniform ...) and pressureInletOutletVelocity.  The inlet
+ * value travels in u_value / k_value / eps_value / T_value.  One byte per boundary face, the inflow mask (phi < 0), selects -- never blends -- per face: an inflow face
+ * is the patch's fixedValue face (pressureInletOutletVelocity: U_b = n (n . U_P), the directionMixed form with value fraction I - n n in the matrix), an outflow face a
+ * zeroGradient face.  An open velocity patch never fixes the flux: phiHbyA takes HbyA's cell value there and adjustPhi may scale it.  The mask is renewed on the device
+ * (a) at the start of a step, (b) after each corrector's flux update, before the velocity is corrected or reconstructed, (c) after createPhi at create, at
+ * fy_ldu_solver_set_inlets and at fy_ldu_solver_write_field_host("U"), which form phi with every open face evaluated as zeroGradient first.  "U_open_inflow" [nb] is
+ * the mask as doubles (0 | 1), read-only.  get_open_boundary_stats: of the last renewal, over the faces of the open patches, the number of inflow faces, the sum of phi
+ * over them (< 0) and over the outflow faces; any pointer may be NULL; FY_ERR_INVALID when no patch carries an open code.  Only this call waits for the device.  The
+ * clock is "open_boundary" of fy_ldu_solver_get_kernel_timing (no launch without an open patch: nothing is allocated, every kernel takes the path it always took). */
+int fy_ldu_solver_get_open_boundary_stats(fy_ldu_solver*, int64_t* inflow_faces, double* inflow_flux, double* outflow_flux);
 /* Heat exchange (fy_ldu_case.thermal.on; FY_ERR_INVALID on a solver without it): the entry points of fy_solver one for one, with the same semantics.  While thermal is
  * on, "T" [nc] (also writable: a non-uniform start), "heatSp" [nc] (W/K), "heatSu" [nc] (W) and, with thermal.beta != 0 and g != 0, "buoyancy" [nc][3] are field names
  * of fy_ldu_solver_read_field_host, and "T" one that fieldAverage accepts. */

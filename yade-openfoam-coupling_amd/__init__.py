@@ -34,6 +34,10 @@ FY_T_INT, FY_T_DOUBLE = 0, 1
 FY_OP_MAX, FY_OP_SUM = 0, 1
 FY_SOLVER_ICO, FY_SOLVER_PIMPLE = 0, 1
 FY_BC_U_FIXED_VALUE, FY_BC_U_ZERO_GRADIENT, FY_BC_U_SLIP = 0, 1, 2
+# open boundaries (fy_ldu_solver only): U inletOutlet / pressureInletOutletVelocity; k, epsilon and T inletOutlet (FY_BC_NUT_* / FY_BC_T_* families)
+FY_BC_U_INLET_OUTLET, FY_BC_U_PRESSURE_INLET_OUTLET = 3, 4
+FY_BC_NUT_INLET_OUTLET = 4
+FY_BC_T_INLET_OUTLET = 2
 FY_BC_P_ZERO_GRADIENT, FY_BC_P_FIXED_VALUE, FY_BC_P_FIXED_FLUX = 0, 1, 2
 FY_PSOLVER_PCG_JACOBI, FY_PSOLVER_PCG_MG = 0, 1
 FY_CONVECTION_LINEAR, FY_CONVECTION_UPWIND, FY_CONVECTION_LINEAR_UPWIND = 0, 1, 2
@@ -1763,7 +1767,8 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
 
     def kernel_timing(self, name):
         """(total_ms, launches) of one instrumented kernel since enable_kernel_timing(True); the clocks here are "solid_stats" and, with flow control on,
-        "flow_control" (every one of its launches is timed and counted), with wall loads "wall_loads", with inlets "inlets" """
+        "flow_control" (every one of its launches is timed and counted), with wall loads "wall_loads", with inlets "inlets", and "open_boundary" (the renewals of the
+        inflow mask: no launch without an open patch)"""
         L = lib()
         L.fy_ldu_solver_get_kernel_timing.argtypes = [C.c_void_p, C.c_char_p, _dp, C.POINTER(C.c_int64)]
         ms = C.c_double(0); n = C.c_int64(0)
@@ -1783,6 +1788,15 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
         g = C.c_double(0); u = C.c_double(0); r = C.c_double(0); d = C.c_double(0); n = C.c_int64(0)
         _check(L.fy_ldu_solver_get_flow_control(self._h, C.byref(g), C.byref(u), C.byref(r), C.byref(d), C.byref(n)))
         return dict(gradient=g.value, ubar=u.value, rAU_ave=r.value, dGradP=d.value, corrections=n.value)
+
+    def open_boundary_stats(self):
+        """the last renewal of the inflow mask over the open patches' faces (fy_ldu_solver_get_open_boundary_stats): inflow_faces, inflow_flux (the sum of phi over
+        them, < 0), outflow_flux; refused by name without an open patch.  The mask itself is get("U_open_inflow") [nb], 0 | 1"""
+        L = lib()
+        L.fy_ldu_solver_get_open_boundary_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), _dp, _dp]
+        n = C.c_int64(0); fi = C.c_double(0); fo = C.c_double(0)
+        _check(L.fy_ldu_solver_get_open_boundary_stats(self._h, C.byref(n), C.byref(fi), C.byref(fo)))
+        return dict(inflow_faces=n.value, inflow_flux=fi.value, outflow_flux=fo.value)
 
     def hold_sources(self, on=True):
         L = lib()

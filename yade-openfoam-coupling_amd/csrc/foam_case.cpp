@@ -786,6 +786,28 @@ int patch_condition(fy_foam_case* c, int F, const std::string& path, size_t pa, 
     const std::string cls = g ? c->g_patch_class[pa] : std::string();
     const bool k_model = has_field(c, F_K);
     const bool zero_grad = ty == "zeroGradient" || ty == "symmetryPlane" || ty == "symmetry" || (g && ty == "cyclic");      // (a scalar on a symmetry plane: the cell value)
+    // open boundaries, general meshes only (DESIGN.md section 3 "Open boundaries"): U inletOutlet | pressureInletOutletVelocity, k and
+    // epsilon inletOutlet [OF-6 inletOutletFvPatchField, pressureInletOutletVelocityFvPatchVectorField, as recalled].  `phi`, if given, must be the case's flux;
+    // `value` is optional and not used.  A block keeps refusing the words with its own lists (below)
+    if (g && ((ty == "inletOutlet" && (F == F_U || F == F_K || F == F_EPS)) || (ty == "pressureInletOutletVelocity" && F == F_U))) {
+        if (cls == "wall" || cls == "symmetryPlane" || cls == "symmetry" || cls == "cyclic")
+            return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s on a %s patch is not supported (an open boundary sits on a patch of type patch in constant/polyMesh/boundary)", path.c_str(), pn,
+                        ty.c_str(), cls.c_str());
+        std::string flux;
+        if (pd.word("phi", &flux) && flux != "phi" && !(c->solver == FY_SOLVER_PIMPLE && !c->phase.empty() && flux == "phi." + c->phase))
+            return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': %s with phi %s is not supported (the case's flux: phi%s)", path.c_str(), pn, ty.c_str(), flux.c_str(),
+                        c->solver == FY_SOLVER_PIMPLE && !c->phase.empty() ? (", phi." + c->phase).c_str() : "");
+        if (ty == "pressureInletOutletVelocity") {
+            if (pd.has("tangentialVelocity")) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': pressureInletOutletVelocity with tangentialVelocity is not supported", path.c_str(), pn);
+            *bc = FY_BC_U_PRESSURE_INLET_OUTLET;
+            return FY_OK;
+        }
+        const auto* iv = pd.tokens("inletValue");
+        const bool ok = iv && !iv->empty() && (*iv)[0] == "uniform" && (F == F_U ? tok_vec(*iv, 1, val) : tok_num(*iv, 1, val));
+        if (!ok) return fail(FY_ERR_UNSUPPORTED, "%s: patch '%s': inletOutlet needs 'inletValue uniform %s'", path.c_str(), pn, F == F_U ? "(x y z)" : F == F_K ? "<k>" : "<epsilon>");
+        *bc = F == F_U ? FY_BC_U_INLET_OUTLET : FY_BC_NUT_INLET_OUTLET;
+        return FY_OK;
+    }
     // [OF-6 fvPatchField::New]: a field's entry on a constraint patch must carry the patch's own type
     if (g && (F == F_U || F == F_P) && (cls == "symmetryPlane" || cls == "symmetry" || cls == "cyclic") && c->g_patch_size[pa] > 0 && ty != cls)
         return fail(FY_ERR_INVALID, "%s: patch '%s' is a %s patch (constant/polyMesh/boundary): its entry must be of that type, not '%s'", path.c_str(), pn, cls.c_str(), ty.c_str());
@@ -905,6 +927,11 @@ int read_field(fy_foam_case* c, int F, std::vector<double>* internal, double* in
         if (!pd || !pd->word("type", &ty)) return fail(FY_ERR_INVALID, "%s: boundaryField has no (typed) entry for patch '%s'", path.c_str(), names[pa].c_str());
         r.text[pa] = entry_text(*pd);
         FY_TRY(patch_condition(c, F, path, pa, names[pa], *pd, ty, &r.bc[pa], &r.val[(size_t)ncomp * pa]));
+        if ((F == F_K || F == F_EPS) && r.bc[pa] == FY_BC_NUT_INLET_OUTLET && !pd->has("value")) {      // a written time directory carries a value: the inlet value
+            char buf[96];
+            std::snprintf(buf, sizeof(buf), "        value uniform %.17g;\n", r.val[pa]);
+            r.text[pa] += buf;
+        }
     }
     return FY_OK;
 }
@@ -1799,9 +1826,12 @@ bool inlet_entry(const fy_foam_case* c, const std::string& pn, const std::string
     std::vector<double> v;
     bool inlet = false;
     if (c->general) {
-        for (const auto& in : c->inlets) if (c->g_patch_name[(size_t)in.patch] == pn) {
+        std::vector<int> with_value;                          // the inlet patches, and the open ones (inletOutlet, pressureInletOutletVelocity): the faces' values as they are now
+        for (const auto& in : c->inlets) with_value.push_back(in.patch);
+        for (size_t q = 0; q < c->bcs[F_U].bc.size(); ++q) if (c->bcs[F_U].bc[q] >= FY_BC_U_INLET_OUTLET) with_value.push_back((int)q);
+        for (int pa : with_value) if (c->g_patch_name[(size_t)pa] == pn) {
             inlet = true;
-            const size_t b0 = (size_t)(c->g_patch_start[(size_t)in.patch] - c->g_internal), n = (size_t)c->g_patch_size[(size_t)in.patch];
+            const size_t b0 = (size_t)(c->g_patch_start[(size_t)pa] - c->g_internal), n = (size_t)c->g_patch_size[(size_t)pa];
             if (3 * (b0 + n) > ub.size()) return false;
             v.assign(ub.begin() + 3 * b0, ub.begin() + 3 * (b0 + n));
         }
@@ -2450,7 +2480,9 @@ int fy_foam_case_write_time_ldu(const fy_foam_case* c, fy_ldu_solver* s, const c
     if ((size_t)cnt != c->fcells) return fail(FY_ERR_INVALID, "fy_foam_case_write_time_ldu: the solver holds %lld cells, the case %zu", (long long)cnt, c->fcells);
     // (alpha: with fy_ldu_solver_hold_sources, before setSourceZero)
     c->u_boundary_now.clear();
-    if (!c->inlets.empty()) {                             // the inlet patches' `value`: the faces' current values
+    bool open_u = false;
+    for (int32_t b : c->bcs[F_U].bc) open_u = open_u || b >= FY_BC_U_INLET_OUTLET;
+    if (!c->inlets.empty() || open_u) {                   // the inlet patches' and the open patches' `value`: the faces' current values
         int64_t nb = 0;
         FY_TRY(fy_ldu_solver_field_count(s, "U_boundary", &nb));
         c->u_boundary_now.resize((size_t)nb);

@@ -3,6 +3,7 @@
 //   ldu_mesh.cpp     host: OpenFOAM's geometry from points / faces / owner / neighbour [OF-6 primitiveMesh*, surfaceInterpolation], cell -> face lists
 //   ldu_kernels.hip  the operators as HIP kernels: one lane per cell GATHERING over the cell's faces, or one lane per face (no scatter, no atomics)
 //   ldu_flow_control.hip  flow-rate control (fy_flow_control_desc): the two sums, the correction, the assembly-time source
+//   open_boundary.hpp / ldu_open_boundary.hip  open boundaries (inletOutlet, pressureInletOutletVelocity): the inflow mask and its three sums
 //   inlets.hpp / .cpp / .hip  inlets (fy_inlets_desc), shared with the block solver: the time functions, the shapes, the step's update kernel
 //   ldu_solver.cpp   sequencing + the C entry points
 #pragma once
@@ -82,6 +83,9 @@ struct LduGeo {
     // u_inlet[patch] != 0 in u_val's place (ldu_u_fixed in ldu_kernels.hip)
     const double* u_face;
     const int32_t* u_inlet;
+    // open boundaries (open_boundary.hpp; null: no patch carries an open code -- every kernel takes the path it always took): one byte per boundary face,
+    // u_inflow[f - nInt] = phi[f] < 0 on the faces of the open patches as of the last renewal, 0 elsewhere
+    const uint8_t* u_inflow;
 };
 
 // what mesh.findCell's stand-in reads beside LduGeo (device pointers): the points, the faces' point lists, the cells' balls, the mesh's bounding box

@@ -29,15 +29,39 @@ __device__ __forceinline__ D3 ldu_u_fixed(const LduGeo& g, int pa, int f) {
     if (g.u_face && g.u_inlet[pa]) return ld3(g.u_face, f - g.nInt);
     return ld3(g.u_val, pa);
 }
-__device__ __forceinline__ D3 Ub(const LduGeo& g, const double* F, int f) {
+// open boundaries (open_boundary.hpp): the condition boundary face f of patch pa takes NOW -- the patch's own code, but on an open patch (inletOutlet,
+// pressureInletOutletVelocity) the code of the condition the face equals by the inflow mask: an outflow face is a zeroGradient face, an inflow face of inletOutlet a
+// fixedValue face with the patch's value, an inflow face of pressureInletOutletVelocity keeps its code (the transform-patch form).  No mask (no open patch): the
+// patch's code, by a test that is uniform over the grid
+__device__ __forceinline__ int ldu_u_code(const LduGeo& g, int pa, int f) {
+    const int bc = g.u_bc[pa];
+    if (!g.u_inflow || bc < FY_BC_U_INLET_OUTLET) return bc;
+    if (!g.u_inflow[f - g.nInt]) return FY_BC_U_ZERO_GRADIENT;
+    return bc == FY_BC_U_INLET_OUTLET ? FY_BC_U_FIXED_VALUE : FY_BC_U_PRESSURE_INLET_OUTLET;
+}
+// ... and of a scalar (k, epsilon, T: FY_BC_NUT_* / FY_BC_T_*, whose zeroGradient is 0 and fixedValue 1 alike) whose inletOutlet code is `open`
+__device__ __forceinline__ int ldu_s_code(const LduGeo& g, int bc, int open, int f) {
+    if (!g.u_inflow || bc != open) return bc;
+    return g.u_inflow[f - g.nInt] ? 1 : 0;
+}
+static_assert(FY_BC_NUT_ZERO_GRADIENT == 0 && FY_BC_NUT_FIXED_VALUE == 1 && FY_BC_T_ZERO_GRADIENT == 0 && FY_BC_T_FIXED_VALUE == 1, "ldu_s_code returns 0 | 1");
+// open_as_zg: every face of an open patch as a zeroGradient face whatever the mask (phiHbyA: the patch is assignable)
+__device__ __forceinline__ D3 Ub(const LduGeo& g, const double* F, int f, bool open_as_zg = false) {
     const int pa = g.patch_of[f - g.nInt];
-    if (g.u_bc[pa] == FY_BC_U_FIXED_VALUE) return ldu_u_fixed(g, pa, f);
+    const int bc = open_as_zg ? g.u_bc[pa] : ldu_u_code(g, pa, f);
+    if (bc == FY_BC_U_FIXED_VALUE) return ldu_u_fixed(g, pa, f);
     const D3 uc = ld3(F, g.own[f]);
-    if (g.u_bc[pa] == FY_BC_U_SLIP) {
+    if (bc == FY_BC_U_SLIP) {
         const double rm = 1.0 / g.magSf[f];
         const D3 S = ld3(g.Sf, f), n = D3{rm * S.x, rm * S.y, rm * S.z};
         const double un = dot3(n, uc);
         return D3{uc.x - un * n.x, uc.y - un * n.y, uc.z - un * n.z};
+    }
+    if (bc == FY_BC_U_PRESSURE_INLET_OUTLET && !open_as_zg) {      // an inflow face: the normal component of the cell's value, U_b = n (n . U_P)
+        const double rm = 1.0 / g.magSf[f];
+        const D3 S = ld3(g.Sf, f), n = D3{rm * S.x, rm * S.y, rm * S.z};
+        const double un = dot3(n, uc);
+        return D3{un * n.x, un * n.y, un * n.z};
     }
     return uc;
 }
@@ -45,18 +69,31 @@ __device__ __forceinline__ D3 Ub(const LduGeo& g, const double* F, int f) {
 // gradientInternalCoeffs U_P; basicSymmetryFvPatchField: snGradTransformDiag = (|n_x|, |n_y|, |n_z|), snGrad = -n (n & U_P) deltaCoeffs]: bd += the per-component
 // diagonal, b += the explicit remainder around the U the matrix is assembled with, bmax / bmin += cmptMax / cmptMin of the coefficient (fvMatrix::relax).  The flux
 // through the face is U_b & Sf = 0 up to rounding: the convection term sees it like a zeroGradient face
-__device__ __forceinline__ void slip_face(const LduGeo& g, int f, double gm, D3 uc, double (&bd)[3], double (&b)[3], double& bmax, double& bmin) {
+// open != 0: an inflow face of pressureInletOutletVelocity, the same transform-patch form for the directionMixed condition with value fraction I - n n, refValue 0,
+// refGrad 0 [OF-6 directionMixedFvPatchField, as recalled]: U_b = n (n . U_P), snGradTransformDiag_q = sqrt(1 - n_q^2) (= diag_q), d = U_b - U_P; the laplacian gives
+// bd_q += gm diag_q, b_q += gm (diag_q U_P,q + d_q); the convection term, whose scalar part dg += fl the caller adds as on a zeroGradient face, gives
+// bd_q -= fl diag_q (valueInternalCoeffs = 1 - diag; formed as (gm - fl) diag_q) and b_q -= fl (U_b,q - (1 - diag_q) U_P,q) (valueBoundaryCoeffs); bmax / bmin take
+// the component maximum and minimum of the diagonal added.  fl: the face's (alpha-weighted) flux, read with open only
+__device__ __forceinline__ void slip_face(const LduGeo& g, int f, double gm, D3 uc, double (&bd)[3], double (&b)[3], double& bmax, double& bmin, int open = 0, double fl = 0.0) {
     const double rm = 1.0 / g.magSf[f];
     const D3 S = ld3(g.Sf, f);
-    const double nn[3] = {rm * S.x, rm * S.y, rm * S.z}, an[3] = {fabs(nn[0]), fabs(nn[1]), fabs(nn[2])}, u3[3] = {uc.x, uc.y, uc.z};
+    const double nn[3] = {rm * S.x, rm * S.y, rm * S.z}, u3[3] = {uc.x, uc.y, uc.z};
+    double an[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) an[q] = open ? sqrt(fmax(1.0 - nn[q] * nn[q], 0.0)) : fabs(nn[q]);
     const double un = dot3(D3{nn[0], nn[1], nn[2]}, uc);
+    // one body for both: the coefficient of the diagonal is gm (symmetry) or gm - fl (open: > 0 on an inflow face, so its component maximum is cf max(diag)); d = U_b - U_P
+    // is -n (n . U_P) or n (n . U_P) - U_P, and a + (-x) has the bits of a - x; the open face alone has a convective explicit part
+    const double cf = open ? gm - fl : gm;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        bd[q] += gm * an[q];
-        b[q] += gm * (an[q] * u3[q] - nn[q] * un);
+        const double ubq = nn[q] * un, dq = open ? ubq - u3[q] : -ubq;
+        bd[q] += cf * an[q];
+        b[q] += gm * (an[q] * u3[q] + dq);
+        if (open) b[q] -= fl * (ubq - (1.0 - an[q]) * u3[q]);
     }
-    bmax += gm * fmax(an[0], fmax(an[1], an[2]));
-    bmin += gm * fmin(an[0], fmin(an[1], an[2]));
+    bmax += cf * fmax(an[0], fmax(an[1], an[2]));
+    bmin += cf * fmin(an[0], fmin(an[1], an[2]));
 }
 __device__ __forceinline__ double pbv(const LduGeo& g, const double* p, int f) {
     const int pa = g.patch_of[f - g.nInt];
@@ -257,14 +294,15 @@ __global__ __launch_bounds__(256) void k_ldu_mom_cells(LduGeo g, const double* _
             if (nb > c) { dg -= M.lower[f]; b[0] += cr.x; b[1] += cr.y; b[2] += cr.z; }
             else { dg -= M.upper[f]; b[0] -= cr.x; b[1] -= cr.y; b[2] -= cr.z; }
         } else {
-            const int pa = g.patch_of[f - g.nInt];
-            if (g.u_bc[pa] == FY_BC_U_FIXED_VALUE) {
+            const int pa = g.patch_of[f - g.nInt], bc = ldu_u_code(g, pa, f);
+            if (bc == FY_BC_U_FIXED_VALUE) {
                 const double gm = g.nu * g.magSf[f] * g.dcNO[f];
                 const D3 ub = ldu_u_fixed(g, pa, f);
                 dg += gm;
                 b[0] += (-phi[f] + gm) * ub.x; b[1] += (-phi[f] + gm) * ub.y; b[2] += (-phi[f] + gm) * ub.z;
             } else {
-                if (g.u_bc[pa] == FY_BC_U_SLIP) slip_face(g, f, g.nu * g.magSf[f] * g.dcNO[f], uo, bd, b, bmax, bmin);      // (UEqn is assembled around U = U.oldTime())
+                if (bc == FY_BC_U_SLIP || bc == FY_BC_U_PRESSURE_INLET_OUTLET)      // (UEqn is assembled around U = U.oldTime())
+                    slip_face(g, f, g.nu * g.magSf[f] * g.dcNO[f], uo, bd, b, bmax, bmin, bc == FY_BC_U_PRESSURE_INLET_OUTLET, phi[f]);
                 dg += phi[f];
             }
         }
@@ -353,8 +391,8 @@ __global__ __launch_bounds__(256) void k_ldu_phiHbyA(LduGeo g, const double* __r
         const int pa = g.patch_of[f - g.nInt];
         fixes = g.u_bc[pa] == FY_BC_U_FIXED_VALUE;
         rf = rAU[g.own[f]];
-        fl = dot3(Ub(g, HbyA, f), S);       // constrainHbyA: U's value where the patch fixes it; a symmetry patch keeps its type on HbyA
-        uf = dot3(Ub(g, Uold, f), S);
+        fl = dot3(Ub(g, HbyA, f, true), S);       // constrainHbyA: U's value where the patch fixes it; a symmetry patch keeps its type on HbyA; an open patch is
+        uf = dot3(Ub(g, Uold, f, true), S);       // assignable: the cell's value on every one of its faces, whatever the mask
     }
     const double phiCorr = phiOld[f] - uf;
     const double coef = fixes ? 0.0 : 1.0 - fmin(fabs(phiCorr) / (fabs(phiOld[f]) + 1e-15), 1.0);
@@ -543,7 +581,7 @@ __global__ __launch_bounds__(256) void k_ldu_pre_coupling(LduGeo g, const double
 // field alpha (nu + nut) [OF-6 gaussLaplacianScheme::fvmLaplacian(vol gamma)]; on the boundary alpha_b (nu + nut_b), nut_b by the patch of 0/nut (ldu_nut_b)
 __device__ __forceinline__ double ldu_k_b(const LduGeo& g, const LduPim& P, const double* __restrict__ k, int f) {
     const int pa = g.patch_of[f - g.nInt];
-    return P.k_bc[pa] == FY_BC_NUT_FIXED_VALUE ? P.k_val[pa] : k[g.own[f]];
+    return ldu_s_code(g, P.k_bc[pa], FY_BC_NUT_INLET_OUTLET, f) == FY_BC_NUT_FIXED_VALUE ? P.k_val[pa] : k[g.own[f]];
 }
 __device__ __forceinline__ double ldu_nut_b(const LduGeo& g, const LduPim& P, int f) {
     if (!P.nut) return 0.0;
@@ -553,7 +591,7 @@ __device__ __forceinline__ double ldu_nut_b(const LduGeo& g, const LduPim& P, in
     if (t == FY_BC_WALL_FUNCTION) return nutk_wall_nut(P.wf_cmu25, P.ywall[f - g.nInt], P.k[c], g.nu, P.wf_yplam, P.wf_kappa, P.wf_E);
     // calculated: correctNut()'s expression on the boundary values (fv_closures.hpp: nut_kepsilon, nut_keqn)
     if (t == FY_BC_NUT_CALCULATED && P.eps) {
-        const double kb = ldu_k_b(g, P, P.k, f), eb = P.eps_bc[pa] == FY_BC_NUT_FIXED_VALUE ? P.eps_val[pa] : P.eps[c];
+        const double kb = ldu_k_b(g, P, P.k, f), eb = ldu_s_code(g, P.eps_bc[pa], FY_BC_NUT_INLET_OUTLET, f) == FY_BC_NUT_FIXED_VALUE ? P.eps_val[pa] : P.eps[c];
         return nut_kepsilon(P.cmu, kb, eb);
     }
     if (t == FY_BC_NUT_CALCULATED) return nut_keqn(P.ck, ldu_k_b(g, P, P.k, f), P.delta_coeff * cbrt(g.V[c]));
@@ -629,13 +667,15 @@ __global__ __launch_bounds__(256) void k_ldu_pmom_cells(LduGeo g, LduPim P, cons
             const int pa = g.patch_of[f - g.nInt];
             divAPhi += fl;                                     // (= phi on a boundary face)
             b[0] += st.x; b[1] += st.y; b[2] += st.z;
-            if (g.u_bc[pa] == FY_BC_U_FIXED_VALUE) {
+            const int bc = ldu_u_code(g, pa, f);
+            if (bc == FY_BC_U_FIXED_VALUE) {
                 const double gm = (g.nu + ldu_nut_b(g, P, f)) * g.magSf[f] * g.dcNO[f];
                 const D3 ub = ldu_u_fixed(g, pa, f);
                 dg += gm;
                 b[0] += (-fl + gm) * ub.x; b[1] += (-fl + gm) * ub.y; b[2] += (-fl + gm) * ub.z;
             } else {
-                if (g.u_bc[pa] == FY_BC_U_SLIP) slip_face(g, f, (g.nu + ldu_nut_b(g, P, f)) * g.magSf[f] * g.dcNO[f], uc, bd, b, bmax, bmin);
+                if (bc == FY_BC_U_SLIP || bc == FY_BC_U_PRESSURE_INLET_OUTLET)
+                    slip_face(g, f, (g.nu + ldu_nut_b(g, P, f)) * g.magSf[f] * g.dcNO[f], uc, bd, b, bmax, bmin, bc == FY_BC_U_PRESSURE_INLET_OUTLET, fl);
                 dg += fl;
             }
         }
@@ -669,7 +709,7 @@ __global__ __launch_bounds__(256) void k_ldu_smagorinsky_nut(LduGeo g, const dou
 // The matrix goes into the momentum matrix's arrays (free once the correctors are done) and is solved as component 0 of a three-component system by the momentum passes
 __device__ __forceinline__ double ldu_x_b(const LduGeo& g, const LduKEqn& K, const double* __restrict__ x, int f) {
     const int pa = g.patch_of[f - g.nInt];
-    return K.x_bc[pa] == FY_BC_NUT_FIXED_VALUE ? K.x_val[pa] : x[g.own[f]];
+    return ldu_s_code(g, K.x_bc[pa], FY_BC_NUT_INLET_OUTLET, f) == FY_BC_NUT_FIXED_VALUE ? K.x_val[pa] : x[g.own[f]];
 }
 __global__ __launch_bounds__(256) void k_ldu_grad_k(LduGeo g, LduPim P, LduKEqn K, double* __restrict__ gk) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -715,7 +755,7 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
             const int pa = g.patch_of[f - g.nInt];
             const double fl = P.alphaf[f] * phi[f];
             sumPhi += phi[f];
-            if (K.x_bc[pa] == FY_BC_NUT_FIXED_VALUE) {
+            if (ldu_s_code(g, K.x_bc[pa], FY_BC_NUT_INLET_OUTLET, f) == FY_BC_NUT_FIXED_VALUE) {
                 const double gb = (g.nu + ldu_nut_b(g, P, f) / K.sigma) * g.magSf[f] * g.dcNO[f];
                 dg += gb; b += (-fl + gb) * K.x_val[pa];
             } else dg += fl;
@@ -750,7 +790,7 @@ __global__ __launch_bounds__(256) void k_ldu_k_cells(LduGeo g, LduPim P, LduKEqn
 // and may each be null (icoFoamYade has no LduPim: 1, 1, 0).  fixedValue face: gb = Deff_b |Sf| dcNO on the diagonal, (gb - F_b) T_b in the source; zeroGradient: F_b
 __device__ __forceinline__ double ldu_T_b(const LduGeo& g, const LduTEqn& E, double tc, int f) {
     const int pa = g.patch_of[f - g.nInt];
-    return E.bc[pa] == FY_BC_T_FIXED_VALUE ? E.val[pa] : tc;
+    return ldu_s_code(g, E.bc[pa], FY_BC_T_INLET_OUTLET, f) == FY_BC_T_FIXED_VALUE ? E.val[pa] : tc;
 }
 __global__ __launch_bounds__(256) void k_ldu_grad_T(LduGeo g, LduTEqn E, double* __restrict__ gT) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -795,7 +835,7 @@ __global__ __launch_bounds__(256) void k_ldu_T_cells(LduGeo g, LduPim P, LduTEqn
         } else {
             const int pa = g.patch_of[f - g.nInt];
             sumF += fl;
-            if (E.bc[pa] == FY_BC_T_FIXED_VALUE) {
+            if (ldu_s_code(g, E.bc[pa], FY_BC_T_INLET_OUTLET, f) == FY_BC_T_FIXED_VALUE) {
                 const double gb = (E.D + ldu_nut_b(g, P, f) * E.rPrt) * g.magSf[f] * g.dcNO[f];
                 dg += gb; b += (gb - fl) * E.val[pa];
             } else dg += fl;
@@ -942,7 +982,7 @@ __global__ __launch_bounds__(256) void k_ldu_k_bound_nut(LduGeo g, LduPim P, Ldu
                 xf = nb > c ? g.w[f] * mo + (1.0 - g.w[f]) * mn : g.w[f] * mn + (1.0 - g.w[f]) * mo;
             } else {
                 const int pa = g.patch_of[f - g.nInt];
-                xf = fmax(K.x_bc[pa] == FY_BC_NUT_FIXED_VALUE ? K.x_val[pa] : xc, kMin);
+                xf = fmax(ldu_s_code(g, K.x_bc[pa], FY_BC_NUT_INLET_OUTLET, f) == FY_BC_NUT_FIXED_VALUE ? K.x_val[pa] : xc, kMin);
             }
             av += g.magSf[f] * xf; asum += g.magSf[f];
         }

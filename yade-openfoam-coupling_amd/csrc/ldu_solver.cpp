@@ -18,6 +18,7 @@
 #include "solid_stats.hpp"
 #include "ldu.hpp"
 #include "ldu_amg.hpp"
+#include "open_boundary.hpp"
 
 namespace fy {
 
@@ -269,7 +270,7 @@ struct LduSolver {
         }));
         if (fresh.on() && need_ref && !fresh.flux_free()) {               // adjustPhi's precondition, as fy_solver_create states it for the block
             bool adjustable = false;
-            for (int pa = 0; pa < hm.nPatches; ++pa) adjustable = adjustable || (hm.psize[(size_t)pa] > 0 && h_ubc[(size_t)pa] == FY_BC_U_ZERO_GRADIENT);
+            for (int pa = 0; pa < hm.nPatches; ++pa) adjustable = adjustable || (hm.psize[(size_t)pa] > 0 && (h_ubc[(size_t)pa] == FY_BC_U_ZERO_GRADIENT || h_ubc[(size_t)pa] >= FY_BC_U_INLET_OUTLET));      // (an open patch is adjustable)
             if (!adjustable)
                 return fail(FY_ERR_UNSUPPORTED, "%s: no patch fixes the pressure and the fixed-value velocity patches do not balance (an inlet's shape carries a net normal flux and no "
                                                 "velocity patch is adjustable): OpenFOAM's adjustPhi ends such a run with 'Continuity error cannot be removed by adjusting the outflow'", who);
@@ -286,12 +287,64 @@ struct LduSolver {
             g.u_face = uFace.p; g.u_inlet = dInlet.p;
             FY_TRY(inl.update(stream, inl.start_time, uFace.p));           // the start time's value, as the 0/U file would hold it
         }
-        FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                 // createPhi with the boundary values as they are now
+        FY_TRY(create_phi());                                              // createPhi with the boundary values as they are now
         FY_HIP(hipStreamSynchronize(stream));
         return FY_OK;
     }
 
+    // open boundaries (open_boundary.hpp; DESIGN.md section 3 "Open boundaries").  Off (no patch carries an open code): nothing allocated, nothing launched,
+    // g.u_inflow null.  mask [nb]: the inflow byte per boundary face; patch [nPatches]: which patches are open for U, k, epsilon or T; sums: the last renewal's
+    // three folded sums (OPEN_SUMS), its own partials so that a renewal never touches a reduction in flight
+    struct Open {
+        bool on = false;
+        DevBuf<uint8_t> mask;
+        DevBuf<int32_t> patch;
+        DevBuf<double> partials, sums, f64;
+        KernelClock clock;
+    } ob;
+    int open_setup(const std::vector<int32_t>& open_patch) {
+        const size_t nb = (size_t)(nf - ni);
+        FY_TRY(up(ob.patch, open_patch));
+        FY_TRY(ob.mask.alloc_exact(std::max<size_t>(nb, 1)));
+        FY_HIP(hipMemsetAsync(ob.mask.p, 0, std::max<size_t>(nb, 1), stream));
+        FY_TRY(ob.partials.alloc_exact((size_t)OPEN_SUMS * (size_t)ldu_red_blocks((int)nb))); FY_TRY(zero(ob.partials));
+        FY_TRY(ob.sums.alloc_exact(OPEN_SUMS)); FY_TRY(zero(ob.sums));
+        ob.clock.per_collect = (size_t)1 << 20;                // every launch is timed and counted while timing is on
+        ob.on = true;
+        g.u_inflow = ob.mask.p;
+        return FY_OK;
+    }
+    // the renewal: the mask from phi as it stands, and the fold of its three sums (no host synchronisation)
+    int open_renew() {
+        if (!ob.on || nf == ni) return FY_OK;
+        ob.clock.begin(stream);
+        FY_TRY(launch_ldu_open_faces(stream, g, ob.patch.p, phi.p, ob.mask.p, ob.partials.p));
+        ob.clock.end(stream);
+        ob.clock.begin(stream);
+        FY_TRY(launch_reduce_finalize(stream, ob.partials.p, nf - ni, OPEN_SUMS, nullptr, ob.sums.p, nullptr, 0));
+        ob.clock.end(stream);
+        return FY_OK;
+    }
+    // createPhi: phi = fvc::flux(U) with every open face evaluated as zeroGradient (the mask cleared first), then the mask of that flux
+    int create_phi() {
+        if (ob.on) FY_HIP(hipMemsetAsync(ob.mask.p, 0, std::max<size_t>((size_t)(nf - ni), 1), stream));
+        FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));
+        return open_renew();
+    }
+    int get_open_stats(int64_t* inflow_faces, double* inflow_flux, double* outflow_flux) {
+        if (!ob.on) return fail(FY_ERR_INVALID, "fy_ldu_solver_get_open_boundary_stats: no patch carries an open code (FY_BC_U_INLET_OUTLET, FY_BC_U_PRESSURE_INLET_OUTLET, FY_BC_NUT_INLET_OUTLET, FY_BC_T_INLET_OUTLET)");
+        FY_HIP(hipSetDevice(device));
+        double h[OPEN_SUMS];
+        FY_HIP(hipMemcpyAsync(h, ob.sums.p, sizeof(h), hipMemcpyDeviceToHost, stream));
+        FY_HIP(hipStreamSynchronize(stream));
+        if (inflow_faces) *inflow_faces = (int64_t)h[OPEN_INFLOW_FACES];
+        if (inflow_flux) *inflow_flux = h[OPEN_INFLOW_FLUX];
+        if (outflow_flux) *outflow_flux = h[OPEN_OUTFLOW_FLUX];
+        return FY_OK;
+    }
+
     ~LduSolver() {
+        ob.clock.destroy();
         fc.clock.destroy();
         inl.clock.destroy();
         if (cpl) fy_destroy(cpl);
@@ -343,10 +396,13 @@ struct LduSolver {
         std::vector<double> uval(c->u_value, c->u_value + 3 * (size_t)hm.nPatches), pval(c->p_value, c->p_value + hm.nPatches);
         need_ref = true;
         h_ubc = ubc;
+        std::vector<int32_t> open_patch((size_t)hm.nPatches, 0);      // the patches that carry an open code for U, k, epsilon or T
         for (int pa = 0; pa < hm.nPatches; ++pa) {
-            if (ubc[(size_t)pa] != FY_BC_U_FIXED_VALUE && ubc[(size_t)pa] != FY_BC_U_ZERO_GRADIENT && ubc[(size_t)pa] != FY_BC_U_SLIP)
-                return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: velocity patch type %d (fixedValue, zeroGradient, symmetry / slip)", ubc[(size_t)pa]);
-            has_slip = has_slip || ubc[(size_t)pa] == FY_BC_U_SLIP;
+            if (ubc[(size_t)pa] != FY_BC_U_FIXED_VALUE && ubc[(size_t)pa] != FY_BC_U_ZERO_GRADIENT && ubc[(size_t)pa] != FY_BC_U_SLIP && ubc[(size_t)pa] != FY_BC_U_INLET_OUTLET &&
+                ubc[(size_t)pa] != FY_BC_U_PRESSURE_INLET_OUTLET)
+                return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: velocity patch type %d (fixedValue, zeroGradient, symmetry / slip, inletOutlet, pressureInletOutletVelocity)", ubc[(size_t)pa]);
+            has_slip = has_slip || ubc[(size_t)pa] == FY_BC_U_SLIP || ubc[(size_t)pa] == FY_BC_U_PRESSURE_INLET_OUTLET;      // (the transform-patch form: a per-component boundary diagonal)
+            if (ubc[(size_t)pa] >= FY_BC_U_INLET_OUTLET) open_patch[(size_t)pa] = 1;
             if (pbc[(size_t)pa] != FY_BC_P_ZERO_GRADIENT && pbc[(size_t)pa] != FY_BC_P_FIXED_VALUE && !(pimple && pbc[(size_t)pa] == FY_BC_P_FIXED_FLUX))
                 return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: pressure patch type %d (zeroGradient, fixedValue; fixedFluxPressure with pimpleFoamYade)", pbc[(size_t)pa]);
             if (pbc[(size_t)pa] == FY_BC_P_FIXED_VALUE) need_ref = false;
@@ -359,8 +415,9 @@ struct LduSolver {
             for (int pa = 0; pa < hm.nPatches; ++pa) {
                 if (c->T_bc) tbc[(size_t)pa] = c->T_bc[pa];
                 if (c->T_value) tval[(size_t)pa] = c->T_value[pa];
-                if (tbc[(size_t)pa] != FY_BC_T_ZERO_GRADIENT && tbc[(size_t)pa] != FY_BC_T_FIXED_VALUE)
-                    return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver_create: unknown T_bc %d on patch %d (FY_BC_T_ZERO_GRADIENT, FY_BC_T_FIXED_VALUE)", tbc[(size_t)pa], pa);
+                if (tbc[(size_t)pa] != FY_BC_T_ZERO_GRADIENT && tbc[(size_t)pa] != FY_BC_T_FIXED_VALUE && tbc[(size_t)pa] != FY_BC_T_INLET_OUTLET)
+                    return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver_create: unknown T_bc %d on patch %d (FY_BC_T_ZERO_GRADIENT, FY_BC_T_FIXED_VALUE, FY_BC_T_INLET_OUTLET)", tbc[(size_t)pa], pa);
+                if (tbc[(size_t)pa] == FY_BC_T_INLET_OUTLET) open_patch[(size_t)pa] = 1;
             }
         }
         cs.T_bc = nullptr; cs.T_value = nullptr;
@@ -429,8 +486,9 @@ struct LduSolver {
                 for (int pa = 0; pa < hm.nPatches; ++pa) {
                     if (c->eps_bc) eb[(size_t)pa] = c->eps_bc[pa];
                     if (c->eps_value) ev[(size_t)pa] = c->eps_value[pa];
-                    if (eb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && eb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE && eb[(size_t)pa] != FY_BC_WALL_FUNCTION)
-                        return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: epsilon patch type %d (zeroGradient, fixedValue, epsilonWallFunction)", eb[(size_t)pa]);
+                    if (eb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && eb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE && eb[(size_t)pa] != FY_BC_WALL_FUNCTION && eb[(size_t)pa] != FY_BC_NUT_INLET_OUTLET)
+                        return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: epsilon patch type %d (zeroGradient, fixedValue, epsilonWallFunction, inletOutlet)", eb[(size_t)pa]);
+                    if (eb[(size_t)pa] == FY_BC_NUT_INLET_OUTLET) open_patch[(size_t)pa] = 1;
                     wf_eps[(size_t)pa] = eb[(size_t)pa] == FY_BC_WALL_FUNCTION;
                 }
                 FY_TRY(up(d_epsbc, eb)); FY_TRY(up(d_epsval, ev));
@@ -444,7 +502,9 @@ struct LduSolver {
                 for (int pa = 0; pa < hm.nPatches; ++pa) {
                     if (c->k_bc) kb[(size_t)pa] = c->k_bc[pa];
                     if (c->k_value) kv[(size_t)pa] = c->k_value[pa];
-                    if (kb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && kb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE) return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: k patch type %d (zeroGradient, fixedValue)", kb[(size_t)pa]);
+                    if (kb[(size_t)pa] != FY_BC_NUT_ZERO_GRADIENT && kb[(size_t)pa] != FY_BC_NUT_FIXED_VALUE && kb[(size_t)pa] != FY_BC_NUT_INLET_OUTLET)
+                        return fail(FY_ERR_UNSUPPORTED, "fy_ldu_solver: k patch type %d (zeroGradient, fixedValue, inletOutlet)", kb[(size_t)pa]);
+                    if (kb[(size_t)pa] == FY_BC_NUT_INLET_OUTLET) open_patch[(size_t)pa] = 1;
                 }
                 FY_TRY(up(d_kbc, kb)); FY_TRY(up(d_kval, kv));
                 FY_TRY(kturb.alloc_exact(n)); FY_TRY(gradk.alloc_exact(3 * n));
@@ -484,7 +544,11 @@ struct LduSolver {
             if (c->drag_law != FY_DRAG_REFERENCE) FY_TRY(cpl->c.set_drag_law(c->drag_law));                  // constant/couplingProperties
             if (c->force_models) FY_TRY(cpl->c.set_force_models(c->force_models));
         }
-        FY_TRY(launch_ldu_flux_of(stream, g, U.p, phi.p));                    // createPhi
+        if (std::find(open_patch.begin(), open_patch.end(), 1) != open_patch.end()) {      // (before the coupling takes &g is fine: it reads g through the pointer)
+            FY_TRY(open_setup(open_patch));
+            ob.clock.on = ss.clock.on;
+        }
+        FY_TRY(create_phi());                                                 // createPhi
         if (c->thermal.on) FY_TRY(thermal_create(c, tbc, tval));              // (before fieldAverage, which may ask for T)
         FY_HIP(hipStreamSynchronize(stream));
         if (c->solid_stats) FY_TRY(set_solid_statistics(1));                  // couplingProperties solidStatistics (before fieldAverage and the monitors, which may ask for its fields)
@@ -648,6 +712,7 @@ struct LduSolver {
             FY_TRY(solve_pressure(final_corr && no == cs.n_non_orth_correctors));
             if (no == cs.n_non_orth_correctors) FY_TRY(launch_ldu_flux_correct(stream, g, p.p, phiHbyA.p, pcoef.p, pcorr.p, phi.p));
         }
+        FY_TRY(open_renew());                                                                                      // open boundaries: the mask of the new flux, before U is corrected
         FY_TRY(launch_ldu_U_correct(stream, g, HbyA.p, rAU.p, p.p, phi.p, U.p, partials.p));                     // :134-137
         double h[2];
         FY_TRY(reduce_read(nc, 2, nullptr, h));
@@ -676,6 +741,7 @@ struct LduSolver {
                 if (p_relax_now > 0 && p_relax_now < 1) FY_TRY(launch_relax_field(stream, p.p, pPrev.p, p_relax_now, (size_t)nc));                  // :41
             }
         }
+        FY_TRY(open_renew());                                                                                      // open boundaries: the mask of the new flux, before U is reconstructed
         FY_TRY(launch_ldu_reconstruct(stream, g, ssf.p, HbyA.p, rAU.p, U.p));                                     // :43-46
         if (fc.on) FY_TRY(flow_correct());                                                                        // fvOptions.correct(Uc) (the continuity sums below read the flux, not U)
         FY_TRY(launch_ldu_pim_continuity(stream, g, pt.p, alpha.p, alpha.p, partials.p));             // :50
@@ -788,6 +854,7 @@ struct LduSolver {
         stepped = true;                    // (from here on the fields move: set_inlets refuses)
         FY_HIP(hipMemcpyAsync(Uold.p, U.p, 3 * (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, stream));    // runTime++: old-time fields
         FY_HIP(hipMemcpyAsync(phiOld.p, phi.p, (size_t)nf * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        FY_TRY(open_renew());                                                                                      // open boundaries: the mask of the old time's flux, before any kernel reads it
         FY_TRY(launch_ldu_grad_vec(stream, g, U.p, vGrad.p));                                                      // :71
         if (pimple) FY_TRY(step_pimple());
         else {
@@ -833,6 +900,7 @@ struct LduSolver {
         if (fc.on) fc.clock.collect();
         if (wl.on()) wl.m.clock.collect();
         if (inl.on()) inl.clock.collect();
+        if (ob.on) ob.clock.collect();
         return FY_OK;
     }
 
@@ -872,6 +940,15 @@ struct LduSolver {
             if (!b.p) FY_TRY(b.alloc_exact(std::max<size_t>(*count, 1)));
             FY_TRY(launch_ldu_boundary_values(stream, g, p.p, U.p, th.eq, s == "p_boundary" ? b.p : nullptr, s == "U_boundary" ? b.p : nullptr, s == "T_boundary" ? b.p : nullptr));
             *ptr = b.p;
+            return FY_OK;
+        }
+        if (s == "U_open_inflow") {                                                // the inflow mask as doubles (0 | 1), as the last renewal left it
+            if (!ob.on) return fail(FY_ERR_INVALID, "fy_ldu_solver field 'U_open_inflow' does not exist in this case (no patch carries an open code)");
+            *count = (size_t)(nf - ni);
+            FY_HIP(hipSetDevice(device));
+            if (!ob.f64.p) FY_TRY(ob.f64.alloc_exact(std::max<size_t>(*count, 1)));
+            FY_TRY(launch_ldu_open_mask_f64(stream, nf - ni, ob.mask.p, ob.f64.p));
+            *ptr = ob.f64.p;
             return FY_OK;
         }
         if (wl.lookup(s, ptr, count)) return FY_OK;                                // wallShearStress_boundary, yPlus_boundary as the last sample left them
@@ -968,7 +1045,7 @@ int fy_ldu_solver_write_field_host(fy_ldu_solver* s, const char* name, const dou
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
     if (nm == "uSource") s->s.ext_source = true;
-    if (nm == "U") FY_TRY(fy::launch_ldu_flux_of(s->s.stream, s->s.g, s->s.U.p, s->s.phi.p));      // createPhi
+    if (nm == "U") FY_TRY(s->s.create_phi());      // createPhi
     FY_HIP(hipStreamSynchronize(s->s.stream));
     return FY_OK;
 }
@@ -1003,15 +1080,17 @@ int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver* s, int on) {
     s->s.fc.clock.reset(); s->s.fc.clock.on = on != 0;
     s->s.wl.m.clock.reset(); s->s.wl.m.clock.on = on != 0;
     s->s.inl.clock.reset(); s->s.inl.clock.on = on != 0;
+    s->s.ob.clock.reset(); s->s.ob.clock.on = on != 0;
     return FY_OK;
 }
 int fy_ldu_solver_get_kernel_timing(fy_ldu_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
     FY_LS(s);
     const std::string k = kernel ? kernel : "";
     if (k == "wall_loads" && s->s.wl.on() && total_ms && launches) { *total_ms = s->s.wl.m.clock.total_ms; *launches = s->s.wl.m.clock.launches; return FY_OK; }
+    if (k == "open_boundary" && total_ms && launches) { *total_ms = s->s.ob.clock.total_ms; *launches = s->s.ob.clock.launches; return FY_OK; }      // (no open patch: no launch)
     if (k == "inlets" && s->s.inl.on() && total_ms && launches) { *total_ms = s->s.inl.clock.total_ms; *launches = s->s.inl.clock.launches; return FY_OK; }
     const bool flow = k == "flow_control" && s->s.fc.on;
-    if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats%s%s%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "", s->s.wl.on() ? ", wall_loads" : "", s->s.inl.on() ? ", inlets" : "");
+    if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats, open_boundary%s%s%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "", s->s.wl.on() ? ", wall_loads" : "", s->s.inl.on() ? ", inlets" : "");
     const fy::KernelClock& c = flow ? s->s.fc.clock : s->s.ss.clock;
     *total_ms = c.total_ms; *launches = c.launches;
     return FY_OK;
@@ -1021,6 +1100,7 @@ int fy_ldu_solver_get_flow_control(fy_ldu_solver* s, double* gradient, double* u
     FY_LS(s);
     return s->s.get_flow_control(gradient, ubar_uncorrected, rAU_ave, dGradP, corrections);
 }
+int fy_ldu_solver_get_open_boundary_stats(fy_ldu_solver* s, int64_t* inflow_faces, double* inflow_flux, double* outflow_flux) { FY_LS(s); return s->s.get_open_stats(inflow_faces, inflow_flux, outflow_flux); }
 int fy_ldu_solver_set_monitors(fy_ldu_solver* s, const fy_monitor_desc* d) { FY_LS(s); return s->s.set_monitors(d); }
 int fy_ldu_solver_monitor_layout(fy_ldu_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_LS(s); return s->s.mon.layout(object, n_values, labels, cap); }
 int fy_ldu_solver_get_monitor_rows(fy_ldu_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
