@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FY_ABI_VERSION 27
+#define FY_ABI_VERSION 28
 
 /* ---- status codes ------------------------------------------------------------------------------------ */
 enum {
@@ -611,6 +611,38 @@ int fy_solver_set_wall_loads(fy_solver*, const fy_wall_loads_desc*);
 int fy_solver_wall_loads_layout(fy_solver*, int object, int32_t* n_values, char* labels, int cap);
 int fy_solver_get_wall_load_rows(fy_solver*, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows);
 
+/* Porous zones (not in the reference, whose solvers carry no fvOptions; DESIGN.md section 3 "Porous zones", DESIGN_FV.md "Porous resistance").  A zone is a set of
+ * cells in which the momentum equation gains an implicit resistance, diagonal in the global axes: per component q
+ *     C_q(c) = nu d_q + 0.5 |U*_c| f_q        the left-hand side gains  a_c V_c C_q(c) U_c,q
+ * d [1/m^2] and f [1/m] >= 0 (OpenFOAM's DarcyForchheimer coefficient mu D + rho |U| / 2 F per unit density, with a diagonal tensor, taken fully implicitly per
+ * component: this library's own operator), a_c = alpha_c with pimpleFoamYade and 1 with icoFoamYade, nu the laminar viscosity, U* the velocity the matrix is assembled
+ * around, |U| = sqrt((u0^2 + u1^2) + u2^2).  The coefficient joins the per-component diagonal a slip patch uses: the solve takes it per component, A() its component
+ * mean, H() what a component has over the mean; UcEqn.relax() takes its component maximum into the dominance test.  The turbulence and T equations get no porous
+ * source, the particle forces are untouched, and the `forces` object keeps leaving the porous contribution out.
+ * set: NULL or n_zones == 0 removes the zones and frees what they held (every kernel then takes the path it took before); a set may be replaced between steps.
+ * `cells` are solver cell labels (fy_solver: i + nx (j + ny k)).  FY_ERR_INVALID by name: more than FY_POROUS_MAX_ZONES zones, an empty zone, a label out of range,
+ * a cell in two zones (or twice in one), a negative or non-finite coefficient, a null cell list.  FY_ERR_UNSUPPORTED: a slab solver (fy_solver_create_slab).
+ * get_porous_stats: per zone z, from the CURRENT U and alpha, cells[z], volume[z] = S V, void_volume[z] = S a V and force[3 z + q] = S a V C_q(U) U_q (per unit
+ * density: multiply by rho for newtons), each array [n_zones] ([n_zones][3]) or NULL; one kernel over the zones' cells on request, folded in a fixed order (the same
+ * bits from run to run); the only porous call that waits for the device; its launches are the "porous_force" clock of fy_solver_get_kernel_timing (the step never
+ * launches it: without a zone the clock counts nothing).  While zones are set, "porousZone" [n] (0: none, 1 + the zone's index; as doubles) and "mom_bd" [n][3] (the
+ * momentum matrix's per-component diagonal: slip patches + zones, as the last assembly left it) are read-only field names; without zones both names and the
+ * statistics are FY_ERR_INVALID. */
+#define FY_POROUS_MAX_ZONES 8
+typedef struct fy_porous_zone {
+    char name[32];
+    double d[3];                  /* Darcy coefficients [1/m^2], per global axis */
+    double f[3];                  /* Forchheimer coefficients [1/m] */
+    int32_t n_cells;
+    const int32_t* cells;         /* [n_cells] solver cell labels; copied by the setter */
+} fy_porous_zone;
+typedef struct fy_porous_desc {
+    int32_t n_zones;
+    fy_porous_zone zones[FY_POROUS_MAX_ZONES];
+} fy_porous_desc;
+int fy_solver_set_porous_zones(fy_solver*, const fy_porous_desc*);
+int fy_solver_get_porous_stats(fy_solver*, int32_t* n_zones, int64_t* cells, double* volume, double* void_volume, double* force);
+
 /* Solid-phase statistics on this solver (not in the reference; DESIGN.md section 3 "Solid-phase statistics").  on != 0: once per step, after the T equation and before
  * fieldAverage and the monitors sample, one more scatter over the stencils of every located particle of EVERY batch forms eight sums per cell c (w: the stencil
  * weight, sum_c w = 1; point-force mode: the containing cell with w = 1; d = 2 r, Vp = pi d^3 / 6, Tp: the temperature the heat exchange holds for the particle at
@@ -804,7 +836,9 @@ int fy_solver_local_cells(fy_solver*);
 
 /* per-kernel HIP-event clocks on the solver stream, accumulated over steps since the last enable(1):
  * kernel = "mg_smooth_l0" (pEqn Laplacian apply fused with the damped-Jacobi update, fine level), "p_apply_dot" (pEqn Laplacian
- * apply + p.Ap inside PCG), "mom_pass" (fused momentum Jacobi pass) */
+ * apply + p.Ap inside PCG), "mom_pass" (fused momentum Jacobi pass), "mom_assemble" (the momentum assembly sweep, one sample per outer iteration; only with enable(2), which switches on this clock beside the others: an
+ * event pair idles the stream for some microseconds, and the step's other clocks were measured without it), "porous_force"
+ * (k_porous_force and its fold: launched by fy_solver_get_porous_stats only, so without a zone it counts no launch) */
 int fy_solver_enable_kernel_timing(fy_solver*, int on);
 int fy_solver_get_kernel_timing(fy_solver*, const char* kernel, double* total_ms, int64_t* launches);
 /* z-slabs: how long the solver's stream sat WAITING for slab exchanges, by phase {step start, particle, momentum, corrector}, accumulated since the
@@ -978,6 +1012,10 @@ int fy_ldu_solver_get_flow_control(fy_ldu_solver*, double* gradient, double* uba
  * over them (< 0) and over the outflow faces; any pointer may be NULL; FY_ERR_INVALID when no patch carries an open code.  Only this call waits for the device.  The
  * clock is "open_boundary" of fy_ldu_solver_get_kernel_timing (no launch without an open patch: nothing is allocated, every kernel takes the path it always took). */
 int fy_ldu_solver_get_open_boundary_stats(fy_ldu_solver*, int64_t* inflow_faces, double* inflow_flux, double* outflow_flux);
+/* Porous zones as on fy_solver (fy_solver_set_porous_zones): `cells` are cell labels of the fy_poly_mesh; the same refusals, read-outs ("porousZone", "mom_bd") and
+ * the "porous_force" clock of fy_ldu_solver_get_kernel_timing */
+int fy_ldu_solver_set_porous_zones(fy_ldu_solver*, const fy_porous_desc*);
+int fy_ldu_solver_get_porous_stats(fy_ldu_solver*, int32_t* n_zones, int64_t* cells, double* volume, double* void_volume, double* force);
 /* Heat exchange (fy_ldu_case.thermal.on; FY_ERR_INVALID on a solver without it): the entry points of fy_solver one for one, with the same semantics.  While thermal is
  * on, "T" [nc] (also writable: a non-uniform start), "heatSp" [nc] (W/K), "heatSu" [nc] (W) and, with thermal.beta != 0 and g != 0, "buoyancy" [nc][3] are field names
  * of fy_ldu_solver_read_field_host, and "T" one that fieldAverage accepts. */
@@ -1025,6 +1063,19 @@ int fy_foam_case_write_time_ldu(const fy_foam_case*, fy_ldu_solver*, const char*
 int fy_foam_case_write_wall_loads_ldu(const fy_foam_case*, fy_ldu_solver*);                         /* fy_foam_case_write_wall_loads for a general case */
 int fy_foam_case_write_monitors_ldu(const fy_foam_case*, fy_ldu_solver*);                           /* fy_foam_case_write_monitors for a general case */
 int fy_foam_case_restore_averages_ldu(const fy_foam_case*, fy_ldu_solver*, int* restored);         /* fy_foam_case_restore_averages for a general case */
+
+/* Porous zones of a case directory, block or general (one reader): the sub-dictionary of constant/couplingProperties
+ *     porousZones { plate { type DarcyForchheimer; box (x0 y0 z0) (x1 y1 z1); d (dx dy dz); f (fx fy fz); } ... }
+ * A cell belongs to a zone if its centre lies in the closed box (boxToCell's rule; the centres are the solver's); `active off;` is accepted and leaves the zone out.
+ * Refused by name with what is accepted (FY_ERR_UNSUPPORTED): any other key (cellZone, coordinateSystem, selectionMode, ...), another type, a box that selects no
+ * cell, boxes that share a cell, a negative or non-finite coefficient, more than FY_POROUS_MAX_ZONES active zones, a decomposed case.  A file without the
+ * sub-dictionary gives no zones.  Nothing is written to a time directory: a restart reads the same file.
+ * _porous_zones: the descriptor for fy_solver_set_porous_zones / fy_ldu_solver_set_porous_zones (the cell lists point into the case object: valid until
+ * fy_foam_case_close).  _make_solver / _make_ldu_solver: fy_foam_case_desc + fy_solver_create (fy_foam_case_poly_mesh + fy_foam_case_ldu_desc +
+ * fy_ldu_solver_create) and the case's zones applied -- the descriptors themselves carry no zones, so a solver created from them alone has none */
+int fy_foam_case_porous_zones(const fy_foam_case*, fy_porous_desc* out);
+int fy_foam_case_make_solver(const fy_foam_case*, const fy_transport*, int device_ordinal, fy_solver** out);
+int fy_foam_case_make_ldu_solver(const fy_foam_case*, const fy_transport*, int device_ordinal, fy_ldu_solver** out);
 
 #ifdef __cplusplus
 }

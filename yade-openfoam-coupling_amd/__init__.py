@@ -412,6 +412,63 @@ class _Inlets:
         _check(f(self._h, C.byref(d) if d is not None else None))
 
 
+POROUS_MAX_ZONES = 8
+
+
+class PorousZone(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("d", C.c_double * 3), ("f", C.c_double * 3), ("n_cells", C.c_int32), ("cells", _ip)]
+
+
+class PorousDesc(C.Structure):
+    _fields_ = [("n_zones", C.c_int32), ("zones", PorousZone * POROUS_MAX_ZONES)]
+
+
+def porous_desc(zones):
+    """fy_porous_desc from [dict(name=, cells=, d=(dx, dy, dz), f=(fx, fy, fz))]: cells are solver cell labels, d in 1/m^2, f in 1/m.  More than POROUS_MAX_ZONES
+    entries keep their count (the setter refuses it by name) and lose the entries past the array"""
+    d = PorousDesc()
+    d.n_zones = len(zones)
+    d._keep = []
+    for z, o in enumerate(zones[:POROUS_MAX_ZONES]):
+        Z = d.zones[z]
+        Z.name = str(o.get("name", f"zone{z}")).encode()[:31]
+        Z.d = (C.c_double * 3)(*[float(x) for x in o.get("d", (0, 0, 0))])
+        Z.f = (C.c_double * 3)(*[float(x) for x in o.get("f", (0, 0, 0))])
+        cells = np.ascontiguousarray(o["cells"], dtype=np.int32).ravel()
+        d._keep.append(cells)
+        Z.n_cells = cells.size
+        Z.cells = _i(cells) if cells.size else None
+    return d
+
+
+def cells_in_box(centres, lo, hi):
+    """the labels of the cells whose centre lies in the closed box [lo, hi] (OpenFOAM's boxToCell), ascending; centres [n][3]"""
+    c = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+    lo = np.asarray(lo, dtype=np.float64); hi = np.asarray(hi, dtype=np.float64)
+    return np.nonzero(np.all((c >= lo) & (c <= hi), axis=1))[0].astype(np.int32)
+
+
+class _Porous:
+    """porous zones on a solver object (Solver: fy_solver_set_porous_zones, LduSolver: fy_ldu_solver_set_porous_zones): a Darcy-Forchheimer resistance, diagonal in
+    the global axes and implicit per component.  While zones are set, get("porousZone") and get("mom_bd") are field names"""
+
+    def set_porous_zones(self, zones=None):
+        """zones = [dict(name=, cells=, d=, f=)] (or a PorousDesc); None or empty: the zones are removed and what they held is freed.  May be called between steps"""
+        f = getattr(lib(), f"{self._AVG_PREFIX}_set_porous_zones")
+        f.argtypes = [C.c_void_p, C.POINTER(PorousDesc)]
+        d = zones if isinstance(zones, PorousDesc) else (porous_desc(zones) if zones else None)
+        _check(f(self._h, C.byref(d) if d is not None else None))
+
+    def porous_stats(self):
+        """[dict(cells, volume, void_volume, force [3])] per zone from the current U (and alpha): force_q = S a V C_q(U) U_q per unit density.  Waits for the device"""
+        f = getattr(lib(), f"{self._AVG_PREFIX}_get_porous_stats")
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _dp, _dp, _dp]
+        n = C.c_int32(0); cnt = (C.c_int64 * POROUS_MAX_ZONES)()
+        vol = np.zeros(POROUS_MAX_ZONES); void = np.zeros(POROUS_MAX_ZONES); force = np.zeros((POROUS_MAX_ZONES, 3))
+        _check(f(self._h, C.byref(n), cnt, _d(vol), _d(void), _d(force)))
+        return [dict(cells=int(cnt[z]), volume=float(vol[z]), void_volume=float(void[z]), force=force[z].copy()) for z in range(n.value)]
+
+
 class _ParticleHeat:
     """particle batches and the heat exchange's particle side on a solver object (Solver: fy_solver_*, LduSolver: fy_ldu_solver_*); the object has _h, _cpl, _batch_n"""
     _AVG_PREFIX = "fy_solver"
@@ -1043,7 +1100,7 @@ def make_case(solver, nx, ny, nz, dx, dt, nu, rho_f=1000.0, rho_p=2650.0, g=(0, 
     return c
 
 
-class Solver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
+class Solver(_Averages, _Monitors, _WallLoads, _Inlets, _Porous, _ParticleHeat):
     """the icoFoamYade / pimpleFoamYade executables' time loop (icoFoamYade.C:65-149, pimpleFoamYade.C:60-114): step() is one
     pass of the loop body, including yadeCoupling.setParticleAction and setSourceZero."""
 
@@ -1065,6 +1122,32 @@ class Solver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
         self._cpl = C.c_void_p(lib().fy_solver_coupling(self._h))
         self.device = int(device)
         self._batch_n = []
+
+    @classmethod
+    def from_foam_case(cls, fc, device=0, transport=None):
+        """the single-domain solver of a case directory opened with FoamCase (fy_foam_case_make_solver: Solver(fc.case) with the porousZones of
+        constant/couplingProperties applied), started from its start-time fields as LduSolver.from_foam_case is"""
+        L = lib()
+        L.fy_foam_case_make_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        self = cls.__new__(cls)
+        self.case, self._h, self._keep = fc.case, C.c_void_p(), (fc, transport)
+        _check(L.fy_foam_case_make_solver(fc._h, C.byref(transport) if transport is not None else None, int(device), C.byref(self._h)))
+        self.n_slabs, self.rank, self.nz_local = 1, 0, fc.case.nz
+        self.n_cells = fc.case.nx * fc.case.ny * fc.case.nz
+        self._cpl = C.c_void_p(L.fy_solver_coupling(self._h))
+        self.device = int(device)
+        self._batch_n = []
+        U, p = fc.initial_fields()
+        self.set("U", U); self.set("p", p)
+        if fc.case.turbulence_model != 0:
+            self.set("nut", fc.initial_nut())
+        if fc.case.turbulence_model in (TURBULENCE_KEQN, TURBULENCE_KEPSILON):
+            self.set("k", fc.initial_k())
+        if fc.case.turbulence_model == TURBULENCE_KEPSILON:
+            self.set("epsilon", fc.initial_epsilon())
+        if fc.case.thermal.on:
+            self.set("T", fc.initial_T())
+        return self
 
     def _size(self, name):
         cnt = C.c_int64(0)
@@ -1205,6 +1288,7 @@ class Solver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
         return ms.value
 
     def enable_kernel_timing(self, on=True):
+        """on = 2: also the "mom_assemble" clock (an event pair around the momentum assembly sweep, which idles the stream for some microseconds)"""
         _check(lib().fy_solver_enable_kernel_timing(self._h, int(on)))
 
     def kernel_timing(self, name):
@@ -1421,6 +1505,16 @@ class FoamCase:
 
     def write(self, solver, time_name):
         _check(lib().fy_foam_case_write_time(self._h, solver._h, str(time_name).encode()))
+
+    def porous_zones(self):
+        """the active porousZones of constant/couplingProperties as set_porous_zones takes them: [dict(name, cells, d, f)], cells = the solver cell labels whose
+        centre lies in the zone's closed box (fy_foam_case_porous_zones); Solver.from_foam_case / LduSolver.from_foam_case apply them"""
+        L = lib()
+        L.fy_foam_case_porous_zones.argtypes = [C.c_void_p, C.POINTER(PorousDesc)]
+        d = PorousDesc()
+        _check(L.fy_foam_case_porous_zones(self._h, C.byref(d)))
+        return [dict(name=d.zones[z].name.decode(), cells=np.ctypeslib.as_array(d.zones[z].cells, shape=(d.zones[z].n_cells,)).astype(np.int32), d=tuple(d.zones[z].d),
+                     f=tuple(d.zones[z].f)) for z in range(d.n_zones)]
 
     _WRITE_MONITORS = "fy_foam_case_write_monitors"
 
@@ -1646,7 +1740,7 @@ class VirtualSlabs:
         self.solvers, self.comms = [], []
 
 
-class LduSolver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
+class LduSolver(_Averages, _Monitors, _WallLoads, _Inlets, _Porous, _ParticleHeat):
     """icoFoamYade's loop body on a general polyhedral mesh in OpenFOAM's addressing (fy_ldu_solver, include/foamyade_hip.h).  mesh: dict with points (n,3),
     face_offsets, face_points, owner, neighbour, n_cells, patch_start, patch_size (tests/poly_meshes.py builds them); u_bc / p_bc / values per patch; the
     controls are fy_ldu_case's (defaults: the icoFoam cavity tutorial's)"""
@@ -1716,11 +1810,17 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
             self.case.inlets = k["inlets"]
         self._create(device, transport)
 
-    def _create(self, device, transport):
+    def _create(self, device, transport, foam_case=None):
+        """foam_case: the handle of a GeneralFoamCase -- fy_foam_case_make_ldu_solver: the same create from the case's own structs, and its porous zones applied"""
         L = lib()
         self._h = C.c_void_p()
         self._tr = transport
-        _check(L.fy_ldu_solver_create(C.byref(self.pm), C.byref(self.case), C.byref(transport) if transport is not None else None, int(device), C.byref(self._h)))
+        tr = C.byref(transport) if transport is not None else None
+        if foam_case is None:
+            _check(L.fy_ldu_solver_create(C.byref(self.pm), C.byref(self.case), tr, int(device), C.byref(self._h)))
+        else:
+            L.fy_foam_case_make_ldu_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+            _check(L.fy_foam_case_make_ldu_solver(foam_case, tr, int(device), C.byref(self._h)))
         self._cpl = C.c_void_p(L.fy_ldu_solver_coupling(self._h))
         self.n_cells = int(self.pm.n_cells)
         self._batch_n = [0]
@@ -1732,7 +1832,7 @@ class LduSolver(_Averages, _Monitors, _WallLoads, _Inlets, _ParticleHeat):
         cls._bind()
         self._keep = fc                    # (the structs point into the case object)
         self.pm, self.case = fc.pm, fc.ldu_case
-        self._create(device, transport)
+        self._create(device, transport, foam_case=fc._h)      # (with the porousZones of constant/couplingProperties)
         U, p = fc.initial_fields()
         self.set("U", U); self.set("p", p)
         if fc.ldu_case.turbulence_model != 0:

@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "foam_dict.hpp"
+#include "ldu.hpp"
 
 // a case's fields (the order of fy_case_desc's and fy_ldu_case's condition arrays); alpha is written only, it has no start-time file
 enum { F_U, F_P, F_NUT, F_K, F_EPS, F_ALPHA, F_T };      // (F_T: the temperature of a case with heatTransfer active)
@@ -76,6 +77,10 @@ struct fy_foam_case {
     std::vector<int32_t> g_patch_neighbour;      // per patch: its cyclic partner, or -1
     std::vector<std::string> g_patch_class;      // the boundary file's `type` per patch (wall | patch | symmetryPlane | symmetry | cyclic)
     fy_flow_control_desc flow{};                 // constant/couplingProperties meanVelocityForce (general cases only; fy_ldu_case.flow_control)
+    // constant/couplingProperties porousZones (block and general cases; fy_foam_case_porous_zones hands them out as a fy_porous_desc): the active zones in file order,
+    // the cells as solver cell labels -- those whose centre lies in the closed box (boxToCell)
+    struct PorousMeta { std::string name; double d[3] = {0, 0, 0}, f[3] = {0, 0, 0}, lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}; std::vector<int32_t> cells; };
+    std::vector<PorousMeta> porous;
     // controlDict functions: the fieldAverage object (desc.average carries its items in this order) and the names of the objects of other types
     struct AvgField { std::string file; int F; std::string solver_name; int ncomp; bool prime2; };      // F: F_U .. F_ALPHA, or -1 (uParticle, uSource: no start-time file)
     std::string avg_name;
@@ -1073,6 +1078,95 @@ int check_general_schemes(const fy_foam_case* c) {
 }
 
 
+// porousZones { <name> { type DarcyForchheimer; box (x0 y0 z0) (x1 y1 z1); d (dx dy dz); f (fx fy fz); active on; } ... } of constant/couplingProperties: the role of
+// the explicitPorositySource fvOption with a diagonal tensor in the global axes -- constant/fvOptions itself is not read, as the reference's solvers do not read it.
+// A cell belongs to a zone if its centre lies in the closed box [OF-6 boxToCell]; the centres are the solver's own (a block's from its origin and cell sizes, a
+// general mesh's from LduHostMesh::build).  Nothing of it is written to a time directory: a restart reads the same file
+int read_porous_zones(fy_foam_case* c, const FoamDict& d, const std::string& path) {
+    c->porous.clear();
+    if (!d.has("porousZones")) return FY_OK;
+    const char* accepted = "type, box, d, f, active";
+    const FoamDict* pz = d.subdict("porousZones");
+    if (!pz) return fail(FY_ERR_INVALID, "%s: porousZones must be a dictionary { <name> { %s } ... }", path.c_str(), accepted);
+    std::vector<double> ctr;                                       // [3 n] cell centres by solver cell label, formed for the first active zone
+    auto centres = [&]() -> int {
+        if (!ctr.empty()) return FY_OK;
+        if (c->general) {
+            fy_poly_mesh pm;
+            FY_TRY(fy_foam_case_poly_mesh(c, &pm));
+            fy::LduHostMesh hm;
+            FY_TRY(hm.build(&pm));
+            ctr = hm.C;
+            return FY_OK;
+        }
+        const fy_case_desc& cd = c->desc;
+        std::vector<double> x[3];
+        const int n[3] = {cd.nx, cd.ny, cd.nz};
+        for (int a = 0; a < 3; ++a) {
+            x[a].resize((size_t)n[a]);
+            double node = cd.origin[a];
+            for (int q = 0; q < n[a]; ++q) {
+                if (c->grading[a].empty()) x[a][(size_t)q] = cd.origin[a] + ((double)q + 0.5) * cd.dx;
+                else { x[a][(size_t)q] = node + 0.5 * c->grading[a][(size_t)q]; node += c->grading[a][(size_t)q]; }
+            }
+        }
+        ctr.resize(3 * (size_t)n[0] * n[1] * n[2]);
+        size_t l = 0;
+        for (int k = 0; k < n[2]; ++k) for (int j = 0; j < n[1]; ++j) for (int i = 0; i < n[0]; ++i, ++l) { ctr[3 * l] = x[0][(size_t)i]; ctr[3 * l + 1] = x[1][(size_t)j]; ctr[3 * l + 2] = x[2][(size_t)k]; }
+        return FY_OK;
+    };
+    std::vector<int> owner;                                        // per cell: 1 + the zone that took it
+    for (const std::string& name : pz->order) {
+        const FoamDict* z = pz->subdict(name);
+        if (!z) return fail(FY_ERR_INVALID, "%s: porousZones.%s must be a dictionary { %s }", path.c_str(), name.c_str(), accepted);
+        for (const std::string& k : z->order)
+            if (k != "type" && k != "box" && k != "d" && k != "f" && k != "active")
+                return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s.%s is not an entry this reader knows (%s; a zone is a box in the global axes)", path.c_str(), name.c_str(), k.c_str(), accepted);
+        std::string w;
+        if (!z->word("type", &w) || w != "DarcyForchheimer")
+            return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s.type %s; accepts DarcyForchheimer", path.c_str(), name.c_str(), w.empty() ? "(missing)" : w.c_str());
+        bool active = true;
+        if (z->has("active") && !z->boolean("active", &active)) { z->word("active", &w); return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s.active %s; accepts on | off", path.c_str(), name.c_str(), w.c_str()); }
+        fy_foam_case::PorousMeta m;
+        m.name = name;
+        const std::vector<std::string>* t = z->tokens("box");
+        bool ok = t && t->size() == 10 && (*t)[0] == "(" && (*t)[4] == ")" && (*t)[5] == "(" && (*t)[9] == ")";
+        for (int a = 0; ok && a < 3; ++a) {
+            char *e0 = nullptr, *e1 = nullptr;
+            m.lo[a] = std::strtod((*t)[(size_t)(1 + a)].c_str(), &e0); m.hi[a] = std::strtod((*t)[(size_t)(6 + a)].c_str(), &e1);
+            ok = *e0 == 0 && *e1 == 0 && std::isfinite(m.lo[a]) && std::isfinite(m.hi[a]);
+        }
+        if (!ok) return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s.box is missing or not two points; accepts (x0 y0 z0) (x1 y1 z1)", path.c_str(), name.c_str());
+        for (const char* key : {"d", "f"}) {
+            double* v = key[0] == 'd' ? m.d : m.f;
+            if (!z->vector3(key, v)) return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s.%s is missing or not a vector; accepts (x y z), per global axis, in %s", path.c_str(), name.c_str(), key, key[0] == 'd' ? "1/m^2" : "1/m");
+            for (int a = 0; a < 3; ++a)
+                if (!std::isfinite(v[a]) || v[a] < 0) return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s.%s has a negative or non-finite component %g; accepts values >= 0", path.c_str(), name.c_str(), key, v[a]);
+        }
+        if (!active) continue;
+        if (c->proc_count > 0)
+            return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s: porous zones are not available on z-slabs (a decomposed case, -parallel); accepts active off", path.c_str(), name.c_str());
+        if (c->porous.size() == FY_POROUS_MAX_ZONES) return fail(FY_ERR_UNSUPPORTED, "%s: porousZones holds more than %d active zones (FY_POROUS_MAX_ZONES)", path.c_str(), FY_POROUS_MAX_ZONES);
+        if (name.size() > 31) return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s: a zone's name has at most 31 characters", path.c_str(), name.c_str());
+        FY_TRY(centres());
+        const size_t n = ctr.size() / 3;
+        owner.resize(n, 0);
+        for (size_t l = 0; l < n; ++l) {
+            bool in = true;
+            for (int a = 0; a < 3; ++a) in = in && ctr[3 * l + (size_t)a] >= m.lo[a] && ctr[3 * l + (size_t)a] <= m.hi[a];
+            if (!in) continue;
+            if (owner[l]) return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s and porousZones.%s overlap (cell %zu lies in both boxes); accepts boxes that share no cell centre", path.c_str(),
+                                      c->porous[(size_t)owner[l] - 1].name.c_str(), name.c_str(), l);
+            owner[l] = (int)c->porous.size() + 1;
+            m.cells.push_back((int32_t)l);
+        }
+        if (m.cells.empty()) return fail(FY_ERR_UNSUPPORTED, "%s: porousZones.%s.box (%g %g %g) (%g %g %g) selects no cell (a cell belongs to the zone if its centre lies in the closed box)", path.c_str(), name.c_str(),
+                                         m.lo[0], m.lo[1], m.lo[2], m.hi[0], m.hi[1], m.hi[2]);
+        c->porous.push_back(std::move(m));
+    }
+    return FY_OK;
+}
+
 // constant/couplingProperties (optional; not a file of the reference, whose closures are fixed in FoamYade.C): the drag closure and the opt-in force
 // models of the case's coupling object -- fy_set_drag_law / fy_set_force_models, applied when a solver is made from the case.  One reader for block and
 // general cases; a missing file or entry leaves the reference's behaviour, a word the case's solver cannot take is refused here
@@ -1203,6 +1297,7 @@ int read_coupling_properties(fy_foam_case* c) {
             f.on = 1;
         }
     }
+    FY_TRY(read_porous_zones(c, d, path));
     return FY_OK;
 }
 
@@ -2587,6 +2682,46 @@ int fy_foam_case_write_wall_loads_ldu(const fy_foam_case* c, fy_ldu_solver* s) {
     if (!c->general) return fail(FY_ERR_INVALID, "fy_foam_case_write_wall_loads_ldu: the case was opened as a block (fy_foam_case_write_wall_loads)");
     return write_wall_loads(c, [s](int q, int32_t* nv) { return fy_ldu_solver_wall_loads_layout(s, q, nv, nullptr, 0); },
                             [s](int q, int64_t first, int64_t mx, double* t, double* v, int64_t* n) { return fy_ldu_solver_get_wall_load_rows(s, q, first, mx, t, v, n); });
+}
+
+int fy_foam_case_porous_zones(const fy_foam_case* c, fy_porous_desc* out) {
+    if (!c || !out) return fail(FY_ERR_INVALID, "fy_foam_case_porous_zones: null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->n_zones = (int32_t)c->porous.size();
+    for (size_t z = 0; z < c->porous.size(); ++z) {
+        const fy_foam_case::PorousMeta& m = c->porous[z];
+        fy_porous_zone& Z = out->zones[z];
+        std::snprintf(Z.name, sizeof(Z.name), "%s", m.name.c_str());
+        for (int a = 0; a < 3; ++a) { Z.d[a] = m.d[a]; Z.f[a] = m.f[a]; }
+        Z.n_cells = (int32_t)m.cells.size(); Z.cells = m.cells.data();
+    }
+    return FY_OK;
+}
+
+int fy_foam_case_make_solver(const fy_foam_case* c, const fy_transport* tr, int device_ordinal, fy_solver** out) {
+    if (!c || !out) return fail(FY_ERR_INVALID, "fy_foam_case_make_solver: null argument");
+    fy_case_desc cd;
+    fy_porous_desc pz;
+    FY_TRY(fy_foam_case_desc(c, &cd));
+    FY_TRY(fy_foam_case_porous_zones(c, &pz));
+    FY_TRY(fy_solver_create(&cd, tr, device_ordinal, out));
+    const int rc = pz.n_zones ? fy_solver_set_porous_zones(*out, &pz) : FY_OK;
+    if (rc != FY_OK) { fy_solver_destroy(*out); *out = nullptr; }
+    return rc;
+}
+
+int fy_foam_case_make_ldu_solver(const fy_foam_case* c, const fy_transport* tr, int device_ordinal, fy_ldu_solver** out) {
+    if (!c || !out) return fail(FY_ERR_INVALID, "fy_foam_case_make_ldu_solver: null argument");
+    fy_poly_mesh pm;
+    fy_ldu_case lc;
+    fy_porous_desc pz;
+    FY_TRY(fy_foam_case_poly_mesh(c, &pm));
+    FY_TRY(fy_foam_case_ldu_desc(c, &lc));
+    FY_TRY(fy_foam_case_porous_zones(c, &pz));
+    FY_TRY(fy_ldu_solver_create(&pm, &lc, tr, device_ordinal, out));
+    const int rc = pz.n_zones ? fy_ldu_solver_set_porous_zones(*out, &pz) : FY_OK;
+    if (rc != FY_OK) { fy_ldu_solver_destroy(*out); *out = nullptr; }
+    return rc;
 }
 
 int fy_foam_case_close(fy_foam_case* c) {

@@ -77,6 +77,15 @@ static void print_functions(const fy_foam_case* fc, const fy_average_desc& av, c
     }
 }
 
+// constant/couplingProperties porousZones: one line per zone
+static void print_porous(const fy_foam_case* fc) {
+    fy_porous_desc pz;
+    if (fy_foam_case_porous_zones(fc, &pz) != FY_OK) return;
+    for (int z = 0; z < pz.n_zones; ++z)
+        std::printf("Porous zone %.32s: DarcyForchheimer, %d cells, d (%g %g %g), f (%g %g %g)\n", pz.zones[z].name, pz.zones[z].n_cells, pz.zones[z].d[0], pz.zones[z].d[1],
+                    pz.zones[z].d[2], pz.zones[z].f[0], pz.zones[z].f[1], pz.zones[z].f[2]);
+}
+
 // icoFoamYade on a general mesh: the same loop around fy_ldu_solver (one domain)
 static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     fy_poly_mesh pm;
@@ -89,8 +98,12 @@ static int run_general(fy_foam_case* fc, const fy_transport* trp, int device) {
     if (lc.flow_control.on)
         std::printf("meanVelocityForce: Ubar (%g %g %g), relaxation %g, superficial %s, initial pressure gradient = %.17g\n", lc.flow_control.ubar[0], lc.flow_control.ubar[1], lc.flow_control.ubar[2],
                     lc.flow_control.relaxation, lc.flow_control.superficial ? "on" : "off", lc.flow_control.gradient0);
+    print_porous(fc);
     fy_ldu_solver* s = nullptr;
+    fy_porous_desc pz;
+    if (fy_foam_case_porous_zones(fc, &pz) != FY_OK) return die("reading the porous zones");
     if (fy_ldu_solver_create(&pm, &lc, trp, device, &s) != FY_OK) return die("fy_ldu_solver_create");
+    if (pz.n_zones && fy_ldu_solver_set_porous_zones(s, &pz) != FY_OK) return die("fy_ldu_solver_set_porous_zones");      // (what fy_foam_case_make_ldu_solver does)
     fy_ldu_solver_hold_sources(s, 1);                   // runTime.write() comes before setSourceZero (icoFoamYade.C:142-147, pimpleFoamYade.C:107-109)
     {
         std::vector<double> U(3 * (size_t)info.n_cells), p((size_t)info.n_cells);
@@ -254,7 +267,11 @@ int main(int argc, char** argv) {
                     cd.thermal.particle_cp, cd.thermal.beta, cd.thermal.T_ref, cd.thermal.T_convection_scheme == FY_CONVECTION_UPWIND ? "upwind" : "linear");
     fy_solver* s = nullptr;
     const bool wall_loads = fy_foam_case_wall_loads_count(fc) > 0;          // (one domain: a slab's create refuses them)
+    if (master) print_porous(fc);
+    fy_porous_desc pz;
+    if (fy_foam_case_porous_zones(fc, &pz) != FY_OK) return die("reading the porous zones");
     if ((comm ? fy_solver_create_slab(&cd, trp, device, comm, &s) : fy_solver_create(&cd, trp, device, &s)) != FY_OK) return die("fy_solver_create");
+    if (pz.n_zones && fy_solver_set_porous_zones(s, &pz) != FY_OK) return die("fy_solver_set_porous_zones");      // (what fy_foam_case_make_solver does; a slab solver refuses them by name)
     // a slab owns the z-planes [srank nz / ssize, (srank + 1) nz / ssize): a contiguous run of the block's cells, `first` cells in
     // (the field files hold the whole block, or -- processor directories -- exactly this rank's cells)
     const size_t n_own = (size_t)fy_solver_local_cells(s), first = info.field_cells == (int64_t)n_own ? 0 : (size_t)srank * n_own;

@@ -1165,7 +1165,7 @@ __global__ __launch_bounds__(256) void k_assemble_momentum(FvGeo g, const double
                                                            const double* __restrict__ alpha, const double* __restrict__ alphaOld, CFace3 alphaf,
                                                            CFace3 phi, const double* __restrict__ uSource, const double* __restrict__ uSourceDrag,
                                                            const double* __restrict__ divG, const double* __restrict__ vGrad, Mom7 M,
-                                                           double* __restrict__ src, double* __restrict__ rAU) {
+                                                           double* __restrict__ src, double* __restrict__ rAU, const PorousDev* __restrict__ por) {
     const int t = fv_block(g, blockIdx.x, gridDim.x) * 256 + (int)threadIdx.x;
     if (t >= g.Nc) return;
     int i, j, k; ijk_of(g, t, i, j, k);
@@ -1259,7 +1259,10 @@ __global__ __launch_bounds__(256) void k_assemble_momentum(FvGeo g, const double
             // along, take part in the dominance test), source += (D_new - D_old) psi; no factor for the equation: relax() does nothing
             // (a slip patch's coefficient differs by component: relax() adds cmptMax(cmptMag(internalCoeffs)) before the test and takes
             // cmptMin (= 0) off afterwards -- all of it joins the test, the scalar diagonal keeps what the test gave)
-            const double dn = fmax(fabs(dg + ((bd[0] + bd[1]) + bd[2])), so) / g.u_relax;
+            // (a porous zone's coefficient joins the test with its component maximum, beside the boundary part as it stands)
+            double dt0 = dg + ((bd[0] + bd[1]) + bd[2]);
+            if (por) dt0 += porous_cell_max(por, c, nu, aP * V, U + 3 * (size_t)c);
+            const double dn = fmax(fabs(dt0), so) / g.u_relax;
             for (int q = 0; q < 3; ++q) s3[q] += (dn - dg) * U[3 * (size_t)c + q];
             dg = dn;
         }
@@ -1269,6 +1272,14 @@ __global__ __launch_bounds__(256) void k_assemble_momentum(FvGeo g, const double
     M.diag[c] = dg;
     for (int q = 0; q < 6; ++q) M.an[q][c] = an[q];
     for (int q = 0; q < 3; ++q) src[3 * (size_t)c + q] = s3[q];
+    // porous zones (porous.hpp; por null: none -- a kernel argument, uniform over the grid): the cell's zone from one byte, and in a zone's cells a V C_q(U) per
+    // component around the U the matrix is assembled with, on the per-component diagonal.  Formed here, after the row's stores (and once more inside the dominance
+    // test above, in zone cells only), so that no register carries it across the sweep; the zone map is read at the storage index (zones run on one domain: c0 = 0) and a V
+    // is formed from the aP the row already holds, so that no scalar register is kept for it either: with no zone the kernel keeps its occupancy
+    if (por) {
+        double pc[3];
+        if (porous_cell(por, c, nu, aP * V, U + 3 * (size_t)c, pc)) for (int q = 0; q < 3; ++q) bd[q] += pc[q];
+    }
     // 1 / UEqn.A(): fvMatrix::A() adds the COMPONENT AVERAGE of the boundary diagonal
     double bav = 0.0;
     if (M.bd) { for (int q = 0; q < 3; ++q) M.bd[3 * (size_t)c + q] = bd[q]; bav = ((bd[0] + bd[1]) + bd[2]) / 3.0; }
@@ -2099,11 +2110,11 @@ int launch_smagorinsky_nut(hipStream_t s, FvGeo g, const double* vGrad, double c
 
 int launch_assemble_momentum(hipStream_t s, FvGeo g, const double* U, const double* Uold, const double* alpha, const double* alphaOld,
                              CFace3 alphaf, CFace3 phi, const double* uSource, const double* uSourceDrag, const double* divG, const double* vGrad,
-                             Mom7 M, double* src, double* rAU) {
+                             Mom7 M, double* src, double* rAU, const PorousDev* por) {
     if (g.upwind >= 3) hipLaunchKernelGGL(k_assemble_momentum<true>, dim3(fv_grid(g)), dim3(256), 0, s, g, U, Uold, alpha, alphaOld, alphaf, phi, uSource,
-                                          uSourceDrag, divG, vGrad, M, src, rAU);
+                                          uSourceDrag, divG, vGrad, M, src, rAU, por);
     else hipLaunchKernelGGL(k_assemble_momentum<false>, dim3(fv_grid(g)), dim3(256), 0, s, g, U, Uold, alpha, alphaOld, alphaf, phi, uSource,
-                            uSourceDrag, divG, vGrad, M, src, rAU);
+                            uSourceDrag, divG, vGrad, M, src, rAU, por);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

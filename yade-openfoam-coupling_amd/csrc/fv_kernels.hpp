@@ -8,6 +8,7 @@
 
 #include "fv_linalg_kernels.hpp"
 #include "monitors.hpp"
+#include "porous.hpp"
 #include "wall_loads.hpp"
 
 namespace fy {

@@ -46,7 +46,8 @@ int launch_smagorinsky_nut(hipStream_t s, FvGeo g, const double* vGrad, double c
 // alphaf.a[0] == nullptr: alphacf is re-formed from alpha (no face array kept)
 int launch_assemble_momentum(hipStream_t s, FvGeo g, const double* U, const double* Uold, const double* alpha, const double* alphaOld,
                              CFace3 alphaf, CFace3 phi, const double* uSource, const double* uSourceDrag, const double* divG,
-                             const double* vGrad /* grad(U) of the current iterate: linearUpwind only */, Mom7 M, double* src, double* rAU);
+                             const double* vGrad /* grad(U) of the current iterate: linearUpwind only */, Mom7 M, double* src, double* rAU,
+                             const PorousDev* por /* porous zones (porous.hpp), or nullptr: none; needs M.bd */);
 // Gauss-linear gradient of magSqr(U) (three per cell): what the NVD / TVD limited schemes' gradient ratio r is formed from (passed to
 // launch_assemble_momentum in vGrad's place when g.upwind >= 3)
 int launch_grad_magsqr(hipStream_t s, FvGeo g, const double* U, double* gradL);

@@ -495,6 +495,34 @@ int Solver::set_wall_loads(const fy_wall_loads_desc* d) {
                         });
 }
 
+int Solver::set_porous_zones(const fy_porous_desc* d) {
+    FY_HIP(hipSetDevice(device));
+    const bool any = d && d->n_zones != 0;
+    if (any && comm->size > 1)
+        return fail(FY_ERR_UNSUPPORTED, "fy_solver_set_porous_zones: porous zones are not available on z-slabs (fy_solver_create_slab over %d ranks, foamYadeHip_mpi -parallel): "
+                                        "run the case on one domain", comm->size);
+    // V as geo_V forms it: dx^3 on the uniform block (FvGeo::V), (hx hy) hz on a graded one
+    if (any && g.c0 != 0) return fail(FY_ERR_UNSUPPORTED, "fy_solver_set_porous_zones: the block carries ghost planes (the assembly sweep reads the zone map at the storage index)");
+    // (the per-component diagonal first: a call that fails, here or in configure, leaves the solver as it was)
+    bool fresh = false;
+    if (any && !mbd.p) { FY_TRY(mbd.alloc_exact(3 * nstore)); fresh = true; const int zrc = zero(mbd); if (zrc != FY_OK) { mbd.release(); return zrc; } }
+    const int rc = por.configure(d, Nc, stream, "fy_solver_set_porous_zones", [this](int c) {
+        if (!g.graded) return g.V;
+        const int i = c % g.nx, j = (c / g.nx) % g.ny, k = c / (g.nx * g.ny);
+        return (h_host[0][(size_t)i] * h_host[1][(size_t)j]) * h_host[2][(size_t)k];
+    });
+    if (rc != FY_OK) { if (fresh) { FY_HIP(hipStreamSynchronize(stream)); mbd.release(); } return rc; }
+    if (fresh) mbd_porous = true;
+    if (!por.on() && mbd_porous) { mbd.release(); mbd_porous = false; }
+    hbya_ready = false;
+    return FY_OK;
+}
+
+int Solver::porous_stats(int32_t* nz, int64_t* cnt, double* volume, double* void_volume, double* force) {
+    FY_HIP(hipSetDevice(device));
+    return por.stats(stream, "fy_solver_get_porous_stats", g.nu, U.p + 3 * (size_t)g.c0, pimple ? alpha.p + g.c0 : nullptr, nz, cnt, volume, void_volume, force);
+}
+
 // fold the block partials, all-reduce over the slabs, read back
 int Solver::reduce_read(int nslots, bool courant, double* h) {
     if (cpl) FY_TRY(cpl->c.poll_results());
@@ -912,8 +940,10 @@ int Solver::step() {
             FY_TRY(FVK(launch_grad_magsqr, stream, g, U.p, gradL.p));
             FY_TRY(halo_cells(gradL, 3, 1));
         }
+        kc[KC_MOM_ASM].begin(stream);
         FY_TRY(FVK(launch_assemble_momentum, stream, g, U.p, Uold.p, alpha.p, /* alphaOld */ alpha.p, face_arrays ? C3(alphaf) : CFace3{}, phi_now(), usrc, uSourceDrag.p,
-                                        divG.p, g.upwind >= 3 ? gradL.p : vGrad.p, M7(), src.p, rAU.p));
+                                        divG.p, g.upwind >= 3 ? gradL.p : vGrad.p, M7(), src.p, rAU.p, por.dev()));
+        kc[KC_MOM_ASM].end(stream);
         rAU_new = true; hbya_ready = false;
         // pimple: rAUcf, phicForces and the predictor's right-hand side in one sweep (k_bmom_faces); uSource ghosts refreshed by the coupling
         const bool bmom_fused = pimple && cs.momentum_predictor && fused_corrector;
@@ -1058,8 +1088,14 @@ int Solver::field(const char* name, double** ptr, size_t* count) {
         *ptr = b.p;
         return FY_OK;
     }
+    if (por.on() && (s == "porousZone" || s == "mom_bd")) {       // read-only (fv_solver_api.cpp); unknown names without a zone
+        FY_HIP(hipSetDevice(device));
+        if (s == "porousZone") return por.zone_field(stream, Nc, ptr, count);
+        *ptr = mbd.p + 3 * (size_t)g.c0; *count = 3 * n;         // slip patches + zones, as the last assembly left it
+        return FY_OK;
+    }
     if (wl.lookup(s, ptr, count)) return FY_OK;                  // wallShearStress_boundary, yPlus_boundary as the last sample left them
-    if (s == "nut_boundary" || s == "nearWallDist") {            // formed on request: nut_boundary() / geo_ywall per boundary face (zeros when laminar)
+    if (s == "nut_boundary" || s == "nearWallDist") {           // formed on request: nut_boundary() / geo_ywall per boundary face (zeros when laminar)
         if (comm->size > 1) return fail(FY_ERR_UNSUPPORTED, "solver field '%s' is not available on z-slabs (fy_solver_create_slab over %d ranks)", s.c_str(), comm->size);
         const size_t nb = 2 * ((size_t)g.ny * g.nz + (size_t)g.nx * g.nz + (size_t)g.nx * g.ny);
         DevBuf<double>& b = s == "nut_boundary" ? bndNut : bndY;

@@ -133,7 +133,7 @@ struct Solver {
     KernelClock clk_mom, clk_pres;   // momentum / pressure phases: one event pair per outer iteration / corrector, read after the step's final
                                      // synchronisation (reading a phase time on the spot stalls the host until the phase has drained)
     bool timing = true;
-    enum { KC_MG_SMOOTH0 = 0, KC_P_APPLY_DOT, KC_MOM_PASS, KC_COUNT };
+    enum { KC_MG_SMOOTH0 = 0, KC_P_APPLY_DOT, KC_MOM_PASS, KC_MOM_ASM, KC_COUNT };      // KC_MOM_ASM: "mom_assemble", the momentum assembly sweep
     KernelClock kc[KC_COUNT];
 
     Face3 F3(DevBuf<double>* a) { Face3 f; for (int d = 0; d < 3; ++d) f.a[d] = a[d].p; return f; }
@@ -323,6 +323,12 @@ struct Solver {
     int balance_check(int inlet_sides, bool inlet_flux, bool* adjust) const;
     int set_inlets(const fy_inlets_desc* d, const char* who);
     int flux_of_U() { return FVK(launch_flux_of, stream, g, U.p, F3(phi)); }      // createPhi with the boundary values as they are now
+    // porous zones (porous.hpp; DESIGN.md section 3 "Porous zones"): the momentum assembly reads por.dev() (null: none); a solver with a zone holds mbd as one with a
+    // slip patch does (mbd_porous: allocated for the zones alone, freed with them).  Off: nothing allocated, nothing launched
+    Porous por;
+    bool mbd_porous = false;
+    int set_porous_zones(const fy_porous_desc* d);
+    int porous_stats(int32_t* nz, int64_t* cnt, double* volume, double* void_volume, double* force);
     Thermal th;
     int thermal_create(const fy_case_desc* c);          // validation + allocation, from create()
     int heat_coefficients();

@@ -139,6 +139,8 @@ int fy_solver_write_field_host(fy_solver* s, const char* name, const double* in)
     if (name && fy::SolidStats::is_name(name))
         return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (formed from the particles of the last coupling call)", name);
     // ("nut_boundary", "wallShearStress_boundary", "yPlus_boundary": the _boundary rule above)
+    if (name && (std::strcmp(name, "porousZone") == 0 || std::strcmp(name, "mom_bd") == 0))
+        return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: '%s' is read-only (porousZone follows from fy_solver_set_porous_zones; mom_bd is rebuilt at every momentum assembly)", name);
     if (name && std::strcmp(name, "nearWallDist") == 0) return fy::fail(FY_ERR_INVALID, "fy_solver_write_field_host: 'nearWallDist' is read-only (it follows from the mesh)");
     FY_HIP(hipSetDevice(s->s.device));
     FY_HIP(hipMemcpyAsync(p, in, n * sizeof(double), hipMemcpyHostToDevice, s->s.stream));
@@ -186,6 +188,11 @@ int fy_solver_get_monitor_rows(fy_solver* s, int object, int64_t first_row, int6
 
 int fy_solver_set_wall_loads(fy_solver* s, const fy_wall_loads_desc* d) { FY_S(s); return s->s.set_wall_loads(d); }
 int fy_solver_set_inlets(fy_solver* s, const fy_inlets_desc* d) { FY_S(s); return s->s.set_inlets(d, "fy_solver_set_inlets"); }
+int fy_solver_set_porous_zones(fy_solver* s, const fy_porous_desc* d) { FY_S(s); return s->s.set_porous_zones(d); }
+int fy_solver_get_porous_stats(fy_solver* s, int32_t* n_zones, int64_t* cells, double* volume, double* void_volume, double* force) {
+    FY_S(s);
+    return s->s.porous_stats(n_zones, cells, volume, void_volume, force);
+}
 int fy_solver_wall_loads_layout(fy_solver* s, int object, int32_t* n_values, char* labels, int cap) { FY_S(s); return s->s.wl.m.layout(object, n_values, labels, cap); }
 int fy_solver_get_wall_load_rows(fy_solver* s, int object, int64_t first_row, int64_t max_rows, double* times, double* values, int64_t* n_rows) {
     FY_S(s);
@@ -269,12 +276,14 @@ int fy_solver_time_p_apply(fy_solver* s, int reps, double* avg_ms) {
 int fy_solver_enable_kernel_timing(fy_solver* s, int on) {
     FY_S(s);
     for (auto& k : s->s.kc) { k.reset(); k.on = on != 0; }
+    s->s.kc[fy::Solver::KC_MOM_ASM].on = on == 2;      // (an event pair idles the stream for some microseconds: the assembly sweep's clock is asked for by itself)
     s->s.avg.clock.reset(); s->s.avg.clock.on = on != 0;
     s->s.mon.clock.reset(); s->s.mon.clock.on = on != 0;
     s->s.wl.m.clock.reset(); s->s.wl.m.clock.on = on != 0;
     s->s.inl.clock.reset(); s->s.inl.clock.on = on != 0;
     for (fy::KernelClock* k : {&s->s.th.clk_coeff, &s->s.th.clk_flux, &s->s.th.clk_asm, &s->s.th.clk_buoy}) { k->reset(); k->on = on != 0; k->per_collect = 64; }
     s->s.ss.clock.reset(); s->s.ss.clock.on = on != 0;
+    s->s.por.clock.reset(); s->s.por.clock.on = on != 0;
     return FY_OK;
 }
 
@@ -298,6 +307,7 @@ int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_
     if (k == "monitors" && total_ms && launches) { *total_ms = s->s.mon.clock.total_ms; *launches = s->s.mon.clock.launches; return FY_OK; }
     if (k == "inlets" && total_ms && launches && s->s.inl.on()) { *total_ms = s->s.inl.clock.total_ms; *launches = s->s.inl.clock.launches; return FY_OK; }
     if (k == "wall_loads" && total_ms && launches && s->s.wl.on()) { *total_ms = s->s.wl.m.clock.total_ms; *launches = s->s.wl.m.clock.launches; return FY_OK; }
+    if (k == "porous_force" && total_ms && launches) { *total_ms = s->s.por.clock.total_ms; *launches = s->s.por.clock.launches; return FY_OK; }      // (no zone: no launch)
     if (k == "solid_stats" && total_ms && launches) { *total_ms = s->s.ss.clock.total_ms; *launches = s->s.ss.clock.launches; return FY_OK; }
     if (k == "field_average" && total_ms && launches) { *total_ms = s->s.avg.clock.total_ms; *launches = s->s.avg.clock.launches; return FY_OK; }
     if ((k == "heat_coeff" || k == "heat_flux" || k == "T_assemble" || k == "buoyancy") && total_ms && launches) {
@@ -305,7 +315,7 @@ int fy_solver_get_kernel_timing(fy_solver* s, const char* kernel, double* total_
         *total_ms = c.total_ms; *launches = c.launches;
         return FY_OK;
     }
-    int idx = k == "mg_smooth_l0" ? fy::Solver::KC_MG_SMOOTH0 : k == "p_apply_dot" ? fy::Solver::KC_P_APPLY_DOT : k == "mom_pass" ? fy::Solver::KC_MOM_PASS : -1;
+    int idx = k == "mg_smooth_l0" ? fy::Solver::KC_MG_SMOOTH0 : k == "p_apply_dot" ? fy::Solver::KC_P_APPLY_DOT : k == "mom_pass" ? fy::Solver::KC_MOM_PASS : k == "mom_assemble" ? fy::Solver::KC_MOM_ASM : -1;
     if (idx < 0 || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s'", k.c_str());
     *total_ms = s->s.kc[idx].total_ms; *launches = s->s.kc[idx].launches;
     return FY_OK;

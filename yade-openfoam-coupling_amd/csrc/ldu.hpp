@@ -15,6 +15,7 @@
 #include "../../include/foamyade_hip.h"
 #include "common.hpp"
 #include "monitors.hpp"
+#include "porous.hpp"
 #include "wall_loads.hpp"
 
 namespace fy {
@@ -173,7 +174,7 @@ int launch_ldu_grad_scalar(hipStream_t s, LduGeo g, const double* p, double* gp)
 int launch_ldu_grad_magsqr(hipStream_t s, LduGeo g, const double* U, double* gradL);                    // fvc::grad(magSqr(U)), boundary value magSqr(U_b): the limiters' gradient
 // UEqn (icoFoamYade.C:79-85): face part (lower / upper, the explicit non-orthogonal flux of the laplacian), then the cell part (diag, b)
 int launch_ldu_assemble_momentum(hipStream_t s, LduGeo g, const double* phi, const double* Uold, const double* uSource, const double* gradU, LduMom M,
-                                 double* face_corr /* [3 nInt] scratch */);
+                                 double* face_corr /* [3 nInt] scratch */, const PorousDev* por /* porous zones (porous.hpp), or nullptr: none; needs M.bdiag */);
 // one Jacobi pass: xn = (b - V gradp - offdiag x) / diag and the L1 residual / normFactor sums of x (slots 0-2 |b - A x|, 3-5 normFactor terms)
 int launch_ldu_mom_pass(hipStream_t s, LduGeo g, LduMom M, const double* rhs /* M.b, or the predictor's full right-hand side */, const double* gradp /* or null */, const double* x, double* xn,
                         const double* xsum3, double* partials);
@@ -192,7 +193,7 @@ int launch_ldu_U_correct(hipStream_t s, LduGeo g, const double* HbyA, const doub
 int launch_ldu_alphaf(hipStream_t s, LduGeo g, const double* alpha, double* alphaf);
 int launch_ldu_pre_coupling(hipStream_t s, LduGeo g, const double* phi, const double* U, const double* vGrad, const double* alphaf, double* ddtU, double* divT);
 int launch_ldu_assemble_momentum_pimple(hipStream_t s, LduGeo g, LduPim P, const double* phi, const double* Uold, const double* U, const double* gradU, LduMom M, double* aphi /* [nF] scratch: alphaPhic */,
-                                        double* fstress /* [3 nF] */, double u_relax, double* rAU);
+                                        double* fstress /* [3 nF] */, double u_relax, double* rAU, const PorousDev* por /* as above */);
 int launch_ldu_smagorinsky_nut(hipStream_t s, LduGeo g, const double* vGrad, double ck, double ce, double delta_coeff, double* nut);
 // LES kEqn: the k equation's matrix into M (face part, then cells: diag, b[3 c] = the source, b[3 c + 1 .. 2] = 0), x3 = (k, 0, 0); after the solve bound() and nut
 int launch_ldu_grad_k(hipStream_t s, LduGeo g, LduPim P, LduKEqn K, double* gk);

@@ -280,7 +280,7 @@ __global__ __launch_bounds__(256) void k_ldu_mom_faces(LduGeo g, const double* _
 // ... cell part: EulerDdtScheme::fvmDdt, negSumDiag, the patches' coefficients (fixedValue: value* 0 / U_b, gradient* -+ deltaCoeffs; zeroGradient: value* 1),
 // == uSource, and the divergence of the explicit flux on the right-hand side
 __global__ __launch_bounds__(256) void k_ldu_mom_cells(LduGeo g, const double* __restrict__ phi, const double* __restrict__ Uold, const double* __restrict__ uSource, LduMom M,
-                                                       const double* __restrict__ corr) {
+                                                       const double* __restrict__ corr, const PorousDev* __restrict__ por) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= g.nCells) return;
     const double Vc = g.V[c], rdt = Vc / g.dt;
@@ -305,6 +305,16 @@ __global__ __launch_bounds__(256) void k_ldu_mom_cells(LduGeo g, const double* _
                     slip_face(g, f, g.nu * g.magSf[f] * g.dcNO[f], uo, bd, b, bmax, bmin, bc == FY_BC_U_PRESSURE_INLET_OUTLET, phi[f]);
                 dg += phi[f];
             }
+        }
+    }
+    // porous zones (porous.hpp; por null: none -- a kernel argument, uniform over the grid): V C_q(U) per component in a zone's cells, around the U the matrix is
+    // assembled with (= U.oldTime()); icoFoamYade has no void fraction (a = 1)
+    if (por) {
+        const int pz = por->zone_of[c];
+        if (pz) {
+            double pc[3];
+            porous_diag(por, pz - 1, g.nu, Vc, uo.x, uo.y, uo.z, pc);
+            bd[0] += pc[0]; bd[1] += pc[1]; bd[2] += pc[2];
         }
     }
     M.diag[c] = dg;
@@ -647,7 +657,7 @@ __global__ __launch_bounds__(256) void k_ldu_pmom_faces(LduGeo g, LduPim P, cons
 __global__ __launch_bounds__(256) void k_ldu_pmom_cells(LduGeo g, LduPim P, const double* __restrict__ phi, const double* __restrict__ alpha, const double* __restrict__ alphaOld,
                                                         const double* __restrict__ alphaf, const double* __restrict__ Uold, const double* __restrict__ U,
                                                         const double* __restrict__ uSourceDrag, LduMom M, const double* __restrict__ aphi, const double* __restrict__ fstress,
-                                                        double u_relax, double* __restrict__ rAU) {
+                                                        double u_relax, double* __restrict__ rAU, const PorousDev* __restrict__ por) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= g.nCells) return;
     const double Vc = g.V[c], rdt = Vc / g.dt;
@@ -683,12 +693,23 @@ __global__ __launch_bounds__(256) void k_ldu_pmom_cells(LduGeo g, LduPim P, cons
     const double S = (alpha[c] - alphaOld[c]) / g.dt + divAPhi / Vc;
     dg -= Vc * S;
     dg -= Vc * uSourceDrag[c];
+    // porous zones (porous.hpp; por null: none -- a kernel argument, uniform over the grid): alpha V C_q(U) per component in a zone's cells, around the U the matrix
+    // is assembled with; it joins the per-component diagonal after the dominance test, which takes its component maximum
+    int pz = 0;
+    double pc[3] = {0.0, 0.0, 0.0};
+    if (por) {
+        pz = por->zone_of[c];
+        if (pz) porous_diag(por, pz - 1, g.nu, alpha[c] * Vc, uc.x, uc.y, uc.z, pc);
+    }
     if (u_relax > 0) {
         // (a symmetry face's coefficient differs by component: relax() adds cmptMax(cmptMag(internalCoeffs)) before the dominance test and takes cmptMin off afterwards)
-        const double dn = fmax(fabs(dg + bmax), offsum) / u_relax - bmin;
+        double dt0 = dg + bmax;
+        if (pz) dt0 += fmax(pc[0], fmax(pc[1], pc[2]));
+        const double dn = fmax(fabs(dt0), offsum) / u_relax - bmin;
         b[0] += (dn - dg) * uc.x; b[1] += (dn - dg) * uc.y; b[2] += (dn - dg) * uc.z;
         dg = dn;
     }
+    if (pz) { bd[0] += pc[0]; bd[1] += pc[1]; bd[2] += pc[2]; }
     M.diag[c] = dg;
     st3(M.b, c, D3{b[0], b[1], b[2]});
     if (M.bdiag) st3(M.bdiag, c, D3{bd[0], bd[1], bd[2]});
@@ -1238,9 +1259,10 @@ int launch_ldu_grad_magsqr(hipStream_t s, LduGeo g, const double* U, double* gra
     FY_LAUNCH_CHECK();
     return FY_OK;
 }
-int launch_ldu_assemble_momentum(hipStream_t s, LduGeo g, const double* phi, const double* Uold, const double* uSource, const double* gradU, LduMom M, double* face_corr) {
+int launch_ldu_assemble_momentum(hipStream_t s, LduGeo g, const double* phi, const double* Uold, const double* uSource, const double* gradU, LduMom M, double* face_corr,
+                                 const PorousDev* por) {
     if (g.nInt > 0) hipLaunchKernelGGL(k_ldu_mom_faces, dim3(div_up(g.nInt, 256)), dim3(256), 0, s, g, phi, Uold, gradU, M, face_corr);      // (U has not been written since runTime++: the limiter sees the current field)
-    hipLaunchKernelGGL(k_ldu_mom_cells, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, phi, Uold, uSource, M, face_corr);
+    hipLaunchKernelGGL(k_ldu_mom_cells, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, phi, Uold, uSource, M, face_corr, por);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }
@@ -1303,9 +1325,9 @@ int launch_ldu_pre_coupling(hipStream_t s, LduGeo g, const double* phi, const do
     return FY_OK;
 }
 int launch_ldu_assemble_momentum_pimple(hipStream_t s, LduGeo g, LduPim P, const double* phi, const double* Uold, const double* U, const double* gradU, LduMom M, double* aphi /* [nF] scratch: alphaPhic */,
-                                        double* fstress, double u_relax, double* rAU) {
+                                        double* fstress, double u_relax, double* rAU, const PorousDev* por) {
     hipLaunchKernelGGL(k_ldu_pmom_faces, dim3(div_up(g.nFaces, 256)), dim3(256), 0, s, g, P, phi, U, P.alpha, P.alphaf, gradU, M, aphi, fstress);
-    hipLaunchKernelGGL(k_ldu_pmom_cells, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, P, phi, P.alpha, P.alphaOld, P.alphaf, Uold, U, P.uSourceDrag, M, aphi, fstress, u_relax, rAU);
+    hipLaunchKernelGGL(k_ldu_pmom_cells, dim3(div_up(g.nCells, 256)), dim3(256), 0, s, g, P, phi, P.alpha, P.alphaOld, P.alphaf, Uold, U, P.uSourceDrag, M, aphi, fstress, u_relax, rAU, por);
     FY_LAUNCH_CHECK();
     return FY_OK;
 }

@@ -163,6 +163,24 @@ struct LduSolver {
         return FY_OK;
     }
 
+    // porous zones (porous.hpp; DESIGN.md section 3 "Porous zones"): the two momentum assemblies read por.dev() (null: none); a solver with a zone holds mbdiag as one
+    // with a symmetry patch does (allocated for the zones alone without one, freed with them).  Off: nothing allocated, nothing launched
+    Porous por;
+    int set_porous_zones(const fy_porous_desc* d) {
+        FY_HIP(hipSetDevice(device));
+        // (the per-component diagonal first: a call that fails, here or in configure, leaves the solver as it was)
+        bool fresh = false;
+        if (d && d->n_zones != 0 && !mbdiag.p) { FY_TRY(mbdiag.alloc_exact(3 * (size_t)nc)); fresh = true; const int zrc = zero(mbdiag); if (zrc != FY_OK) { mbdiag.release(); return zrc; } }
+        const int rc = por.configure(d, nc, stream, "fy_ldu_solver_set_porous_zones", [this](int c) { return hm.V[(size_t)c]; });
+        if (rc != FY_OK) { if (fresh) { FY_HIP(hipStreamSynchronize(stream)); mbdiag.release(); } return rc; }
+        if (!por.on() && !has_slip) mbdiag.release();
+        return FY_OK;
+    }
+    int porous_stats(int32_t* nz, int64_t* cnt, double* volume, double* void_volume, double* force) {
+        FY_HIP(hipSetDevice(device));
+        return por.stats(stream, "fy_ldu_solver_get_porous_stats", g.nu, U.p, pimple ? alpha.p : nullptr, nz, cnt, volume, void_volume, force);
+    }
+
     // flow-rate control (fy_flow_control_desc; ldu_flow_control.hip; DESIGN.md section 3 "Flow-rate control").  Off: nothing allocated, nothing launched.  The host
     // keeps no value of the state: `cur` says which of the two records the step reads now, and flips at each momentum assembly
     struct Flow {
@@ -360,7 +378,7 @@ struct LduSolver {
         return FY_OK;
     }
     int zero(DevBuf<double>& b) { if (b.n) FY_HIP(hipMemsetAsync(b.p, 0, b.n * sizeof(double), stream)); return FY_OK; }
-    LduMom M() { return LduMom{mdiag.p, mlower.p, mupper.p, mb.p, has_slip ? mbdiag.p : nullptr}; }
+    LduMom M() { return LduMom{mdiag.p, mlower.p, mupper.p, mb.p, (has_slip || por.on()) ? mbdiag.p : nullptr}; }
 
     int create(const fy_poly_mesh* m, const fy_ldu_case* c, const fy_transport* tr, int dev) {
         th.part.who = "fy_ldu_solver"; th.part.desc = "fy_ldu_case";
@@ -788,7 +806,7 @@ struct LduSolver {
                 if (th.buoyant) FY_TRY(launch_buoyancy(stream, (size_t)nc, th.T.p, th.d.beta, th.d.T_ref, cs.g, uSource.p, th.buoy.p, th.usrc_sum.p));
             }
             if (g.gradL) FY_TRY(launch_ldu_grad_magsqr(stream, g, U.p, gradL.p));
-            FY_TRY(launch_ldu_assemble_momentum_pimple(stream, g, P(), phi.p, Uold.p, U.p, vGrad.p, M(), pt.p, fstress.p, u_relax_now, rAU.p));      // UcEqn.H:3-13
+            FY_TRY(launch_ldu_assemble_momentum_pimple(stream, g, P(), phi.p, Uold.p, U.p, vGrad.p, M(), pt.p, fstress.p, u_relax_now, rAU.p, por.dev()));      // UcEqn.H:3-13
             FY_TRY(launch_ldu_forces(stream, g, P(), rAU.p, rAUf.p, phiForces.p));                               // UcEqn.H:15-20
             if (cs.momentum_predictor) {                                                                          // UcEqn.H:22-33
                 // (first outer iteration: p and its patches' gradients stand as when the coupling's gradP was formed, pimpleFoamYade.C:74 -- the same field, not formed again)
@@ -868,7 +886,7 @@ struct LduSolver {
             if (ext_source || fc.on) { FY_TRY(launch_copy_f64(stream, uSourceSum.p, uSource.p, 3 * (size_t)nc)); FY_TRY(launch_add_f64(stream, uSourceSum.p, fc.on ? fc.usrc.p : uSourceExt.p, 3 * (size_t)nc)); src = uSourceSum.p; }
             if (th.buoyant) { FY_TRY(launch_buoyancy(stream, (size_t)nc, th.T.p, th.d.beta, th.d.T_ref, cs.g, src, th.buoy.p, th.usrc_sum.p)); src = th.usrc_sum.p; }
             if (g.gradL) FY_TRY(launch_ldu_grad_magsqr(stream, g, Uold.p, gradL.p));
-            FY_TRY(launch_ldu_assemble_momentum(stream, g, phi.p, Uold.p, src, vGrad.p, M(), fcorr.p));                // :79-85 (grad U of the iterate it is assembled from = vGrad)
+            FY_TRY(launch_ldu_assemble_momentum(stream, g, phi.p, Uold.p, src, vGrad.p, M(), fcorr.p, por.dev()));     // :79-85 (grad U of the iterate it is assembled from = vGrad)
             if (cs.momentum_predictor) {
                 FY_TRY(launch_ldu_grad_scalar(stream, g, p.p, gradp.p));
                 int it = 0;
@@ -949,6 +967,12 @@ struct LduSolver {
             if (!ob.f64.p) FY_TRY(ob.f64.alloc_exact(std::max<size_t>(*count, 1)));
             FY_TRY(launch_ldu_open_mask_f64(stream, nf - ni, ob.mask.p, ob.f64.p));
             *ptr = ob.f64.p;
+            return FY_OK;
+        }
+        if (por.on() && (s == "porousZone" || s == "mom_bd")) {                     // read-only; unknown names without a zone
+            FY_HIP(hipSetDevice(device));
+            if (s == "porousZone") return por.zone_field(stream, nc, ptr, count);
+            *ptr = mbdiag.p; *count = 3 * n;                                       // symmetry patches + zones, as the last assembly left it
             return FY_OK;
         }
         if (wl.lookup(s, ptr, count)) return FY_OK;                                // wallShearStress_boundary, yPlus_boundary as the last sample left them
@@ -1081,6 +1105,7 @@ int fy_ldu_solver_enable_kernel_timing(fy_ldu_solver* s, int on) {
     s->s.wl.m.clock.reset(); s->s.wl.m.clock.on = on != 0;
     s->s.inl.clock.reset(); s->s.inl.clock.on = on != 0;
     s->s.ob.clock.reset(); s->s.ob.clock.on = on != 0;
+    s->s.por.clock.reset(); s->s.por.clock.on = on != 0;
     return FY_OK;
 }
 int fy_ldu_solver_get_kernel_timing(fy_ldu_solver* s, const char* kernel, double* total_ms, int64_t* launches) {
@@ -1088,6 +1113,7 @@ int fy_ldu_solver_get_kernel_timing(fy_ldu_solver* s, const char* kernel, double
     const std::string k = kernel ? kernel : "";
     if (k == "wall_loads" && s->s.wl.on() && total_ms && launches) { *total_ms = s->s.wl.m.clock.total_ms; *launches = s->s.wl.m.clock.launches; return FY_OK; }
     if (k == "open_boundary" && total_ms && launches) { *total_ms = s->s.ob.clock.total_ms; *launches = s->s.ob.clock.launches; return FY_OK; }      // (no open patch: no launch)
+    if (k == "porous_force" && total_ms && launches) { *total_ms = s->s.por.clock.total_ms; *launches = s->s.por.clock.launches; return FY_OK; }      // (no zone: no launch)
     if (k == "inlets" && s->s.inl.on() && total_ms && launches) { *total_ms = s->s.inl.clock.total_ms; *launches = s->s.inl.clock.launches; return FY_OK; }
     const bool flow = k == "flow_control" && s->s.fc.on;
     if ((k != "solid_stats" && !flow) || !total_ms || !launches) return fy::fail(FY_ERR_INVALID, "unknown kernel clock '%s' (solid_stats, open_boundary%s%s%s)", k.c_str(), s->s.fc.on ? ", flow_control" : "", s->s.wl.on() ? ", wall_loads" : "", s->s.inl.on() ? ", inlets" : "");
@@ -1099,6 +1125,11 @@ int fy_ldu_solver_set_flow_control(fy_ldu_solver* s, const fy_flow_control_desc*
 int fy_ldu_solver_get_flow_control(fy_ldu_solver* s, double* gradient, double* ubar_uncorrected, double* rAU_ave, double* dGradP, int64_t* corrections) {
     FY_LS(s);
     return s->s.get_flow_control(gradient, ubar_uncorrected, rAU_ave, dGradP, corrections);
+}
+int fy_ldu_solver_set_porous_zones(fy_ldu_solver* s, const fy_porous_desc* d) { FY_LS(s); return s->s.set_porous_zones(d); }
+int fy_ldu_solver_get_porous_stats(fy_ldu_solver* s, int32_t* n_zones, int64_t* cells, double* volume, double* void_volume, double* force) {
+    FY_LS(s);
+    return s->s.porous_stats(n_zones, cells, volume, void_volume, force);
 }
 int fy_ldu_solver_get_open_boundary_stats(fy_ldu_solver* s, int64_t* inflow_faces, double* inflow_flux, double* outflow_flux) { FY_LS(s); return s->s.get_open_stats(inflow_faces, inflow_flux, outflow_flux); }
 int fy_ldu_solver_set_monitors(fy_ldu_solver* s, const fy_monitor_desc* d) { FY_LS(s); return s->s.set_monitors(d); }
