@@ -493,6 +493,9 @@ typedef struct fy_case_desc {
        divSchemes div(alphaPhic,k): k_convection_scheme FY_CONVECTION_LINEAR | _UPWIND; solvers.k: k_tol / k_rel_tol / k_max_iter;
        relaxationFactors equations k: k_relax (<= 0: none) */
     int32_t k_bc[6]; double k_value[6]; double k_initial;
+    /* k_convection_scheme and eps_convection_scheme (below) -- fy_case_defaults: FY_CONVECTION_UPWIND; fy_ldu_case_defaults: FY_CONVECTION_LINEAR.
+       THE TWO DEFAULTS DIFFER: a case that runs on both solvers, or is compared across them, names both schemes (on a side that carries a flux
+       the two schemes put k 6e-3 of its maximum apart within one step) */
     int32_t k_convection_scheme;
     double k_tol, k_rel_tol; int32_t k_max_iter;
     double k_relax;
@@ -503,7 +506,7 @@ typedef struct fy_case_desc {
        k uses the k_* fields above; epsilon its own.  Boundary types zeroGradient | fixedValue | FY_BC_WALL_FUNCTION (below) */
     double ras_cmu, ras_c1, ras_c2, ras_c3, ras_sigmak, ras_sigmaeps;   /* fy_case_defaults: 0.09, 1.44, 1.92, 0, 1, 1.3 */
     int32_t eps_bc[6]; double eps_value[6]; double eps_initial;
-    int32_t eps_convection_scheme;
+    int32_t eps_convection_scheme;               /* FY_CONVECTION_LINEAR | _UPWIND for div(alphaPhic,epsilon); default: see k_convection_scheme */
     double eps_tol, eps_rel_tol; int32_t eps_max_iter;
     double eps_relax;
     /* wall functions [OF-6 nutkWallFunction / epsilonWallFunction]: nut_w = nu (y+ kappa / ln(E y+) - 1) above yPlusLam, else 0, with
@@ -931,6 +934,8 @@ typedef struct fy_ldu_case {
     double k_initial;
     const int32_t* k_bc;             /* NULL: zeroGradient everywhere; FY_BC_NUT_INLET_OUTLET: k_value where the flux enters */
     const double* k_value;
+    /* k_convection_scheme and eps_convection_scheme (below) -- fy_case_defaults: FY_CONVECTION_UPWIND; fy_ldu_case_defaults: FY_CONVECTION_LINEAR.
+     * THE TWO DEFAULTS DIFFER: a case that runs on both solvers, or is compared across them, names both schemes */
     int32_t k_convection_scheme;
     double k_tol, k_rel_tol; int32_t k_max_iter;
     double k_relax;
@@ -942,10 +947,10 @@ typedef struct fy_ldu_case {
     double eps_initial;
     const int32_t* eps_bc;           /* NULL: zeroGradient everywhere; FY_BC_NUT_INLET_OUTLET: eps_value where the flux enters */
     const double* eps_value;
-    int32_t eps_convection_scheme;
+    int32_t eps_convection_scheme;   /* default: see k_convection_scheme */
     double eps_tol, eps_rel_tol; int32_t eps_max_iter;
     double eps_relax;
-    double wf_kappa, wf_E;           /* the wall functions' constants [OF-6 nutkWallFunction]; fy_ldu_case_defaults: 0.41, 9.8 */
+    double wf_kappa, wf_E;          /* the wall functions' constants [OF-6 nutkWallFunction]; fy_ldu_case_defaults: 0.41, 9.8 */
     int32_t drag_law;                /* constant/couplingProperties as in fy_case_desc: FY_DRAG_* and FY_FORCE_* flags, zero = the reference's behaviour */
     uint32_t force_models;
     fy_average_desc average;         /* controlDict functions: the fieldAverage object as in fy_case_desc (all zero: none), applied at fy_ldu_solver_create */

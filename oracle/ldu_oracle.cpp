@@ -67,9 +67,11 @@ extern "C" struct orc_ldu_case {
     // turbulence_model 2: LES kEqn -- the 0/k file (k_initial, per patch 0 zeroGradient / 1 fixedValue), div(alphaPhic,k) (0 linear, 1 upwind), solvers.k, relaxationFactors k;
     // nut_bc may then be 3 (calculated: Ck sqrt(k_b) delta once correctNut() has run, the file's value before)
     double k_initial; const int* k_bc; const double* k_value; int k_convection_scheme; double k_tol, k_rel_tol; int k_max_iter; double k_relax;
-    // turbulence_model 3: RAS kEpsilon (no wall functions on a general mesh) -- coefficients, the 0/epsilon file and its controls; k as above; nut_bc 3: Cmu k_b^2 / eps_b
+    // turbulence_model 3: RAS kEpsilon -- coefficients, the 0/epsilon file and its controls; k as above; nut_bc 3: Cmu k_b^2 / eps_b
     double ras_cmu, ras_c1, ras_c2, ras_c3, ras_sigmak, ras_sigmaeps;
     double eps_initial; const int* eps_bc; const double* eps_value; int eps_convection_scheme; double eps_tol, eps_rel_tol; int eps_max_iter; double eps_relax;
+    // wall functions as in fv_oracle.cpp: nut_bc 2 nutkWallFunction (kEqn / kEpsilon), eps_bc 2 epsilonWallFunction [OF-6]; kappa, E (Cmu = ras_cmu); y = nearWallDist
+    double wf_kappa, wf_E;
 };
 extern "C" struct orc_ldu_stats {
     double courant_mean, courant_max, cont_sum_local, cont_global, cont_cumulative;
@@ -163,12 +165,82 @@ struct Ldu {
     real kb_of(int pa, int c) const { return k_bc[pa] == 1 ? k_val[pa] : kturb[c]; }
     real les_delta(int c) const { return cs.les_delta_coeff * std::cbrt(V[c]); }
     // nut on boundary face f (patch pa, cell c): zeroGradient, fixedValue, or calculated [OF-6 GeometricField::operator=: nut_ = Ck sqrt(k_) delta assigns the patches too]
-    real nut_bnd(int pa, int c) const {
+    // ... or nutkWallFunction (2) [OF-6 nutkWallFunctionFvPatchScalarField::nut()], as fv_oracle.cpp's nut_boundary with the face's nearWallDist
+    real nut_bnd(int f) const {
         if (nut.empty()) return 0.0;
-        if (nut_bc[pa] == 1 || (nut_bc[pa] == 3 && !nut_live)) return nut_val[pa];
+        const int pa = patch_of[f - nInt], c = own[f];
+        if (nut_bc[pa] == 1 || ((nut_bc[pa] == 2 || nut_bc[pa] == 3) && !nut_live)) return nut_val[pa];
         if (nut_bc[pa] == 3 && cs.turbulence_model == 3) { const real kb = kb_of(pa, c); return cs.ras_cmu * (kb * kb) / eb_of(pa, c); }
         if (nut_bc[pa] == 3) return cs.les_ck * std::sqrt(kb_of(pa, c)) * les_delta(c);
+        if (nut_bc[pa] == 2) {
+            real ypl = 11.0;
+            for (int it = 0; it < 10; ++it) ypl = std::log(rmax(cs.wf_E * ypl, 1.0)) / cs.wf_kappa;
+            const real yPlus = std::pow((real)cs.ras_cmu, (real)0.25) * ywall[f - nInt] * std::sqrt(kturb[c]) / cs.nu;
+            return yPlus > ypl ? cs.nu * (yPlus * cs.wf_kappa / std::log(cs.wf_E * yPlus) - 1.0) : 0.0;
+        }
         return nut[c];
+    }
+    // ---- wall functions.  nearWallDist [OF-6 nearWallDist::correct -> cellDistFuncs::getPointNeighbours, smallestDist; face::nearestPointClassify]: y_f = min over the
+    // faces g of f's patch that share a point with f (f included) of |C_own(f) - nearest point of g|; a triangle is measured as itself, any other face as the fan of
+    // triangles (face centre, p_i, p_i+1)
+    vec ywall;                                         // per boundary face; 0 off the wall-function patches
+    std::vector<int> wall_faces_n;                     // per cell: its faces on epsilonWallFunction patches (kEpsilon)
+    static V3 nearest_on_triangle(V3 p, V3 a, V3 b, V3 c) {         // the Voronoi regions of the vertices, the edges and the interior
+        const V3 ab = b - a, ac = c - a, ap = p - a;
+        const real d1 = dot(ab, ap), d2 = dot(ac, ap);
+        if (d1 <= 0 && d2 <= 0) return a;
+        const V3 bp = p - b;
+        const real d3 = dot(ab, bp), d4 = dot(ac, bp);
+        if (d3 >= 0 && d4 <= d3) return b;
+        const real vc = d1 * d4 - d3 * d2;
+        if (vc <= 0 && d1 >= 0 && d3 <= 0) return a + (d1 / (d1 - d3)) * ab;
+        const V3 cp = p - c;
+        const real d5 = dot(ab, cp), d6 = dot(ac, cp);
+        if (d6 >= 0 && d5 <= d6) return c;
+        const real vb = d5 * d2 - d1 * d6;
+        if (vb <= 0 && d2 >= 0 && d6 <= 0) return a + (d2 / (d2 - d6)) * ac;
+        const real va = d3 * d6 - d5 * d4;
+        if (va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0) return b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) * (c - b);
+        const real r = 1.0 / (va + vb + vc);
+        return a + (vb * r) * ab + (vc * r) * ac;
+    }
+    void setup_wall_functions() {
+        ywall.assign(nFaces - nInt, 0.0);
+        wall_faces_n.assign(nCells, 0);
+        const bool keps = cs.turbulence_model == 3;
+        for (int pa = 0; pa < nPatches; ++pa) {
+            const bool wf_eps = keps && eps_bc[pa] == 2;
+            if (!(wf_eps || nut_bc[pa] == 2)) continue;
+            for (int f = pstart[pa]; f < pstart[pa] + psize[pa]; ++f) {
+                if (wf_eps) ++wall_faces_n[own[f]];
+                const V3 P = C[own[f]];
+                real best = 1e300;
+                for (int g = pstart[pa]; g < pstart[pa] + psize[pa]; ++g) {
+                    bool shares = false;
+                    for (int a = foff[f]; a < foff[f + 1] && !shares; ++a) for (int b = foff[g]; b < foff[g + 1]; ++b) if (fpts[a] == fpts[b]) { shares = true; break; }
+                    if (!shares) continue;
+                    const int* q = &fpts[foff[g]];
+                    const int n = foff[g + 1] - foff[g];
+                    if (n == 3) { best = rmin(best, mag(P - nearest_on_triangle(P, pts[q[0]], pts[q[1]], pts[q[2]]))); continue; }
+                    for (int a = 0; a < n; ++a) best = rmin(best, mag(P - nearest_on_triangle(P, pts[q[a]], pts[q[(a + 1) % n]], Cf[g])));
+                }
+                ywall[f - nInt] = best;
+            }
+        }
+    }
+    // epsilonWallFunction [OF-6 epsilonWallFunctionFvPatchScalarField::calculate]: what a cell with W faces on such patches has imposed on its epsilon, and its production
+    //   eps = (1/W) sum_f Cmu^3/4 k^3/2 / (kappa y_f),   G = (1/W) sum_f (nut_w + nu) |snGrad U| Cmu^1/4 sqrt(k) / (kappa y_f),   snGrad U = (U_b - U_P) deltaCoeffs
+    void wall_cell(int c, real& eps_w, real& G_w) const {
+        const real cmu75 = std::pow((real)cs.ras_cmu, (real)0.75), cmu25 = std::pow((real)cs.ras_cmu, (real)0.25), kc = kturb[c];
+        real se = 0.0, sg = 0.0;
+        for (int f : cfaces[c]) {
+            if (f < nInt || eps_bc[patch_of[f - nInt]] != 2) continue;
+            const real y = ywall[f - nInt];
+            const V3 d = dcNO[f] * (Ub(U, f) - at(U, c));
+            se += cmu75 * std::pow(kc, (real)1.5) / (cs.wf_kappa * y);
+            sg += (nut_bnd(f) + cs.nu) * mag(d) * cmu25 * std::sqrt(kc) / (cs.wf_kappa * y);
+        }
+        eps_w = se / (real)wall_faces_n[c]; G_w = sg / (real)wall_faces_n[c];
     }
     bool pimple = false;
     orc_ldu_stats st{};
@@ -314,6 +386,7 @@ struct Ldu {
                 kturb.assign(nc, cs.k_initial);
                 k_bc.assign(nPatches, 0); k_val.assign(nPatches, 0.0);
                 for (int pa = 0; pa < nPatches; ++pa) { if (cs.k_bc) k_bc[pa] = cs.k_bc[pa]; if (cs.k_value) k_val[pa] = cs.k_value[pa]; }
+                setup_wall_functions();
             }
             // fvc::reconstruct's tensor per cell: inv(sum_f Sf Sf / |Sf|) [OF-6 fvcReconstruct.C]
             vec T(9 * nc, 0.0);
@@ -441,7 +514,7 @@ struct Ldu {
         }
         for (int f = nInt; f < nFaces; ++f) {
             const int b = f - nInt, pa = patch_of[b], c = own[f];
-            const real nutb = nut_bnd(pa, c);
+            const real nutb = nut_bnd(f);
             const real g = (cs.nu + nutb) * magSf[f] * dcNO[f];        // (alphac's boundary value is 1)
             divAPhi[c] += phi[f];
             real t[3];
@@ -597,7 +670,9 @@ struct Ldu {
     //   mode 0 (kEqn, X = k):       Su = alpha G,           c1 = 2/3 alpha divU,           c2 = Ce alpha sqrt(k)/delta, DkEff = nut + nu
     //   mode 1 (kEpsilon, X = eps): Su = C1 alpha G eps/k,  c1 = (2/3 C1 - C3) alpha divU, c2 = C2 alpha eps/k,         DepsilonEff = nut/sigmaEps + nu
     //   mode 2 (kEpsilon, X = k):   Su = alpha G,           c1 = 2/3 alpha divU,           c2 = alpha eps/k,            DkEff = nut/sigmak + nu; then nut = Cmu k^2/eps
-    // (no wall functions on a general mesh: they need nearWallDist)
+    // epsilonWallFunction (eps_bc 2, kEpsilon): in the cells with such faces G is the wall function's in both equations, and the epsilon equation has their value
+    // imposed after relax() [OF-6 epsEqn.boundaryManipulate -> fvMatrix::setValues]: the row becomes diag x = diag eps_w and starts from eps_w, its off-diagonal
+    // coefficients go, and its neighbours' coefficients towards it move, times eps_w, to their sources.  Such a patch is never asked for a face value (zeroGradient)
     void turb_eqn(int mode) {
         const size_t nc = nCells;
         const real kMin = 1e-15;
@@ -633,7 +708,7 @@ struct Ldu {
             const int b = f - nInt, pa = patch_of[b], c = own[f];
             sumPhi[c] += phi[f];
             const real fl = alphaf[f] * phi[f];
-            if (xbc[pa] == 1) { const real gb = (cs.nu + nut_bnd(pa, c) / sigma) * magSf[f] * dcNO[f]; bint[b] += gb; bsrc[3 * (size_t)b] += (-fl + gb) * xval[pa]; }
+            if (xbc[pa] == 1) { const real gb = (cs.nu + nut_bnd(f) / sigma) * magSf[f] * dcNO[f]; bint[b] += gb; bsrc[3 * (size_t)b] += (-fl + gb) * xval[pa]; }
             else bint[b] += fl;
         }
         for (size_t c = 0; c < nc; ++c) {
@@ -641,7 +716,9 @@ struct Ldu {
             const real tr2 = 2.0 * (T[0] + T[4] + T[8]);
             real GG = 0.0;
             for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) GG += T[3 * a + b] * ((T[3 * a + b] + T[3 * b + a]) - (a == b ? (real(1) / 3) * tr2 : 0.0));
-            const real G = nut[c] * GG, divU = sumPhi[c] / V[c], xc = Xf[c], aP = alpha[c];
+            real G = nut[c] * GG;
+            const real divU = sumPhi[c] / V[c], xc = Xf[c], aP = alpha[c];
+            if (mode != 0 && wall_faces_n[c]) { real ew; wall_cell((int)c, ew, G); }
             real Su, c1, c2;
             if (mode == 0) { Su = aP * G; c1 = (real(2) / 3) * aP * divU; c2 = cs.les_ce * aP * std::sqrt(xc) / les_delta((int)c); }
             else if (mode == 1) { const real kc = kturb[c]; Su = cs.ras_c1 * aP * G * xc / kc; c1 = ((real(2) / 3) * cs.ras_c1 - cs.ras_c3) * aP * divU; c2 = cs.ras_c2 * aP * xc / kc; }
@@ -656,12 +733,27 @@ struct Ldu {
                 diag[c] += dn - dg;
             }
         }
+        vec x0 = Xf;
+        if (mode == 1) {
+            vec ew(nc, 0.0);
+            for (size_t c = 0; c < nc; ++c) if (wall_faces_n[c]) { real gw; wall_cell((int)c, ew[c], gw); }
+            for (int f = 0; f < nInt; ++f) {                      // (every row reads the assembled coefficients: they are zeroed below)
+                const int o = own[f], n = nei[f];
+                if (wall_faces_n[n] && !wall_faces_n[o]) src[3 * (size_t)o] -= upper[f] * ew[n];
+                if (wall_faces_n[o] && !wall_faces_n[n]) src[3 * (size_t)n] -= lower[f] * ew[o];
+            }
+            for (int f = 0; f < nInt; ++f) if (wall_faces_n[own[f]] || wall_faces_n[nei[f]]) { lower[f] = 0.0; upper[f] = 0.0; }
+            for (size_t c = 0; c < nc; ++c) if (wall_faces_n[c]) {
+                for (int f : cfaces[c]) if (f >= nInt) bsrc[3 * (size_t)(f - nInt)] = 0.0;
+                src[3 * c] = dgc((int)c) * ew[c]; x0[c] = ew[c];
+            }
+        }
         // the scalar equation through the three-component Jacobi solve (components 1 and 2 are 0 = 0: converged from the start)
         vec keepU = U;
         const bool slip = has_slip; has_slip = false;
         const real ut = cs.u_tol, ur = cs.u_rel_tol; const int um = cs.u_max_iter;
         if (mode == 1) { cs.u_tol = cs.eps_tol; cs.u_rel_tol = cs.eps_rel_tol; cs.u_max_iter = cs.eps_max_iter; } else { cs.u_tol = cs.k_tol; cs.u_rel_tol = cs.k_rel_tol; cs.u_max_iter = cs.k_max_iter; }
-        for (size_t c = 0; c < nc; ++c) { U[3 * c] = Xf[c]; U[3 * c + 1] = 0.0; U[3 * c + 2] = 0.0; }
+        for (size_t c = 0; c < nc; ++c) { U[3 * c] = x0[c]; U[3 * c + 1] = 0.0; U[3 * c + 2] = 0.0; }
         k_iters += solve_momentum(vec(3 * nc, 0.0));
         vec x(nc);
         for (size_t c = 0; c < nc; ++c) x[c] = U[3 * c];

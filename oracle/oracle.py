@@ -513,7 +513,7 @@ class LduCase(C.Structure):
                 ("k_initial", C.c_double), ("k_bc", _ip), ("k_value", _dp), ("k_convection_scheme", C.c_int), ("k_tol", C.c_double), ("k_rel_tol", C.c_double),
                 ("k_max_iter", C.c_int), ("k_relax", C.c_double), ("ras_cmu", C.c_double), ("ras_c1", C.c_double), ("ras_c2", C.c_double), ("ras_c3", C.c_double),
                 ("ras_sigmak", C.c_double), ("ras_sigmaeps", C.c_double), ("eps_initial", C.c_double), ("eps_bc", _ip), ("eps_value", _dp), ("eps_convection_scheme", C.c_int),
-                ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double), ("eps_max_iter", C.c_int), ("eps_relax", C.c_double)]
+                ("eps_tol", C.c_double), ("eps_rel_tol", C.c_double), ("eps_max_iter", C.c_int), ("eps_relax", C.c_double), ("wf_kappa", C.c_double), ("wf_E", C.c_double)]
 
 
 class LduStats(C.Structure):
@@ -577,7 +577,7 @@ class LduSolver:
                  adjust_time_step=0, max_co=1.0, max_delta_t=1e300, turbulence_model=0, les_ck=0.094, les_ce=1.048, les_delta_coeff=1.0, nut_initial=0.0,
                  nut_bc=None, nut_val=None, convection_scheme=0, convection_limiter_k=1.0, k_initial=0.0, k_bc=None, k_val=None, k_convection_scheme=0, k_tol=1e-6,
                  k_rel_tol=0.0, k_max_iter=1000, k_relax=0.0, ras_cmu=0.09, ras_c1=1.44, ras_c2=1.92, ras_c3=0.0, ras_sigmak=1.0, ras_sigmaeps=1.3, eps_initial=0.0,
-                 eps_bc=None, eps_val=None, eps_convection_scheme=0, eps_tol=1e-6, eps_rel_tol=0.0, eps_max_iter=1000, eps_relax=0.0, wide=False):
+                 eps_bc=None, eps_val=None, eps_convection_scheme=0, eps_tol=1e-6, eps_rel_tol=0.0, eps_max_iter=1000, eps_relax=0.0, wf_kappa=0.41, wf_E=9.8, wide=False):
         """solver = 1: pimpleFoamYade -- step(source, alpha, drag) then takes the void fraction and the implicit drag coefficient the coupling would leave.
         wide: the long-double build (fields cross the interface as doubles through get / set; view() is not available there)"""
         self.wide = bool(wide)
@@ -603,7 +603,7 @@ class LduSolver:
                             u_relax, u_relax_final, p_relax, p_relax_final, adjust_time_step, max_co, max_delta_t, turbulence_model, les_ck, les_ce,
                             les_delta_coeff, nut_initial, _i(k["nb"]), _d(k["nv"]), convection_scheme, convection_limiter_k, k_initial, _i(k["kb"]), _d(k["kv"]),
                             k_convection_scheme, k_tol, k_rel_tol, k_max_iter, k_relax, ras_cmu, ras_c1, ras_c2, ras_c3, ras_sigmak, ras_sigmaeps, eps_initial,
-                            _i(k["eb"]), _d(k["ev"]), eps_convection_scheme, eps_tol, eps_rel_tol, eps_max_iter, eps_relax)
+                            _i(k["eb"]), _d(k["ev"]), eps_convection_scheme, eps_tol, eps_rel_tol, eps_max_iter, eps_relax, wf_kappa, wf_E)
         self.pimple = solver == 1
         self.nc, self.nf, self.ni = int(mesh["n_cells"]), len(k["own"]), len(k["nei"])
         self.h = self.L.orc_ldu_create(k["points"].shape[0], _d(k["points"]), self.nf, self.ni, _i(k["foff"]), _i(k["fpts"]), _i(k["own"]), _i(k["nei"]),

@@ -142,6 +142,28 @@ add("pimple_kEqn_upwind", 1, CLOSURE, closed_box(), k_convection_scheme=1, **KEQ
 add("pimple_kEpsilon", 1, CLOSURE, closed_box(), **KEPS)
 add("pimple_kEpsilon_wall_functions", 1, CLOSURE, closed_box(), **dict(KEPS, **WALLS))
 add("pimple_graded_smagorinsky", 1, TILE_ODD, closed_box(), graded=True, turbulence_model=1, nut_initial=1e-5)
+# ---- closures on sides that carry a flux.  In a closed box the transport sweeps (k_assemble_turb / k_turb_finish, the oracle's turb_eqn) never see the boundary
+# convection term, the negative diagonal contribution of inflow through a zeroGradient patch (and fvMatrix::relax's dominance test with it), a divU in SuSp that
+# is not the pressure solve's residual, bound()'s face average at a fixed-value patch, or a wall-function cell beside an inlet.  Every case names its k (and
+# epsilon) scheme: fy_case_defaults says upwind, fy_ldu_case_defaults linear, and a case that leaves it open compares two different equations across solvers
+K_IN = dict(k_bc=[0, 0, 0, 0, 1, 0], k_value=[0, 0, 0, 0, 2e-4, 0])
+E_IN = dict(eps_bc=[0, 0, 0, 0, 1, 0], eps_value=[0, 0, 0, 0, 2e-3, 0])
+WALLS_C5 = dict(nut_bc=[2] * 4 + [0, 0], nut_value=[0.0] * 6, eps_bc=[2] * 4 + [1, 0], eps_value=[1e-3] * 4 + [2e-3, 0])       # wall-function sides, inlet, outlet
+add("pimple_c5_smagorinsky", 1, CLOSURE, c5_set(), turbulence_model=1, nut_initial=1e-5, les_ck=0.2)
+add("pimple_c5_kEqn_linear_k_inlet", 1, CLOSURE, c5_set(), k_convection_scheme=0, **KEQN, **K_IN)
+add("pimple_c5_kEqn_upwind_zeroGradient_relaxed", 1, CLOSURE, c5_set(), k_convection_scheme=1, k_relax=0.9, **KEQN)      # inflow through a zeroGradient k patch
+add("pimple_c5_kEqn_linear_zeroGradient_relaxed", 1, CLOSURE, c5_set(), k_convection_scheme=0, k_relax=0.8, **KEQN)
+add("pimple_c5_slip_kEqn_calculated_nut", 1, CLOSURE, c5_set(SLIP), k_convection_scheme=0, nut_bc=[3] * 6, nut_value=[2e-5] * 6, **KEQN, **K_IN)
+add("pimple_c5_kEpsilon_inlet", 1, CLOSURE, c5_set(), k_convection_scheme=1, eps_convection_scheme=0, eps_relax=0.8, **KEPS, **K_IN, **E_IN)
+add("pimple_c5_kEpsilon_wall_functions", 1, CLOSURE, c5_set(), k_convection_scheme=1, eps_convection_scheme=0, **KEPS, **K_IN, **WALLS_C5)
+# (with k = 1e-4 the walls' y+ = Cmu^1/4 y sqrt(k) / nu is 3.4: nut_w = 0, the laminar branch.  The same with k = 8e-3, y+ 30 above yPlusLam = 11.53: the logarithmic one)
+add("pimple_c5_kEpsilon_wall_functions_log_layer", 1, CLOSURE, c5_set(), k_convection_scheme=0, eps_convection_scheme=1, k_bc=K_IN["k_bc"], k_value=[0, 0, 0, 0, 8e-3, 0],
+    **dict(KEPS, k_initial=8e-3, eps_initial=0.2, nut_initial=3e-5), **dict(WALLS_C5, eps_value=[0.2] * 6))
+add("pimple_free_outlet_kEqn", 1, CLOSURE, dict(free_outlet(), g=(0, 0, -9.81)), k_convection_scheme=0, **KEQN)           # adjustPhi acts; the inlet's k is zeroGradient
+add("pimple_graded_c5_kEqn", 1, TILE_ODD, c5_set(), graded=True, k_convection_scheme=0, **KEQN, **K_IN)
+add("pimple_graded_c5_kEpsilon_wall_functions", 1, TILE_ODD, c5_set(), graded=True, k_convection_scheme=1, eps_convection_scheme=1, **KEPS, **K_IN, **WALLS_C5)
+# (two z-slabs, held to the single-domain reference: the inlet belongs to the first slab and the outlet to the last)
+add("pimple_c5_19x11x12_kEqn_slabs2", 1, (19, 11, 12), c5_set(), slabs=2, k_convection_scheme=0, **KEQN, **K_IN)
 # ---- driver branches
 for solver, tag, bcs in ((0, "ico_cavity", cavity()), (1, "pimple_box", closed_box())):
     for n_outer, n_corr, n_no in ((1, 1, 0), (1, 2, 0), (1, 3, 1), (2, 1, 0), (3, 2, 0)):

@@ -13,8 +13,9 @@ max |x - wide| / max |wide|.
 Each case is there for the branch of a kernel or of the driver that it reaches; `omit` lists the names a case leaves out, with the reason; `zero` the names
 that are identically zero on it.
 
-Not in this list, because oracle/ldu_oracle.cpp does not carry them: the T equation (tests/test_ldu_heat.py), meanVelocityForce (tests/test_flow_control.py),
-wall functions (tests/test_ldu_wall_functions.py) and the wall loads (tests/test_wall_loads.py).  They keep their own tests."""
+Not in this list, because oracle/ldu_oracle.cpp does not carry them: the T equation (tests/test_ldu_heat.py), meanVelocityForce (tests/test_flow_control.py)
+and the wall loads (tests/test_wall_loads.py).  They keep their own tests.  (Wall functions are carried -- nearWallDist, the wall cells' production and imposed
+epsilon: pimple_through_flow_kEpsilon_wall_functions; the case reader's rules for them stay in tests/test_ldu_wall_functions.py.)"""
 import numpy as np
 
 import golden_cases as gc
@@ -236,9 +237,25 @@ add("pimple_wavy_smagorinsky", 1, "wavy", closed_box(), turbulence_model=1, nut_
 add("pimple_wavy_kEqn_linear", 1, "wavy", closed_box(), k_convection_scheme=0, **KEQN, **CALCULATED)
 add("pimple_wavy_kEqn_upwind_relaxed", 1, "wavy", closed_box(), k_convection_scheme=1, k_relax=0.9, **KEQN, **CALCULATED)
 add("pimple_wavy_kEpsilon", 1, "wavy", closed_box(), k_convection_scheme=1, eps_convection_scheme=1, eps_relax=0.8, eps_bc=[0, 0, 1, 1, 0, 0], eps_val=[0, 0, 2e-3, 3e-3, 0, 0], **KEPS, **CALCULATED)
+# ---- closures on patches that carry a flux (fv_sweep_cases.py says what a closed box leaves out of the transport sweeps: the mode 0 / 1 / 2 path of
+# ldu_kernels.hip and ldu_solver.cpp, the oracle's turb_eqn).  IN_OUT patches: inlet, outlet, walls, sides.  Every case names its k (and epsilon) scheme
+TF = dict(through_flow(0.03), g=(0.0, 0.0, -9.81))
+K_IN = dict(k_bc=[1, 0, 0, 0], k_val=[2e-4, 0, 0, 0])
+E_IN = dict(eps_bc=[1, 0, 0, 0], eps_val=[2e-3, 0, 0, 0])
+add("pimple_through_flow_smagorinsky", 1, "wavy_in_out", TF, turbulence_model=1, nut_initial=1e-5, les_ck=0.2)
+add("pimple_through_flow_kEqn_linear_k_inlet", 1, "wavy_in_out", TF, k_convection_scheme=0, nut_bc=[3, 0, 3, 0], nut_val=[1e-5, 0, 1e-5, 0], **KEQN, **K_IN)
+add("pimple_through_flow_kEqn_upwind_zeroGradient_relaxed", 1, "wavy_in_out", TF, k_convection_scheme=1, k_relax=0.9, **KEQN)      # inflow through a zeroGradient k patch
+add("pimple_through_flow_kEqn_linear_zeroGradient_relaxed", 1, "wavy_in_out", TF, k_convection_scheme=0, k_relax=0.8, **KEQN)
+add("pimple_through_flow_kEpsilon", 1, "wavy_in_out", TF, k_convection_scheme=1, eps_convection_scheme=0, eps_relax=0.8, **KEPS, **K_IN, **E_IN)
+add("pimple_through_flow_kEpsilon_wall_functions", 1, "wavy_in_out", TF, k_convection_scheme=1, eps_convection_scheme=0, nut_bc=[0, 0, 2, 0], nut_val=[0.0] * 4,
+    eps_bc=[1, 0, 2, 0], eps_val=[2e-3, 0, 1e-3, 0], **KEPS, **K_IN)
+# (with k = 1e-4 the walls' y+ = Cmu^1/4 y sqrt(k) / nu is 3: nut_w = 0, the laminar branch.  The same with k = 8e-3, y+ 24 .. 27 above yPlusLam = 11.53: the logarithmic one)
+add("pimple_through_flow_kEpsilon_wall_functions_log_layer", 1, "wavy_in_out", TF, k_convection_scheme=0, eps_convection_scheme=1, nut_bc=[0, 0, 2, 0], nut_val=[0.0] * 4,
+    eps_bc=[1, 0, 2, 0], eps_val=[0.2, 0, 0.2, 0], k_bc=[1, 0, 0, 0], k_val=[8e-3, 0, 0, 0], **dict(KEPS, k_initial=8e-3, eps_initial=0.2, nut_initial=3e-5))
+add("pimple_free_outlet_kEqn", 1, "wavy_in_out", through_flow(0.03, fixed_outlet=False), k_convection_scheme=0, **KEQN)            # adjustPhi acts
 
 LAMINAR_SINGLE = [n for n, c in CASES.items() if not c["kw"].get("turbulence_model")]        # (the bit fixture's list)
-SENSITIVITY = ("ico_wavy", "pimple_tetrahedra", "pimple_wavy_kEqn_linear")
+SENSITIVITY = ("ico_wavy", "pimple_tetrahedra", "pimple_wavy_kEqn_linear", "pimple_through_flow_kEqn_linear_k_inlet")
 
 
 # ---- the two sides' solvers --------------------------------------------------------------------------------------------------------------------------

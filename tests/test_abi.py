@@ -72,6 +72,22 @@ def test_no_cpu_fallback_without_device(product):
     assert "error 2" in str(e.value)
 
 
+def test_the_two_defaults_of_the_closures_convection_schemes_differ_as_documented(product):
+    """fy_case_defaults (both solvers of the block) leaves div(alphaPhic,k) and div(alphaPhic,epsilon) at upwind, fy_ldu_case_defaults at linear, as
+    include/foamyade_hip.h says at both pairs of members: a comparison of the two solvers that names no scheme compares two different k equations
+    (the defaults fill a structure on the host: no device is needed)"""
+    for solver in (product.FY_SOLVER_ICO, product.FY_SOLVER_PIMPLE):
+        c = product.case_defaults(solver)
+        assert (c.k_convection_scheme, c.eps_convection_scheme) == (product.FY_CONVECTION_UPWIND, product.FY_CONVECTION_UPWIND)
+    product.LduSolver._bind()
+    g = product.LduCase()
+    product.lib().fy_ldu_case_defaults(ctypes.byref(g))
+    assert (g.k_convection_scheme, g.eps_convection_scheme) == (product.FY_CONVECTION_LINEAR, product.FY_CONVECTION_LINEAR)
+    assert (product.FY_CONVECTION_LINEAR, product.FY_CONVECTION_UPWIND) == (0, 1)
+    hdr = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "foamyade_hip.h")).read())
+    assert hdr.count("fy_case_defaults: FY_CONVECTION_UPWIND; fy_ldu_case_defaults: FY_CONVECTION_LINEAR") == 2      # stated at both structures
+
+
 def test_product_never_touches_the_oracle():
     pkg = os.path.join(ROOT, "yade-openfoam-coupling_amd")
     hits = subprocess.run(["grep", "-rIl", "-E", r"oracle/|liboracle|import oracle|from oracle", pkg, os.path.join(ROOT, "include")],

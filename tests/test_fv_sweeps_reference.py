@@ -6,7 +6,9 @@
   * the wide build (liboracle_ld.so) really computes with a 64-bit mantissa, and says so loudly where it does not;
   * with every count frozen both builds do the same number of iterations, and the double build stays within 1e-17 .. 1e-12 of the wide one in every field
     group over the whole case list (seeded random coupling fields) -- the window tests/test_fv_sweeps_parity.py relies on for its device bound of
-    50 x max(e_oracle, 2^-52).  Measured: DESIGN.md, parity section."""
+    50 x max(e_oracle, 2^-52);
+  * the other convection scheme of k on a side that carries a flux lands a factor 1e8 above that bound (the two solvers' defaults differ: a case names its scheme).
+Measured: DESIGN.md, parity section."""
 import json
 import os
 
@@ -16,7 +18,7 @@ import pytest
 import fv_sweep_cases as fc
 
 NAMES = list(fc.CASES)
-_runs = {}
+_runs, _env = {}, []
 
 
 def coupling_of(c):
@@ -74,13 +76,38 @@ def test_every_omission_carries_its_reason():
             assert nm in fc.GROUP_OF and len(why) > 10, (c["name"], nm)
 
 
+def envelope(oracle):
+    """e_oracle over the whole list, printed case by case; measured once"""
+    if not _env:
+        e = fc.Envelope()
+        for name in NAMES:
+            dbl, wide = both_builds(oracle, name)
+            for step in range(2):
+                w = e.add(name, step, fc.distances(fc.CASES[name], dbl[step], wide[step]))
+                print(f"{name:45s} step {step + 1}  " + "  ".join(f"{g} {w[g][0]:.2e} {w[g][1]}" for g in fc.GROUPS))
+        print(e.report())
+        _env.append(e)
+    return _env[0]
+
+
 def test_double_build_stays_within_rounding_of_the_wide_one(oracle):
     """e_oracle per group and step: the largest distance of the double build from the wide one over the whole case list"""
-    e = fc.Envelope()
-    for name in NAMES:
-        dbl, wide = both_builds(oracle, name)
-        for step in range(2):
-            w = e.add(name, step, fc.distances(fc.CASES[name], dbl[step], wide[step]))
-            print(f"{name:45s} step {step + 1}  " + "  ".join(f"{g} {w[g][0]:.2e} {w[g][1]}" for g in fc.GROUPS))
-    print(e.report())
-    e.check_window()
+    envelope(oracle).check_window()
+
+
+def test_the_other_k_scheme_lands_far_above_the_bound(oracle):
+    """the double build with upwind convection of k against the wide build with the case's linear one, on the through-flow with a k inlet: k leaves the bound the
+    device gets in its group by more than a factor 1000 (expected: 1e-3 or more against a bound near 1e-11) -- a solver that ran its own default instead of the
+    named scheme cannot pass the parity test"""
+    e = envelope(oracle)
+    name = "pimple_c5_kEqn_linear_k_inlet"
+    c = fc.CASES[name]
+    assert c["kw"]["k_convection_scheme"] == 0
+    other = dict(c, kw=dict(c["kw"], k_convection_scheme=1))
+    off = fc.run_oracle(oracle, other, coupling_of(c), wide=False)
+    _, wide = both_builds(oracle, name)
+    for step in range(2):
+        v = fc.distances(c, off[step], wide[step])[fc.GROUP_OF["k"]]["k"]
+        bound = e.bound(fc.GROUP_OF["k"], step)
+        print(f"{name} step {step + 1}: k {v:.2e}  bound {bound:.2e}")
+        assert v > 1000.0 * bound, (step, v, bound)

@@ -5,6 +5,7 @@ rebuilt before every step (held to a plain oracle run bit for bit in tests/test_
   1. the per-face path is the uniform path: the same bits as a plain uniform value, while the side's own u_value holds something else
   2. a jet profile scaled by a table that changes every step, against the reference: the general-mesh solver at tests/test_ldu_parity.py's bounds (U 2e-6, p 1e-5,
      phi 5e-6 of the field's maximum), the block solver on the lattice at the same bounds, block against general-mesh solver at 1e-7 / 1e-6
+     (and with kEqn, k too at 1e-7, once with each k scheme: the scheme is NAMED wherever the two solvers meet, their defaults differ)
   3. the value's timing: U_boundary after each step is the reference's value at start_time + sum dt to 1e-14, the flow-rate inlet's flux is -Q(t)
   4. refusals by name
 
@@ -171,8 +172,9 @@ VARIANTS = {
     "upwind": (dict(convection_scheme=1), dict(convection_scheme=1)),
     "no_predictor": (dict(momentum_predictor=0), dict(momentum_predictor=0)),
     "pimple_two_outer": (dict(solver=1, n_outer_correctors=2), dict(solver=1, n_outer=2)),
-    "kEqn": (dict(solver=1, turbulence_model=2, nut_initial=2e-5, les_delta_coeff=1.0, k_initial=2e-4, k_tol=1e-12),
-             dict(solver=1, turbulence_model=2, nut_initial=2e-5, les_delta_coeff=1.0, k_initial=2e-4, k_tol=1e-12)),
+    # (the k scheme is named on both sides: fy_case_defaults says upwind, fy_ldu_case_defaults and the oracle's LduSolver linear)
+    "kEqn": (dict(solver=1, turbulence_model=2, nut_initial=2e-5, les_delta_coeff=1.0, k_initial=2e-4, k_tol=1e-12, k_convection_scheme=0),
+             dict(solver=1, turbulence_model=2, nut_initial=2e-5, les_delta_coeff=1.0, k_initial=2e-4, k_tol=1e-12, k_convection_scheme=0)),
 }
 
 
@@ -221,11 +223,7 @@ def test_general_mesh_jet_with_a_table_matches_the_reference(product, oracle, ki
     h.close()
 
 
-# The kEqn variant runs on the general mesh only (above).  The block solver's k equation differs from the general-mesh solver's and the oracle's wherever a boundary
-# carries a flux, with or without inlets: on this lattice with a PLAIN uniform inlet and no inlet set, k differs by 6.1e-4 of its maximum after the first step and U by
-# 4.6e-6 after four (block against either of the other two, which agree to 2e-15); with the jet it is U 2.5e-6 against this file's 2e-6.  tests/test_ldu_parity.py holds
-# the two solvers' kEqn to each other in a closed box only.  The block's turbulence sweeps are held to the uniform path bit for bit instead (section 1)
-BLOCK_CASES = [("lattice", v) for v in VARIANTS if v != "kEqn"] + [("graded", "plain")]
+BLOCK_CASES = [("lattice", v) for v in VARIANTS] + [("graded", "plain")]
 
 
 @pytest.mark.parametrize("kind,variant", BLOCK_CASES)
@@ -254,6 +252,26 @@ def test_block_equals_the_general_mesh_solver_on_the_lattice(product):
         f.step(); g.step()
     close(g.get("U"), f.get("U"), 1e-7, "U"); close(g.get("p"), f.get("p"), 1e-6, "p")
     assert np.array_equal(zmin_of(mesh, g.get("U_boundary")), f.get("U_boundary").reshape(-1, 3)[Z0:Z0 + NX * NY])
+    f.close(); g.close()
+
+
+@pytest.mark.parametrize("scheme", [0, 1])
+def test_block_kEqn_equals_the_general_mesh_solver_on_the_lattice(product, scheme):
+    """both HIP solvers with LES kEqn, a plain uniform inlet and no inlet set, the k scheme named on both sides (0 linear, 1 upwind): k to 1e-7 of its maximum after
+    the first step and after four, U and p at the bounds of the test above.  Left to each side's default the two run different schemes and k differs by 6e-4 here"""
+    mesh = lattice_mesh()
+    kw = dict(VARIANTS["kEqn"][0], k_convection_scheme=scheme)
+    kw.pop("solver")
+    U0 = np.random.RandomState(3).rand(mesh["n_cells"], 3) * 0.05
+    f = product.Solver(block_case(product, 1, False, **kw))
+    g = product.LduSolver(mesh, DT, NU, U_BC, u_val(), P_BC, solver=1, **TOL, **kw)
+    f.set("U", U0); g.set("U", U0)
+    for step in range(4):
+        f.step(); g.step()
+        if step in (0, 3):
+            close(g.get("k"), f.get("k"), 1e-7, "k after step %d" % (step + 1))
+    close(g.get("U"), f.get("U"), 1e-7, "U"); close(g.get("p"), f.get("p"), 1e-6, "p")
+    assert not np.allclose(f.get("k"), 2e-4, rtol=1e-3) and np.abs(f.get("U")).max() > 0.1
     f.close(); g.close()
 
 

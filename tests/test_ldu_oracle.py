@@ -420,6 +420,101 @@ def test_les_kEqn_on_a_lattice_reproduces_the_structured_restatement(oracle, var
     f.close(); g.close()
 
 
+# ---- the closures on a through-flow: z- inlet fixedValue (0, 0, 0.3), z+ outlet zeroGradient with p = 0, walls on x and y.  In a closed box (the tests above and below)
+# turb_eqn never sees the boundary convection term, inflow through a zeroGradient patch (a negative diagonal contribution, and fvMatrix::relax's dominance test with
+# it), a divU that is more than the pressure solve's residual, bound()'s face average at a fixed-value patch.  The k / epsilon schemes are NAMED on both sides:
+# fv_case's default is upwind (1), LduSolver's linear (0)
+TF_DIMS, TF_H, TF_DT, TF_NU = (6, 5, 7), 0.01, 2e-3, 1e-5
+TF_K_IN, TF_E_IN = dict(k_bc=[0, 0, 0, 0, 1, 0], k_value=[0, 0, 0, 0, 5e-4, 0]), dict(eps_bc=[0, 0, 0, 0, 1, 0], eps_value=[0, 0, 0, 0, 3e-4, 0])
+TF_KEQN = dict(turbulence_model=2, nut_initial=3e-5, les_delta_coeff=0.8, k_initial=2e-4, k_tol=1e-13)
+TF_KEPS = dict(turbulence_model=3, nut_initial=3e-5, k_initial=2e-4, eps_initial=1.2e-4, k_tol=1e-13, eps_tol=1e-13)
+TF_WF = dict(k_initial=8e-3, eps_initial=0.2, nut_bc=[2] * 4 + [0, 0], nut_value=[3e-5] * 4 + [0, 0], k_bc=[0, 0, 0, 0, 1, 0], k_value=[0, 0, 0, 0, 8e-3, 0])
+THROUGH_FLOW = {
+    "kEqn_linear_zeroGradient": (dict(TF_KEQN, k_convection_scheme=0), False),
+    "kEqn_linear_k_inlet": (dict(TF_KEQN, k_convection_scheme=0, **TF_K_IN), False),
+    "kEqn_linear_k_inlet_relaxed": (dict(TF_KEQN, k_convection_scheme=0, k_relax=0.8, **TF_K_IN), False),
+    "kEqn_upwind_relaxed": (dict(TF_KEQN, k_convection_scheme=1, k_relax=0.8), False),
+    "kEpsilon_linear_linear_inlets": (dict(TF_KEPS, k_convection_scheme=0, eps_convection_scheme=0, **TF_K_IN, **TF_E_IN), False),
+    "kEpsilon_upwind_linear_relaxed": (dict(TF_KEPS, k_convection_scheme=1, eps_convection_scheme=0, k_relax=0.8, eps_relax=0.7), False),
+    "kEqn_linear_k_inlet_cloud": (dict(TF_KEQN, k_convection_scheme=0, **TF_K_IN), True),
+    "kEqn_upwind_zeroGradient_cloud": (dict(TF_KEQN, k_convection_scheme=1), True),
+    "kEpsilon_upwind_upwind_inlets_cloud": (dict(TF_KEPS, k_convection_scheme=1, eps_convection_scheme=1, **TF_K_IN, **TF_E_IN), True),
+    # wall functions on the four sides (nutkWallFunction, epsilonWallFunction), the wall cells of the first layer beside the inlet: what pins the general oracle's
+    # nearWallDist, wall-cell production and fvMatrix::setValues to the structured restatement's.  k is large enough for y+ = Cmu^1/4 y sqrt(k) / nu to lie above
+    # yPlusLam (11.53) in every wall cell: nut_w takes its logarithmic branch
+    "kEpsilon_wall_functions": (dict(TF_KEPS, **TF_WF, k_convection_scheme=1, eps_convection_scheme=0, eps_relax=0.8, eps_bc=[2] * 4 + [1, 0], eps_value=[0.2] * 6), False),
+    "kEpsilon_wall_functions_cloud": (dict(TF_KEPS, **TF_WF, k_convection_scheme=0, eps_convection_scheme=1, eps_bc=[2] * 4 + [1, 0], eps_value=[0.2] * 6), True),
+    "kEqn_wall_function_nut": (dict(TF_KEQN, **TF_WF, k_convection_scheme=0), False),
+}
+
+
+def through_flow_pair(kw):
+    """(fv_oracle, ldu_oracle, mesh) on the through-flow lattice; kw in fv_case's spelling, the general side's patch arrays renamed"""
+    nx, ny, nz = TF_DIMS
+    mesh = pm.hex_block(nx, ny, nz, (nx * TF_H, ny * TF_H, nz * TF_H))
+    tol = dict(p_tol=1e-13, p_rel_tol=0.0, p_final_tol=1e-13, p_final_rel_tol=0.0, u_tol=1e-13, p_max_iter=5000)
+    u_bc, p_bc, u_val = [0, 0, 0, 0, 0, 1], [0, 0, 0, 0, 0, 1], [(0, 0, 0)] * 4 + [(0, 0, 0.3), (0, 0, 0)]
+    gkw = {{"k_value": "k_val", "eps_value": "eps_val", "nut_value": "nut_val"}.get(k, k): v for k, v in kw.items()}
+    f = orc.FvSolver(orc.fv_case(1, nx, ny, nz, TF_H, TF_DT, TF_NU, u_bc=u_bc, u_val=u_val, p_bc=p_bc, p_solver=0, **kw, **tol))
+    g = orc.LduSolver(mesh, TF_DT, TF_NU, u_bc, u_val, p_bc, solver=1, **gkw, **tol)
+    return f, g, mesh
+
+
+def through_flow_cloud(rs, cloud):
+    """400 particles in the lower half of the box, down to the inlet's faces; or none"""
+    nx, ny, nz = TF_DIMS
+    rec = np.zeros((400 if cloud else 0, 10))
+    if cloud:
+        rec[:, 0:3] = rs.random_sample((400, 3)) * np.array([nx, ny, 0.5 * nz]) * TF_H
+        rec[:, 3:6] = 0.05 * rs.standard_normal((400, 3)); rec[:, 9] = 0.3 * TF_H
+    return rec
+
+
+@pytest.mark.parametrize("variant", list(THROUGH_FLOW))
+def test_closures_on_a_through_flow_reproduce_the_structured_restatement(oracle, variant):
+    """kEqn and kEpsilon with an inlet and an outlet, three steps, the general oracle against fv_oracle.cpp on the lattice: k, epsilon, nut, U and p to 1e-10 of the
+    structured side's maximum (measured: <= 1.9e-14, p <= 2.2e-13 through the pressure solve; the two restatements differ in summation order only, and a wrong
+    or differently chosen term shows at 1e-3).  With a cloud the general side takes the
+    void fraction, the drag coefficient and the source the structured side's coupling left, and a cell on the inlet carries particles"""
+    kw, cloud = THROUGH_FLOW[variant]
+    f, g, mesh = through_flow_pair(kw)
+    nx, ny, nz = TF_DIMS
+    rs = np.random.RandomState(17)
+    names = ["k", "nut", "U", "p"] + (["epsilon"] if kw["turbulence_model"] == 3 else [])
+    for step in range(3):
+        cap = {}
+        f.step(through_flow_cloud(rs, cloud), capture=cap)
+        g.step(source=cap["uSource"].reshape(-1, 3), alpha=cap["alpha"].ravel(), drag=cap["uSourceDrag"].ravel())
+        if cloud:
+            assert cap["alpha"].ravel()[:nx * ny].min() < 0.9
+        for nm in names:
+            a, b = f.get(nm).ravel(), pm.to_lattice(mesh, g.get(nm).reshape(nx * ny * nz, -1)).ravel()
+            err = np.abs(b - a).max() / np.abs(a).max()
+            print(variant, "step", step + 1, nm, err)
+            assert err < 1e-10, (nm, step, err)
+    assert not np.allclose(f.get("k"), kw["k_initial"], rtol=1e-3) and f.get("k").min() > 0 and np.abs(f.get("U")).max() > 0.1
+    if 2 in kw.get("nut_bc", []):                    # the wall function acts, in its logarithmic branch: y+ > yPlusLam with y = half a cell and the smallest k
+        y_plus = 0.09 ** 0.25 * (0.5 * TF_H) * np.sqrt(f.get("k").min()) / TF_NU
+        print(variant, "smallest y+", y_plus)
+        assert y_plus > 11.6
+    f.close(); g.close()
+
+
+def test_the_two_oracles_default_k_schemes_differ(oracle):
+    """why the scheme is named: fv_case leaves k_convection_scheme at upwind, LduSolver at linear, and the same kEqn through-flow then differs in k by more than 1e-4
+    of its maximum after the first step -- the size of the figure that was once read as a defect of the block solver's k equation on a side that carries a flux"""
+    f, g, mesh = through_flow_pair(dict(TF_KEQN))
+    cap = {}
+    f.step(np.zeros((0, 10)), capture=cap)
+    g.step(source=cap["uSource"].reshape(-1, 3), alpha=cap["alpha"].ravel(), drag=cap["uSourceDrag"].ravel())
+    kf, kg = f.get("k"), pm.to_lattice(mesh, g.get("k"))
+    err = np.abs(kg - kf).max() / kf.max()
+    print("k, each side's default scheme:", err)
+    assert err > 1e-4
+    assert f.case.k_convection_scheme == 1 and g.case.k_convection_scheme == 0
+    f.close(); g.close()
+
+
 def test_ras_kEpsilon_on_a_lattice_reproduces_the_structured_restatement(oracle):
     """RASModel kEpsilon (DPMTurbulenceModels.C:70-71) on the general mesh, without wall functions: the epsilon equation, then k with the new epsilon, nut = Cmu k^2 / epsilon,
     against fv_oracle.cpp's on the same block with a cloud and a moving wall -- non-default coefficients, upwind convection and relaxation of both, fixed-value patches of k

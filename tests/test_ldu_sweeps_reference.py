@@ -7,7 +7,8 @@
   * with every count frozen both builds do the same number of iterations, and the double build stays within 1e-17 .. 1e-12 of the wide one in every field
     group over the whole case list (seeded random coupling fields) -- the window tests/test_ldu_sweeps_parity.py relies on for its device bound of
     50 x max(e_oracle, 2^-52);
-  * that bound sees a coefficient wrong in the ninth digit: the double build with nu scaled by 1 + 1e-9 lands above it.
+  * that bound sees a coefficient wrong in the ninth digit: the double build with nu scaled by 1 + 1e-9 lands above it;
+  * and the other convection scheme of k on a through-flow lands a factor 1e8 above it (the two solvers' defaults differ: a case names its scheme).
 Measured: DESIGN.md, parity section."""
 import json
 import os
@@ -118,3 +119,21 @@ def test_a_coefficient_wrong_in_the_ninth_digit_lands_above_the_bound(oracle, na
         v, nm = lc.worst(lc.distances(c, off[step], wide[step]))["assembled"]
         print(f"{name} step {step + 1}: assembled {v:.2e} ({nm})  bound {e.bound('assembled', step):.2e}")
         assert v > e.bound("assembled", step), (step, nm, v)
+
+
+def test_the_other_k_scheme_lands_far_above_the_bound(oracle):
+    """the double build with upwind convection of k against the wide build with the case's linear one, on the through-flow with a k inlet: k leaves the bound the
+    device gets in its group by more than a factor 1000 (expected: 1e-3 or more against a bound near 1e-11) -- a solver that ran its own default instead of the
+    named scheme cannot pass the parity test"""
+    e = envelope(oracle)
+    name = "pimple_through_flow_kEqn_linear_k_inlet"
+    c = lc.CASES[name]
+    assert c["kw"]["k_convection_scheme"] == 0
+    other = dict(c, kw=dict(c["kw"], k_convection_scheme=1))
+    off = lc.run_oracle(oracle, other, coupling_of(c), wide=False)
+    _, wide = both_builds(oracle, name)
+    for step in range(2):
+        v = lc.distances(c, off[step], wide[step])[lc.GROUP_OF["k"]]["k"]
+        bound = e.bound(lc.GROUP_OF["k"], step)
+        print(f"{name} step {step + 1}: k {v:.2e}  bound {bound:.2e}")
+        assert v > 1000.0 * bound, (step, v, bound)
